@@ -31,6 +31,9 @@ Objects in the JSON beside the driver contract:
                 communication time (step with exchange - step without) and a bit-identity check of the averaged grads.
 
 `--workload generator` runs only configs[1] (or `--size 1024 --batch 4`: configs[4]) as the headline line.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (train: the loss dictionary and the
+updated G / D / EMA weights; generator: the image and the parameter gradients; sample: the images), for output-for-output
+comparison of two builds on identical inputs.
 """
 import argparse
 import json
@@ -39,6 +42,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -99,7 +103,45 @@ def parse():
     ap.add_argument('--no-sub', action='store_true', help='skip the sub-benchmarks (configs[1], configs[4])')
     ap.add_argument('--no-pmc', action='store_true', help='skip the live rocprofv3 --pmc passes (roofline.traffic falls back to '
                                                           'the committed summary, labelled static)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy '
+                         '(float32 / float64, at most 64 MB in all; larger outputs as a fixed, seeded sample of their elements)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_LIMIT_BYTES = 60 << 20          # array data; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32 (float64 stays float64), in its own shape.
+    The arrays share DUMP_LIMIT_BYTES: smallest first, each gets at most an even share of what is left, and one
+    above its share is replaced by a sample of its elements at positions drawn from a fixed seed (sorted; the same positions in
+    every run with the same arguments)."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = DUMP_LIMIT_BYTES
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        cap = left // ((len(items) - i) * t.element_size())
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+    print(f'dumped {len(items)} outputs of the last timed step to {out_dir} ({(DUMP_LIMIT_BYTES - left) / 2 ** 20:.1f} MB)',
+          file=sys.stderr, flush=True)
+
+
+def flat_params(module, grads=False):
+    """all parameters (or their gradients, zeros where a parameter has none) of a module, in parameters() order, as one vector"""
+    if grads:
+        return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in module.parameters()])
+    return torch.cat([p.detach().reshape(-1) for p in module.parameters()])
 
 
 class KernelTimer:
@@ -556,8 +598,9 @@ def max_over_ranks(elapsed, world, dev):
     return elapsed
 
 
-def run_generator(size, B, steps, warmup, dev, world, rank, timer, G=None):
-    """configs[1] / configs[4]: generator forward + backward; returns (elapsed_s, roofline | None)."""
+def run_generator(size, B, steps, warmup, dev, world, rank, timer, G=None, outputs=None):
+    """configs[1] / configs[4]: generator forward + backward; returns (elapsed_s, roofline | None).  `outputs` (a dict) receives
+    what the last timed step computed: the image and every parameter's gradient."""
     from transeditor_amd.model_spatial_query import Generator
     from transeditor_amd.utils import distributed as D
     token = 2 * (int(math.log2(size)) - 1)
@@ -581,6 +624,7 @@ def run_generator(size, B, steps, warmup, dev, world, rank, timer, G=None):
         img = G(zs[i], ps[i])[0]
         (img * wimg).sum().backward()
         sync.all_reduce()                                          # no-op at world == 1
+        return img
 
     for i in range(warmup):
         step(i)
@@ -589,11 +633,13 @@ def run_generator(size, B, steps, warmup, dev, world, rank, timer, G=None):
     timer.enabled = timer.installed
     t0 = time.perf_counter()
     for i in range(steps):
-        step(warmup + i)
+        img = step(warmup + i)
     fence(world)
     elapsed = time.perf_counter() - t0
     timer.enabled = False
     elapsed = max_over_ranks(elapsed, world, dev)
+    if outputs is not None:
+        outputs.update(image=img, generator_grads=flat_params(G, grads=True))
     roof = timer.roofline(elapsed, steps) if timer.installed else None
     sync.remove_hooks()
     for p in params:
@@ -620,16 +666,19 @@ def run_sampling(args, size, B, dev, base):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            fn(zs[args.warmup + i], p)
+            out = fn(zs[args.warmup + i], p)
         torch.cuda.synchronize()
-        return time.perf_counter() - t0
+        return time.perf_counter() - t0, out
 
     def plain(z, q):
         with torch.no_grad():
             return G(z, q)
-    t_plain = timed(plain)
-    t_cache = timed(GeneratorSampler(G, use_graph=False))
-    t_graph = timed(GeneratorSampler(G, use_graph=True))
+    t_plain, _ = timed(plain)
+    t_cache, _ = timed(GeneratorSampler(G, use_graph=False))
+    t_graph, last = timed(GeneratorSampler(G, use_graph=True))
+    if args.dump_outputs:                                          # the headline is the graph replay: what its last call returned
+        last = last if isinstance(last, (tuple, list)) else (last,)
+        dump_outputs(args.dump_outputs, {'image' if i == 0 else f'output{i}': t for i, t in enumerate(last) if torch.is_tensor(t)})
     out = dict(base, metric=f'{size}x{size} images/sec/GPU, frozen generator sampling loop (inference-only pipeline)',
                value=B * args.steps / t_graph, ms_per_step=1e3 * t_graph / args.steps,
                config={'workload': f'FFHQ-{size} g_ema sampling loop (test_spatial_query.py:20-31), batch {B}, no_grad, '
@@ -843,7 +892,11 @@ def main():
         return
 
     if args.workload == 'generator':
-        elapsed, roof = run_generator(size, B, args.steps, args.warmup, dev, world, rank, timer)
+        last = {} if rank == 0 and args.dump_outputs else None
+        elapsed, roof = run_generator(size, B, args.steps, args.warmup, dev, world, rank, timer, outputs=last)
+        if last is not None:
+            dump_outputs(args.dump_outputs, last)
+            last = None
         if rank == 0:
             cfg = 'configs[4]' if size >= 1024 else 'configs[1]'
             out = dict(base, value=world * B * args.steps / elapsed, ms_per_step=1e3 * elapsed / args.steps,
@@ -888,12 +941,18 @@ def main():
     clock.enabled = True
     t0 = time.perf_counter()
     for i in range(args.steps):
-        ts.iteration(i, reals[i % 4])
+        losses = ts.iteration(i, reals[i % 4])
     fence(world)
     elapsed = time.perf_counter() - t0
     timer.enabled = False
     clock.enabled = False
     elapsed = max_over_ranks(elapsed, world, dev)
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the iteration holds after the last timed step: its loss dictionary and the updated weights
+        dump_outputs(args.dump_outputs, {**{f'loss_{k}': v for k, v in losses.items()},
+                                         'generator_params': flat_params(ts.generator),
+                                         'discriminator_params': flat_params(ts.discriminator),
+                                         'g_ema_params': flat_params(ts.g_ema)})
 
     n_r1 = sum(1 for i in range(args.steps) if i % targs.d_reg_every == 0)
     n_path = sum(1 for i in range(args.steps) if i % targs.g_reg_every == 0)

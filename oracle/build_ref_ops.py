@@ -11,10 +11,10 @@ are plain __global__ functions) - four source files, no other dependency, so the
     under /tmp (never inside this repository) which is deleted afterwards;
   * only the two shared objects land in oracle/_ref/ (git-ignored; shipped to the GPU box with the snapshot like our own .so).
 
-What they are used for: tests/test_gpu_reference_kernels.py runs the reference's real kernels on the MI355X beside ours (K1
-bit for bit, K2 to round-off) and pins the oracle's restatement of fused_bias_act_kernel.cu:26-47 - the one piece of
-arithmetic in the golden fixtures that was "restatement, not reference" (VERDICT round 3, weak item 4).  Nothing under
-transeditor_amd/ ever loads them.
+What they are used for: oracle/gen_ref_kernels.py runs the reference's real kernels on the MI355X and stores their outputs in
+tests/golden/reference_kernels.npz, against which tests/test_gpu_reference_kernels.py holds ours (K1 bit for bit, K2 to
+round-off) and pins the oracle's restatement of fused_bias_act_kernel.cu:26-47 - the one piece of arithmetic in the golden
+fixtures that was "restatement, not reference" (VERDICT round 3, weak item 4).  Nothing under transeditor_amd/ ever loads them.
 """
 import os
 import shutil

@@ -320,6 +320,21 @@ def gen_schema(M):
     npz('state_dict_schema', **d)
 
 
+def gen_checkpoint_schema(M):
+    """state_dict schema (keys, shapes, dtypes, parameter order) of the models in a reference training checkpoint, constructed
+    as tests/test_reference_checkpoint.py writes one (32 px, 8 tokens, channel multiplier 2)."""
+    d = {}
+    for tag, m in (('g', M.Generator(32, 512, 512, 8, channel_multiplier=2, layer_noise_injection=False, use_spatial_mapping=True,
+                                      num_region=1, n_trans=8, pixel_norm_op_dim=1, no_trans=False)),
+                   ('d', M.Discriminator(32, channel_multiplier=2))):
+        sd = m.state_dict()
+        d[tag + '.keys'] = np.array(list(sd.keys()))
+        d[tag + '.shapes'] = np.array([','.join(map(str, v.shape)) for v in sd.values()])
+        d[tag + '.dtypes'] = np.array([str(v.dtype).replace('torch.', '') for v in sd.values()])
+        d[tag + '.param_names'] = np.array([n for n, _ in m.named_parameters()])
+    npz('reference_checkpoint32_schema', **d)
+
+
 TRAIN_SIZE, TRAIN_BATCH = 32, 4
 TRAIN_PROBES = {'g': ['adjust_style.weight', 'conv1.activate.bias', 'to_rgb1.bias', 'interact.3.mlp.0.bias',
                       'convs.5.conv.modulation.bias'],
