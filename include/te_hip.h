@@ -474,6 +474,66 @@ int te_mt_ema_f32(const int64_t* table, const int32_t* chunks, int n_tensors, in
 int te_chan_scale_f32(float* out, const float* x, const float* s, int64_t rows, int64_t hw, te_stream_t stream);
 int te_chan_dot_f32(float* out, const float* a, const float* b, int64_t rows, int64_t hw, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * L1  LPIPS-VGG perceptual distance (utils/lpips/__init__.py:12-39, networks_basic.py:21-87, pretrained_networks.py:98-136), the
+ * pieces the convolution family does not cover (conv1_2 ... conv5_3 run as TE_CONV_3X3 / 3X3W / 3X3W6 with the bias in the epilogue
+ * and ReLU as te_bias_act_f32 with alpha 0).  NCHW fp32 throughout.
+ *
+ * Stem: ScalingLayer (x - shift) / scale, shift (-.030, -.088, -.188), scale (.458, .448, .450), applied BEFORE the zero padding of
+ * conv1_1 (nn.Conv2d(3, 64, 3, padding=1) on the scaled tensor), then bias and ReLU:
+ *     out[n,o] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * s(x)[n,c,y+ky-1,x+kx-1])        w [64,3,3,3] (torchvision layout), b [64]
+ * te_lpips_stem_dgrad_f32: the data gradient with the relu1_1 mask (y1 = the stem output) and the 1/scale fold:
+ *     gx[n,c] = (1/scale[c]) * sum_{o,ky,kx} w[o,c,ky,kx] * (g * (y1 > 0))[n,o,y+1-ky,x+1-kx]
+ */
+int te_lpips_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, te_stream_t stream);
+int te_lpips_stem_dgrad_f32(float* gx, const float* g, const float* y1, const float* w, int N, int H, int W, te_stream_t stream);
+/* 2x2 / stride 2 max-pool (pretrained_networks.py: features[4, 9, 16, 23] = nn.MaxPool2d(2, 2)) over `planes` = N * C planes of
+ * H x W (both even).  Window order row-major; torch's rule: an element replaces the running maximum if it is greater OR NaN (the
+ * first of equal maxima wins, a NaN propagates).  The backward recomputes the window's index from x and writes ALL of gx (the
+ * gradient at the index, 0 elsewhere; no zero fill needed). */
+int te_maxpool2_fwd_f32(float* out, const float* x, int64_t planes, int H, int W, te_stream_t stream);
+int te_maxpool2_bwd_f32(float* gx, const float* g, const float* x, int64_t planes, int H, int W, te_stream_t stream);
+/* LPIPS head of one layer (networks_basic.py:65-73: normalize_tensor (utils/lpips/__init__.py:43-45), (f0 - f1)^2, lin = 1x1 conv
+ * without bias (NetLinLayer, :99-108), spatial_average (:12-13)).
+ *   te_lpips_normalize_f32: out = x / (sqrt(sum_c x^2) + 1e-10)   (normalise-only mode: the cached target features)
+ *   te_lpips_head_fwd_f32 : partial[n, j] = sum over the j-th block of 256 pixels of sum_c w[c] (f[n,c,p] / (|f[n,:,p]| + 1e-10)
+ *                           - t[nt,c,p])^2, j < te_lpips_head_blocks(HW); t are NORMALISED target features of batch Nt = N or 1
+ *                           (nt = 0: one target broadcast over the pred batch, as the projector's --batch > 1 relies on)
+ *   te_lpips_dist_f32     : d[n] = sum_{l < L} (sum_j partial_l[n, j]) / hw[l], layers in order (the reference's val += res[l]);
+ *                           partial / hw are HOST arrays of L <= 8 entries
+ *   te_lpips_head_bwd_f32 : gradient w.r.t. f given gd[N] (the gradient of d): with r = |f[n,:,p]|, u_c = 2 w_c (f_c / (r + eps)
+ *                           - t_c) gd[n] / HW,
+ *                               gf = u / (r + eps) - f (f . u) / (r (r + eps)^2)
+ *                           then gf += gin (may be NULL: the max-pool gradient arriving at the same tap) and, if relu_mask, gf = 0
+ *                           where f <= 0 (the tap is a ReLU output).  DEVIATION: at a pixel whose feature vector is exactly zero,
+ *                           torch autograd of the reference formula gives NaN (sqrt backward 0/0); here the second term is 0 at r = 0,
+ *                           so gf = u / eps there, the finite limit.
+ * Fixed-order reductions only (per-block tree, then a sequential sum over blocks and layers): bit-reproducible. */
+int te_lpips_normalize_f32(float* out, const float* x, int N, int C, int64_t HW, te_stream_t stream);
+int te_lpips_head_blocks(int64_t HW);
+int te_lpips_head_fwd_f32(float* partial, const float* f, const float* t, const float* w, int N, int Nt, int C, int64_t HW,
+                          te_stream_t stream);
+int te_lpips_dist_f32(float* d, const float* const* partial, const int64_t* hw, int L, int N, te_stream_t stream);
+int te_lpips_head_bwd_f32(float* gf, const float* gin, const float* gd, const float* f, const float* t, const float* w, int N, int Nt,
+                          int C, int64_t HW, int relu_mask, te_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * L2  noise regulariser of the projector (projector_optimization.py:21-49) over a whole list of n <= 32 noise maps [B,1,s,s]
+ * (maps / sizes / grads are HOST arrays of device pointers and sizes; s a power of two or <= 8):
+ *   te_noise_reg_fwd_f32  : loss[0] = sum over maps, and over scales s, s/2, ... down to the first <= 8, of
+ *                           mean(n * roll(n,1,dims=3))^2 + mean(n * roll(n,1,dims=2))^2, the next scale being the 2x2 mean
+ *                           (reshape + mean([3, 5])); ONE block in the reference's summation order.  `ws` (te_noise_reg_ws_floats) keeps
+ *                           the per-scale means and the downsampled maps for the backward
+ *   te_noise_reg_bwd_f32  : grads[i] = gloss[0] * d loss / d map i (written, one block per map); `tws` is a second workspace of the
+ *                           same size; `ws` as the forward left it
+ *   te_noise_normalize_f32: in place, map = (map - mean) / std, std unbiased over the whole map (noise_normalize_, :44-49)
+ */
+int64_t te_noise_reg_ws_floats(const int* sizes, int n, int B);
+int te_noise_reg_fwd_f32(float* loss, float* ws, float* const* maps, const int* sizes, int n, int B, te_stream_t stream);
+int te_noise_reg_bwd_f32(float* const* grads, float* tws, const float* gloss, const float* ws, float* const* maps, const int* sizes,
+                         int n, int B, te_stream_t stream);
+int te_noise_normalize_f32(float* const* maps, const int* sizes, int n, int B, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,19 @@ _SIGNATURES = {
     'te_mt_ema_f32': (C.c_int, [_P, _P, _I, _I, _I, C.c_double, _P]),
     'te_chan_scale_f32': (C.c_int, [_P, _P, _P, _L, _L, _P]),
     'te_chan_dot_f32': (C.c_int, [_P, _P, _P, _L, _L, _P]),
+    'te_lpips_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    'te_lpips_stem_dgrad_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    'te_maxpool2_fwd_f32': (C.c_int, [_P, _P, _L, _I, _I, _P]),
+    'te_maxpool2_bwd_f32': (C.c_int, [_P, _P, _P, _L, _I, _I, _P]),
+    'te_lpips_normalize_f32': (C.c_int, [_P, _P, _I, _I, _L, _P]),
+    'te_lpips_head_blocks': (C.c_int, [_L]),
+    'te_lpips_head_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
+    'te_lpips_dist_f32': (C.c_int, [_P, _P, _P, _I, _I, _P]),
+    'te_lpips_head_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _P]),
+    'te_noise_reg_ws_floats': (C.c_int64, [_P, _I, _I]),
+    'te_noise_reg_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    'te_noise_reg_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'te_noise_normalize_f32': (C.c_int, [_P, _P, _I, _I, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -719,6 +732,121 @@ def chan_dot(a, b):
     return out
 
 
+# --------------------------------------------------------------------------------------------- L1 LPIPS-VGG pieces
+def lpips_stem_fwd(x, w, b):
+    """ScalingLayer -> conv1_1 -> bias -> ReLU: x [N,3,H,W] -> [N,64,H,W]"""
+    x = x.contiguous()
+    N, _, H, W = x.shape
+    out = torch.empty(N, 64, H, W, device=x.device, dtype=x.dtype)
+    _check(lib().te_lpips_stem_fwd_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(b), N, H, W, _stream()), 'te_lpips_stem_fwd_f32')
+    return out
+
+
+def lpips_stem_dgrad(g, y1, w):
+    """data gradient of the stem w.r.t. the UNSCALED input (relu1_1 mask from its output y1)"""
+    g = g.contiguous()
+    N, _, H, W = g.shape
+    gx = torch.empty(N, 3, H, W, device=g.device, dtype=g.dtype)
+    _check(lib().te_lpips_stem_dgrad_f32(_ptr(gx), _ptr(g), _ptr(y1), _ptr(w), N, H, W, _stream()), 'te_lpips_stem_dgrad_f32')
+    return gx
+
+
+def maxpool2_fwd(x):
+    x = x.contiguous()
+    N, Cn, H, W = x.shape
+    out = torch.empty(N, Cn, H // 2, W // 2, device=x.device, dtype=x.dtype)
+    _check(lib().te_maxpool2_fwd_f32(_ptr(out), _ptr(x), N * Cn, H, W, _stream()), 'te_maxpool2_fwd_f32')
+    return out
+
+
+def maxpool2_bwd(g, x):
+    g = g.contiguous()
+    N, Cn, H, W = x.shape
+    gx = torch.empty_like(x)
+    _check(lib().te_maxpool2_bwd_f32(_ptr(gx), _ptr(g), _ptr(x), N * Cn, H, W, _stream()), 'te_maxpool2_bwd_f32')
+    return gx
+
+
+def lpips_normalize(x):
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    _check(lib().te_lpips_normalize_f32(_ptr(out), _ptr(x), x.shape[0], x.shape[1], x.shape[2] * x.shape[3], _stream()),
+           'te_lpips_normalize_f32')
+    return out
+
+
+def lpips_head_fwd(f, t_hat, w):
+    """per-block partial sums [N, blocks] of one layer's head (t_hat: normalised target features, batch N or 1)"""
+    f = f.contiguous()
+    N, Cn, H, W = f.shape
+    nb = lib().te_lpips_head_blocks(H * W)
+    partial = torch.empty(N, nb, device=f.device, dtype=f.dtype)
+    _check(lib().te_lpips_head_fwd_f32(_ptr(partial), _ptr(f), _ptr(t_hat), _ptr(w), N, t_hat.shape[0], Cn, H * W, _stream()),
+           'te_lpips_head_fwd_f32')
+    return partial
+
+
+def lpips_dist(partials, hws):
+    """d[N] = sum over layers (in order) of the spatial means"""
+    L, N = len(partials), partials[0].shape[0]
+    d = torch.empty(N, device=partials[0].device, dtype=torch.float32)
+    ptrs = (C.c_void_p * L)(*[_ptr(p) for p in partials])
+    hw = (C.c_int64 * L)(*hws)
+    _check(lib().te_lpips_dist_f32(_ptr(d), ptrs, hw, L, N, _stream()), 'te_lpips_dist_f32')
+    return d
+
+
+def lpips_head_bwd(gd, f, t_hat, w, gin=None, relu_mask=True):
+    f = f.contiguous()
+    N, Cn, H, W = f.shape
+    gf = torch.empty_like(f)
+    _check(lib().te_lpips_head_bwd_f32(_ptr(gf), _ptr(gin.contiguous()) if gin is not None else None, _ptr(gd.contiguous()), _ptr(f),
+                                       _ptr(t_hat), _ptr(w), N, t_hat.shape[0], Cn, H * W, 1 if relu_mask else 0, _stream()),
+           'te_lpips_head_bwd_f32')
+    return gf
+
+
+# --------------------------------------------------------------------------------------------- L2 noise regulariser
+def _noise_list(maps):
+    n = len(maps)
+    if n == 0:
+        raise RuntimeError('te_hip: the noise regulariser needs at least one noise map')
+    B = maps[0].shape[0]
+    for m in maps:
+        if m.ndim != 4 or m.shape[0] != B or m.shape[1] != 1 or m.shape[2] != m.shape[3]:
+            raise RuntimeError(f'te_hip: noise maps must be [B,1,s,s] with one B, got {tuple(m.shape)}')
+    ptrs = (C.c_void_p * n)(*[_ptr(m) for m in maps])
+    sizes = (C.c_int * n)(*[m.shape[2] for m in maps])
+    return ptrs, sizes, n, B
+
+
+def noise_reg_fwd(maps):
+    """-> (loss [1], workspace for noise_reg_bwd)"""
+    ptrs, sizes, n, B = _noise_list(maps)
+    nws = lib().te_noise_reg_ws_floats(sizes, n, B)
+    if nws < 0:
+        raise RuntimeError(f'te_noise_reg_ws_floats failed ({nws})')
+    loss = torch.empty(1, device=maps[0].device, dtype=torch.float32)
+    ws = torch.empty(nws, device=maps[0].device, dtype=torch.float32)
+    _check(lib().te_noise_reg_fwd_f32(_ptr(loss), _ptr(ws), ptrs, sizes, n, B, _stream()), 'te_noise_reg_fwd_f32')
+    return loss, ws
+
+
+def noise_reg_bwd(gloss, ws, maps):
+    ptrs, sizes, n, B = _noise_list(maps)
+    grads = [torch.empty_like(m) for m in maps]
+    gptrs = (C.c_void_p * n)(*[_ptr(g) for g in grads])
+    tws = torch.empty_like(ws)
+    _check(lib().te_noise_reg_bwd_f32(gptrs, _ptr(tws), _ptr(gloss.reshape(1).contiguous()), _ptr(ws), ptrs, sizes, n, B, _stream()),
+           'te_noise_reg_bwd_f32')
+    return grads
+
+
+def noise_normalize_(maps):
+    ptrs, sizes, n, B = _noise_list(maps)
+    _check(lib().te_noise_normalize_f32(ptrs, sizes, n, B, _stream()), 'te_noise_normalize_f32')
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -730,7 +858,9 @@ def _install_roctx():
              'wgrad_slabs', 'wgrad_reduce', 'rgb_fwd', 'rgb_dgrad', 'rgb_expand', 'rgb_wgrad_slabs', 'small_gemm',
              'small_gemm_splitk', 'small_gemm_batched', 'minibatch_stddev_fwd', 'minibatch_stddev_bwd',
              'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd', 'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd',
-             'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot']
+             'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
+             'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'noise_reg_fwd',
+             'noise_reg_bwd', 'noise_normalize_']
     g = globals()
 
     def wrap(fn, name):

@@ -1,0 +1,317 @@
+// LPIPS-VGG perceptual distance (utils/lpips/networks_basic.py:21-87, pretrained_networks.py:98-136): the kernels whose shapes the
+// convolution family does not cover.  conv1_2 ... conv5_3 run on the plain 3x3 convolution (op/modconv.py planner); here:
+//
+//     stem   : ScalingLayer -> conv1_1 (3 -> 64, pad 1) -> bias -> ReLU, and its data gradient (64 -> 3, relu1_1 mask, 1/scale)
+//     pool   : 2x2 / stride 2 max-pool forward and backward (torch's rule: first maximum in row-major order, NaN propagates)
+//     head   : normalize_tensor, squared difference, lin weights, spatial mean (per-block partials + a fixed-order sum) and the
+//              gradient with respect to the pred features
+//
+// One thread per output pixel everywhere; every reduction is a fixed-order loop or a fixed-shape tree (no atomics).
+#include "te_common.h"
+
+namespace {
+
+// ScalingLayer (networks_basic.py:89-96): (x - shift) / scale
+__constant__ float kShift[3] = {-.030f, -.088f, -.188f};
+__constant__ float kScale[3] = {.458f, .448f, .450f};
+constexpr float kEps = 1e-10f;   // normalize_tensor eps (utils/lpips/__init__.py:43-45)
+
+// out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * s(x)[n,c,y+ky-1,x+kx-1]); s(x) is zero outside the image (the scaling
+// happens BEFORE nn.Conv2d's zero padding).  w: [64,3,3,3] in LDS, 27 scaled inputs per thread in registers.
+__global__ __launch_bounds__(256) void stem_fwd_kernel(float* __restrict__ out, const float* __restrict__ x,
+                                                       const float* __restrict__ w, const float* __restrict__ b, int H, int W) {
+    __shared__ float ws[64 * 27];
+    __shared__ float bs[64];
+    for (int i = threadIdx.x; i < 64 * 27; i += 256) ws[i] = w[i];
+    if (threadIdx.x < 64) bs[threadIdx.x] = b[threadIdx.x];
+    __syncthreads();
+    const int n = blockIdx.y;
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int yy = (int)(p / W), xx = (int)(p % W);
+    float in[27];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* xc = x + ((int64_t)n * 3 + c) * HW;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int iy = yy + ky - 1, ix = xx + kx - 1;
+                const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
+                in[c * 9 + ky * 3 + kx] = ok ? (xc[(int64_t)iy * W + ix] - kShift[c]) / kScale[c] : 0.f;
+            }
+        }
+    }
+    float* o = out + (int64_t)n * 64 * HW + p;
+    for (int m = 0; m < 64; ++m) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 27; ++k) acc = fmaf(ws[m * 27 + k], in[k], acc);
+        acc += bs[m];
+        o[(int64_t)m * HW] = acc > 0.f ? acc : (acc != acc ? acc : 0.f);
+    }
+}
+
+// gx[n,c,y,x] = (1/scale[c]) * sum_{o,ky,kx} w[o,c,ky,kx] * g[n,o,y+1-ky,x+1-kx] * (y1[n,o,...] > 0)
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(float* __restrict__ gx, const float* __restrict__ g,
+                                                         const float* __restrict__ y1, const float* __restrict__ w, int H, int W) {
+    __shared__ float ws[64 * 27];
+    for (int i = threadIdx.x; i < 64 * 27; i += 256) ws[i] = w[i];
+    __syncthreads();
+    const int n = blockIdx.y;
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int yy = (int)(p / W), xx = (int)(p % W);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    const float* gn = g + (int64_t)n * 64 * HW;
+    const float* yn = y1 + (int64_t)n * 64 * HW;
+    for (int o = 0; o < 64; ++o) {
+        const float* go = gn + (int64_t)o * HW;
+        const float* yo = yn + (int64_t)o * HW;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int oy = yy + 1 - ky;
+            if (oy < 0 || oy >= H) continue;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ox = xx + 1 - kx;
+                if (ox < 0 || ox >= W) continue;
+                const int64_t q = (int64_t)oy * W + ox;
+                const float gv = yo[q] > 0.f ? go[q] : 0.f;
+                const int t = ky * 3 + kx;
+                a0 = fmaf(ws[o * 27 + t], gv, a0);
+                a1 = fmaf(ws[o * 27 + 9 + t], gv, a1);
+                a2 = fmaf(ws[o * 27 + 18 + t], gv, a2);
+            }
+        }
+    }
+    float* gxn = gx + (int64_t)n * 3 * HW + p;
+    gxn[0] = a0 / kScale[0];
+    gxn[HW] = a1 / kScale[1];
+    gxn[2 * HW] = a2 / kScale[2];
+}
+
+// index (0..3, row-major) of the window's maximum under torch's rule (max_pool2d: `val > max || isnan(val)` updates)
+__device__ __forceinline__ int pool_argmax(const float* __restrict__ x, int64_t q, int W, float& m) {
+    const float v[4] = {x[q], x[q + 1], x[q + W], x[q + W + 1]};
+    int idx = 0;
+    m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (v[k] > m || v[k] != v[k]) { m = v[k]; idx = k; }
+    return idx;
+}
+
+__global__ __launch_bounds__(256) void pool_fwd_kernel(float* __restrict__ out, const float* __restrict__ x, int64_t total, int H, int W) {
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t plane = i / ((int64_t)Ho * Wo);
+    const int r = (int)(i - plane * Ho * Wo);
+    const int oy = r / Wo, ox = r % Wo;
+    float m;
+    pool_argmax(x, plane * H * W + (int64_t)(2 * oy) * W + 2 * ox, W, m);
+    out[i] = m;
+}
+
+// every input pixel belongs to exactly one window: all four are written (no zero fill)
+__global__ __launch_bounds__(256) void pool_bwd_kernel(float* __restrict__ gx, const float* __restrict__ g, const float* __restrict__ x,
+                                                       int64_t total, int H, int W) {
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t plane = i / ((int64_t)Ho * Wo);
+    const int r = (int)(i - plane * Ho * Wo);
+    const int oy = r / Wo, ox = r % Wo;
+    const int64_t q = plane * H * W + (int64_t)(2 * oy) * W + 2 * ox;
+    float m;
+    const int idx = pool_argmax(x, q, W, m);
+    const float gv = g[i];
+    gx[q] = idx == 0 ? gv : 0.f;
+    gx[q + 1] = idx == 1 ? gv : 0.f;
+    gx[q + W] = idx == 2 ? gv : 0.f;
+    gx[q + W + 1] = idx == 3 ? gv : 0.f;
+}
+
+__device__ __forceinline__ float block_sum256(float v, float* part) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) part[wid] = v;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// 1 / (sqrt(sum_c x^2) + eps), correctly rounded in every kernel that uses it: the normalise-only mode (cached target) and the
+// head's own normalisation of the pred features agree bit for bit, so d(x, x) == 0 exactly
+__device__ __forceinline__ float norm_inv(float s) { return __fdiv_rn(1.f, __fadd_rn(__fsqrt_rn(s), kEps)); }
+
+// normalize_tensor: out = x / (sqrt(sum_c x^2) + eps)
+__global__ __launch_bounds__(256) void normalize_kernel(float* __restrict__ out, const float* __restrict__ x, int C, int64_t HW) {
+    const int n = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const float* xn = x + (int64_t)n * C * HW + p;
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) { const float v = xn[(int64_t)c * HW]; s = fmaf(v, v, s); }
+    const float inv = norm_inv(s);
+    float* on = out + (int64_t)n * C * HW + p;
+    for (int c = 0; c < C; ++c) on[(int64_t)c * HW] = __fmul_rn(xn[(int64_t)c * HW], inv);
+}
+
+// partial[n, blockIdx.x] = sum over the block's pixels of sum_c w[c] * (f[n,c,p] / (|f[n,:,p]| + eps) - t[nt,c,p])^2
+__global__ __launch_bounds__(256) void head_fwd_kernel(float* __restrict__ partial, const float* __restrict__ f,
+                                                       const float* __restrict__ t, const float* __restrict__ w, int Nt, int C,
+                                                       int64_t HW) {
+#pragma clang fp contract(off)   // (f * inv) rounded before the subtraction, as the normalise-only mode stores it: d(x, x) == 0
+    __shared__ float part[4];
+    const int n = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float v = 0.f;
+    if (p < HW) {
+        const float* fn = f + (int64_t)n * C * HW + p;
+        const float* tn = t + (int64_t)(Nt == 1 ? 0 : n) * C * HW + p;
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) { const float a = fn[(int64_t)c * HW]; s = fmaf(a, a, s); }
+        const float inv = norm_inv(s);
+        for (int c = 0; c < C; ++c) {
+            const float d = fn[(int64_t)c * HW] * inv - tn[(int64_t)c * HW];
+            v = fmaf(w[c] * d, d, v);      // (explicit fma: kept)
+        }
+    }
+    const float s = block_sum256(v, part);
+    if (threadIdx.x == 0) partial[(int64_t)n * gridDim.x + blockIdx.x] = s;
+}
+
+// d/df of the head at one pixel (see te_hip.h): u_c = 2 w_c (fhat_c - t_c) gd[n] / HW,
+//     g = u / (r + eps) - f (f . u) / (r (r + eps)^2)      (second term 0 at r = 0)
+// then gf = (gin + g) * (relu_mask ? (f > 0) : 1)
+__global__ __launch_bounds__(256) void head_bwd_kernel(float* __restrict__ gf, const float* __restrict__ gin, const float* __restrict__ gd,
+                                                       const float* __restrict__ f, const float* __restrict__ t, const float* __restrict__ w,
+                                                       int Nt, int C, int64_t HW, int relu_mask) {
+    const int n = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int64_t base = (int64_t)n * C * HW + p;
+    const float* fn = f + base;
+    const float* tn = t + (int64_t)(Nt == 1 ? 0 : n) * C * HW + p;
+    const float sc = 2.f * gd[n] / (float)HW;
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) { const float a = fn[(int64_t)c * HW]; s = fmaf(a, a, s); }
+    const float r = __fsqrt_rn(s), re = r + kEps, inv = norm_inv(s);
+    float dot = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float a = fn[(int64_t)c * HW];
+        const float u = sc * w[c] * (__fmul_rn(a, inv) - tn[(int64_t)c * HW]);
+        dot = fmaf(a, u, dot);
+    }
+    const float k = r > 0.f ? dot / (r * re * re) : 0.f;
+    float* gn = gf + base;
+    const float* gi = gin ? gin + base : nullptr;
+    for (int c = 0; c < C; ++c) {
+        const float a = fn[(int64_t)c * HW];
+        const float u = sc * w[c] * (__fmul_rn(a, inv) - tn[(int64_t)c * HW]);
+        float gv = u * inv - a * k;
+        if (gi) gv += gi[(int64_t)c * HW];
+        if (relu_mask && !(a > 0.f)) gv = 0.f;
+        gn[(int64_t)c * HW] = gv;
+    }
+}
+
+struct DistArgs {
+    const float* partial[8];
+    int nblk[8];
+    int64_t hw[8];
+};
+
+// d[n] = sum_l (sum_b partial_l[n, b]) / HW_l, layers in order 0..L-1 (networks_basic.py:80-82: val = res[0]; val += res[l])
+__global__ __launch_bounds__(64) void dist_kernel(float* __restrict__ d, DistArgs a, int L, int N) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;
+    float val = 0.f;
+    for (int l = 0; l < L; ++l) {
+        const float* pl = a.partial[l] + (int64_t)n * a.nblk[l];
+        float s = 0.f;
+        for (int b = 0; b < a.nblk[l]; ++b) s += pl[b];
+        const float m = s / (float)a.hw[l];
+        val = l == 0 ? m : val + m;
+    }
+    d[n] = val;
+}
+
+}  // namespace
+
+extern "C" int te_lpips_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, te_stream_t stream) {
+    TE_REQUIRE(out && x && w && b, TE_ERR_NULL, "te_lpips_stem_fwd_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_lpips_stem_fwd_f32: bad dims");
+    const int64_t HW = (int64_t)H * W;
+    stem_fwd_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, w, b, H, W);
+    return te::launch_status("te_lpips_stem_fwd_f32");
+}
+
+extern "C" int te_lpips_stem_dgrad_f32(float* gx, const float* g, const float* y1, const float* w, int N, int H, int W,
+                                       te_stream_t stream) {
+    TE_REQUIRE(gx && g && y1 && w, TE_ERR_NULL, "te_lpips_stem_dgrad_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_lpips_stem_dgrad_f32: bad dims");
+    const int64_t HW = (int64_t)H * W;
+    stem_dgrad_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(gx, g, y1, w, H, W);
+    return te::launch_status("te_lpips_stem_dgrad_f32");
+}
+
+extern "C" int te_maxpool2_fwd_f32(float* out, const float* x, int64_t planes, int H, int W, te_stream_t stream) {
+    TE_REQUIRE(out && x, TE_ERR_NULL, "te_maxpool2_fwd_f32: NULL pointer");
+    TE_REQUIRE(planes > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, TE_ERR_SHAPE, "te_maxpool2_fwd_f32: H, W must be even");
+    const int64_t total = planes * (H / 2) * (W / 2);
+    pool_fwd_kernel<<<(unsigned)te::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(out, x, total, H, W);
+    return te::launch_status("te_maxpool2_fwd_f32");
+}
+
+extern "C" int te_maxpool2_bwd_f32(float* gx, const float* g, const float* x, int64_t planes, int H, int W, te_stream_t stream) {
+    TE_REQUIRE(gx && g && x, TE_ERR_NULL, "te_maxpool2_bwd_f32: NULL pointer");
+    TE_REQUIRE(planes > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, TE_ERR_SHAPE, "te_maxpool2_bwd_f32: H, W must be even");
+    const int64_t total = planes * (H / 2) * (W / 2);
+    pool_bwd_kernel<<<(unsigned)te::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(gx, g, x, total, H, W);
+    return te::launch_status("te_maxpool2_bwd_f32");
+}
+
+extern "C" int te_lpips_normalize_f32(float* out, const float* x, int N, int C, int64_t HW, te_stream_t stream) {
+    TE_REQUIRE(out && x, TE_ERR_NULL, "te_lpips_normalize_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && C > 0 && HW > 0 && N < 65536, TE_ERR_SHAPE, "te_lpips_normalize_f32: bad dims");
+    normalize_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, C, HW);
+    return te::launch_status("te_lpips_normalize_f32");
+}
+
+extern "C" int te_lpips_head_blocks(int64_t HW) { return HW > 0 ? (int)te::cdiv(HW, 256) : TE_ERR_SHAPE; }
+
+extern "C" int te_lpips_head_fwd_f32(float* partial, const float* f, const float* t, const float* w, int N, int Nt, int C, int64_t HW,
+                                     te_stream_t stream) {
+    TE_REQUIRE(partial && f && t && w, TE_ERR_NULL, "te_lpips_head_fwd_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && C > 0 && HW > 0 && N < 65536 && (Nt == 1 || Nt == N), TE_ERR_SHAPE, "te_lpips_head_fwd_f32: bad dims");
+    head_fwd_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(partial, f, t, w, Nt, C, HW);
+    return te::launch_status("te_lpips_head_fwd_f32");
+}
+
+extern "C" int te_lpips_head_bwd_f32(float* gf, const float* gin, const float* gd, const float* f, const float* t, const float* w, int N,
+                                     int Nt, int C, int64_t HW, int relu_mask, te_stream_t stream) {
+    TE_REQUIRE(gf && gd && f && t && w, TE_ERR_NULL, "te_lpips_head_bwd_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && C > 0 && HW > 0 && N < 65536 && (Nt == 1 || Nt == N), TE_ERR_SHAPE, "te_lpips_head_bwd_f32: bad dims");
+    head_bwd_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(gf, gin, gd, f, t, w, Nt, C, HW, relu_mask);
+    return te::launch_status("te_lpips_head_bwd_f32");
+}
+
+extern "C" int te_lpips_dist_f32(float* d, const float* const* partial, const int64_t* hw, int L, int N, te_stream_t stream) {
+    TE_REQUIRE(d && partial && hw, TE_ERR_NULL, "te_lpips_dist_f32: NULL pointer");
+    TE_REQUIRE(L >= 1 && L <= 8 && N > 0, TE_ERR_SHAPE, "te_lpips_dist_f32: 1 <= L <= 8 layers");
+    DistArgs a{};
+    for (int l = 0; l < L; ++l) {
+        TE_REQUIRE(partial[l] && hw[l] > 0, TE_ERR_NULL, "te_lpips_dist_f32: layer %d", l);
+        a.partial[l] = partial[l];
+        a.hw[l] = hw[l];
+        a.nblk[l] = (int)te::cdiv(hw[l], 256);
+    }
+    dist_kernel<<<(unsigned)te::cdiv(N, 64), 64, 0, (hipStream_t)stream>>>(d, a, L, N);
+    return te::launch_status("te_lpips_dist_f32");
+}
