@@ -6,11 +6,14 @@
  *   - every pointer is a DEVICE pointer to contiguous fp32 unless stated; the CALLER owns every
  *     buffer (the Python host allocates through the torch caching allocator);
  *   - functions only ENQUEUE work on `stream` (a hipStream_t passed as void*): no allocation,
- *     no synchronisation; safe to call from several host threads.  No global mutable state takes part in any RESULT; the only
- *     process-wide state are five debug / A-B switches that select between kernels with the same results (bit-identical for
- *     te_conv_wino6_form, te_conv_s2s6_form, te_conv_t2s6_form and te_wgrad_t2_wide, fp32-equivalent for te_wgrad_split_bf16; all
- *     atomics, initialised from the environment, never written by the product's own code paths) and the per-thread last-error
- *     string;
+ *     no synchronisation; safe to call from several host threads.  The process-wide mutable state behind this ABI is:
+ *       - te_wgrad_split_bf16 (initialised from TE_SPLIT_BF16; the Python layer writes it): selects the split bf16 or the fp32
+ *         weight-gradient kernel and with it the slab partition - results are fp32-equivalent, not bit-identical, across its values;
+ *       - four test and tool hooks, te_conv_wino6_form, te_conv_s2s6_form, te_conv_t2s6_form and te_wgrad_t2_wide, which select
+ *         between kernels of one kind with bit-identical results (tests compare the two live kernels of a kind on one input);
+ *       - TE_XCD_INTERLEAVED, read once from the environment: the order in which the convolution launches hand tiles to the XCDs
+ *         (te_common.h); results are bit-identical;
+ *       - the per-thread last-error string;
  *   - return 0 on success, a negative TE_ERR_* for argument validation failures, or a positive
  *     hipError_t if the launch failed; nothing throws across the ABI.  te_last_error_string()
  *     describes the calling thread's most recent failure.
@@ -230,27 +233,24 @@ int te_conv_s2s6_supported(int B, int K, int M, int H, int W);
 int te_conv_t2s6_supported(int B, int K, int M, int H, int W);
 /* 1 if TE_CONV_1X1S6 covers the problem: K % 64 == 0, M % 128 == 0, H * W % 256 == 0 and a grid of at least half the CUs */
 int te_conv_p1s6_supported(int B, int K, int M, int H, int W);
-/* Kernel form of TE_CONV_3X3W6 (a DEBUG / A-B switch, process-wide - the one piece of mutable state behind this ABI besides
- * te_wgrad_split_bf16; the results do not depend on it; returns the previous value; anything but 0 .. 3 only queries):
+/* Kernel form of TE_CONV_3X3W6 (a test and tool hook, process-wide; the results do not depend on it; returns the previous value;
+ * anything but 1 .. 3 only queries):
  *   2 = two-image (round 6, default): as 1, but a block owns 128 output channels - every staged half tile is multiplied by two
  *       64-channel weight images, so the style scale / B^T d / three-piece split of an input element is done once per 128 output
  *       channels instead of once per 64; launches with M % 128 != 0, or whose grid would leave CUs without a block, run form 1
  *       (3 = the two-image form wherever M % 128 == 0, whatever the grid: tests);
  *   1 = ping-pong (round 5): the two waves of every SIMD work half a stage apart - one feeds the matrix pipe from its
- *       half tile while the other transforms / splits / writes the next half tile and renews half of the weight image;
- *   0 = block-phase (round 4): all eight waves multiply, barrier, all eight waves stage, barrier.
- * All forms issue the same products in the same order per output element: results are bit-identical.  TE_W6_FORM in the
- * environment sets the initial value (A/B measurements). */
+ *       half tile while the other transforms / splits / writes the next half tile and renews half of the weight image.
+ * All forms issue the same products in the same order per output element: results are bit-identical. */
 int te_conv_wino6_form(int form);
-/* Kernel form of TE_CONV_S2S6 (returns the previous value; form < 0 only queries), a process-wide A/B switch like the one above:
+/* Kernel form of TE_CONV_S2S6 (returns the previous value; anything but 0 .. 2 only queries), a test and tool hook like the one above:
  *   1 = (round 6, default) the two-image form: a block owns 128 output channels and multiplies every staged half tile by two
  *       64-channel weight images (half the fetches, split arithmetic and LDS writes per MFMA) where M % 128 == 0 and the grid
  *       still gives every CU a block, the ping-pong form elsewhere (2 = the two-image form wherever M % 128 == 0: tests);
  *   0 = ping-pong (round 5).
- * Same products in the same order per output element: results are bit-identical.  TE_S2S6_FORM in the environment sets the
- * initial value. */
+ * Same products in the same order per output element: results are bit-identical. */
 int te_conv_s2s6_form(int form);
-/* the same switch for TE_CONV_T2S6 (t2s6q_kernel / t2s6_kernel; TE_T2S6_FORM) */
+/* the same hook for TE_CONV_T2S6 (t2s6q_kernel / t2s6_kernel) */
 int te_conv_t2s6_form(int form);
 /* TE_CONV_T2S6 only: `ws` of te_conv_ws_f32 / te_conv_res_f32 is an OPTIONAL scratch of te_conv_t2s6_ws_floats(B, K, H) = B * K * H
  * floats through which the body kernel hands the (style-scaled) last input column to the kernel that computes the last output
@@ -283,14 +283,14 @@ int te_wgrad_pair_form(int kind, int Co, int Ci, int H, int W);
  * six exact piece products per multiply-add, fp32 accumulation - fp32-equivalent slabs, same layout, same reducers).
  * te_wgrad_split_supported: 1 where it applies (Co % 64 == 0, Ci % 64 == 0; kind TE_CONV_3X3: W % 32 == 0; kind TE_CONV_T2 - direct
  * form, nine taps x six products - W % 16 == 0; round 6: kind TE_CONV_1X1 with Co % 128 == 0, Ci % 128 == 0, W % 16 == 0).
- * te_wgrad_split_bf16(0 | 1): process-wide switch (environment TE_SPLIT_WGRAD at load time), returns the previous value; any other
+ * te_wgrad_split_bf16(0 | 1): process-wide switch (environment TE_SPLIT_BF16 at load time), returns the previous value; any other
  * argument only queries.  With the switch on, te_wgrad_f32 / te_wgrad_group_f32 take the kernel where it applies and the fp32
- * kernel elsewhere. */
+ * kernel elsewhere; te_wgrad_slab_count and te_wgrad_group_plan plan their chunks from the same switch. */
 int te_wgrad_split_supported(int kind, int Co, int Ci, int H, int W);
 int te_wgrad_split_bf16(int on);
 /* Round 6: form of the split transposed-kind kernel - 1 (default): a block owns 64 channels of the (2H+1) x (2W+1) tensor x 128 of the
  * H x W one where Ci % 128 == 0 (half the staging work and re-reads of the big tensor per MFMA), 0: 64 x 64 everywhere.  Bit-identical
- * slabs; returns the previous value, any other argument only queries; TE_WGRAD_T2_WIDE in the environment sets the initial value. */
+ * slabs; returns the previous value, any other argument only queries.  A test and tool hook (see the conventions above). */
 int te_wgrad_t2_wide(int on);
 int te_wgrad_f32(float* slabs, const float* g, const float* x, int kind, int B, int Co, int Ci, int H,
                  int W, int S, te_stream_t stream);

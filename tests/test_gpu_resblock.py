@@ -220,3 +220,42 @@ def test_discriminator_stem_plus_first_block_node(frozen):
     flip = max(rel_l2(a, b) for a, b in zip(free, gref))
     print(f'stem + first block (frozen={frozen}): pinned worst {worst:.2e} ({st["flips"]} of {st["elements"]} slopes pinned); free slopes {flip:.2e}')
     assert flip < 2e-2
+
+
+def test_resblock_backward_launches_the_kinds_its_forward_planned():
+    """The forward decides each data gradient's convolution kind once and keeps it next to the packed weights: flipping
+    modconv.USE_SPLIT_BF16 between forward and backward changes what the planners answer, but the backward still launches the split
+    kernels its buffers were packed for.  The weight gradients follow the flag (fp32 kernels, another slab partition): dx and every
+    parameter gradient match an unflipped run at 5e-6."""
+    from transeditor_amd import _lib
+    from transeditor_amd.op import modconv
+    B, cin, cout, H = 32, 128, 256, 64
+    w1, w2, ws = torch.empty(cin, cin, 3, 3), torch.empty(cout, cin, 3, 3), torch.empty(cout, cin, 1, 1)
+    h = H // 2
+    kinds = lambda: (modconv.fwd_kinds('3x3', B, w1, H, H)[1], modconv.bwd_kinds('3x3', B, w1, H, H)[1],
+                     modconv.fwd_kinds('down', B, w2, h, h)[1], modconv.bwd_kinds('down', B, w2, h, h)[1],
+                     modconv.plain_1x1_kinds(B, ws, h, h)[1], modconv.plain_1x1_kinds(B, ws, h, h, dgrad=True)[1])
+    assert modconv.USE_SPLIT_BF16
+    assert kinds() == (_lib.CONV_3X3W6, _lib.CONV_3X3W6, _lib.CONV_S2S6, _lib.CONV_T2S6, _lib.CONV_1X1S6, _lib.CONV_1X1S6)
+    rb, _ = _block(cin, cout, 9)
+    assert rb._standard()
+    params = list(rb.parameters())
+    x = synth.normal((B, cin, H, H), 'rb.once.x').to(DEV)
+    gy = synth.normal((B, cout, h, h), 'rb.once.g').to(DEV)
+
+    def grads(flip):
+        xd = x.clone().requires_grad_(True)
+        out = rb(xd)
+        assert 'ResBlock' in type(out.grad_fn).__name__
+        try:
+            if flip:
+                modconv.USE_SPLIT_BF16 = False
+                assert _lib.wgrad_split() == 0 and _lib.CONV_3X3W6 not in kinds() and _lib.CONV_1X1S6 not in kinds()
+            return torch.autograd.grad((out * gy).sum(), [xd] + params)
+        finally:
+            modconv.USE_SPLIT_BF16 = True
+
+    want, got = grads(False), grads(True)
+    assert _lib.wgrad_split() == 1
+    for n, a, b in zip(['dx'] + [n for n, _ in rb.named_parameters()], got, want):
+        assert rel_err(a, b) < 5e-6, n

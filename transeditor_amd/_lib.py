@@ -374,19 +374,19 @@ def p1s6_ok(B, K, M, H, W):
 
 
 def wino6_form(form=-1):
-    """kernel form of TE_CONV_3X3W6: 2 = two-image (default; M % 128 == 0, else ping-pong), 1 = ping-pong, 0 = block-phase (bit-identical
-    results); returns the previous value (-1: query only)"""
+    """test and tool hook: kernel form of TE_CONV_3X3W6 - 2 = two-image (default; M % 128 == 0 and a block per CU, else ping-pong),
+    3 = two-image wherever M % 128 == 0, 1 = ping-pong (bit-identical results); returns the previous value (any other value: query only)"""
     return int(lib().te_conv_wino6_form(form))
 
 
 def s2s6_form(form=-1):
-    """kernel form of TE_CONV_S2S6: 1 = two-image (default; M % 128 == 0 and a block per CU, else ping-pong), 2 = two-image wherever
-    M % 128 == 0, 0 = ping-pong (bit-identical results); returns the previous value (-1: query only)"""
+    """test and tool hook: kernel form of TE_CONV_S2S6 - 1 = two-image (default; M % 128 == 0 and a block per CU, else ping-pong),
+    2 = two-image wherever M % 128 == 0, 0 = ping-pong (bit-identical results); returns the previous value (-1: query only)"""
     return int(lib().te_conv_s2s6_form(form))
 
 
 def t2s6_form(form=-1):
-    """kernel form of TE_CONV_T2S6: as s2s6_form"""
+    """test and tool hook: kernel form of TE_CONV_T2S6, as s2s6_form"""
     return int(lib().te_conv_t2s6_form(form))
 
 
@@ -449,13 +449,15 @@ def wgrad_slabs(g, x, kind, H, W, group=False):
 
 
 def wgrad_t2_wide(on=-1):
-    """form of the split transposed-kind weight-gradient kernel: 1 = 64 x 128 channels per block where Ci % 128 == 0 (default), 0 = 64 x 64
-    (bit-identical slabs); returns the previous value (-1: query only)"""
+    """test and tool hook: form of the split transposed-kind weight-gradient kernel - 1 = 64 x 128 channels per block where
+    Ci % 128 == 0 (default), 0 = 64 x 64 (bit-identical slabs); returns the previous value (-1: query only)"""
     return int(lib().te_wgrad_t2_wide(on))
 
 
 def wgrad_split(on=-1):
-    """switch of the split-bf16 weight-gradient kernel (csrc/wgrad6.hip): 0 / 1 sets it, returns the previous value (-1: query only)"""
+    """switch of the split-bf16 weight-gradient kernels (csrc/wgrad6.hip), initialised from TE_SPLIT_BF16 and written by
+    op/modconv.set_split_bf16: 0 / 1 sets it, returns the previous value (-1: query only).  The slab plan (wgrad_slabs) follows it, so
+    the weight gradient is fp32-equivalent but not bit-identical across its values."""
     return int(lib().te_wgrad_split_bf16(on))
 
 

@@ -839,7 +839,7 @@ __device__ __forceinline__ void pack_tiles(const PackJob& q, float* tile) {
                 const size_t ps = (size_t)T * MT * 512;
                 dst[at] = (unsigned short)h; dst[at + ps] = (unsigned short)mm; dst[at + 2 * ps] = (unsigned short)ll;
             }
-            if (t6) {      // TE_PACK_T6FWD / T6SWAP: the plain layout of the same weights behind the split one (thin fp32 regions of TE_CONV_T2S6)
+            if (t6) {      // TE_PACK_T6FWD / T6SWAP: the plain layout of the same weights behind the split one (edge kernel of TE_CONV_T2S6)
                 float* wp2 = q.wp + t6_plain_offset(q.K, q.M);
                 for (int e = threadIdx.x; e < NE; e += 256) {
                     if (fwd) {
@@ -1208,27 +1208,6 @@ static ConvPlan conv_plan(int kind, int B, int K, int M, int H, int W) {
     return pl;
 }
 
-// a non-blocking side stream + fork / join events per (host thread, device): the autograd engine's backward threads call the ABI
-// concurrently, each gets its own.  Created on first use, never destroyed (they live as long as the process).
-struct SideStream { hipStream_t stream; hipEvent_t fork, join; bool ok; };
-static SideStream* side_stream() {
-    static const bool enabled = getenv("TE_T2_SIDE_STREAM") && atoi(getenv("TE_T2_SIDE_STREAM")) != 0;      // OFF by default, see te_conv_res_f32
-    if (!enabled) return nullptr;
-    constexpr int MAXDEV = 16;
-    static thread_local SideStream tab[MAXDEV] = {};
-    static thread_local bool tried[MAXDEV] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
-    if (!tried[dev]) {
-        tried[dev] = true;
-        SideStream& t = tab[dev];
-        t.ok = hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&t.fork, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&t.join, hipEventDisableTiming) == hipSuccess;
-    }
-    return tab[dev].ok ? &tab[dev] : nullptr;
-}
-
 extern "C" int64_t te_conv_t2s6_ws_floats(int B, int K, int H) { return (B > 0 && K > 0 && H > 0) ? (int64_t)B * K * H : TE_ERR_SHAPE; }
 
 extern "C" int te_conv_splitk_count(int kind, int B, int K, int M, int H, int W) {
@@ -1255,53 +1234,19 @@ extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const flo
     if (kind == TE_CONV_3X3W) return te_wino_launch(out, in, wp, isc, osc, bias, res, mask_ref, mask_gain, act, B, K, M, H, W, s);
     if (kind == TE_CONV_3X3W6) return te_wino6_launch(out, in, wp, isc, osc, bias, res, mask_ref, mask_gain, act, B, K, M, H, W, s);
     if (kind == TE_CONV_S2S6) return te_s2s6_launch(out, in, wp, isc, osc, bias, res, mask_ref, mask_gain, act, B, K, M, H, W, s);
+    if (kind == TE_CONV_T2S6) {
+        // body cells on the bf16 pipe (t2s6.hip); the last output row and column (cells i = H, j = W) by t2_edge_kernel from the plain
+        // copy of the weights behind the split layout (TE_PACK_T6FWD / TE_PACK_T6SWAP).  `ws` (optional for this kind:
+        // te_conv_t2s6_ws_floats = B K H floats) takes the last input column from the body kernel to the edge kernel; without it the edge
+        // kernel gathers the column itself (one cache line per element: slower)
+        const int rc = te_t2s6_launch(out, in, wp, isc, osc, bias, act, B, K, M, H, W, s, ws);
+        if (rc) return rc;
+        return te_t2s6_edge_launch(out, in, wp + t6_plain_offset(K, M), isc, osc, bias, act, B, K, M, H, W, roundup(K, KPAD), roundup(M, MPAD),
+                                   s, ws);
+    }
     ConvArgs a{};
     a.out = out; a.ws = ws; a.in = in; a.wp = wp; a.isc = isc; a.osc = osc; a.bias = bias; a.res = res; a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
     a.B = B; a.K = K; a.M = M; a.Kp = roundup(K, KPAD); a.Mp = roundup(M, MPAD); a.H = H; a.W = W;
-    if (kind == TE_CONV_T2S6) {
-        // body cells on the bf16 pipe; the last output row and column (cells i = H, j = W) from the plain copy of the weights behind the
-        // split layout (TE_PACK_T6FWD / TE_PACK_T6SWAP): since round 6 by t2_edge_kernel (below); under TE_T2_EDGE=0 as two thin regions of
-        // the fp32 kernel, the round-5 path this comment describes.  The thin launch is a few dozen
-        // blocks that each walk the whole channel loop (130 - 150 us of latency for < 1 GFLOP: 28 % of a 128-channel launch,
-        // tools/block_overhead_probe.py); it writes other output pixels than the body, so it runs on a SIDE stream of this host thread,
-        // forked from and joined back into the caller's stream with events (also legal inside a stream capture), concurrently with
-        // the body kernel - OPT-IN (TE_T2_SIDE_STREAM=1).  Measured (round 5, same box, alternating runs): the launch alone gains 3 - 11 %
-        // (168 / 172 / 172 / 97 against 163 / 164 / 155 / 89 TFLOP/s at the four large shapes), the training iteration LOSES 2 % (118.5 /
-        // 119.6 against 121.4 / 122.1 img/s: three more runtime calls per launch on a host thread that is already the pacemaker of the
-        // short kernels around it).  Default: both launches on the caller's stream, one after the other.
-        a.wp = wp + t6_plain_offset(K, M);
-        a.ws = nullptr; a.ksplit = 1; a.kchunk = a.Kp;
-        a.Hi = H; a.Wi = W; a.Ho = 2 * H + 1; a.Wo = 2 * W + 1;
-        const int r[2][4] = {{0, W, H + 1, 1}, {H, 0, 1, W}};
-        const int tc = conv_plan(TE_CONV_T2, B, K, M, H, W).tc;
-        // Round 6: the two lines as ONE small vector-ALU launch (t2s6.hip, t2_edge_kernel: 15 - 30 us instead of 130 - 150); TE_T2_EDGE=0
-        // brings the thin regions of the fp32 kernel back (A/B measurements, tests).
-        static const bool edge_kernel = [] { const char* e = getenv("TE_T2_EDGE"); return !e || atoi(e) != 0; }();
-        if (edge_kernel) {
-            // `ws` (optional for this kind: te_conv_t2s6_ws_floats = B K H floats) takes the last input column from the body kernel
-            // to the edge kernel; without it the edge kernel gathers the column itself (one cache line per element: slower)
-            int rc = te_t2s6_launch(out, in, wp, isc, osc, bias, act, B, K, M, H, W, s, ws);
-            if (rc) return rc;
-            return te_t2s6_edge_launch(out, in, a.wp, isc, osc, bias, act, B, K, M, H, W, a.Kp, a.Mp, s, ws);
-        }
-        SideStream* side = side_stream();
-        int rc;
-        if (side && hipEventRecord(side->fork, s) == hipSuccess && hipStreamWaitEvent(side->stream, side->fork, 0) == hipSuccess) {
-            rc = launch_regions<TE_CONV_T2>(a, r, 2, side->stream, tc);
-            const hipError_t e1 = hipEventRecord(side->join, side->stream);
-            const int rc2 = te_t2s6_launch(out, in, wp, isc, osc, bias, act, B, K, M, H, W, s);
-            const hipError_t e2 = hipStreamWaitEvent(s, side->join, 0);       // (join even if a launch failed: the stream stays consistent)
-            if (rc) return rc;
-            if (rc2) return rc2;
-            if (e1 != hipSuccess || e2 != hipSuccess) return te::fail((int)(e1 != hipSuccess ? e1 : e2), "te_conv_f32(TE_CONV_T2S6): side-stream join failed");
-        } else {
-            rc = te_t2s6_launch(out, in, wp, isc, osc, bias, act, B, K, M, H, W, s);
-            if (rc) return rc;
-            rc = launch_regions<TE_CONV_T2>(a, r, 2, s, tc);
-            if (rc) return rc;
-        }
-        return te::launch_status("te_conv_f32(TE_CONV_T2S6)");
-    }
     const ConvPlan pl = conv_plan(kind, B, K, M, H, W);
     const int tc = pl.tc;
     a.ksplit = pl.ksplit; a.kchunk = pl.kchunk;

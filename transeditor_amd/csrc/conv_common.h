@@ -34,7 +34,7 @@ int te_wino6_launch(float* out, const float* in, const float* U, const float* is
 int te_s2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, const float* res,
                    const float* mask_ref, float mask_gain, int act, int B, int K, int M, int H, int W, hipStream_t s);
 // csrc/t2s6.hip: body cells of the transposed 3x3 / stride 2 convolution on the bf16 matrix pipe; kind TE_CONV_T2S6 (conv.hip adds the
-// last output row / column through the fp32 kernel), weights packed TE_PACK_T6FWD / TE_PACK_T6SWAP
+// last output row / column through te_t2s6_edge_launch), weights packed TE_PACK_T6FWD / TE_PACK_T6SWAP
 int te_t2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, int act,
                    int B, int K, int M, int H, int W, hipStream_t s, float* colbuf = nullptr);
 // ... and its last output row / column as one small vector-ALU launch (round 6; wplain = the Wp[tap][Kp][Mp] copy behind the split layout;

@@ -632,9 +632,8 @@ extern "C" int te_conv_s2s6_supported(int B, int K, int M, int H, int W) {
 
 // kernel form of TE_CONV_S2S6: 0 = ping-pong (s2s6_kernel, round 5); 1 (round 6, default) = the two-image form s2s6q_kernel where
 // M % 128 == 0 and the grid still gives every CU a block (it has half as many blocks), the ping-pong form elsewhere; 2 = the two-image
-// form wherever M % 128 == 0 (tests).  Same results bit for bit.  A process-wide A/B switch like te_conv_wino6_form (te_hip.h);
-// TE_S2S6_FORM in the environment sets the initial value.
-static std::atomic<int> g_s2_form{[] { const char* e = getenv("TE_S2S6_FORM"); return e ? atoi(e) : 1; }()};
+// form wherever M % 128 == 0 (tests).  Same results bit for bit.  A test and tool hook like te_conv_wino6_form (te_hip.h).
+static std::atomic<int> g_s2_form{1};
 extern "C" int te_conv_s2s6_form(int form) {
     const int old = g_s2_form.load(std::memory_order_relaxed);
     if (form >= 0 && form <= 2) g_s2_form.store(form, std::memory_order_relaxed);

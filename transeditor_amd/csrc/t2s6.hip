@@ -733,8 +733,8 @@ extern "C" int te_conv_t2s6_supported(int B, int K, int M, int H, int W) {
 
 // kernel form of TE_CONV_T2S6: 0 = ping-pong (t2s6_kernel); 1 = the two-image form t2s6q_kernel where M % 128 == 0 and the grid still
 // gives every CU a block, the ping-pong form elsewhere; 2 = the two-image form wherever M % 128 == 0 (tests).  Same results bit for bit.
-// A process-wide A/B switch like te_conv_wino6_form (te_hip.h); TE_T2S6_FORM in the environment sets the initial value.
-static std::atomic<int> g_t2_form{[] { const char* e = getenv("TE_T2S6_FORM"); return e ? atoi(e) : 1; }()};
+// A test and tool hook like te_conv_wino6_form (te_hip.h).
+static std::atomic<int> g_t2_form{1};
 extern "C" int te_conv_t2s6_form(int form) {
     const int old = g_t2_form.load(std::memory_order_relaxed);
     if (form >= 0 && form <= 2) g_t2_form.store(form, std::memory_order_relaxed);
@@ -742,7 +742,7 @@ extern "C" int te_conv_t2s6_form(int form) {
 }
 
 // the body cells [0, H) x [0, W) of the transposed convolution (output rows 0 .. 2H - 1, columns 0 .. 2W - 1); conv.hip adds the last
-// output row and column as two thin regions of the fp32 kernel
+// output row and column with te_t2s6_edge_launch (below)
 int te_t2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, int act,
                    int B, int K, int M, int H, int W, hipStream_t s, float* colbuf) {
     TE_REQUIRE(te_conv_t2s6_supported(B, K, M, H, W), TE_ERR_UNSUPPORTED,

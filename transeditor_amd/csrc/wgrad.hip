@@ -534,11 +534,8 @@ inline int pick_nwp(int Co, int Ci) { return (Co <= 64 && Ci <= 64) ? 2 : 4; }
 // The pair form (WINO) of the 3x3 kernel: 8-wave tile only (twelve accumulators plus the 4-wave tile's 34 staging registers do
 // not fit 256 VGPRs), stages of whole pair couples (a k-step = 4 cells).  Measured on the same box at the FFHQ-256 batch-16
 // shapes (profiles/experiments/r04_wgrad_pair_ab.log): 125.6 -> 153.4, 124.4 -> 158.4, 133.0 -> 171.4 TFLOP/s algorithmic,
-// same deviation from an fp64 reference (1.0e-6 vs 1.1e-6 relative).  TE_WGRAD_DIRECT=1 (read once) keeps the direct form, for A/B runs.
-inline bool pair_form_3x3(int Co, int Ci, int NC) {
-    static const bool direct = getenv("TE_WGRAD_DIRECT") && atoi(getenv("TE_WGRAD_DIRECT"));
-    return !direct && pick_nwp(Co, Ci) == 4 && NC % 4 == 0;
-}
+// same deviation from an fp64 reference (1.0e-6 vs 1.1e-6 relative).
+inline bool pair_form_3x3(int Co, int Ci, int NC) { return pick_nwp(Co, Ci) == 4 && NC % 4 == 0; }
 
 template <int KIND, int NWP, bool WINO>
 void launch_wgrad_t(const WgArgs& a, hipStream_t s) {

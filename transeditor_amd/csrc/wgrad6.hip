@@ -1003,18 +1003,8 @@ __global__ __launch_bounds__(WT, 1) void wgrad6p_kernel(const Wg6Args p) {
         }
 }
 
-// on by default; TE_SPLIT_WGRAD=0 (or TE_SPLIT_BF16=0, the switch of all split kernels) keeps the fp32 kernel - A/B measurements
-std::atomic<int> g_wg6_on{[] {
-    const char* e = getenv("TE_SPLIT_WGRAD");
-    if (e) return atoi(e) ? 1 : 0;
-    const char* a = getenv("TE_SPLIT_BF16");
-    return (a && atoi(a) == 0) ? 0 : 1;
-}()};
-
-// TE_SPLIT_WGRAD_T2=0: the transposed kind alone stays on the fp32 kernel (A/B measurements)
-std::atomic<int> g_wg6t_on{[] { const char* e = getenv("TE_SPLIT_WGRAD_T2"); return (e && atoi(e) == 0) ? 0 : 1; }()};
-// TE_SPLIT_WGRAD_1X1=0: the 1x1 kind alone stays on the fp32 kernel (A/B measurements)
-std::atomic<int> g_wg6p_on{[] { const char* e = getenv("TE_SPLIT_WGRAD_1X1"); return (e && atoi(e) == 0) ? 0 : 1; }()};
+// on by default; TE_SPLIT_BF16=0 (the switch of all split kernels) keeps the fp32 kernel
+std::atomic<int> g_wg6_on{[] { const char* e = getenv("TE_SPLIT_BF16"); return (e && atoi(e) == 0) ? 0 : 1; }()};
 
 }  // namespace
 
@@ -1032,8 +1022,8 @@ extern "C" int te_wgrad_split_bf16(int on) {
 }
 
 // form of the transposed-kind kernel: 1 (default) = the wide form (64 x 128 channels per block) where Ci % 128 == 0, 0 = 64 x 64 everywhere;
-// bit-identical slabs.  A process-wide A/B switch (te_hip.h); TE_WGRAD_T2_WIDE in the environment sets the initial value.
-static std::atomic<int> g_wg6t_wide{[] { const char* e = getenv("TE_WGRAD_T2_WIDE"); return e ? atoi(e) : 1; }()};
+// bit-identical slabs.  A test and tool hook (te_hip.h).
+static std::atomic<int> g_wg6t_wide{1};
 extern "C" int te_wgrad_t2_wide(int on) {
     const int old = g_wg6t_wide.load(std::memory_order_relaxed);
     if (on == 0 || on == 1) g_wg6t_wide.store(on, std::memory_order_relaxed);
@@ -1065,7 +1055,6 @@ int te_wgrad6_launch(float* slabs, const float* g, const float* x, int kind, int
     a.slabs = slabs; a.g = g; a.x = x; a.B = B; a.Co = Co; a.Ci = Ci; a.H = H; a.W = W; a.S = S; a.NB = NB; a.tiles_x = W / 32;
     dim3 grid((unsigned)(B / NB * S), (unsigned)te::cdiv(Co, TC), (unsigned)te::cdiv(Ci, TC));
     if (kind == TE_CONV_1X1) {
-        if (!g_wg6p_on.load(std::memory_order_relaxed)) return 0;
         if ((int64_t)NB * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW) return 0;           // 32-bit byte offsets inside a sample group
         static std::atomic<uint64_t> attr_done_p1{0};
         te::allow_big_lds(attr_done_p1, (const void*)wgrad6p_kernel, 160 * 1024);
@@ -1073,7 +1062,6 @@ int te_wgrad6_launch(float* slabs, const float* g, const float* x, int kind, int
         return 1;
     }
     if (kind == TE_CONV_T2) {
-        if (!g_wg6t_on.load(std::memory_order_relaxed)) return 0;
         // 32-bit byte offsets inside a sample group: lane * plane * 4 over the 64 channels of a tile, for the (2H+1) x (2W+1) tensor and
         // for the H x W one (the fp32 kernel takes the launch otherwise, as for the 3x3 kind below)
         if ((int64_t)NB * std::max(Co, Ci) * (2 * (int64_t)H + 1) * (2 * (int64_t)W + 1) * 4 >= (int64_t)OOBW) return 0;

@@ -18,13 +18,8 @@
 //   input    : d = style scale * in, t = B^T d (fp32, as in wino.hip), split, two channels packed per dword, written to
 //              T[piece][component][row][k half][pair][8 bf16]: a wave's B operand is one conflict-free ds_read_b128 per piece
 //   products : per (tap row, component): 3 + 3 operand reads, 6 MFMAs into the component's accumulator tile
-// Block: 512 threads, tile 64 output channels x 8 rows x 32 columns; wave (wm, wr) = 32 channels x rows {2 wr, 2 wr + 1} x 16 pairs x
-// 4 components (64 accumulator registers).  LDS: 72 KB of weights + 60 KB of transformed input per stage = one block per CU, two
-// waves per SIMD.  Epilogue = wino.hip's (output transform, demodulation scale, bias, leaky ReLU, residual, mask).
-// Measured (tools/wino6_check.py, batch 16): 225 / 248 / 261 / 265 TFLOP/s algorithmic at 128 -> 128 @256^2, 256 -> 256 @128^2,
-// 512 -> 512 @64^2 / @32^2 against 167 / 173 / 177 / 176 of wino.hip and 134 - 140 of the direct kernel on the same box; with the
-// staging compiled out the MFMA loop alone runs at 368: a stage's MFMAs and its staging do not overlap inside the one resident block
-// (variants that tried - per-tap-row weight DMA, smaller double-buffered tiles on paper - lost to barriers or L2 bandwidth).
+// Block: 512 threads, tile 64 output channels x 8 rows x 32 columns.  Epilogue = wino.hip's (output transform, demodulation scale, bias,
+// leaky ReLU, residual, mask).
 #include "conv_common.h"
 
 namespace {
@@ -36,18 +31,8 @@ typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-#ifndef W6_CG
-#define W6_CG 1          // components per MFMA group (1: a chain of six dependent MFMAs per group; 2: two accumulators alternate)
-#endif
-#ifndef W6_PIPE
-#define W6_PIPE 1        // read the operands of the next group before issuing the MFMAs of the current one
-#endif
-constexpr int WT = 512, KC = 16, TW = 32, NP = TW / 2, BM = 64, TH = 8, R = TH + 2;
+constexpr int WT = 512, KC = 16, TW = 32, NP = TW / 2, BM = 64, TH = 8;
 constexpr int U_CHUNKS = 36 * 2 * 64;                   // 16-byte chunks of a stage's weights: [piece 3][ky 3][c 4][mtile 2][64 lanes]
-constexpr int N_UC = U_CHUNKS / WT;                     // 9 per thread
-constexpr int T_DWORDS = 3 * 4 * R * 2 * NP * 4;        // [piece][c][row][k half][pair][4 dwords]
-constexpr int N_ITEMS = R * NP * 8;                     // (row, pair, channel pair) items of a stage: 1280
-constexpr int N_IN = (N_ITEMS + WT - 1) / WT;           // 3 per thread (the last one bounds-checked)
 
 struct Wino6Args {
     float* out; const float* in; const u32x4* U; const float* isc; const float* osc; const float* bias; const float* res;
@@ -56,243 +41,10 @@ struct Wino6Args {
     int lgpw;      // log2 of the column PAIRS one sample contributes to a tile row: 4 (W >= 32); 3 (W == 16: two samples side by side, round 6)
 };
 
-__device__ __forceinline__ unsigned bf16_rn(float x) {          // round to nearest even (finite inputs)
-    unsigned u = __builtin_bit_cast(unsigned, x);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-// x -> (h, m, l) as 16-bit patterns
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
-    h = bf16_rn(x);
-    const float r = x - __builtin_bit_cast(float, h << 16);
-    m = bf16_rn(r);
-    const float r2 = r - __builtin_bit_cast(float, m << 16);
-    l = bf16_rn(r2);
-}
-
-__global__ __launch_bounds__(WT, 2) void wino6_kernel(const Wino6Args p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    u32x4* ul = reinterpret_cast<u32x4*>(smem_raw);                                   // weights, 16-byte chunks
-    unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + U_CHUNKS * 16);             // transformed input, dwords
-    const u32x4* tl4 = reinterpret_cast<const u32x4*>(smem_raw + U_CHUNKS * 16);
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int wm = wid >> 2, wr = wid & 3;
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mb = jx % p.mblocks;
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
-    const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
-    const int x0 = tx * TW, y0 = ty * TH;
-    const float* inb = p.in + (size_t)b * p.K * p.H * p.W;
-    const float* iscb = p.isc ? p.isc + (size_t)b * p.K : nullptr;
-    const bool edge = (x0 == 0) || (x0 + TW == p.W) || (y0 == 0) || (y0 + TH == p.H);      // block-uniform
-
-    f32x16 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
-    // ---- staging geometry.  Input item e = tid + 512 i -> (pair jj = e % 16, channel pair q = (e / 16) % 8, row = e / 128)
-    // Edge tiles read the same four floats per item from an address moved INSIDE the row / image (one float right at the left image
-    // border, one left at the right border, the nearest valid row above / below) and patch the vector afterwards: no per-element
-    // branches, same number of loads as the interior path.  e_flag: bit 0 left, bit 1 right, bit 2 row outside.
-    int g_off[N_IN], l_off[N_IN], e_flag[N_IN];
-#pragma unroll
-    for (int i = 0; i < N_IN; ++i) {
-        const int e = tid + WT * i;
-        const int jj = e & 15, q = (e >> 4) & 7, row = e >> 7;
-        const int gy = y0 - 1 + row;
-        const bool left = x0 == 0 && jj == 0, right = x0 + TW == p.W && jj == NP - 1, rowout = gy < 0 || gy >= p.H;
-        e_flag[i] = (left ? 1 : 0) | (right ? 2 : 0) | (rowout ? 4 : 0);
-        const int gyc = gy < 0 ? 0 : (gy >= p.H ? p.H - 1 : gy);
-        g_off[i] = (2 * q * p.H + gyc) * p.W + x0 + 2 * jj - 1 + (left ? 1 : 0) - (right ? 1 : 0);
-        l_off[i] = e < N_ITEMS ? ((row * 2 + (q >> 2)) * NP + jj) * 4 + (q & 3) : -1;     // + ((piece * 4 + c) * R) * 2 * NP * 4
-    }
-    const size_t plane = (size_t)p.H * p.W;
-    const int MT = p.M >> 5;
-    f32x4 rin[N_IN][2];
-    float rsc[N_IN][2];
-    const int nstage = p.K / KC;
-    auto issue = [&](int s) {
-        const float* base = inb + (size_t)s * KC * plane;
-#pragma unroll
-        for (int i = 0; i < N_IN; ++i) {
-            if (l_off[i] < 0) continue;
-            const int e = tid + WT * i, q = (e >> 4) & 7;
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                rsc[i][h2] = iscb ? iscb[s * KC + 2 * q + h2] : 1.f;
-                const float* src = base + g_off[i] + h2 * plane;
-                rin[i][h2] = *reinterpret_cast<const f32x4u*>(src);      // (edge tiles: patched in scale(), when the load has landed)
-            }
-        }
-    };
-    // weights: chunk idx = tid + 512 r -> slot idx / 64 = (piece, ky, c, mtile), lane idx % 64; copied global -> LDS by the LDS-DMA path
-    // (global_load_lds_dwordx4: a wave's 64 lanes land on 64 consecutive 16-byte chunks = one fragment slot; no staging registers, no
-    // ds_write pass).  Issued when the MFMAs of a stage are done, in flight under the transform / split of the input tile.
-    auto issue_u = [&](int s) {
-        const u32x4* us = p.U + (size_t)s * 36 * MT * 64;
-#pragma unroll
-        for (int r = 0; r < N_UC; ++r) {
-            const int idx = tid + WT * r, slot = idx >> 6;
-            const u32x4* g = us + ((size_t)(slot >> 1) * MT + 2 * mb + (slot & 1)) * 64 + (idx & 63);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                             (__attribute__((address_space(3))) void*)(ul + (idx & ~63)), 16, 0, 0);
-        }
-    };
-    // commit in two halves around the weight DMA: `scale` consumes the loaded registers (the only wait on the vector-memory counter,
-    // taken while no DMA is in flight - with one in flight the compiler would wait for IT at the first use of a loaded value),
-    // `commit` transforms, splits and writes the input tile while the DMA runs
-    f32x4 dv[N_IN][2];
-    auto scale = [&]() {
-#pragma unroll
-        for (int i = 0; i < N_IN; ++i) {
-            if (l_off[i] < 0) continue;
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                f32x4 v = rin[i][h2];
-                if (edge) {
-                    const int f = e_flag[i];
-                    if (f & 1) { v[3] = v[2]; v[2] = v[1]; v[1] = v[0]; v[0] = 0.f; }        // loaded from column 0: element 0 is column -1
-                    if (f & 2) { v[0] = v[1]; v[1] = v[2]; v[2] = v[3]; v[3] = 0.f; }        // loaded one column early: element 3 is column W
-                    if (f & 4) { v[0] = 0.f; v[1] = 0.f; v[2] = 0.f; v[3] = 0.f; }
-                }
-                dv[i][h2] = v * rsc[i][h2];
-            }
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int i = 0; i < N_IN; ++i) {
-            if (l_off[i] < 0) continue;
-            const f32x4 e = dv[i][0], o = dv[i][1];                               // even / odd channel of the pair
-            const f32x2 t[4] = {{e[0] - e[2], o[0] - o[2]}, {e[1] + e[2], o[1] + o[2]}, {e[2] - e[1], o[2] - o[1]}, {e[1] - e[3], o[1] - o[3]}};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                // three-piece split of the channel pair: v_cvt_pk_bf16_f32 packs (even, odd) into one dword = the LDS element
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t[c], bf16x2));
-                const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xFFFF0000u)};
-                const f32x2 r1 = t[c] - hf;
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, bf16x2));
-                const f32x2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xFFFF0000u)};
-                const f32x2 r2 = r1 - mf;
-                const unsigned l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
-                tl[l_off[i] + (0 * 4 + c) * (R * 2 * NP * 4)] = h;
-                tl[l_off[i] + (1 * 4 + c) * (R * 2 * NP * 4)] = m;
-                tl[l_off[i] + (2 * 4 + c) * (R * 2 * NP * 4)] = l;
-            }
-        }
-    };
-    const int rr = l31 >> 4, jj = l31 & 15;
-    const int b_chunk = ((2 * wr + rr) * 2 + half) * NP + jj;          // + ((piece * 4 + c) * R + ky) * 2 * NP       (16-byte chunks)
-    const int a_chunk = wm * 64 + lane;                                 // + ((piece * 3 + ky) * 4 + c) * 128
-
-    issue(0);
-    scale();
-    __builtin_amdgcn_sched_barrier(0);
-    issue_u(0);
-    __builtin_amdgcn_sched_barrier(0);
-    commit();
-    __syncthreads();
-    for (int s = 0; s < nstage; ++s) {
-        if (s + 1 < nstage) issue(s + 1);
-#ifndef W6_SKIP_MFMA
-        {
-            // groups of CG components of one tap row: 3 + 3 operand reads and 6 MFMAs per component.  W6_PIPE: the operands of group
-            // g + 1 are read before the MFMAs of group g are issued; CG = 2 alternates two accumulators (no back-to-back dependent MFMAs)
-            constexpr int CG = W6_CG, NG = 12 / CG;
-            bf16x8 av[2][CG][3], bv[2][CG][3];
-            auto rd = [&](int g, int slot) {
-                const int ky = g / (4 / CG), c0 = (g % (4 / CG)) * CG;
-#pragma unroll
-                for (int cc = 0; cc < CG; ++cc)
-#pragma unroll
-                    for (int pc = 0; pc < 3; ++pc) {
-                        av[slot][cc][pc] = __builtin_bit_cast(bf16x8, ul[a_chunk + ((pc * 3 + ky) * 4 + c0 + cc) * 128]);
-                        bv[slot][cc][pc] = __builtin_bit_cast(bf16x8, tl4[b_chunk + ((pc * 4 + c0 + cc) * R + ky) * 2 * NP]);
-                    }
-            };
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
-            if (W6_PIPE) rd(0, 0);
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                const int slot = W6_PIPE ? (g & 1) : 0, c0 = (g % (4 / CG)) * CG;
-                if (W6_PIPE) { if (g + 1 < NG) rd(g + 1, (g + 1) & 1); }
-                else rd(g, 0);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-#pragma unroll
-                    for (int cc = 0; cc < CG; ++cc)
-                        acc[c0 + cc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][cc][PA[q]], bv[slot][cc][PB[q]], acc[c0 + cc], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#endif
-        __syncthreads();
-#ifndef W6_SKIP_COMMIT
-        if (s + 1 < nstage) {
-            scale();
-            __builtin_amdgcn_sched_barrier(0);
-            issue_u(s + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            commit();
-        }
-#endif
-        __syncthreads();
-    }
-    // epilogue: output transform (two adjacent columns per accumulator element), then the direct kernel's epilogue stages
-    const int mbase = mb * BM + wm * 32;
-    const size_t off0 = ((size_t)b * p.M + mbase) * plane + (size_t)(y0 + 2 * wr + rr) * p.W + x0 + 2 * jj;
-    const float g_pos = p.act == 3 ? 1.4142135623730951f : 1.f;
-    // (the 16 demodulation scales / biases of this lane are loaded up front: inside the store loop every load would wait behind the
-    //  previous row's store - the compiler cannot prove `out` does not alias them - i.e. 16 serialized L2 round trips per block)
-    float scv[16], biv[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = mbase + (r & 3) + 8 * (r >> 2) + 4 * half;
-        scv[r] = p.osc ? p.osc[(size_t)b * p.M + m] : 1.f;
-        biv[r] = p.bias ? p.bias[m] : 0.f;
-    }
-    f32x2 resv[16], mrefv[16];                      // likewise the residual / mask rows of the discriminator's launches
-    if (p.res) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            resv[r] = *reinterpret_cast<const f32x2*>(p.res + off0 + (size_t)((r & 3) + 8 * (r >> 2) + 4 * half) * plane);
-    }
-    if (p.mref) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            mrefv[r] = *reinterpret_cast<const f32x2*>(p.mref + off0 + (size_t)((r & 3) + 8 * (r >> 2) + 4 * half) * plane);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int dm = (r & 3) + 8 * (r >> 2) + 4 * half;
-        float v0 = acc[0][r] + acc[1][r] + acc[2][r];
-        float v1 = acc[1][r] - acc[2][r] - acc[3][r];
-        const float sc = scv[r], bi = biv[r];
-        v0 = v0 * sc + bi;
-        v1 = v1 * sc + bi;
-        if (p.act >= 3) {
-            v0 = (v0 > 0.f ? v0 : v0 * 0.2f) * g_pos;
-            v1 = (v1 > 0.f ? v1 : v1 * 0.2f) * g_pos;
-        }
-        const size_t o = off0 + (size_t)dm * plane;
-        if (p.res) { v0 += resv[r][0]; v1 += resv[r][1]; }
-        if (p.mref) {
-            v0 *= mrefv[r][0] > 0.f ? p.mgain : 0.2f * p.mgain;
-            v1 *= mrefv[r][1] > 0.f ? p.mgain : 0.2f * p.mgain;
-        }
-        f32x2 v; v[0] = v0; v[1] = v1;
-        *reinterpret_cast<f32x2*>(p.out + o) = v;
-    }
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Round 5: the PING-PONG form of the same kernel (wino6p_kernel).  wino6_kernel above alternates "all eight waves multiply" and "all
-// eight waves stage" between two block-wide barriers, so the matrix pipe idles while the next stage is transformed, split and written
-// (measured: 36 % of the kernel).  Double-buffering the whole stage does not fit (2 x 132 KB), so the tile is cut the other way:
+// Round 5: the PING-PONG form (wino6p_kernel).  The round-4 form alternated "all eight waves multiply" and "all eight waves stage"
+// between two block-wide barriers, so the matrix pipe idled while the next stage was transformed, split and written (measured: 36 % of
+// the kernel).  Double-buffering the whole stage does not fit (2 x 132 KB), so the tile is cut the other way:
 //
 //   * the 8-row tile is two HALF tiles of 4 rows (6 input rows each, 36 KB of transformed pieces per half: T0, T1); the weights of a
 //     stage (72 KB) stay ONE image shared by both halves: 144 KB of LDS;
@@ -310,7 +62,7 @@ __global__ __launch_bounds__(WT, 2) void wino6_kernel(const Wino6Args p) {
 //     barrier of X(s), behind which group 0 starts to read it.  Four barriers per stage (mid-X, end-X, mid-Y, end-Y), each of them a
 //     point where the multiplying wave has its operands for the next six MFMAs in registers already;
 //   * the mid-phase barrier sits in front of group 5's MFMAs (whose operands were read before it) and in front of the first Ub read.
-// Same arithmetic, same packed weights, same epilogue and the same supported shapes as wino6_kernel; TE_W6_FORM=0 selects the old form.
+// Same arithmetic, same packed weights and same epilogue as the round-4 form.
 constexpr int PH = 4, PR = PH + 2;
 constexpr int TP_PLANE = PR * 2 * NP * 4;                 // dwords of one (piece, component) plane of a half tile
 constexpr int TP_DWORDS = 12 * TP_PLANE;                  // 9 216 dwords = 36 KB
@@ -621,7 +373,7 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
         d[7] = ((unsigned long long)nstage << 48) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFFFull);
     }
 #endif
-    // epilogue: as wino6_kernel (output transform, demodulation scale, bias, leaky ReLU, residual, mask); group 0 is here one phase early
+    // epilogue: as wino.hip (output transform, demodulation scale, bias, leaky ReLU, residual, mask); group 0 is here one phase early
     const int wr = grp * 2 + wrl;
     const int mbase = mb * BM + wm * 32;
     const int bo = b + (jj >> p.lgpw);                                  // this lane's output sample
@@ -687,7 +439,7 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
 //     M0: 72 MFMAs + the fetch of stage s + 1 (consumed one multiplying phase later)    SA: weight DMA only
 //     M1: 72 MFMAs + the staging arithmetic (rin -> res) behind them                       SB: weight DMA + res -> T_g(s + 1)
 // Both groups run the SAME straight-line loop body (M0 SA M1 SB), group 1 one staging phase late: no role branch around the MFMA streams, two
-// copies of the stream (one per accumulator set).  Same products in the same order per output element as wino6p / wino6: bit-identical.
+// copies of the stream (one per accumulator set).  Same products in the same order per output element as wino6p: bit-identical.
 template <bool ISC>
 __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -909,7 +661,7 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
         ph += 4;
     }
 
-    // epilogue: as wino6_kernel, once per accumulator set
+    // epilogue: as wino6p_kernel, once per accumulator set
     const int wr = grp * 2 + wrl;
     const float g_pos = p.act == 3 ? 1.4142135623730951f : 1.f;
 #pragma unroll
@@ -960,15 +712,15 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
 
 }  // namespace
 
-// kernel form of TE_CONV_3X3W6: 1 = ping-pong (wino6p_kernel, round 5, default), 0 = block-phase (wino6_kernel, round 4); same results
-// bit for bit (same products, same accumulation order per output element).  TE_W6_FORM in the environment sets the initial value.
-// 2 (round 6, default) = the two-image form wino6q_kernel where M % 128 == 0 and the grid still gives every CU a block (it has half
-// as many blocks as the ping-pong form: measured slower on small grids, e.g. 39 against 22 us at 3 x 64 -> 256 @16x64), the ping-pong
-// form elsewhere; 3 = the two-image form wherever M % 128 == 0 (tests).
-static std::atomic<int> g_w6_form{[] { const char* e = getenv("TE_W6_FORM"); return e ? atoi(e) : 2; }()};
+// kernel form of TE_CONV_3X3W6, a test and tool hook (te_hip.h): 1 = ping-pong (wino6p_kernel, round 5); 2 (round 6, default) = the
+// two-image form wino6q_kernel where M % 128 == 0 and the grid still gives every CU a block (it has half as many blocks as the ping-pong
+// form: measured slower on small grids, e.g. 39 against 22 us at 3 x 64 -> 256 @16x64), the ping-pong form elsewhere; 3 = the two-image
+// form wherever M % 128 == 0 (tests).  All forms give the same results bit for bit (same products, same accumulation order per output
+// element).
+static std::atomic<int> g_w6_form{2};
 extern "C" int te_conv_wino6_form(int form) {
     const int old = g_w6_form.load(std::memory_order_relaxed);
-    if (form >= 0 && form <= 3) g_w6_form.store(form, std::memory_order_relaxed);
+    if (form >= 1 && form <= 3) g_w6_form.store(form, std::memory_order_relaxed);
     return old;
 }
 
@@ -1021,7 +773,7 @@ int te_wino6_launch(float* out, const float* in, const float* U, const float* is
             te::allow_big_lds(attr_done_q, (const void*)wino6q_kernel<false>, 160 * 1024);
             wino6q_kernel<false><<<dim3((unsigned)blocks2), WT, lds, s>>>(a);
         }
-    } else if (form >= 1 || W < TW) {          // (the side-by-side form of 16-column images exists in the ping-pong / two-image kernels only)
+    } else {
         const size_t lds = (size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4;
         static std::atomic<uint64_t> attr_done_p{0}, attr_done_ps{0};
         if (isc) {
@@ -1031,11 +783,6 @@ int te_wino6_launch(float* out, const float* in, const float* U, const float* is
             te::allow_big_lds(attr_done_p, (const void*)wino6p_kernel<false>, 160 * 1024);
             wino6p_kernel<false><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
         }
-    } else {
-        const size_t lds = (size_t)U_CHUNKS * 16 + (size_t)T_DWORDS * 4;
-        static std::atomic<uint64_t> attr_done{0};
-        te::allow_big_lds(attr_done, (const void*)wino6_kernel, 160 * 1024);
-        wino6_kernel<<<dim3((unsigned)blocks), WT, lds, s>>>(a);
     }
     return te::launch_status("te_conv_f32(TE_CONV_3X3W6)");
 }

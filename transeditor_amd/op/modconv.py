@@ -321,8 +321,9 @@ def _bwd_pack_kind(kind):
 
 
 # 3x3 / stride 1 launches that the 1-D Winograd F(2,3) kernel covers (csrc/wino.hip: >= 32x32 images, K % 8 == 0, M % 128 == 0 - the
-# launches that carry the FLOPs of both networks) use it: same result to fp32 round-off, 2/3 of the MFMAs.  The choice is a pure
-# function of the problem shape, so the forward (which packs the data-gradient layout ahead) and the backward agree on it.
+# launches that carry the FLOPs of both networks) use it: same result to fp32 round-off, 2/3 of the MFMAs.  A forward that packs the
+# data-gradient layout ahead also keeps the convolution kind it was packed for, and the backward launches that kind: the module flags
+# below may change in between without a layout reaching a kernel that reads another.
 USE_WINOGRAD = True      # False: the direct kernel everywhere (A/B measurements)
 # the Winograd form on the bf16 matrix pipe (TE_CONV_3X3W6: three-piece split, fp32-equivalent results) where it applies;
 # TE_SPLIT_BF16=0 (or False here): fp32 matrix instructions everywhere (A/B measurements)
@@ -332,7 +333,7 @@ USE_SPLIT_BF16 = os.environ.get('TE_SPLIT_BF16', '1') != '0'
 def fwd_kinds(kind, B, w, H, W):
     """(weight pack kind, convolution kind code) of the forward launch; H, W = low-resolution size"""
     if kind == '3x3' and USE_WINOGRAD:
-        if USE_SPLIT_BF16 and (W >= 32 or USE_SPLIT_W16) and _lib.wino6_ok(B, w.shape[1], w.shape[0], H, W):
+        if USE_SPLIT_BF16 and _lib.wino6_ok(B, w.shape[1], w.shape[0], H, W):
             return _lib.PACK_W6FWD, _lib.CONV_3X3W6
         if _lib.wino_ok(B, w.shape[1], w.shape[0], H, W):
             return _lib.PACK_WFWD, _lib.CONV_3X3W
@@ -357,8 +358,6 @@ def plain_1x1_kinds(B, w, H, W, dgrad=False):
     return (_lib.PACK_DGRAD if dgrad else _lib.PACK_FWD), _lib.CONV_1X1
 
 
-# TE_SPLIT_W16=0: the 16-column 3x3 launches (two samples side by side in a tile row of the split Winograd kernel, round 6) stay on the fp32 kernel (A/B)
-USE_SPLIT_W16 = os.environ.get('TE_SPLIT_W16', '1') != '0'
 # TE_SPLIT_S2=0: the stride-2 launches stay on the fp32 matrix instructions while the 3x3 stride-1 ones keep the split form (A/B)
 USE_SPLIT_S2 = os.environ.get('TE_SPLIT_S2', '1') != '0'
 USE_SPLIT_T2 = os.environ.get('TE_SPLIT_T2', '1') != '0'
@@ -367,7 +366,7 @@ USE_SPLIT_T2 = os.environ.get('TE_SPLIT_T2', '1') != '0'
 def bwd_kinds(kind, B, w, H, W):
     """the same for the data gradient (a convolution from Co to Ci channels)"""
     if kind == '3x3' and USE_WINOGRAD:
-        if USE_SPLIT_BF16 and (W >= 32 or USE_SPLIT_W16) and _lib.wino6_ok(B, w.shape[0], w.shape[1], H, W):
+        if USE_SPLIT_BF16 and _lib.wino6_ok(B, w.shape[0], w.shape[1], H, W):
             return _lib.PACK_W6DGRAD, _lib.CONV_3X3W6
         if _lib.wino_ok(B, w.shape[0], w.shape[1], H, W):
             return _lib.PACK_WDGRAD, _lib.CONV_3X3W
@@ -380,12 +379,14 @@ def bwd_kinds(kind, B, w, H, W):
 
 
 def _fwd_raw(x, w, kind, isc=None, osc=None, bias=None, act=0, wscale=1.0, with_bwd_pack=False):
-    """with_bwd_pack: also return the data-gradient packing of w (one launch packs both layouts)."""
+    """with_bwd_pack: also return (the data-gradient packing of w, the convolution kind it is packed for) - one launch packs both
+    layouts; _dgrad_raw(wp=...) launches that kind."""
     H, W = _lowres_hw(kind, False, x)
     pk, ck = fwd_kinds(kind, x.shape[0], w, H, W)
     if with_bwd_pack:
-        wp, wpb = packed2(w, pk, bwd_kinds(kind, x.shape[0], w, H, W)[0], wscale)
-        return _lib.conv(x, wp, ck, w.shape[0], H, W, isc, osc, bias, act), wpb
+        pkb, ckb = bwd_kinds(kind, x.shape[0], w, H, W)
+        wp, wpb = packed2(w, pk, pkb, wscale)
+        return _lib.conv(x, wp, ck, w.shape[0], H, W, isc, osc, bias, act), (wpb, ckb)
     if _STATE.pack_cache is not None and torch.is_grad_enabled() is False:
         # (a no-grad forward inside a training loop: the same weights meet a backward later in the iteration)
         wp, _ = packed2(w, pk, bwd_kinds(kind, x.shape[0], w, H, W)[0], wscale)
@@ -396,11 +397,14 @@ def _fwd_raw(x, w, kind, isc=None, osc=None, bias=None, act=0, wscale=1.0, with_
 
 def _dgrad_raw(g, w, kind, isc=None, osc=None, wscale=1.0, wp=None):
     """data gradient: g is shaped like the conv OUTPUT; returns a tensor shaped like the conv input.
-    isc scales the channels of g ([B,Co]), osc the channels of the result ([B,Ci]).  wp: w already packed for it."""
+    isc scales the channels of g ([B,Co]), osc the channels of the result ([B,Ci]).  wp: (w already packed for it, convolution kind)
+    as _fwd_raw(with_bwd_pack=True) returned them; None plans both now."""
     H, W = _lowres_hw(kind, True, g)
-    pk, ck = bwd_kinds(kind, g.shape[0], w, H, W)          # ('up': the strided kind is its adjoint; 'down': the transposed one)
     if wp is None:
+        pk, ck = bwd_kinds(kind, g.shape[0], w, H, W)      # ('up': the strided kind is its adjoint; 'down': the transposed one)
         wp = packed(w, pk, wscale)
+    else:
+        wp, ck = wp
     return _lib.conv(g, wp, ck, w.shape[1], H, W, isc, osc)
 
 
@@ -492,11 +496,10 @@ class _ConvWgrad(Function):
 def set_split_bf16(on):
     """ONE switch for every split-bf16 kernel: the convolution kinds (gated here, by USE_SPLIT_BF16) and the weight-gradient kernels
     (gated in the library, te_wgrad_split_bf16).  Assigning `modconv.USE_SPLIT_BF16 = x` does the same (module property below), so an
-    A/B that flips the Python flag can no longer leave the weight gradient on the other arithmetic.  TE_SPLIT_WGRAD=0 in the
-    environment keeps the weight gradient alone on the fp32 kernels."""
+    A/B that flips the Python flag can no longer leave the weight gradient on the other arithmetic."""
     on = bool(on)
     globals()['USE_SPLIT_BF16'] = on
-    _lib.wgrad_split(1 if (on and os.environ.get('TE_SPLIT_WGRAD', '1') != '0') else 0)
+    _lib.wgrad_split(int(on))
     return on
 
 
@@ -680,7 +683,7 @@ class _ModConvFused(Function):
             ctx.act, ctx.kind, ctx.wscale = act, kind, wscale
             return out
         ctx.wp_bwd = None
-        if ctx.needs_input_grad[0]:         # a backward will want dx: pack the data-gradient layout in the same launch
+        if ctx.needs_input_grad[0]:         # a backward will want dx: pack the data-gradient layout in the same launch (+ its kind)
             out, ctx.wp_bwd = _fwd_raw(x, w, kind, isc, osc, bias, _act_code(act), wscale, with_bwd_pack=True)
         else:
             out = _fwd_raw(x, w, kind, isc, osc, bias, _act_code(act), wscale)

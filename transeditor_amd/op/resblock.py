@@ -61,12 +61,15 @@ class _ResBlock(Function):
             need_x = need[0] or need[14] or need[15]          # the block's input gradient feeds dimg, dw0, db0
         front = need_x or need[1] or need[2]                  # anything upstream of the blur wants a gradient
         H, W = x.shape[2], x.shape[3]
-        # conv1 (+ its data-gradient packing when dx will be asked for)
+        # conv1 (+ its data-gradient packing when dx will be asked for).  Each data gradient's convolution kind is decided here, once,
+        # and kept with its packed weights: the backward launches it without asking the planners again (op/modconv.py)
         pk1, ck1 = fwd_kinds('3x3', x.shape[0], w1, H, W)       # (the Winograd form where it applies: op/modconv.py)
         if need_x:
-            wp1, wp1b = packed2(w1, pk1, bwd_kinds('3x3', x.shape[0], w1, H, W)[0], s1)
+            pk1b, ck1b = bwd_kinds('3x3', x.shape[0], w1, H, W)
+            wp1, wp1b = packed2(w1, pk1, pk1b, s1)
+            bwd1 = (wp1b, ck1b)
         else:
-            wp1, wp1b = packed(w1, pk1, s1), None
+            wp1, bwd1 = packed(w1, pk1, s1), None
         y1 = _lib.conv(x, wp1, ck1, w1.shape[0], H, W, None, None, b1, 3)
         pm = (pad_main[0], pad_main[1], pad_main[0], pad_main[1])
         yb = _lib.upfirdn2d_raw(y1, k_main, (1, 1), (1, 1), pm)
@@ -75,9 +78,11 @@ class _ResBlock(Function):
         h, w_ = (yb.shape[2] - 1) // 2, (yb.shape[3] - 1) // 2
         pk2, ck2 = fwd_kinds('down', x.shape[0], w2, h, w_)     # (the split-bf16 form of the strided convolution where it applies)
         if front:
-            wp2, wp2b = packed2(w2, pk2, bwd_kinds('down', x.shape[0], w2, h, w_)[0], s2)     # (the layout _dgrad_raw's launch will ask for)
+            pk2b, ck2b = bwd_kinds('down', x.shape[0], w2, h, w_)
+            wp2, wp2b = packed2(w2, pk2, pk2b, s2)
+            bwd2 = (wp2b, ck2b)
         else:
-            wp2, wp2b = packed(w2, pk2, s2), None
+            wp2, bwd2 = packed(w2, pk2, s2), None
         act2 = 3 if abs(_SQRT2 * gain - _SQRT2) < 1e-6 else 4
         if act2 == 4 and abs(_SQRT2 * gain - 1.0) > 1e-6:
             raise RuntimeError(f'resblock: leaky-ReLU gain {_SQRT2 * gain} is not one the kernels fuse (sqrt(2) or 1)')
@@ -90,12 +95,14 @@ class _ResBlock(Function):
         # of csrc/p1s6.hip where it applies (round 6)
         pks, cks = plain_1x1_kinds(x.shape[0], ws, xs.shape[2], xs.shape[3])
         if need_x:
-            wps, wpsb = packed2(ws, pks, plain_1x1_kinds(x.shape[0], ws, xs.shape[2], xs.shape[3], dgrad=True)[0], ss * gain)
+            pksb, cksb = plain_1x1_kinds(x.shape[0], ws, xs.shape[2], xs.shape[3], dgrad=True)
+            wps, wpsb = packed2(ws, pks, pksb, ss * gain)
+            bwds = (wpsb, cksb)
         else:
-            wps, wpsb = packed(ws, pks, ss * gain), None
+            wps, bwds = packed(ws, pks, ss * gain), None
         out = _lib.conv(xs, wps, cks, ws.shape[0], xs.shape[2], xs.shape[3], None, None, None, 0, res=y2)
         ctx.save_for_backward(x, w1, b1, w2, b2, ws, k_main, k_skip, y1, yb, y2, xs, img, w0, b0)
-        ctx.packs = (wp1b, wp2b, wpsb)
+        ctx.packs = (bwd1, bwd2, bwds)
         ctx.cfg = (s1, s2, ss, tuple(pad_main), tuple(pad_skip), gain, pm, ps, s0, need_x)
         return out
 
@@ -121,7 +128,7 @@ class _ResBlock(Function):
             first = tuple(next(gs) if n else None for n in need[:6])
             tail = (next(gs) if need[14] else None, next(gs) if need[15] else None) if ctx.stem else (None, None)
             return first + (None,) * 8 + tail + (None,)
-        wp1b, wp2b, wpsb = ctx.packs
+        bwd1, bwd2, bwds = ctx.packs
         g = g.contiguous()
         front = need_x or need[1] or need[2]
         gx = gw1 = gb1 = gw2 = gb2 = gws = None
@@ -131,7 +138,7 @@ class _ResBlock(Function):
             gw2 = _wgrad_plain(g2, yb, 'down', 3, s2)
         g1 = None
         if front:
-            g_yb = _dgrad_raw(g2, w2, 'down', wscale=s2, wp=wp2b)
+            g_yb = _dgrad_raw(g2, w2, 'down', wscale=s2, wp=bwd2)
             _, g_pad = _geometry(y1.shape[2:], k_main.shape, (1, 1), (1, 1), pm)
             if tuple(k_main.shape) == (4, 4) and g_yb.shape[3] >= 4:
                 # adjoint blur with conv1's leaky-ReLU gradient in the epilogue + bias-gradient partials: one pass
@@ -148,13 +155,13 @@ class _ResBlock(Function):
             gws = _wgrad_plain(g, xs, '1x1', 1, ss * gain)
         gw0 = gb0 = None
         if need_x:
-            g_xs = _lib.conv(g, wpsb, plain_1x1_kinds(x.shape[0], ws, xs.shape[2], xs.shape[3], dgrad=True)[1], ws.shape[1],
-                             xs.shape[2], xs.shape[3])
+            (wpsb, cksb), (wp1b, ck1b) = bwds, bwd1
+            g_xs = _lib.conv(g, wpsb, cksb, ws.shape[1], xs.shape[2], xs.shape[3])
             _, gp_s = _geometry(x.shape[2:], k_skip.shape, (1, 1), (2, 2), ps)
             gx_b = _lib.upfirdn2d_raw(g_xs, flipped_taps(k_skip), (2, 2), (1, 1), gp_s)
             # data gradient of conv1 + the skip branch's gradient in its epilogue (+ the stem's activation gradient)
-            gx = _lib.conv(g1, wp1b, bwd_kinds('3x3', x.shape[0], w1, x.shape[2], x.shape[3])[1], w1.shape[1], x.shape[2], x.shape[3],
-                           None, None, None, 0, res=gx_b, mask_ref=x if ctx.stem else None, mask_gain=_SQRT2)
+            gx = _lib.conv(g1, wp1b, ck1b, w1.shape[1], x.shape[2], x.shape[3], None, None, None, 0, res=gx_b,
+                           mask_ref=x if ctx.stem else None, mask_gain=_SQRT2)
         if ctx.stem:
             gpre, gx = gx, None                               # gradient w.r.t. the stem's pre-activation
             M = w0.shape[0]

@@ -36,7 +36,7 @@ class _ModConvRGB(Function):
         w3 = w.reshape(w.shape[0], w.shape[1], -1)
         d, wsq = _lib.demod_fwd(w3, s, wscale, eps)
         keep_cache(ctx)
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0]:         # (wp_bwd: packed weights and convolution kind of the data gradient, decided here)
             a, wp_bwd = _fwd_raw(x, w, '3x3', s, d, bias, 3, wscale, with_bwd_pack=True)
         else:
             a, wp_bwd = _fwd_raw(x, w, '3x3', s, d, bias, 3, wscale), None
