@@ -292,6 +292,11 @@ int te_wgrad_split_bf16(int on);
  * H x W one where Ci % 128 == 0 (half the staging work and re-reads of the big tensor per MFMA), 0: 64 x 64 everywhere.  Bit-identical
  * slabs; returns the previous value, any other argument only queries.  A test and tool hook (see the conventions above). */
 int te_wgrad_t2_wide(int on);
+/* Kernel that te_wgrad_f32 (NB = 1) / te_wgrad_group_f32 (NB samples per slab) run for this problem under the current switches, for
+ * 16-byte aligned g and x (misaligned operands take the fp32 kernel): TE_WG6_FP32 (the fp32 kernel) or one of the split forms.  The
+ * launch dispatches on this function; a host query for tests. */
+enum { TE_WG6_FP32 = 0, TE_WG6_3X3 = 1, TE_WG6_3X3_PAIR = 2, TE_WG6_T2_WIDE = 3, TE_WG6_T2 = 4, TE_WG6_T2_MASKED = 5, TE_WG6_1X1 = 6 };
+int te_wgrad6_form(int kind, int B, int Co, int Ci, int H, int W, int NB);
 int te_wgrad_f32(float* slabs, const float* g, const float* x, int kind, int B, int Co, int Ci, int H,
                  int W, int S, te_stream_t stream);
 /* GROUPED form for the PLAIN (unmodulated) weight gradient of small images: NB consecutive samples share one slab

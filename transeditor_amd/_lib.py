@@ -55,6 +55,7 @@ _SIGNATURES = {
     'te_wgrad_split_supported': (C.c_int, [_I, _I, _I, _I, _I]),
     'te_wgrad_split_bf16': (C.c_int, [_I]),
     'te_wgrad_t2_wide': (C.c_int, [_I]),
+    'te_wgrad6_form': (C.c_int, [_I, _I, _I, _I, _I, _I, _I]),
     'te_wgrad_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'te_wgrad_group_plan': (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P]),
     'te_wgrad_group_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
@@ -401,10 +402,23 @@ def conv_out_shape(kind, B, M, H, W):
     return (B, M, H, W)
 
 
+def _aligned16(t):
+    """t, or a fresh (16-byte aligned) copy of it when its data is not: a contiguous view at an offset into its storage keeps
+    that offset through .contiguous()"""
+    if t is None or t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, mask_ref=None, mask_gain=1.0):
     """H, W = LOW-resolution size (see te_hip.h).  x [B,K,Hin,Win].  res: residual added after the activation; mask_ref:
-    leaky-ReLU gradient mask (saved output of the layer this data gradient lands on) applied last."""
+    leaky-ReLU gradient mask (saved output of the layer this data gradient lands on) applied last.  The kinds that read
+    residual / mask (and TE_CONV_1X1S6 its input) with 16-byte accesses get aligned copies of misaligned operands."""
     x = x.contiguous()
+    if kind == CONV_1X1S6:
+        x = _aligned16(x)
+    res = _aligned16(res.contiguous()) if res is not None else None
+    mask_ref = _aligned16(mask_ref.contiguous()) if mask_ref is not None else None
     B, K = x.shape[0], x.shape[1]
     out = torch.empty(conv_out_shape(kind, B, M, H, W), device=x.device, dtype=x.dtype)
     if res is not None and tuple(res.shape) != tuple(out.shape):
@@ -419,8 +433,7 @@ def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, m
     if kind == CONV_T2S6:          # scratch for the last input column (body kernel -> edge kernel; te_hip.h)
         ws = torch.empty(B * K * H, device=x.device, dtype=x.dtype)
     _check(lib().te_conv_res_f32(_ptr(out), _ptr(ws), _ptr(x), _ptr(wp), _ptr(isc), _ptr(osc), _ptr(bias),
-                                 _ptr(res.contiguous()) if res is not None else None,
-                                 _ptr(mask_ref.contiguous()) if mask_ref is not None else None, mask_gain, act, kind, B, K, M, H, W,
+                                 _ptr(res), _ptr(mask_ref), mask_gain, act, kind, B, K, M, H, W,
                                  _stream()),
            'te_conv_res_f32')
     return out
@@ -464,6 +477,14 @@ def wgrad_split(on=-1):
 def wgrad_split_ok(kind, Co, Ci, H, W):
     """does the split-bf16 weight-gradient kernel cover this problem?  (taken only while wgrad_split() is on)"""
     return bool(lib().te_wgrad_split_supported(kind, Co, Ci, H, W))
+
+
+WGRAD6_FORMS = ('fp32', 'w6', 'w6pair', 't2wide', 't2narrow', 't2masked', 'p1')      # te_wgrad6_form codes (te_hip.h)
+
+
+def wgrad6_form(kind, B, Co, Ci, H, W, NB=1):
+    """name of the kernel wgrad_slabs runs for this problem (16-byte aligned operands; NB samples per slab), see WGRAD6_FORMS"""
+    return WGRAD6_FORMS[lib().te_wgrad6_form(kind, B, Co, Ci, H, W, NB)]
 
 
 def wgrad_pair_form(kind, Co, Ci, H, W):

@@ -1046,54 +1046,72 @@ extern "C" int te_wgrad_split_supported(int kind, int Co, int Ci, int H, int W) 
     return 0;
 }
 
+// which kernel te_wgrad_f32 / te_wgrad_group_f32 run for this problem (16-byte aligned operands; misaligned ones take the fp32 kernel):
+// the one decision te_wgrad6_launch dispatches on, and a host query for tests (te_hip.h)
+extern "C" int te_wgrad6_form(int kind, int B, int Co, int Ci, int H, int W, int NB) {
+    if (B <= 0 || NB <= 0 || W <= 0) return TE_WG6_FP32;
+    const int sup = te_wgrad_split_supported(kind, Co, Ci, H, W);
+    if (!g_wg6_on.load(std::memory_order_relaxed) || !sup) return TE_WG6_FP32;
+    if (kind == TE_CONV_1X1)             // 32-bit byte offsets inside a sample group
+        return (int64_t)NB * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW ? TE_WG6_FP32 : TE_WG6_1X1;
+    if (kind == TE_CONV_T2) {
+        // 32-bit byte offsets inside a sample group: lane * plane * 4 over the 64 channels of a tile, for the (2H+1) x (2W+1) tensor and
+        // for the H x W one (the fp32 kernel takes the launch otherwise, as for the 3x3 kind below)
+        if ((int64_t)NB * std::max(Co, Ci) * (2 * (int64_t)H + 1) * (2 * (int64_t)W + 1) * 4 >= (int64_t)OOBW) return TE_WG6_FP32;
+        if (Co % TC == 0 && Ci % (2 * TC) == 0 && g_wg6t_wide.load(std::memory_order_relaxed)) return TE_WG6_T2_WIDE;
+        return (Co % TC == 0 && Ci % TC == 0) ? TE_WG6_T2 : TE_WG6_T2_MASKED;
+    }
+    if (sup == 2) {                      // sample-pair form
+        if (NB != 1 || B % 2 != 0) return TE_WG6_FP32;
+        return (int64_t)2 * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW ? TE_WG6_FP32 : TE_WG6_3X3_PAIR;
+    }
+    return (int64_t)NB * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW ? TE_WG6_FP32 : TE_WG6_3X3;
+}
+
 // returns 1 when the launch was taken, 0 when the caller has to use the fp32 kernel, < 0 on error
 int te_wgrad6_launch(float* slabs, const float* g, const float* x, int kind, int B, int Co, int Ci, int H, int W, int S, int NB, hipStream_t s) {
-    const int sup = te_wgrad_split_supported(kind, Co, Ci, H, W);
-    if (!g_wg6_on.load(std::memory_order_relaxed) || !sup) return 0;
+    const int form = te_wgrad6_form(kind, B, Co, Ci, H, W, NB);
+    if (form == TE_WG6_FP32) return 0;
     if (((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x)) & 15) != 0) return 0;
     Wg6Args a{};
     a.slabs = slabs; a.g = g; a.x = x; a.B = B; a.Co = Co; a.Ci = Ci; a.H = H; a.W = W; a.S = S; a.NB = NB; a.tiles_x = W / 32;
     dim3 grid((unsigned)(B / NB * S), (unsigned)te::cdiv(Co, TC), (unsigned)te::cdiv(Ci, TC));
-    if (kind == TE_CONV_1X1) {
-        if ((int64_t)NB * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW) return 0;           // 32-bit byte offsets inside a sample group
-        static std::atomic<uint64_t> attr_done_p1{0};
-        te::allow_big_lds(attr_done_p1, (const void*)wgrad6p_kernel, 160 * 1024);
-        wgrad6p_kernel<<<dim3(grid.x, (unsigned)(Co / (2 * TC)), (unsigned)(Ci / (2 * TC))), WT, (size_t)8 * PI * 16, s>>>(a);
-        return 1;
-    }
-    if (kind == TE_CONV_T2) {
-        // 32-bit byte offsets inside a sample group: lane * plane * 4 over the 64 channels of a tile, for the (2H+1) x (2W+1) tensor and
-        // for the H x W one (the fp32 kernel takes the launch otherwise, as for the 3x3 kind below)
-        if ((int64_t)NB * std::max(Co, Ci) * (2 * (int64_t)H + 1) * (2 * (int64_t)W + 1) * 4 >= (int64_t)OOBW) return 0;
-        const size_t lds = (size_t)(NGR * GI + 2 * XI) * 16;
-        if (Co % TC == 0 && Ci % (2 * TC) == 0 && g_wg6t_wide.load(std::memory_order_relaxed)) {      // wide form: 64 x 128 channels per block
+    switch (form) {
+        case TE_WG6_1X1: {
+            static std::atomic<uint64_t> attr_done_p1{0};
+            te::allow_big_lds(attr_done_p1, (const void*)wgrad6p_kernel, 160 * 1024);
+            wgrad6p_kernel<<<dim3(grid.x, (unsigned)(Co / (2 * TC)), (unsigned)(Ci / (2 * TC))), WT, (size_t)8 * PI * 16, s>>>(a);
+            return 1;
+        }
+        case TE_WG6_T2_WIDE: {           // wide form: 64 x 128 channels per block
             static std::atomic<uint64_t> attr_done_tw{0};
             te::allow_big_lds(attr_done_tw, (const void*)wgrad6tw_kernel, 160 * 1024);
             wgrad6tw_kernel<<<dim3(grid.x, grid.y, (unsigned)(Ci / (2 * TC))), WT, (size_t)(NGR * GI + 4 * XI) * 16, s>>>(a);
             return 1;
         }
-        if (Co % TC == 0 && Ci % TC == 0) {
+        case TE_WG6_T2: {
             static std::atomic<uint64_t> attr_done_t{0};
             te::allow_big_lds(attr_done_t, (const void*)wgrad6t_kernel<false>, 160 * 1024);
-            wgrad6t_kernel<false><<<grid, WT, lds, s>>>(a);
-        } else {
+            wgrad6t_kernel<false><<<grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s>>>(a);
+            return 1;
+        }
+        case TE_WG6_T2_MASKED: {
             static std::atomic<uint64_t> attr_done_tn{0};
             te::allow_big_lds(attr_done_tn, (const void*)wgrad6t_kernel<true>, 160 * 1024);
-            wgrad6t_kernel<true><<<grid, WT, lds, s>>>(a);
+            wgrad6t_kernel<true><<<grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s>>>(a);
+            return 1;
         }
-        return 1;
+        case TE_WG6_3X3_PAIR: {
+            static std::atomic<uint64_t> attr_done_p{0};
+            te::allow_big_lds(attr_done_p, (const void*)wgrad6_kernel<true>, 160 * 1024);
+            wgrad6_kernel<true><<<dim3((unsigned)(B / 2 * S), 1, 1), WT, (size_t)N_IMG * IMG * 16, s>>>(a);
+            return 1;
+        }
+        default: {
+            static std::atomic<uint64_t> attr_done{0};
+            te::allow_big_lds(attr_done, (const void*)wgrad6_kernel<false>, 160 * 1024);
+            wgrad6_kernel<false><<<grid, WT, (size_t)N_IMG * IMG * 16, s>>>(a);
+            return 1;
+        }
     }
-    if (sup == 2) {                                       // sample-pair form
-        if (NB != 1 || B % 2 != 0) return 0;
-        if ((int64_t)2 * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW) return 0;
-        static std::atomic<uint64_t> attr_done_p{0};
-        te::allow_big_lds(attr_done_p, (const void*)wgrad6_kernel<true>, 160 * 1024);
-        wgrad6_kernel<true><<<dim3((unsigned)(B / 2 * S), 1, 1), WT, (size_t)N_IMG * IMG * 16, s>>>(a);
-        return 1;
-    }
-    if ((int64_t)NB * std::max(Co, Ci) * H * W * 4 >= (int64_t)OOBW) return 0;
-    static std::atomic<uint64_t> attr_done{0};
-    te::allow_big_lds(attr_done, (const void*)wgrad6_kernel<false>, 160 * 1024);
-    wgrad6_kernel<false><<<grid, WT, (size_t)N_IMG * IMG * 16, s>>>(a);
-    return 1;
 }

@@ -528,11 +528,28 @@ def _nonzero(s):
     sum_p x U to fp32 accuracy instead of 0 / garbage (the former guard, 1.2e-38, let s U flush to zero), and the outputs move by less
     than 1e-20 |x w| - far below half an ulp of anything they are added to.  Both scales are guarded (the demodulation coefficient
     is rsqrt(... + 1e-8) > 0 in the model, but modconv_closed takes any osc).  What the division form cannot remove: under
-    create_graph, d(dP/ds)/ds is two terms of size |dP/ds| / |s| that cancel analytically; their round-off, ~6e-8 |dP/ds| / |s|, is
-    what a channel with a small style scale adds to a second-order gradient (pinned second-order parity: tests/test_gpu_timed_second_order.py)."""
+    create_graph, d(dP/ds)/ds is two terms of size |dP/ds| / |s| that cancel analytically; their round-off, up to ~1e-6 |dP/ds| / |s|
+    (each term carries the round-off of a pixel reduction: 8e-7 measured at a floored scale; at |s| = 1e-3 the error stays below
+    1e-4 of the gradient on every op route), is what a channel with a small style
+    scale adds to a second-order gradient (pinned second-order parity: tests/test_gpu_timed_second_order.py).
+    The move is invisible to autograd (identity derivative, _Floor), so FIRST derivatives at a floored scale - an exact zero
+    included - are the ones at the scale itself.  Second derivatives with respect to a floored scale carry no meaning: the round-off
+    above is then ~1e-6 |dP/ds| / 1e-20, finite but arbitrary (every other first and second derivative is unaffected; checked in
+    tests/test_gpu_conv_routes.py).  Only the chan_scale composite (USE_CLOSED_MODCONV off) differentiates twice through a zero scale."""
     if s is None:
         return None
-    return torch.where(s.abs() < _SCALE_FLOOR, torch.where(s < 0, -_SCALE_FLOOR, _SCALE_FLOOR).to(s.dtype), s)
+    return _Floor.apply(s)
+
+
+class _Floor(Function):
+    """_nonzero's move of tiny scales, with the identity as its derivative (a torch.where would send no gradient to them)"""
+    @staticmethod
+    def forward(ctx, s):
+        return torch.where(s.abs() < _SCALE_FLOOR, torch.where(s < 0, -_SCALE_FLOOR, _SCALE_FLOOR).to(s.dtype), s)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
 
 
 def _rgb_ok(w, d, x_like, kind):
