@@ -1,6 +1,6 @@
 """Benchmark of the TransEditor hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 16 --warmup 5
+    python bench.py --gpus 1 --steps 16 --warmup 5 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,10 @@ cadence exactly; other K over-represent them, never under-represent).  With N > 
 scaling, data parallel) and every backward ends in the bucketed gradient all-reduce over RCCL/xGMI.  Rank 0 prints
 ONE JSON line.
 
+A plain run does only what its headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line.  `--full` adds the legs marked [full] below, each in runs of its own after the timed steps (off by default; the
+--no-cpu-baseline / --no-sub / --no-pmc switches drop single legs of a --full run).
+
 Objects in the JSON beside the driver contract:
   roofline      the MFMA convolution launches (forward / data-gradient / weight-gradient of every 3x3 kind, G and D) in the timed
                 region, timed live with HIP events on the launch stream.  `frac` = executed matrix-pipe work / peak, per pipe:
@@ -20,17 +24,21 @@ Objects in the JSON beside the driver contract:
                 bf16-pipe-equivalent TFLOP/s); `dominant_kernel` = the split-bf16 Winograd kernel alone against the bf16 peak;
                 `achieved_algorithmic` = algorithmic FLOPs / time (round 4's "frac" divided this by the fp32 peak: kept as
                 `algorithmic_vs_fp32_peak`); `whole_step_frac` = frac x the share of the wall-clock step those launches take.
-                `traffic`, `mfma_util_pct`, `mhz` and `counters` come from rocprofv3 --pmc passes spawned by THIS run after the
-                timed region (N = 1; `traffic_source` "live", or "static" = the committed summary if the passes could not run).
+                [full] `traffic`, `mfma_util_pct`, `mhz` and `counters` come from rocprofv3 --pmc passes spawned by THIS run after
+                the timed region (N = 1; `traffic_source` "live"); otherwise, or if the passes could not run, `traffic` is the
+                committed summary's, `traffic_source` "static".
   substeps      HIP-event time of each sub-step (D / R1 / G / path) and the cadence-weighted ms per iteration.
-  sub_benchmarks  (N = 1) configs[1] generator fwd+bwd at batch 16 and configs[4] FFHQ-1024 generator fwd+bwd at
+  sub_benchmarks  [full] (N = 1) configs[1] generator fwd+bwd at batch 16 and configs[4] FFHQ-1024 generator fwd+bwd at
                 batch 4, each with its own value and roofline.
-  cpu_baseline  (N = 1) the CPU oracle (oracle/te_oracle.py, a port of the reference's algorithm) running the same
+  cpu_baseline  [full] (N = 1) the CPU oracle (oracle/te_oracle.py, a port of the reference's algorithm) running the same
                 training iteration on this box's host cores on a bounded sample.
-  comm          (N > 1) backend, bytes all-reduced per iteration, isolated per-bucket all-reduce time, the exposed
-                communication time (step with exchange - step without) and a bit-identity check of the averaged grads.
+  comm          (N > 1) backend, library versions and devices found by the preflight; [full] bytes all-reduced per iteration,
+                isolated per-bucket all-reduce time, the exposed communication time (step with exchange - step without) and a
+                bit-identity check of the averaged grads.
 
-`--workload generator` runs only configs[1] (or `--size 1024 --batch 4`: configs[4]) as the headline line.
+`--workload generator` runs only configs[1] (or `--size 1024 --batch 4`: configs[4]) as the headline line ([full]: with counters
+and its CPU baseline).  `--workload sample` times the cache + hipGraph sampling path ([full]: also the training-path forward and
+the cache alone).
 `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (train: the loss dictionary and the
 updated G / D / EMA weights; generator: the image and the parameter gradients; sample: the images), for output-for-output
 comparison of two builds on identical inputs.
@@ -98,11 +106,15 @@ def parse():
                     help='train = BASELINE configs[2]/[3], the full G+D iteration (default, = the metric); '
                          'generator = configs[1] / configs[4] generator fwd+bwd only; sample = the inference-only pipeline '
                          '(frozen g_ema sampling loop, test_spatial_query.py:20-31)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure what it does not need, each in runs of its own: the sub-benchmarks, '
+                         'the live counter passes, the CPU baseline (N = 1), the communication evidence (N > 1) and the other '
+                         'sampling paths (--workload sample)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--no-sub', action='store_true', help='skip the sub-benchmarks (configs[1], configs[4])')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the live rocprofv3 --pmc passes (roofline.traffic falls back to '
-                                                          'the committed summary, labelled static)')
+    ap.add_argument('--no-sub', action='store_true', help='with --full: skip the sub-benchmarks (configs[1], configs[4])')
+    ap.add_argument('--no-pmc', action='store_true', help='with --full: skip the live rocprofv3 --pmc passes (roofline.traffic '
+                                                          'falls back to the committed summary, labelled static)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy '
                          '(float32 / float64, at most 64 MB in all; larger outputs as a fixed, seeded sample of their elements)')
@@ -110,6 +122,17 @@ def parse():
     if args.steps < 1:
         ap.error('--steps must be at least 1')
     return args
+
+
+def extra_legs(args, world, dist_on):
+    """what this run measures beside its headline, after the timed steps and in runs of its own: nothing without --full;
+    with it every leg that applies to the workload and world size and that no --no-* option switches off"""
+    full, train = args.full, args.workload == 'train'
+    return {'sub_benchmarks': full and train and world == 1 and not args.no_sub,
+            'counters': full and world == 1 and args.workload != 'sample',      # (live unless --no-pmc)
+            'cpu_baseline': full and world == 1 and args.workload != 'sample' and not args.no_cpu_baseline,
+            'comm': full and train and dist_on,
+            'sampling_paths': full and args.workload == 'sample'}
 
 
 DUMP_LIMIT_BYTES = 60 << 20          # array data; with the .npy headers the files stay under 64 MB
@@ -647,10 +670,10 @@ def run_generator(size, B, steps, warmup, dev, world, rank, timer, G=None, outpu
     return elapsed, roof
 
 
-def run_sampling(args, size, B, dev, base):
+def run_sampling(args, size, B, dev, base, paths):
     """(f.3) the reference's sample_generation loop (test_spatial_query.py:20-31): a frozen generator under no_grad,
-    fixed batch, fresh latents every iteration.  Three ways: the training-path forward, the frozen-weight cache, and the
-    cache + hipGraph replay (inference.GeneratorSampler)."""
+    fixed batch, fresh latents every iteration.  The headline is the frozen-weight cache + hipGraph replay
+    (inference.GeneratorSampler); with `paths` (--full) the training-path forward and the cache alone are timed before it."""
     from transeditor_amd.inference import GeneratorSampler
     from transeditor_amd.model_spatial_query import Generator
     token = 2 * (int(math.log2(size)) - 1)
@@ -673,21 +696,21 @@ def run_sampling(args, size, B, dev, base):
     def plain(z, q):
         with torch.no_grad():
             return G(z, q)
-    t_plain, _ = timed(plain)
-    t_cache, _ = timed(GeneratorSampler(G, use_graph=False))
-    t_graph, last = timed(GeneratorSampler(G, use_graph=True))
+    secs = {}                                                      # (the line's order: training path, cache, graph)
+    if paths:
+        secs['training_path'], _ = timed(plain)
+        secs['cache'], _ = timed(GeneratorSampler(G, use_graph=False))
+    secs['graph'], last = timed(GeneratorSampler(G, use_graph=True))
     if args.dump_outputs:                                          # the headline is the graph replay: what its last call returned
         last = last if isinstance(last, (tuple, list)) else (last,)
         dump_outputs(args.dump_outputs, {'image' if i == 0 else f'output{i}': t for i, t in enumerate(last) if torch.is_tensor(t)})
+    rate = {'training_path': 'training_path_forward_img_s', 'cache': 'frozen_weight_cache_img_s', 'graph': 'cache_plus_hipgraph_img_s'}
     out = dict(base, metric=f'{size}x{size} images/sec/GPU, frozen generator sampling loop (inference-only pipeline)',
-               value=B * args.steps / t_graph, ms_per_step=1e3 * t_graph / args.steps,
+               value=B * args.steps / secs['graph'], ms_per_step=1e3 * secs['graph'] / args.steps,
                config={'workload': f'FFHQ-{size} g_ema sampling loop (test_spatial_query.py:20-31), batch {B}, no_grad, '
                                    f'{args.steps} batches = {B * args.steps} samples', 'global_batch': B, 'parallelism': 'dp1'},
-               sampling={'training_path_forward_img_s': B * args.steps / t_plain,
-                         'frozen_weight_cache_img_s': B * args.steps / t_cache,
-                         'cache_plus_hipgraph_img_s': B * args.steps / t_graph,
-                         'ms_per_batch': {'training_path': 1e3 * t_plain / args.steps, 'cache': 1e3 * t_cache / args.steps,
-                                          'graph': 1e3 * t_graph / args.steps}})
+               sampling={**{rate[k]: B * args.steps / v for k, v in secs.items()},
+                         'ms_per_batch': {k: 1e3 * v / args.steps for k, v in secs.items()}})
     out['detail'] = write_detail(out)
     line = json.loads(compact_line(out))
     line['sampling'] = {k: _num(v) for k, v in out['sampling'].items() if not isinstance(v, dict)}
@@ -878,6 +901,7 @@ def main():
         backend = 'gloo' if share else 'nccl'                       # "nccl" == RCCL on ROCm
         comm_info, watchdog = comm_preflight(args, backend, world, rank, local_rank, dev)
     assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}'
+    legs = extra_legs(args, world, dist_on)
 
     size = args.size
     B = args.batch if args.batch is not None else (4 if size >= 1024 else 16)
@@ -888,7 +912,7 @@ def main():
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic'}
 
     if args.workload == 'sample':
-        run_sampling(args, size, B if args.batch is not None else 8, dev, base)
+        run_sampling(args, size, B if args.batch is not None else 8, dev, base, legs['sampling_paths'])
         return
 
     if args.workload == 'generator':
@@ -907,10 +931,10 @@ def main():
                                **_arithmetic_switches()})
             if roof:
                 out['roofline'] = roof
-                if world == 1:
+                if legs['counters']:
                     torch.cuda.synchronize()
                     attach_counters(roof, live=not args.no_pmc)
-            if world == 1 and not args.no_cpu_baseline:
+            if legs['cpu_baseline']:
                 out['cpu_baseline'] = cpu_baseline_generator(size)
         final_line(out if rank == 0 else None, rank, world, dist_on)
         if dist_on:
@@ -972,7 +996,9 @@ def main():
     if cw:
         out['substeps']['cadence_weighted_images_per_sec_per_gpu'] = 1e3 * B / cw
 
-    if dist_on:
+    if dist_on and not legs['comm']:
+        out['comm'] = comm_info                                    # (what the preflight found; the measurements need --full)
+    if legs['comm']:
         # ---- comm evidence, outside the timed region
         import torch.distributed as dist
         ts.g_step()                                                # leaves averaged G grads in place
@@ -1008,7 +1034,7 @@ def main():
         if not chk['identical_across_ranks'] and rank == 0:       # reported in the line itself; never lose the measurement over it
             print(f'WARNING: averaged gradients differ across ranks: {chk}', file=sys.stderr, flush=True)
 
-    if world == 1 and rank == 0 and not args.no_sub:
+    if rank == 0 and legs['sub_benchmarks']:
         # ---- named sub-benchmarks: configs[1] (the generator of the train step, same weights) and configs[4]
         sub = {}
         el, roof = run_generator(size, B, 10, 3, dev, 1, 0, timer, G=ts.generator)
@@ -1025,10 +1051,10 @@ def main():
                 'config': 'BASELINE configs[4]: FFHQ-1024 generator fwd+bwd, batch 4, 4 warm-up + 10 timed steps',
                 'value': 4 * 10 / el, 'unit': 'images/sec', 'ms_per_step': 1e3 * el / 10, 'roofline': _slim(roof)}
         out['sub_benchmarks'] = sub
-    if world == 1 and rank == 0 and 'roofline' in out:
+    if rank == 0 and legs['counters'] and 'roofline' in out:
         torch.cuda.synchronize()
         attach_counters(out['roofline'], live=not args.no_pmc)       # counters of THIS run, outside the timed region
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and legs['cpu_baseline']:
         out['cpu_baseline'] = cpu_baseline_train(size)
     final_line(out, rank, world, dist_on)
     if dist_on:
