@@ -1,0 +1,106 @@
+"""Compare the gfx950 machine code of the split-bf16 kernels between two source trees (a refactor's "same code" check; no GPU needed).
+
+    python tools/isa_compare.py PARENT_TREE BRANCH_TREE [-o profiles/NAME.txt] [--keep DIR]
+
+Both trees are compiled with build.py's flags plus --save-temps; for every kernel of wino6 / s2s6 / t2s6 / p1s6 / wgrad6 the table gives
+registers, scratch, LDS, occupancy, instruction counts by class (parent | branch) and whether the instruction streams are identical after
+dropping comments, directives and the function number inside local labels.  Exit status 1 if any kernel differs.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from transeditor_amd.build import EXTRA_FLAGS, FLAGS, _hipcc  # noqa: E402
+
+FILES = ['wino6', 's2s6', 't2s6', 'p1s6', 'wgrad6']
+RES = [('VGPR', r'; NumVgprs: (\d+)'), ('AGPR', r'; NumAgprs: (\d+)'), ('SGPR', r'; TotalNumSgprs: (\d+)'),
+       ('scratch', r'; ScratchSize: (\d+)'), ('LDS', r'; LDSByteSize: (\d+)'), ('occ', r'; Occupancy: (\d+)')]
+CLASSES = [('MFMA', r'v_mfma'), ('ds_read', r'ds_read|ds_load'), ('ds_write', r'ds_write|ds_store'), ('gload_lds', r'global_load_lds|buffer_load.* lds'),
+           ('gload', r'(global|buffer)_load'), ('gstore', r'(global|buffer)_store'), ('VALU', r'v_'), ('s_waitcnt', r's_waitcnt'),
+           ('s_barrier', r's_barrier')]
+
+
+def compile_tree(tree, out):
+    os.makedirs(out, exist_ok=True)
+    procs = []
+    for f in FILES:
+        src = os.path.join(os.path.abspath(tree), 'transeditor_amd', 'csrc', f + '.hip')
+        cmd = [_hipcc(), *FLAGS, *EXTRA_FLAGS.get(f + '.hip', []), '--save-temps', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', f + '.o']
+        procs.append((f, subprocess.Popen(cmd, cwd=out, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+    for f, p in procs:
+        log, _ = p.communicate()
+        if p.returncode != 0:
+            raise RuntimeError(f'hipcc failed on {tree}/{f}.hip:\n{log.decode()}')
+
+
+def kernels(out):
+    """{demangled-ish kernel name: (resources, instruction list)} of every kernel in the device assembly of a compiled tree."""
+    found = {}
+    for f in FILES:
+        text = open(os.path.join(out, f + '-hip-amdgcn-amd-amdhsa-gfx950.s')).read()
+        for m in re.finditer(r'^(_Z\w+):.*?^\.Lfunc_end\d+:(.*?^; Occupancy: \d+)', text, re.S | re.M):
+            name = subprocess.check_output(['c++filt', m.group(1)]).decode().strip()
+            name = re.sub(r'\(anonymous namespace\)::|\(.*\)$|^void ', '', name)
+            ins = []
+            for line in m.group(0).split('\n')[1:]:
+                line = line.split(';')[0].strip()
+                if not line or line.startswith('.') and not line.endswith(':'):
+                    continue
+                ins.append(re.sub(r'\.L(BB|func_end)\d+', r'.L\1', re.sub(r'\s+', ' ', line)))
+            res = {k: int(re.search(pat, m.group(2)).group(1)) for k, pat in RES}
+            found[f + ': ' + name] = (res, ins)
+    return found
+
+
+def classify(ins):
+    counts = {k: 0 for k, _ in CLASSES}
+    for line in ins:
+        for k, pat in CLASSES:
+            if re.match(pat, line):
+                counts[k] += 1
+                break
+    return counts
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('parent')
+    ap.add_argument('branch')
+    ap.add_argument('-o', '--output')
+    ap.add_argument('--keep', help='directory for the compiler outputs (default: a temporary one)')
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        base = a.keep or tmp
+        sides = []
+        for tag, tree in (('parent', a.parent), ('branch', a.branch)):
+            compile_tree(tree, os.path.join(base, tag))
+            sides.append(kernels(os.path.join(base, tag)))
+    par, br = sides
+    lines = ['machine code of the split-bf16 kernels, parent | branch (build.py flags + --save-temps, gfx950)', '']
+    ndiff = 0
+    for name in sorted(set(par) | set(br)):
+        if name not in par or name not in br:
+            lines.append(f'{name}: only in {"parent" if name in par else "branch"}')
+            ndiff += 1
+            continue
+        (rp, ip), (rb, ib) = par[name], br[name]
+        cp, cb = classify(ip), classify(ib)
+        same = ip == ib
+        ndiff += not same or rp != rb
+        lines.append(f'{name}: instruction stream {"IDENTICAL" if same else "DIFFERS"} ({len(ip)} | {len(ib)} lines)')
+        lines.append('    ' + '  '.join(f'{k} {rp[k]}|{rb[k]}' for k, _ in RES) + ('' if rp == rb else '   <-- RESOURCES DIFFER'))
+        lines.append('    ' + '  '.join(f'{k} {cp[k]}|{cb[k]}' for k, _ in CLASSES))
+    lines += ['', f'{len(par)} kernels in the parent, {len(br)} in the branch, {ndiff} differ']
+    text = '\n'.join(lines) + '\n'
+    sys.stdout.write(text)
+    if a.output:
+        open(a.output, 'w').write(text)
+    return 1 if ndiff else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -28,16 +28,9 @@
 //           half wave); the item's four pixels end up as four whole 16-byte LDS elements per piece (ds_write_b128: 12 writes per stage).
 //           Pixel 4 q + e of the half tile lives at position 32 e + q, so the 32 lanes of a write fill 512 contiguous bytes, and a wave's two
 //           B fragments (positions 64 wn + 32 n + lane) are the ADJACENT pixels 4 lane + 2 wn + n: one 8-byte store per accumulator row.
-#include "conv_common.h"
+#include "split6_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WT = 512, GT = 256, KS = 64, NKS = 4, BM = 64, TPX = 256, HPX = 128;
 constexpr int U_SLOTS = NKS * 3 * 2;                     // 24 fragment slots of 1 KB per weight image; two images in LDS
@@ -49,9 +42,6 @@ struct P1Args {
     int B, K, M, HW, ntiles, mblocks, tiles_per_sample, nt8;
 };
 
-__device__ __forceinline__ void p1_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void p1_wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* ul = reinterpret_cast<u32x4*>(smem_raw);                                   // weight image, 16-byte chunks
@@ -59,10 +49,8 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wn = wq & 1, gt = tid & (GT - 1);
     u32x4* tl = reinterpret_cast<u32x4*>(smem_raw + 2 * U_SLOTS * 1024) + grp * T_CHUNKS;   // this group's half tile
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mbq = jx % p.mblocks;
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mbq;
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mbq)) return;
     const int b = tile / p.tiles_per_sample, p0 = (tile - b * p.tiles_per_sample) * TPX + HPX * grp;    // first pixel of this group's half
     const size_t plane = (size_t)p.HW;
     const float* inb = p.in + (size_t)b * p.K * plane;
@@ -105,28 +93,7 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
     auto arith = [&](int k) {
         if (k < 0 || k >= N_SLOT) return;
         const int u = k >> 2, j = k & 3, cp = u >> 2, e = u & 3;
-        if (j == 0) {
-            te = rin[2 * cp][e]; to = rin[2 * cp + 1][e];
-            const f32x2 t = {te, to};
-            const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));      // (even, odd) channel in one dword
-            res[e][0][cp] = h;
-            fe = __builtin_bit_cast(float, h << 16);
-            fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-        } else if (j == 1) {
-            te -= fe; to -= fo;
-        } else if (j == 2) {
-            const f32x2 t = {te, to};
-            const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-            res[e][1][cp] = m;
-            fe = __builtin_bit_cast(float, m << 16);
-            fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-        } else {
-            te -= fe; to -= fo;
-            const f32x2 t = {te, to};
-            res[e][2][cp] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-            asm volatile("" : "+v"(res[e][2][cp]));
-        }
-        asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));          // (pin the step where it is written: wino6.hip)
+        split6_step4(j, rin[2 * cp][e], rin[2 * cp + 1][e], te, to, fe, fo, res[e][0][cp], res[e][1][cp], res[e][2][cp]);
     };
     auto write_res = [&]() {
 #pragma unroll
@@ -148,7 +115,6 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
         const u32x4* ua = ul + MSET * (U_SLOTS * 64) + a_chunk;            // (image j = 2 s + MSET: buffer j & 1 == MSET)
         auto rd_a = [&](int ks, int pc) { av[ks & 1][pc] = __builtin_bit_cast(bf16x8, ua[(ks * 3 + pc) * 128]); };
         auto rd_b = [&](int ks, int n, int pc) { bv[ks & 1][n][pc] = __builtin_bit_cast(bf16x8, tl[b_chunk + (pc * NKS + ks) * 2 * HPX + n * 32]); };
-        constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) { rd_a(0, pc); rd_b(0, 0, pc); rd_b(0, 1, pc); }
         __builtin_amdgcn_s_setprio(1);
@@ -161,7 +127,7 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
                 for (int n = 0; n < 2; ++n) {
                     const int i = q * 2 + n;                             // MFMA index inside the k step (12)
 #ifndef P1_SKIP_MFMA
-                    acc[MSET][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[ks & 1][PA[q]], bv[ks & 1][n][PB[q]], acc[MSET][n], 0, 0, 0);
+                    split6_product(q, av[ks & 1], bv[ks & 1][n], acc[MSET][n], acc[MSET][n]);
 #endif
                     if (ks + 1 < NKS && i < 9) {                         // operands of the next k step: 3 + 6 reads
                         if (i < 3) rd_a(ks + 1, i);
@@ -178,7 +144,7 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
                 }
         }
         __builtin_amdgcn_s_setprio(0);
-        p1_barrier();                                    // end of phase
+        split6_barrier();                                    // end of phase
     };
     // one phase in the staging role.  In phase ph the other group multiplies with image ph >> 1; this group brings in its part (ph & 1:
     // group 1 part 0 in even phases, group 0 part 1 in odd ones) of image (ph >> 1) + 1, whose buffer was last read in phase ph - 1 (ph even)
@@ -190,8 +156,8 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
 #ifndef P1_SKIP_ARITH
         if (write) write_res();
 #endif
-        p1_wait_vm();     // (also waits for the fetch of the next stage issued in this group's last multiplying phase: long landed)
-        p1_barrier();                                    // end of phase
+        split6_wait_vm();     // (also waits for the fetch of the next stage issued in this group's last multiplying phase: long landed)
+        split6_barrier();                                    // end of phase
     };
 
     // prologue: every group splits and writes its half of stage 0 and fetches stage 1; group 0 brings in the whole weight image 0
@@ -204,7 +170,7 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
     fetch_half(0, min(1, nstage - 1));
     fetch_half(1, min(1, nstage - 1));
     if (grp == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // (the weight DMA has landed; the 8 loads of stage 1 stay in flight)
-    p1_barrier();
+    split6_barrier();
     int ph = 0;
     if (grp == 1) { stage(0, false); ph = 1; }
     for (int s = 0; s < nstage; ++s) {
@@ -261,8 +227,6 @@ int te_p1s6_launch(float* out, const float* in, const float* U, const float* res
     a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.ntiles, 8) : 0;
     const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
     const size_t lds = 2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)T_CHUNKS * 16;
-    static std::atomic<uint64_t> attr_done{0};
-    te::allow_big_lds(attr_done, (const void*)p1s6_kernel, 160 * 1024);
-    p1s6_kernel<<<dim3((unsigned)blocks), WT, lds, s>>>(a);
+    split6_launch<p1s6_kernel>(dim3((unsigned)blocks), WT, lds, s, a);
     return te::launch_status("te_conv_f32(TE_CONV_1X1S6)");
 }

@@ -20,16 +20,9 @@
 //     kx & 1, index c + (kx >> 1) - one conflict-free ds_read_b128 per piece (the pad makes two input rows a multiple of 16 chunks).
 // Every input element of the tile is inside the image (2 (H - 1) + 2 = 2 H: no padding, no edge cases); the epilogue is the direct
 // kernel's (demodulation scale, bias, leaky ReLU, residual, mask).
-#include "conv_common.h"
+#include "split6_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WT = 512, GT = 256, KC = 16, BM = 64;
 constexpr int TH = 8, TWO = 16, PH = 4;                       // output tile 8 x 16, half tile 4 rows
@@ -65,8 +58,6 @@ struct S2Args {
     int B, K, M, H, W, Hi, Wi, ntiles, mblocks, tiles_x, tiles_y, nt8;
 };
 
-__device__ __forceinline__ void s2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void s2_wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ISC: the launch carries style scales (a template parameter: `if (p.isc)` around the scale loads was one of the conditional updates of
 // the fetch registers that made the compiler keep two copies of them - see fetch_item and profiles/experiments/r05_s2s6_phase_profile.log)
@@ -79,10 +70,8 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + U_SLOTS * 1024) + grp * TP_DWORDS;      // this group's half tile
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mb = jx % p.mblocks;
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mb;
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mb)) return;
     const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
     const int x0 = tx * TWO, y0 = ty * TH, yh = y0 + PH * grp;
     const size_t iplane = (size_t)p.Hi * p.Wi, oplane = (size_t)p.H * p.W;
@@ -175,28 +164,11 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
             }
         } else if (k < N_SLOT) {
             const int u = (k - P_IN) >> 2, j = (k - P_IN) & 3, i = u >> 2, c = u & 3;
+            float ve = 0.f, vo = 0.f;
             if (j == 0) {
-                te = rin[i][0][c]; to = rin[i][1][c];                              // even / odd channel of the pair at position c
-                const f32x2 t = {te, to};
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][0] = h;
-                fe = __builtin_bit_cast(float, h << 16);
-                fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-            } else if (j == 1) {
-                te -= fe; to -= fo;
-            } else if (j == 2) {
-                const f32x2 t = {te, to};
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][1] = m;
-                fe = __builtin_bit_cast(float, m << 16);
-                fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-            } else {
-                te -= fe; to -= fo;
-                const f32x2 t = {te, to};
-                res[i][c][2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                asm volatile("" : "+v"(res[i][c][2]));
+                ve = rin[i][0][c]; vo = rin[i][1][c];                              // even / odd channel of the pair at position c
             }
-            asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));        // (pin the step here: see wino6.hip)
+            split6_step4(j, ve, vo, te, to, fe, fo, res[i][c][0], res[i][c][1], res[i][c][2]);
         }
     };
     auto write_res = [&]() {
@@ -227,7 +199,7 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
         if (ISC) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     }
-    s2_barrier();
+    split6_barrier();
     const int nphase = 2 * nstage;
 #ifdef S2_PROF
     unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -245,7 +217,6 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
                 if (q < 3) av[slot][q] = __builtin_bit_cast(bf16x8, ul[a_chunk + (q * NTAP + t) * 128]);
                 else bv[slot][q - 3] = __builtin_bit_cast(bf16x8, tl4[b_chunk + ((ky * 2) * 2 + (kx & 1)) * CI + (kx >> 1) + (q - 3) * (TP_PLANE / 4)]);
             };
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
             for (int q = 0; q < 6; ++q) rd1(0, 0, q);
             __builtin_amdgcn_s_setprio(1);
@@ -253,16 +224,15 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
             for (int t = 0; t < NTAP; ++t) {
                 const int slot = t & 1;
 #ifdef S2_PROF
-                if (t == UA_TAPS - 1) { S2_T(ta); s2_barrier(); S2_T(tb); S2_ACC(0, t0, ta); S2_ACC(1, ta, tb); pc[2] -= tb; }
+                if (t == UA_TAPS - 1) { S2_T(ta); split6_barrier(); S2_T(tb); S2_ACC(0, t0, ta); S2_ACC(1, ta, tb); pc[2] -= tb; }
 #else
-                if (t == UA_TAPS - 1) s2_barrier();    // mid-phase barrier: in front of tap 4's MFMAs (operands read) and of the first read of half b
+                if (t == UA_TAPS - 1) split6_barrier();    // mid-phase barrier: in front of tap 4's MFMAs (operands read) and of the first read of half b
 #endif
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < 6; ++q) {
 #ifndef ST_SKIP_MFMA     // (experiment switches ST_*: timing decomposition only, results are wrong)
-                    if (q < 5) accl = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[q]], bv[slot][PB[q]], accl, 0, 0, 0);
-                    else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[q]], bv[slot][PB[q]], acc, 0, 0, 0);
+                    split6_product(q, av[slot], bv[slot], acc, accl);
 #endif
                     if (t + 1 < NTAP && q < 3) { rd1(t + 1, slot ^ 1, 2 * q); rd1(t + 1, slot ^ 1, 2 * q + 1); }
 #ifndef ST_NO_ARITH
@@ -301,23 +271,23 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
 #ifndef ST_NO_DSW
             write_res();
 #endif
-            if (work && grp == 1) s2_wait_vm();
+            if (work && grp == 1) split6_wait_vm();
             S2_T(ta);
-            s2_barrier();
+            split6_barrier();
             S2_T(tb);
 #ifndef ST_NO_DMA
             if (work && grp == 0) {
                 if (DMA_PRIO) __builtin_amdgcn_s_setprio(DMA_PRIO);
                 issue_u(0, cs);
                 if (DMA_PRIO) __builtin_amdgcn_s_setprio(0);
-                s2_wait_vm();
+                split6_wait_vm();
             }
 #endif
             S2_T(tc);
             S2_ACC(3, t0, ta); S2_ACC(4, ta, tb); S2_ACC(5, tb, tc);
         }
         S2_T(t8);
-        if (!last) s2_barrier();
+        if (!last) split6_barrier();
         S2_T(t9);
         S2_ACC(6, t8, t9);
     }
@@ -388,10 +358,8 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + U_SLOTS * 1024) + grp * TP_DWORDS;      // this group's half tile
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mbq = jx % p.mblocks;               // (mblocks = M / 128 for this form)
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mbq;               // (mblocks = M / 128 for this form)
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mbq)) return;
     const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
     const int x0 = tx * TWO, y0 = ty * TH, yh = y0 + PH * grp;
     const size_t iplane = (size_t)p.Hi * p.Wi, oplane = (size_t)p.H * p.W;
@@ -467,28 +435,11 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
             }
         } else if (k < N_SLOT) {
             const int u = (k - P_IN) >> 2, j = (k - P_IN) & 3, i = u >> 2, c = u & 3;
+            float ve = 0.f, vo = 0.f;
             if (j == 0) {
-                te = rin[i][0][c]; to = rin[i][1][c];
-                const f32x2 t = {te, to};
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][0] = h;
-                fe = __builtin_bit_cast(float, h << 16);
-                fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-            } else if (j == 1) {
-                te -= fe; to -= fo;
-            } else if (j == 2) {
-                const f32x2 t = {te, to};
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][1] = m;
-                fe = __builtin_bit_cast(float, m << 16);
-                fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-            } else {
-                te -= fe; to -= fo;
-                const f32x2 t = {te, to};
-                res[i][c][2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                asm volatile("" : "+v"(res[i][c][2]));
+                ve = rin[i][0][c]; vo = rin[i][1][c];
             }
-            asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));
+            split6_step4(j, ve, vo, te, to, fe, fo, res[i][c][0], res[i][c][1], res[i][c][2]);
         }
     };
     auto write_res = [&]() {
@@ -516,19 +467,17 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
             if (q < 3) av[slot][q] = __builtin_bit_cast(bf16x8, ul[a_chunk + (q * NTAP + t) * 128]);
             else bv[slot][q - 3] = __builtin_bit_cast(bf16x8, tl4[b_chunk + ((ky * 2) * 2 + (kx & 1)) * CI + (kx >> 1) + (q - 3) * (TP_PLANE / 4)]);
         };
-        constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
         for (int q = 0; q < 6; ++q) rd1(0, 0, q);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int t = 0; t < NTAP; ++t) {
             const int slot = t & 1;
-            if (t == UA_TAPS - 1) s2_barrier();        // mid-phase barrier
+            if (t == UA_TAPS - 1) split6_barrier();        // mid-phase barrier
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
-                if (q < 5) accl[MSET] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[q]], bv[slot][PB[q]], accl[MSET], 0, 0, 0);
-                else acc[MSET] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[q]], bv[slot][PB[q]], acc[MSET], 0, 0, 0);
+                split6_product(q, av[slot], bv[slot], acc[MSET], accl[MSET]);
                 if (t + 1 < NTAP && q < 3) { rd1(t + 1, slot ^ 1, 2 * q); rd1(t + 1, slot ^ 1, 2 * q + 1); }
                 const int k = t * 6 + q;
                 if (MSET == 0) {
@@ -544,7 +493,7 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        s2_barrier();                                  // end of phase
+        split6_barrier();                                  // end of phase
     };
     // one phase in the staging role (wino6q_kernel: stage): image cs = (ph + 1) >> 1 is the one whose half this phase renews - group 1
     // (even ph) half b in FRONT of the mid-phase barrier, group 0 (odd ph) half a BEHIND it; WRITE: the parked split results go to LDS
@@ -554,13 +503,13 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
         if (grp == 1 && work) issue_u(1, cs);
         __builtin_amdgcn_sched_barrier(0);
         if (write) write_res();
-        if (grp == 1 && work) s2_wait_vm();
-        s2_barrier();                                  // mid-phase
+        if (grp == 1 && work) split6_wait_vm();
+        split6_barrier();                                  // mid-phase
         if (grp == 0 && work) {
             issue_u(0, cs);
-            s2_wait_vm();
+            split6_wait_vm();
         }
-        s2_barrier();                                  // end of phase
+        split6_barrier();                                  // end of phase
     };
 
     // prologue: every group splits and writes its half of stage 0; group 0 brings in the whole weight image 0
@@ -571,8 +520,8 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
 #pragma unroll
     for (int k = 0; k < N_SLOT; ++k) arith(k);
     write_res();
-    s2_wait_vm();
-    s2_barrier();
+    split6_wait_vm();
+    split6_barrier();
     int ph = 0;
     if (grp == 1) { stage(0, false); ph = 1; }
     for (int s = 0; s < nstage; ++s) {
@@ -657,22 +606,11 @@ int te_s2s6_launch(float* out, const float* in, const float* U, const float* isc
     const size_t lds = (size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4;
     const int form = g_s2_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
-    static std::atomic<uint64_t> attr_done{0}, attr_done_sc{0}, attr_done_q{0}, attr_done_qs{0};
     if (form >= 1 && M % (2 * BM) == 0 && (form == 2 || blocks_q >= te::kNumCU)) {
         a.mblocks = M / (2 * BM);
-        if (isc) {
-            te::allow_big_lds(attr_done_qs, (const void*)s2s6q_kernel<true>, 160 * 1024);
-            s2s6q_kernel<true><<<dim3((unsigned)blocks_q), WT, lds, s>>>(a);
-        } else {
-            te::allow_big_lds(attr_done_q, (const void*)s2s6q_kernel<false>, 160 * 1024);
-            s2s6q_kernel<false><<<dim3((unsigned)blocks_q), WT, lds, s>>>(a);
-        }
-    } else if (isc) {
-        te::allow_big_lds(attr_done_sc, (const void*)s2s6_kernel<true>, 160 * 1024);
-        s2s6_kernel<true><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
+        SPLIT6_LAUNCH_ISC(s2s6q_kernel, isc, dim3((unsigned)blocks_q), WT, lds, s, a);
     } else {
-        te::allow_big_lds(attr_done, (const void*)s2s6_kernel<false>, 160 * 1024);
-        s2s6_kernel<false><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
+        SPLIT6_LAUNCH_ISC(s2s6_kernel, isc, dim3((unsigned)blocks), WT, lds, s, a);
     }
     return te::launch_status("te_conv_f32(TE_CONV_S2S6)");
 }

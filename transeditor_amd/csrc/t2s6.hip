@@ -29,16 +29,9 @@
 // 128 -> 128 @128^2 under the phase profiler - and the un-profiled launch times did not move (158 - 166 TFLOP/s before and after,
 // r06_t2s6_check_double_buffered.log): the kernel sits at the part's power limit, the saved cycles came back as a lower clock.  Kept for
 // the simpler protocol.  (s2s6.hip keeps the half-by-half protocol: two of its 54 KB images do not fit beside its 61 KB of half tiles.)
-#include "conv_common.h"
+#include "split6_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WT = 512, GT = 256, KC = 16, BM = 64;
 constexpr int TH = 8, TWC = 16, PH = 4;                       // cell tile 8 x 16, half tile 4 cell rows
@@ -73,8 +66,6 @@ struct T2Args {
     int B, K, M, H, W, Ho, Wo, ntiles, mblocks, tiles_x, tiles_y, nt8;
 };
 
-__device__ __forceinline__ void t2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void t2_wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ISC: the launch carries style scales (template parameter; see s2s6.hip)
 template <bool ISC>
@@ -86,10 +77,8 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + 2 * U_SLOTS * 1024) + grp * TP_DWORDS;  // this group's half tile (behind the two weight images)
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mb = jx % p.mblocks;
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mb;
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mb)) return;
     const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
     const int x0 = tx * TWC, y0 = ty * TH, yh = y0 + PH * grp;
     const size_t iplane = (size_t)p.H * p.W, oplane = (size_t)p.Ho * p.Wo;
@@ -177,28 +166,11 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
             }
         } else if (k < N_SLOT) {
             const int c = (k - 1) >> 2, j = (k - 1) & 3;
+            float ve = 0.f, vo = 0.f;
             if (j == 0) {
-                te = rin[0][c]; to = rin[1][c];                              // even / odd channel of the pair at position c
-                const f32x2 t = {te, to};
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[c][0] = h;
-                fe = __builtin_bit_cast(float, h << 16);
-                fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-            } else if (j == 1) {
-                te -= fe; to -= fo;
-            } else if (j == 2) {
-                const f32x2 t = {te, to};
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[c][1] = m;
-                fe = __builtin_bit_cast(float, m << 16);
-                fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-            } else {
-                te -= fe; to -= fo;
-                const f32x2 t = {te, to};
-                res[c][2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                asm volatile("" : "+v"(res[c][2]));
+                ve = rin[0][c]; vo = rin[1][c];                              // even / odd channel of the pair at position c
             }
-            asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));        // (pin the step here: see wino6.hip)
+            split6_step4(j, ve, vo, te, to, fe, fo, res[c][0], res[c][1], res[c][2]);
         }
     };
     auto write_res = [&]() {
@@ -226,7 +198,7 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
         if (ISC) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     }
-    t2_barrier();
+    split6_barrier();
     const int nphase = 2 * nstage;
 #ifdef T2_PROF
     unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -245,7 +217,6 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
                 if (qq < 3) av[slot][qq] = __builtin_bit_cast(bf16x8, ua[(qq * NTAP + t) * 128]);
                 else bv[slot][qq - 3] = __builtin_bit_cast(bf16x8, tl4[b_chunk - (ky == 2 ? 2 * CW : 0) - (kx == 2 ? 1 : 0) + (qq - 3) * (TP_PLANE / 4)]);
             };
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
             for (int qq = 0; qq < 6; ++qq) rd1(0, 0, qq);
             __builtin_amdgcn_s_setprio(1);
@@ -256,7 +227,7 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
 #pragma unroll
                 for (int qq = 0; qq < 6; ++qq) {
 #ifndef ST_SKIP_MFMA     // (experiment switches ST_*: timing decomposition only, results are wrong)
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[qq]], bv[slot][PB[qq]], acc[c], 0, 0, 0);
+                    split6_product(qq, av[slot], bv[slot], acc[c], acc[c]);
 #endif
                     if (t + 1 < NTAP && qq < 3) { rd1(t + 1, slot ^ 1, 2 * qq); rd1(t + 1, slot ^ 1, 2 * qq + 1); }
 #ifndef ST_NO_ARITH
@@ -286,12 +257,12 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
             write_res();
 #endif
             T2_T(ta);
-            t2_wait_vm();
+            split6_wait_vm();
             T2_T(tb);
             T2_ACC(3, t0, ta); T2_ACC(4, ta, tb);
         }
         T2_T(t8);
-        if (!last) t2_barrier();
+        if (!last) split6_barrier();
         T2_T(t9);
         T2_ACC(6, t8, t9);
     }
@@ -351,10 +322,8 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + 2 * U_SLOTS * 1024) + grp * TP_DWORDS;
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mbq = jx % p.mblocks;               // (mblocks = M / 128 for this form)
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mbq;               // (mblocks = M / 128 for this form)
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mbq)) return;
     const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
     const int x0 = tx * TWC, y0 = ty * TH, yh = y0 + PH * grp;
     const size_t iplane = (size_t)p.H * p.W, oplane = (size_t)p.Ho * p.Wo;
@@ -430,28 +399,11 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
             }
         } else if (k < N_SLOT) {
             const int c = (k - 1) >> 2, j = (k - 1) & 3;
+            float ve = 0.f, vo = 0.f;
             if (j == 0) {
-                te = rin[0][c]; to = rin[1][c];
-                const f32x2 t = {te, to};
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[c][0] = h;
-                fe = __builtin_bit_cast(float, h << 16);
-                fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-            } else if (j == 1) {
-                te -= fe; to -= fo;
-            } else if (j == 2) {
-                const f32x2 t = {te, to};
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[c][1] = m;
-                fe = __builtin_bit_cast(float, m << 16);
-                fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-            } else {
-                te -= fe; to -= fo;
-                const f32x2 t = {te, to};
-                res[c][2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                asm volatile("" : "+v"(res[c][2]));
+                ve = rin[0][c]; vo = rin[1][c];
             }
-            asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));
+            split6_step4(j, ve, vo, te, to, fe, fo, res[c][0], res[c][1], res[c][2]);
         }
     };
     auto write_res = [&]() {
@@ -478,7 +430,6 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
             if (qq < 3) av[slot][qq] = __builtin_bit_cast(bf16x8, ua[(qq * NTAP + t) * 128]);
             else bv[slot][qq - 3] = __builtin_bit_cast(bf16x8, tl4[b_chunk - (ky == 2 ? 2 * CW : 0) - (kx == 2 ? 1 : 0) + (qq - 3) * (TP_PLANE / 4)]);
         };
-        constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
         for (int qq = 0; qq < 6; ++qq) rd1(0, 0, qq);
         __builtin_amdgcn_s_setprio(1);
@@ -488,7 +439,7 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int qq = 0; qq < 6; ++qq) {
-                acc[MSET][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[qq]], bv[slot][PB[qq]], acc[MSET][c], 0, 0, 0);
+                split6_product(qq, av[slot], bv[slot], acc[MSET][c], acc[MSET][c]);
                 if (t + 1 < NTAP && qq < 3) { rd1(t + 1, slot ^ 1, 2 * qq); rd1(t + 1, slot ^ 1, 2 * qq + 1); }
                 const int k = t * 6 + qq;
                 if (MSET == 0) {
@@ -501,7 +452,7 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        t2_barrier();                                  // end of phase
+        split6_barrier();                                  // end of phase
     };
     // one phase in the staging role: this group's part (ph & 1) of image (ph >> 1) + 1 into the buffer image (ph >> 1) - 1 was read from,
     // waited for at the end of the phase; WRITE: the parked split results go to the half tile
@@ -510,8 +461,8 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
         if (cw < nimg) issue_u(ph & 1, cw);
         __builtin_amdgcn_sched_barrier(0);
         if (write) write_res();
-        t2_wait_vm();
-        t2_barrier();                                  // end of phase
+        split6_wait_vm();
+        split6_barrier();                                  // end of phase
     };
 
     // prologue: every group splits and writes its half of stage 0; group 0 brings in the whole weight image 0
@@ -521,8 +472,8 @@ __global__ __launch_bounds__(WT, 2) void t2s6q_kernel(const T2Args p) {
 #pragma unroll
     for (int k = 0; k < N_SLOT; ++k) arith(k, 0);
     write_res();
-    t2_wait_vm();
-    t2_barrier();
+    split6_wait_vm();
+    split6_barrier();
     int ph = 0;
     if (grp == 1) { stage(0, false); ph = 1; }
     for (int s = 0; s < nstage; ++s) {
@@ -757,26 +708,13 @@ int te_t2s6_launch(float* out, const float* in, const float* U, const float* isc
     a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.ntiles, 8) : 0;
     const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
     const size_t lds = 2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4;
-    static std::atomic<uint64_t> attr_done{0};
     const int form = g_t2_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
     if (form >= 1 && M % (2 * BM) == 0 && (form == 2 || blocks_q >= te::kNumCU)) {
-        static std::atomic<uint64_t> attr_done_q{0}, attr_done_qs{0};
         a.mblocks = M / (2 * BM);
-        if (isc) {
-            te::allow_big_lds(attr_done_qs, (const void*)t2s6q_kernel<true>, 160 * 1024);
-            t2s6q_kernel<true><<<dim3((unsigned)blocks_q), WT, lds, s>>>(a);
-        } else {
-            te::allow_big_lds(attr_done_q, (const void*)t2s6q_kernel<false>, 160 * 1024);
-            t2s6q_kernel<false><<<dim3((unsigned)blocks_q), WT, lds, s>>>(a);
-        }
-    } else if (isc) {
-        static std::atomic<uint64_t> attr_done_sc{0};
-        te::allow_big_lds(attr_done_sc, (const void*)t2s6_kernel<true>, 160 * 1024);
-        t2s6_kernel<true><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
+        SPLIT6_LAUNCH_ISC(t2s6q_kernel, isc, dim3((unsigned)blocks_q), WT, lds, s, a);
     } else {
-        te::allow_big_lds(attr_done, (const void*)t2s6_kernel<false>, 160 * 1024);
-        t2s6_kernel<false><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
+        SPLIT6_LAUNCH_ISC(t2s6_kernel, isc, dim3((unsigned)blocks), WT, lds, s, a);
     }
     return te::launch_status("te_conv_f32(TE_CONV_T2S6)");
 }

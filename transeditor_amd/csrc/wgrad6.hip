@@ -24,16 +24,9 @@
 // (waves 0-1: gradient row y + 1, waves 2-3: input row y + 2; a lane = 16 cells of one channel = whole 16-byte LDS elements) from
 // registers loaded during step y - 1, and the loads of the rows after that are issued at the head of the step: every global load
 // has a whole step (>= 2 300 cycles) to land.  One workgroup barrier per step.
-#include "conv_common.h"
-#include <atomic>
+#include "split6_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WT = 256;                       // 4 waves
 constexpr int TC = 64;                        // channels per block, both sides
@@ -50,7 +43,6 @@ struct Wg6Args {
 __device__ __forceinline__ f32x4 buf_load4w(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
-__device__ __forceinline__ void w6g_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 
 // Round 6 (operand traffic 2.49x / 3.65x the algorithmic bytes in the counters).  Two changes of ORDER, no change of work:
@@ -179,7 +171,8 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
             const f32x2 t = {v0, v1};
             pcs[2][d] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
         }
-        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(f0), "+v"(f1));          // (pin the step where it is written: wino6.hip)
+        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(f0), "+v"(f1));          // (own copy of split6_step4<false>: through the shared step the
+                                                                             //  register allocation of this kernel changes; see split6_common.h)
     };
     // element index of this lane inside an image: ((piece * 4 + j) * 2 + kh) * 64 + lane
     const int w_elem = kh * TC + lane;
@@ -240,7 +233,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
 #pragma unroll
             for (int i = 0; i < NRAW; ++i) asm volatile("" :: "v"(rw[i]));
         }
-        w6g_barrier();
+        split6_barrier();
 #ifdef WG6_PROF
         pc_head += __builtin_readcyclecounter() - th0;
 #endif
@@ -330,7 +323,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
 #endif
 #pragma unroll
             for (int i = 0; i < NRAW; ++i) rw[i] = rn[i];
-            w6g_barrier();
+            split6_barrier();
 #ifdef WG6_PROF
             { const unsigned long long tm2 = __builtin_readcyclecounter(); pc_mult += tm1 - tm0; pc_bar += tm2 - tm1; ++nstep_done; }
 #endif
@@ -446,24 +439,8 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
             if (u < 5) { v0 = rg[4 * u]; v1 = u < 4 ? rg[4 * u + 2] : 0.f; }
             else if (u < 9) { v0 = rg[4 * (u - 5) + 1]; v1 = rg[4 * (u - 5) + 3]; }
             else { v0 = rx[2 * (u - 9)]; v1 = rx[2 * (u - 9) + 1]; }
-            const f32x2 t = {v0, v1};
-            const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-            d0 = h;
-            f0 = __builtin_bit_cast(float, h << 16);
-            f1 = __builtin_bit_cast(float, h & 0xFFFF0000u);
-        } else if (step == 1) {
-            v0 -= f0; v1 -= f1;
-            const f32x2 t = {v0, v1};
-            const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-            d1 = m;
-            f0 = __builtin_bit_cast(float, m << 16);
-            f1 = __builtin_bit_cast(float, m & 0xFFFF0000u);
-        } else {
-            v0 -= f0; v1 -= f1;
-            const f32x2 t = {v0, v1};
-            d2 = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
         }
-        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(f0), "+v"(f1));
+        split6_step3(step, v0, v1, v0, v1, f0, f1, d0, d1, d2);
     };
     const int w_elem = q * TC + lane;             // + ((piece * 3 + component) * 2) * 64 (g) / (piece * 2) * 64 (x)
     auto write_g = [&](int gimg, int comp, int pc) {          // component 0: even columns, 1: odd columns, 2: even columns from the second on
@@ -528,7 +505,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(rx[i]));
         }
-        w6g_barrier();
+        split6_barrier();
 #ifdef WG6_PROF
         pc_head += __builtin_readcyclecounter() - th0;
 #endif
@@ -575,7 +552,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) rx[i] = nx[i];
             s0 += 2; s0 -= s0 >= NGR ? NGR : 0;
-            w6g_barrier();
+            split6_barrier();
 #ifdef WG6_PROF
             { const unsigned long long tm2 = __builtin_readcyclecounter(); pc_mult += tm1 - tm0; pc_bar += tm2 - tm1; ++nstep_done; }
 #endif
@@ -674,24 +651,8 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
             if (u < 5) { v0 = rg[4 * u]; v1 = u < 4 ? rg[4 * u + 2] : 0.f; }
             else if (u < 9) { v0 = rg[4 * (u - 5) + 1]; v1 = rg[4 * (u - 5) + 3]; }
             else { v0 = rx[2 * (u - 9)]; v1 = rx[2 * (u - 9) + 1]; }
-            const f32x2 t = {v0, v1};
-            const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-            d0 = h;
-            f0 = __builtin_bit_cast(float, h << 16);
-            f1 = __builtin_bit_cast(float, h & 0xFFFF0000u);
-        } else if (step == 1) {
-            v0 -= f0; v1 -= f1;
-            const f32x2 t = {v0, v1};
-            const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-            d1 = m;
-            f0 = __builtin_bit_cast(float, m << 16);
-            f1 = __builtin_bit_cast(float, m & 0xFFFF0000u);
-        } else {
-            v0 -= f0; v1 -= f1;
-            const f32x2 t = {v0, v1};
-            d2 = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
         }
-        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(f0), "+v"(f1));
+        split6_step3(step, v0, v1, v0, v1, f0, f1, d0, d1, d2);
     };
     const int w_elem = q * TC + lane;             // + ((piece * 3 + component) * 2) * 64 (g) / (piece * 2) * 64 (x)
     auto write_g = [&](int gimg, int comp, int pc) {          // component 0: even columns, 1: odd columns, 2: even columns from the second on
@@ -756,7 +717,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(rx[i]));
         }
-        w6g_barrier();
+        split6_barrier();
 #ifdef WG6_PROF
         pc_head += __builtin_readcyclecounter() - th0;
 #endif
@@ -807,7 +768,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) rx[i] = nx[i];
             s0 += 2; s0 -= s0 >= NGR ? NGR : 0;
-            w6g_barrier();
+            split6_barrier();
 #ifdef WG6_PROF
             { const unsigned long long tm2 = __builtin_readcyclecounter(); pc_mult += tm1 - tm0; pc_bar += tm2 - tm1; ++nstep_done; }
 #endif
@@ -887,6 +848,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6p_kernel(const Wg6Args p) {
         }
     };
     // split of one packed pair in three steps (wgrad6t_kernel: unit_step); units 0..3: the g unit, 4..7: the x unit
+    // (own copy of split6_step3: through the shared step the register allocation of this kernel changes; see split6_common.h)
     unsigned pg[3][4], px[3][4];
     float v0 = 0.f, v1 = 0.f, f0 = 0.f, f1 = 0.f;
     auto unit_step = [&](const float (&rg)[8], const float (&rx)[8], int u, int step) {
@@ -956,7 +918,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6p_kernel(const Wg6Args p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) { asm volatile("" :: "v"(rg[i])); asm volatile("" :: "v"(rx[i])); }       // (wait for the first step's registers here)
         }
-        w6g_barrier();
+        split6_barrier();
         for (int y = ya; y < yb; ++y) {
             load8(ng, gblk, p.Co, bb, cx, y + 2);             // registers of the step after next
             load8(nx, xblk, p.Ci, bb, cx, y + 2);
@@ -984,7 +946,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6p_kernel(const Wg6Args p) {
                 }
 #pragma unroll
             for (int i = 0; i < 8; ++i) { rg[i] = ng[i]; rx[i] = nx[i]; }
-            w6g_barrier();
+            split6_barrier();
         }
     }
     }
@@ -1078,39 +1040,27 @@ int te_wgrad6_launch(float* slabs, const float* g, const float* x, int kind, int
     dim3 grid((unsigned)(B / NB * S), (unsigned)te::cdiv(Co, TC), (unsigned)te::cdiv(Ci, TC));
     switch (form) {
         case TE_WG6_1X1: {
-            static std::atomic<uint64_t> attr_done_p1{0};
-            te::allow_big_lds(attr_done_p1, (const void*)wgrad6p_kernel, 160 * 1024);
-            wgrad6p_kernel<<<dim3(grid.x, (unsigned)(Co / (2 * TC)), (unsigned)(Ci / (2 * TC))), WT, (size_t)8 * PI * 16, s>>>(a);
+            split6_launch<wgrad6p_kernel>(dim3(grid.x, (unsigned)(Co / (2 * TC)), (unsigned)(Ci / (2 * TC))), WT, (size_t)8 * PI * 16, s, a);
             return 1;
         }
         case TE_WG6_T2_WIDE: {           // wide form: 64 x 128 channels per block
-            static std::atomic<uint64_t> attr_done_tw{0};
-            te::allow_big_lds(attr_done_tw, (const void*)wgrad6tw_kernel, 160 * 1024);
-            wgrad6tw_kernel<<<dim3(grid.x, grid.y, (unsigned)(Ci / (2 * TC))), WT, (size_t)(NGR * GI + 4 * XI) * 16, s>>>(a);
+            split6_launch<wgrad6tw_kernel>(dim3(grid.x, grid.y, (unsigned)(Ci / (2 * TC))), WT, (size_t)(NGR * GI + 4 * XI) * 16, s, a);
             return 1;
         }
         case TE_WG6_T2: {
-            static std::atomic<uint64_t> attr_done_t{0};
-            te::allow_big_lds(attr_done_t, (const void*)wgrad6t_kernel<false>, 160 * 1024);
-            wgrad6t_kernel<false><<<grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s>>>(a);
+            split6_launch<wgrad6t_kernel<false>>(grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s, a);
             return 1;
         }
         case TE_WG6_T2_MASKED: {
-            static std::atomic<uint64_t> attr_done_tn{0};
-            te::allow_big_lds(attr_done_tn, (const void*)wgrad6t_kernel<true>, 160 * 1024);
-            wgrad6t_kernel<true><<<grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s>>>(a);
+            split6_launch<wgrad6t_kernel<true>>(grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s, a);
             return 1;
         }
         case TE_WG6_3X3_PAIR: {
-            static std::atomic<uint64_t> attr_done_p{0};
-            te::allow_big_lds(attr_done_p, (const void*)wgrad6_kernel<true>, 160 * 1024);
-            wgrad6_kernel<true><<<dim3((unsigned)(B / 2 * S), 1, 1), WT, (size_t)N_IMG * IMG * 16, s>>>(a);
+            split6_launch<wgrad6_kernel<true>>(dim3((unsigned)(B / 2 * S), 1, 1), WT, (size_t)N_IMG * IMG * 16, s, a);
             return 1;
         }
         default: {
-            static std::atomic<uint64_t> attr_done{0};
-            te::allow_big_lds(attr_done, (const void*)wgrad6_kernel<false>, 160 * 1024);
-            wgrad6_kernel<false><<<grid, WT, (size_t)N_IMG * IMG * 16, s>>>(a);
+            split6_launch<wgrad6_kernel<false>>(grid, WT, (size_t)N_IMG * IMG * 16, s, a);
             return 1;
         }
     }

@@ -20,16 +20,9 @@
 //   products : per (tap row, component): 3 + 3 operand reads, 6 MFMAs into the component's accumulator tile
 // Block: 512 threads, tile 64 output channels x 8 rows x 32 columns.  Epilogue = wino.hip's (output transform, demodulation scale, bias,
 // leaky ReLU, residual, mask).
-#include "conv_common.h"
+#include "split6_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WT = 512, KC = 16, TW = 32, NP = TW / 2, BM = 64, TH = 8;
 constexpr int U_CHUNKS = 36 * 2 * 64;                   // 16-byte chunks of a stage's weights: [piece 3][ky 3][c 4][mtile 2][64 lanes]
@@ -87,8 +80,6 @@ __device__ unsigned long long te_w6p_prof_buf[2048 * 8 * 8];
 #ifndef W6P_PRIO
 #define W6P_PRIO 1           // 1: a wave raises its priority while it multiplies (+1 - 1.5 % over 0); 3: static priority for group 1 (-3 %)
 #endif
-__device__ __forceinline__ void w6p_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void w6p_wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ISC: the launch carries style scales.  A template parameter, and the fetch of the staging role is unconditional (clamped to the last
 // stage): with `if (iscb)` / `if (fetch)` around the loads the compiler kept two copies of the 26 fetch registers and moved them twice per
@@ -108,10 +99,8 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + U_CHUNKS * 16) + grp * TP_DWORDS;      // this group's half tile
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mb = jx % p.mblocks;
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mb;
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mb)) return;
     // W == 16 (round 6): a tile row holds TWO samples side by side - pairs 0-7 = sample b, pairs 8-15 = sample b + 1 (lgpw = 3); every
     // column pair is transformed from its own four input columns, so only the staging geometry and the output addresses know about it
     const int pwm = (1 << p.lgpw) - 1;
@@ -219,33 +208,13 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
             }
         } else if (k < N_SLOT) {
             const int u = (k - P_IN) >> 2, j = (k - P_IN) & 3, i = u >> 2, c = u & 3;
+            float ve = 0.f, vo = 0.f;
             if (j == 0) {
                 const f32x4 e = rin[i][0], o = rin[i][1];                         // even / odd channel of the pair
-                te = c == 0 ? e[0] - e[2] : (c == 1 ? e[1] + e[2] : (c == 2 ? e[2] - e[1] : e[1] - e[3]));
-                to = c == 0 ? o[0] - o[2] : (c == 1 ? o[1] + o[2] : (c == 2 ? o[2] - o[1] : o[1] - o[3]));
-                const f32x2 t = {te, to};
-                // v_cvt_pk_bf16_f32 packs (even, odd) into one dword = the LDS element
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][0] = h;
-                fe = __builtin_bit_cast(float, h << 16);
-                fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-            } else if (j == 1) {
-                te -= fe; to -= fo;
-            } else if (j == 2) {
-                const f32x2 t = {te, to};
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][1] = m;
-                fe = __builtin_bit_cast(float, m << 16);
-                fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-            } else {
-                te -= fe; to -= fo;
-                const f32x2 t = {te, to};
-                res[i][c][2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                asm volatile("" : "+v"(res[i][c][2]));
+                ve = c == 0 ? e[0] - e[2] : (c == 1 ? e[1] + e[2] : (c == 2 ? e[2] - e[1] : e[1] - e[3]));
+                vo = c == 0 ? o[0] - o[2] : (c == 1 ? o[1] + o[2] : (c == 2 ? o[2] - o[1] : o[1] - o[3]));
             }
-            // (pin the step HERE: the values have no use before the staging phase, and the compiler otherwise sinks the whole
-            //  program behind the mid-phase barrier)
-            asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));
+            split6_step4(j, ve, vo, te, to, fe, fo, res[i][c][0], res[i][c][1], res[i][c][2]);
         }
     };
     auto write_res = [&]() {
@@ -273,7 +242,7 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
         if (ISC) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     }
-    w6p_barrier();
+    split6_barrier();
     const int nphase = 2 * nstage;
     if (W6P_PRIO == 3 && grp == 1) __builtin_amdgcn_s_setprio(1);
 #ifdef W6P_PROF
@@ -294,7 +263,6 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
                 if (q < 3) av[slot][q] = __builtin_bit_cast(bf16x8, ul[a_chunk + ((q * 3 + ky) * 4 + c) * 128]);
                 else bv[slot][q - 3] = __builtin_bit_cast(bf16x8, tl4[b_chunk + (((q - 3) * 4 + c) * PR + ky) * 2 * NP]);
             };
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
             for (int q = 0; q < 6; ++q) rd1(0, 0, q);
             if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(1);
@@ -302,15 +270,15 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
             for (int g = 0; g < 12; ++g) {
                 const int slot = g & 1, c = g & 3;
 #ifdef W6P_PROF
-                if (g == 5) { W6P_T(ta); w6p_barrier(); W6P_T(tb); W6P_ACC(0, t0, ta); W6P_ACC(1, ta, tb); pc[2] -= tb; }
+                if (g == 5) { W6P_T(ta); split6_barrier(); W6P_T(tb); W6P_ACC(0, t0, ta); W6P_ACC(1, ta, tb); pc[2] -= tb; }
 #else
-                if (g == 5) w6p_barrier();             // mid-phase barrier (every phase, the last one too: no branch in the MFMA stream)
+                if (g == 5) split6_barrier();             // mid-phase barrier (every phase, the last one too: no branch in the MFMA stream)
 #endif
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < 6; ++q) {
 #ifndef W6_SKIP_MFMA
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[q]], bv[slot][PB[q]], acc[c], 0, 0, 0);
+                    split6_product(q, av[slot], bv[slot], acc[c], acc[c]);
 #endif
                     if (g + 1 < 12 && q < 3) { rd1(g + 1, slot ^ 1, 2 * q); rd1(g + 1, slot ^ 1, 2 * q + 1); }
 #ifndef W6_SKIP_COMMIT
@@ -346,21 +314,21 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
 #ifndef W6_SKIP_COMMIT
             write_res();
 #endif
-            if (grp == 1 && work) w6p_wait_vm();
+            if (grp == 1 && work) split6_wait_vm();
             W6P_T(ta);
-            w6p_barrier();
+            split6_barrier();
             W6P_T(tb);
             if (grp == 0 && work) {
                 if (DMA_PRIO) __builtin_amdgcn_s_setprio(DMA_PRIO);
                 issue_u(0, cs);
                 if (DMA_PRIO) __builtin_amdgcn_s_setprio(0);
-                w6p_wait_vm();
+                split6_wait_vm();
             }
             W6P_T(tc);
             W6P_ACC(3, t0, ta); W6P_ACC(4, ta, tb); W6P_ACC(5, tb, tc);
         }
         W6P_T(t8);
-        if (!last) w6p_barrier();
+        if (!last) split6_barrier();
         W6P_T(t9);
         W6P_ACC(6, t8, t9);
     }
@@ -449,10 +417,8 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + U_CHUNKS * 16) + grp * TP_DWORDS;      // this group's half tile
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int tq = jx / p.mblocks, mbq = jx % p.mblocks;               // (mblocks = M / 128 for this form)
-    const int tile = p.nt8 ? (int)(((int64_t)xcd * p.ntiles) >> 3) + tq : tq * 8 + xcd;
-    if (tile >= (p.nt8 ? (int)(((int64_t)(xcd + 1) * p.ntiles) >> 3) : p.ntiles)) return;
+    int tile, mbq;               // (mblocks = M / 128 for this form)
+    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mbq)) return;
     const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
     const int x0 = tx * TW, y0 = ty * TH, yh = y0 + PH * grp;
     const float* inb = p.in + (size_t)b * p.K * p.H * p.W;
@@ -539,30 +505,13 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
             }
         } else if (k < N_SLOT) {
             const int u = (k - P_IN) >> 2, j = (k - P_IN) & 3, i = u >> 2, c = u & 3;
+            float ve = 0.f, vo = 0.f;
             if (j == 0) {
                 const f32x4 e = rin[i][0], o = rin[i][1];
-                te = c == 0 ? e[0] - e[2] : (c == 1 ? e[1] + e[2] : (c == 2 ? e[2] - e[1] : e[1] - e[3]));
-                to = c == 0 ? o[0] - o[2] : (c == 1 ? o[1] + o[2] : (c == 2 ? o[2] - o[1] : o[1] - o[3]));
-                const f32x2 t = {te, to};
-                const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][0] = h;
-                fe = __builtin_bit_cast(float, h << 16);
-                fo = __builtin_bit_cast(float, h & 0xFFFF0000u);
-            } else if (j == 1) {
-                te -= fe; to -= fo;
-            } else if (j == 2) {
-                const f32x2 t = {te, to};
-                const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                res[i][c][1] = m;
-                fe = __builtin_bit_cast(float, m << 16);
-                fo = __builtin_bit_cast(float, m & 0xFFFF0000u);
-            } else {
-                te -= fe; to -= fo;
-                const f32x2 t = {te, to};
-                res[i][c][2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-                asm volatile("" : "+v"(res[i][c][2]));
+                ve = c == 0 ? e[0] - e[2] : (c == 1 ? e[1] + e[2] : (c == 2 ? e[2] - e[1] : e[1] - e[3]));
+                vo = c == 0 ? o[0] - o[2] : (c == 1 ? o[1] + o[2] : (c == 2 ? o[2] - o[1] : o[1] - o[3]));
             }
-            asm volatile("" : "+v"(te), "+v"(to), "+v"(fe), "+v"(fo));
+            split6_step4(j, ve, vo, te, to, fe, fo, res[i][c][0], res[i][c][1], res[i][c][2]);
         }
     };
     auto write_res = [&]() {
@@ -586,19 +535,18 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
             if (q < 3) av[slot][q] = __builtin_bit_cast(bf16x8, ul[a_chunk + ((q * 3 + ky) * 4 + c) * 128]);
             else bv[slot][q - 3] = __builtin_bit_cast(bf16x8, tl4[b_chunk + (((q - 3) * 4 + c) * PR + ky) * 2 * NP]);
         };
-        constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
 #pragma unroll
         for (int q = 0; q < 6; ++q) rd1(0, 0, q);
         if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int g = 0; g < 12; ++g) {
             const int slot = g & 1, c = g & 3;
-            if (g == 5) w6p_barrier();             // mid-phase barrier
+            if (g == 5) split6_barrier();             // mid-phase barrier
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
 #ifndef W6_SKIP_MFMA
-                acc[MSET][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[slot][PA[q]], bv[slot][PB[q]], acc[MSET][c], 0, 0, 0);
+                split6_product(q, av[slot], bv[slot], acc[MSET][c], acc[MSET][c]);
 #endif
                 if (g + 1 < 12 && q < 3) { rd1(g + 1, slot ^ 1, 2 * q); rd1(g + 1, slot ^ 1, 2 * q + 1); }
                 const int k = g * 6 + q;
@@ -617,7 +565,7 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
             }
         }
         if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        w6p_barrier();                             // end of phase
+        split6_barrier();                             // end of phase
     };
     // one phase in the staging role.  p = global phase index; image cs = (p + 1) >> 1 is the one whose half this phase renews:
     // group 1 (even p) renews Ub(cs) in FRONT of the mid-phase barrier (its partner reads it right behind), group 0 (odd p) renews
@@ -631,13 +579,13 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
 #ifndef W6_SKIP_COMMIT
         if (write) write_res();
 #endif
-        if (grp == 1 && work) w6p_wait_vm();
-        w6p_barrier();                             // mid-phase
+        if (grp == 1 && work) split6_wait_vm();
+        split6_barrier();                             // mid-phase
         if (grp == 0 && work) {
             issue_u(0, cs);
-            w6p_wait_vm();
+            split6_wait_vm();
         }
-        w6p_barrier();                             // end of phase
+        split6_barrier();                             // end of phase
     };
 
     // prologue: every group transforms and writes its half of stage 0; group 0 brings in the whole weight image 0
@@ -648,8 +596,8 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
 #pragma unroll
     for (int k = 0; k < N_SLOT; ++k) arith(k);
     write_res();
-    w6p_wait_vm();
-    w6p_barrier();
+    split6_wait_vm();
+    split6_barrier();
     int ph = 0;
     if (grp == 1) { stage(0, false); ph = 1; }
     for (int s = 0; s < nstage; ++s) {
@@ -765,24 +713,10 @@ int te_wino6_launch(float* out, const float* in, const float* U, const float* is
         a.mblocks = M / (2 * BM);
         const int64_t blocks2 = blocks_q;
         const size_t lds = (size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4;
-        static std::atomic<uint64_t> attr_done_q{0}, attr_done_qs{0};
-        if (isc) {
-            te::allow_big_lds(attr_done_qs, (const void*)wino6q_kernel<true>, 160 * 1024);
-            wino6q_kernel<true><<<dim3((unsigned)blocks2), WT, lds, s>>>(a);
-        } else {
-            te::allow_big_lds(attr_done_q, (const void*)wino6q_kernel<false>, 160 * 1024);
-            wino6q_kernel<false><<<dim3((unsigned)blocks2), WT, lds, s>>>(a);
-        }
+        SPLIT6_LAUNCH_ISC(wino6q_kernel, isc, dim3((unsigned)blocks2), WT, lds, s, a);
     } else {
         const size_t lds = (size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4;
-        static std::atomic<uint64_t> attr_done_p{0}, attr_done_ps{0};
-        if (isc) {
-            te::allow_big_lds(attr_done_ps, (const void*)wino6p_kernel<true>, 160 * 1024);
-            wino6p_kernel<true><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
-        } else {
-            te::allow_big_lds(attr_done_p, (const void*)wino6p_kernel<false>, 160 * 1024);
-            wino6p_kernel<false><<<dim3((unsigned)blocks), WT, lds, s>>>(a);
-        }
+        SPLIT6_LAUNCH_ISC(wino6p_kernel, isc, dim3((unsigned)blocks), WT, lds, s, a);
     }
     return te::launch_status("te_conv_f32(TE_CONV_3X3W6)");
 }
