@@ -521,6 +521,24 @@ int te_lpips_head_fwd_f32(float* partial, const float* f, const float* t, const 
 int te_lpips_dist_f32(float* d, const float* const* partial, const int64_t* hw, int L, int N, te_stream_t stream);
 int te_lpips_head_bwd_f32(float* gf, const float* gin, const float* gd, const float* f, const float* t, const float* w, int N, int Nt,
                           int C, int64_t HW, int relu_mask, te_stream_t stream);
+/* Paired head, forward only (metrics/evaluate_query.py:234-236: percept(image[::2], image[1::2]); replaces networks_basic.py:65-73 for
+ * both images of a pair at once).  f [2N, C, HW]: the tap activations of an interleaved batch, images 2n and 2n+1 are a pair.
+ *     partial[n, j] = sum over the j-th block of 256 pixels of
+ *                     sum_c w[c] (f[2n,c,p] / (|f[2n,:,p]| + 1e-10) - f[2n+1,c,p] / (|f[2n+1,:,p]| + 1e-10))^2,  j < te_lpips_head_blocks(HW)
+ * (the split of te_lpips_head_fwd_f32, so te_lpips_dist_f32 reduces the partials unchanged).  Both sides are normalised in the
+ * kernel; no normalised tensor is written.  Each side's f * inv is rounded before the subtraction (no contraction) and the difference
+ * is formed before squaring, so an identical pair gives exactly 0.  The channel loop is split over the block (CG = 4 slices for
+ * HW >= 256, up to 16 for HW <= 64); a pixel's squared norm is summed in fp64 (slice sums added in slice order) and 1 / (norm + eps)
+ * rounded to fp32 once, so it may differ from te_lpips_head_fwd_f32's fp32 chain in the last bit: at PPL's scale (sides 1e-4 apart)
+ * the norm's error is the largest term of the result's.  Fixed-shape reductions, no atomics: bit-reproducible. */
+int te_lpips_pair_head_fwd_f32(float* partial, const float* f, const float* w, int N, int C, int64_t HW, te_stream_t stream);
+/* Crop + bilinear resize to the LPIPS input (metrics/evaluate_query.py:222-232: image[:, :, 3c:7c, 2c:6c], then
+ * F.interpolate(size=(256, 256), mode='bilinear', align_corners=False) when the factor exceeds 1).
+ *     out [B,3,h,w] from the window [y0:y0+hc, x0:x0+wc] of img [B,3,H,W] (contiguous; the window is read in place), hc = fy * h,
+ *     wc = fx * w with integer fy, fx >= 1; per axis: src = f * (i + 0.5) - 0.5, taps floor(src) and the next sample inside the
+ *     window, weights 1 - frac and frac, x mixed first, then y (torch's upsample_bilinear2d).  f = 1 is a windowed copy. */
+int te_crop_resize_bilinear_f32(float* out, const float* img, int B, int H, int W, int y0, int x0, int hc, int wc, int h, int w,
+                                te_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * L2  noise regulariser of the projector (projector_optimization.py:21-49) over a whole list of n <= 32 noise maps [B,1,s,s]

@@ -100,6 +100,8 @@ _SIGNATURES = {
     'te_lpips_head_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
     'te_lpips_dist_f32': (C.c_int, [_P, _P, _P, _I, _I, _P]),
     'te_lpips_head_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _P]),
+    'te_lpips_pair_head_fwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _L, _P]),
+    'te_crop_resize_bilinear_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'te_noise_reg_ws_floats': (C.c_int64, [_P, _I, _I]),
     'te_noise_reg_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
     'te_noise_reg_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
@@ -829,6 +831,30 @@ def lpips_head_bwd(gd, f, t_hat, w, gin=None, relu_mask=True):
     return gf
 
 
+def lpips_pair_head_fwd(f, w):
+    """per-block partial sums [N, blocks] of one layer's head for an interleaved batch f [2N,C,H,W] (images 2n, 2n+1 are a pair)"""
+    if f.shape[0] % 2:
+        raise RuntimeError(f'te_hip: the paired LPIPS head needs an even batch, got {f.shape[0]}')
+    f = f.contiguous()
+    N, Cn, H, W = f.shape[0] // 2, f.shape[1], f.shape[2], f.shape[3]
+    nb = lib().te_lpips_head_blocks(H * W)
+    partial = torch.empty(N, nb, device=f.device, dtype=f.dtype)
+    _check(lib().te_lpips_pair_head_fwd_f32(_ptr(partial), _ptr(f), _ptr(w), N, Cn, H * W, _stream()), 'te_lpips_pair_head_fwd_f32')
+    return partial
+
+
+def crop_resize_bilinear(img, y0, x0, hc, wc, h, w):
+    """window [y0:y0+hc, x0:x0+wc] of img [B,3,H,W], bilinear (align_corners=False) to [B,3,h,w]; hc / h and wc / w integers"""
+    img = img.contiguous()
+    B, Cn, H, W = img.shape
+    if Cn != 3:
+        raise RuntimeError(f'te_hip: crop_resize_bilinear expects [B,3,H,W] images, got {tuple(img.shape)}')
+    out = torch.empty(B, 3, h, w, device=img.device, dtype=img.dtype)
+    _check(lib().te_crop_resize_bilinear_f32(_ptr(out), _ptr(img), B, H, W, y0, x0, hc, wc, h, w, _stream()),
+           'te_crop_resize_bilinear_f32')
+    return out
+
+
 # --------------------------------------------------------------------------------------------- L2 noise regulariser
 def _noise_list(maps):
     n = len(maps)
@@ -882,7 +908,7 @@ def _install_roctx():
              'small_gemm_splitk', 'small_gemm_batched', 'minibatch_stddev_fwd', 'minibatch_stddev_bwd',
              'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd', 'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd',
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
-             'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'noise_reg_fwd',
+             'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_']
     g = globals()
 

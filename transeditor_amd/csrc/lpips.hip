@@ -5,8 +5,11 @@
 //     pool   : 2x2 / stride 2 max-pool forward and backward (torch's rule: first maximum in row-major order, NaN propagates)
 //     head   : normalize_tensor, squared difference, lin weights, spatial mean (per-block partials + a fixed-order sum) and the
 //              gradient with respect to the pred features
+//     pair   : the same head for an interleaved batch of pairs, both sides normalised in the kernel, the channel loop split over
+//              the block (the PPL metric, transeditor_amd/metrics.py)
+//     crop   : window + integer-factor bilinear resize to the LPIPS input
 //
-// One thread per output pixel everywhere; every reduction is a fixed-order loop or a fixed-shape tree (no atomics).
+// One thread per output pixel everywhere except the paired head; every reduction is a fixed-order loop or a fixed-shape tree (no atomics).
 #include "te_common.h"
 
 namespace {
@@ -149,6 +152,10 @@ __device__ __forceinline__ float block_sum256(float v, float* part) {
 // head's own normalisation of the pred features agree bit for bit, so d(x, x) == 0 exactly
 __device__ __forceinline__ float norm_inv(float s) { return __fdiv_rn(1.f, __fadd_rn(__fsqrt_rn(s), kEps)); }
 
+// the paired head's form: the same quantity from an fp64 sum of squares, rounded to fp32 once.  At PPL's scale the two sides of a pair
+// differ by 1e-4 of their size, so an error of 1e-7 in a side's norm is 1e-3 of every difference at that pixel, all with one sign
+__device__ __forceinline__ float norm_inv_f64(double s) { return (float)(1.0 / (sqrt(s) + (double)kEps)); }
+
 // normalize_tensor: out = x / (sqrt(sum_c x^2) + eps)
 __global__ __launch_bounds__(256) void normalize_kernel(float* __restrict__ out, const float* __restrict__ x, int C, int64_t HW) {
     const int n = blockIdx.y;
@@ -219,6 +226,108 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(float* __restrict__ gf, c
         if (relu_mask && !(a > 0.f)) gv = 0.f;
         gn[(int64_t)c * HW] = gv;
     }
+}
+
+// Paired head (PPL, metrics/evaluate_query.py:234 through networks_basic.py:65-73): images 2n and 2n+1 of an interleaved batch are a
+// pair; both sides are normalised here, nothing normalised is stored.  A block is 16 waves over a tile of PT = min(256, HW rounded up
+// to 64) pixels: PT / 64 waves side by side along the pixels (consecutive lanes read consecutive pixels of one channel plane), the
+// other factor CG = 1024 / PT (4 at PT = 256, 16 at PT = 64; whole part) splits the channel loop.  Pass 1: each thread's sum of squares over its channel slice for
+// both sides, in fp64 -> LDS -> every thread adds the CG slices of its pixel in slice order, so all CG threads of a pixel hold the
+// same norm; 1 / (norm + eps) is rounded to fp32 once (norm_inv_f64).
+// Pass 2: the slice's terms, (a * inv_a) and (b * inv_b) each rounded, then the difference, then the square (never a^2 + b^2 - 2ab).
+// Reduction: wave shuffle tree, 16 wave sums in LDS, added in wave order by thread 0 (no atomics).
+constexpr int kPairThreads = 1024;
+
+__global__ __launch_bounds__(kPairThreads) void pair_head_kernel(float* __restrict__ partial, const float* __restrict__ f,
+                                                                 const float* __restrict__ w, int C, int64_t HW, int PT) {
+#pragma clang fp contract(off)   // as head_fwd_kernel: both products rounded before the subtraction, d(x, x) == 0
+    __shared__ double ssa[kPairThreads], ssb[kPairThreads];
+    __shared__ float part[kPairThreads / 64];
+    const int n = blockIdx.y;
+    const int CG = kPairThreads / PT;
+    const int pix = threadIdx.x % PT, cg = threadIdx.x / PT;      // PT is a multiple of 64: a wave has one cg, 64 consecutive pixels
+    const int64_t p = (int64_t)blockIdx.x * PT + pix;
+    const int cpg = (C + CG - 1) / CG;
+    const int c0 = cg * cpg, c1 = min(C, c0 + cpg);
+    const bool live = p < HW;
+    const float* fa = f + (int64_t)(2 * n) * C * HW + p;
+    const float* fb = fa + (int64_t)C * HW;
+    double sa = 0.0, sb = 0.0;
+    if (live) {
+        // squares are exact in fp64 and the sums of up to a few hundred of them round far below fp32: the norm carries no
+        // accumulation error.  Two chains per side keep loads in flight.
+        double qa[2] = {0.0, 0.0}, qb[2] = {0.0, 0.0};
+        int c = c0;
+        for (; c + 2 <= c1; c += 2) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double a = fa[(int64_t)(c + k) * HW], b = fb[(int64_t)(c + k) * HW];
+                qa[k] = fma(a, a, qa[k]);
+                qb[k] = fma(b, b, qb[k]);
+            }
+        }
+        if (c < c1) {
+            const double a = fa[(int64_t)c * HW], b = fb[(int64_t)c * HW];
+            qa[0] = fma(a, a, qa[0]);
+            qb[0] = fma(b, b, qb[0]);
+        }
+        sa = qa[0] + qa[1];
+        sb = qb[0] + qb[1];
+    }
+    ssa[threadIdx.x] = sa;
+    ssb[threadIdx.x] = sb;
+    __syncthreads();
+    float v = 0.f;
+    if (live) {
+        sa = ssa[pix];
+        sb = ssb[pix];
+        for (int g = 1; g < CG; ++g) { sa += ssa[g * PT + pix]; sb += ssb[g * PT + pix]; }
+        const float ia = norm_inv_f64(sa), ib = norm_inv_f64(sb);
+        for (int c = c0; c < c1; ++c) {
+            const float d = fa[(int64_t)c * HW] * ia - fb[(int64_t)c * HW] * ib;
+            v = fmaf(w[c] * d, d, v);      // (explicit fma: kept)
+        }
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) part[wid] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = part[0];
+        for (int k = 1; k < kPairThreads / 64; ++k) s += part[k];
+        partial[(int64_t)n * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// Window [y0, y0+hc) x [x0, x0+wc) of img [B,3,H,W] resampled by the integer factor fy = hc / h, fx = wc / w with the arithmetic of
+// F.interpolate(mode='bilinear', align_corners=False) applied to the window alone (upsample_bilinear2d: src = scale * (dst + 0.5) - 0.5
+// clamped at 0, second tap i0 + 1 unless i0 is the window's last row / column, weights l1 = src - i0, l0 = 1 - l1; rows first mixed
+// along x, then along y).  Factor 1: src = dst, l1 = 0, a windowed copy.  One thread per output pixel, lanes along x.
+__device__ __forceinline__ void bilinear_tap(int dst, int factor, int in_size, int& i0, int& i1, float& l0, float& l1) {
+    float src = (float)factor * ((float)dst + 0.5f) - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    i0 = (int)src;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    l1 = src - (float)i0;
+    l0 = 1.f - l1;
+}
+
+__global__ __launch_bounds__(256) void crop_resize_kernel(float* __restrict__ out, const float* __restrict__ img, int H, int W, int y0,
+                                                          int x0, int hc, int wc, int h, int w) {
+#pragma clang fp contract(off)
+    const int64_t plane = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)h * w) return;
+    const int oy = (int)(i / w), ox = (int)(i % w);
+    int ya, yb, xa, xb;
+    float ly0, ly1, lx0, lx1;
+    bilinear_tap(oy, hc / h, hc, ya, yb, ly0, ly1);
+    bilinear_tap(ox, wc / w, wc, xa, xb, lx0, lx1);
+    const float* src = img + plane * H * W + (int64_t)y0 * W + x0;
+    const float* ra = src + (int64_t)ya * W;
+    const float* rb = src + (int64_t)yb * W;
+    out[plane * h * w + i] = ly0 * (lx0 * ra[xa] + lx1 * ra[xb]) + ly1 * (lx0 * rb[xa] + lx1 * rb[xb]);
 }
 
 struct DistArgs {
@@ -314,4 +423,27 @@ extern "C" int te_lpips_dist_f32(float* d, const float* const* partial, const in
     }
     dist_kernel<<<(unsigned)te::cdiv(N, 64), 64, 0, (hipStream_t)stream>>>(d, a, L, N);
     return te::launch_status("te_lpips_dist_f32");
+}
+
+static int pair_tile(int64_t HW) { return HW >= 256 ? 256 : (int)(te::cdiv(HW, 64) * 64); }
+
+extern "C" int te_lpips_pair_head_fwd_f32(float* partial, const float* f, const float* w, int N, int C, int64_t HW, te_stream_t stream) {
+    TE_REQUIRE(partial && f && w, TE_ERR_NULL, "te_lpips_pair_head_fwd_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && C > 0 && HW > 0 && N < 65536, TE_ERR_SHAPE, "te_lpips_pair_head_fwd_f32: bad dims");
+    const int PT = pair_tile(HW);
+    // one partial per 256 pixels: the split of te_lpips_head_blocks, so te_lpips_dist_f32 adds them as it adds the unpaired head's
+    pair_head_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), kPairThreads, 0, (hipStream_t)stream>>>(partial, f, w, C, HW, PT);
+    return te::launch_status("te_lpips_pair_head_fwd_f32");
+}
+
+extern "C" int te_crop_resize_bilinear_f32(float* out, const float* img, int B, int H, int W, int y0, int x0, int hc, int wc, int h,
+                                           int w, te_stream_t stream) {
+    TE_REQUIRE(out && img, TE_ERR_NULL, "te_crop_resize_bilinear_f32: NULL pointer");
+    TE_REQUIRE(B > 0 && B < 21845 && H > 0 && W > 0 && h > 0 && w > 0, TE_ERR_SHAPE, "te_crop_resize_bilinear_f32: bad dims");
+    TE_REQUIRE(y0 >= 0 && x0 >= 0 && hc > 0 && wc > 0 && (int64_t)y0 + hc <= H && (int64_t)x0 + wc <= W, TE_ERR_SHAPE,
+               "te_crop_resize_bilinear_f32: window [%d:%d+%d, %d:%d+%d] outside %dx%d", y0, y0, hc, x0, x0, wc, H, W);
+    TE_REQUIRE(hc % h == 0 && wc % w == 0, TE_ERR_SHAPE, "te_crop_resize_bilinear_f32: the window must be an integer multiple of the output");
+    crop_resize_kernel<<<dim3((unsigned)te::cdiv((int64_t)h * w, 256), 3 * B), 256, 0, (hipStream_t)stream>>>(out, img, H, W, y0, x0, hc,
+                                                                                                             wc, h, w);
+    return te::launch_status("te_crop_resize_bilinear_f32");
 }

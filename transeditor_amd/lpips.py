@@ -5,6 +5,7 @@ utils/lpips/__init__.py:12-39, dist_model.py:55-67 and :90, networks_basic.py:21
     d = percept(pred, target)                      # [N,1,1,1]; target of batch 1 broadcasts over pred
     tf = percept.target_features(target)           # a fixed target through the trunk once ...
     d = percept(pred, tf)                          # ... and reused: bit-identical to percept(pred, target)
+    d = percept.pair_distance(images)              # [2N,3,H,W] -> [N]: images 2n and 2n+1, forward only (the PPL metric)
 
 Weights come from local files only (nothing is downloaded, torchvision is not imported): `vgg_path` is a torchvision vgg16 state
 dict (features.{0,2,...,28}.{weight,bias}), `lin_path` the LPIPS v0.1 head file (lin{0..4}.model.1.weight [1,C,1,1]).  The trunk is
@@ -188,6 +189,29 @@ class PerceptualLoss(torch.nn.Module):
         target = target.detach().contiguous()
         acts = self._trunk(target)
         return TargetFeatures([_lib.lpips_normalize(acts[i]) for i in TAPS], tuple(target.shape))
+
+    @torch.no_grad()
+    def pair_distance(self, images, normalize=False):
+        """[2N,3,H,W] -> [N]: the distance of images 2n and 2n+1 (metrics/evaluate_query.py:234: percept(image[::2], image[1::2])).
+        Forward only.  The trunk runs once over the interleaved batch; an activation is dropped once its tap's head and the next
+        layer have read it; the heads normalise both sides themselves (te_lpips_pair_head_fwd_f32), so no normalised features are
+        stored."""
+        if images.ndim != 4 or images.shape[1] != 3 or images.shape[0] % 2:
+            raise ValueError(f'PerceptualLoss.pair_distance: expected [2N,3,H,W] images, got {tuple(images.shape)}')
+        if images.shape[2] % 16 or images.shape[3] % 16:
+            raise ValueError(f'PerceptualLoss: H and W must be multiples of 16, got {images.shape[2]}x{images.shape[3]}')
+        if normalize:
+            images = 2 * images - 1
+        a = _lib.lpips_stem_fwd(images.detach(), self._w(0), self.b0)
+        partials, hws = [], []
+        for i in range(1, 13):
+            if (i - 1) in POOL_AFTER:
+                a = _lib.maxpool2_fwd(a)
+            a = self._conv_fwd(i, a)
+            if i in TAPS:
+                partials.append(_lib.lpips_pair_head_fwd(a, self._lin(TAPS.index(i))))
+                hws.append(a.shape[2] * a.shape[3])
+        return _lib.lpips_dist(partials, hws)
 
     def forward(self, pred, target, normalize=False):
         """[N,1,1,1]: the reference calls model.forward(target, pred); the squared difference is symmetric"""
