@@ -557,6 +557,32 @@ int te_noise_reg_bwd_f32(float* const* grads, float* tws, const float* gloss, co
                          int n, int B, te_stream_t stream);
 int te_noise_normalize_f32(float* const* maps, const int* sizes, int n, int B, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M1  precision / recall / density / coverage (metrics/prdc.py) of two feature sets x [N,D] (real) and y [M,D] (fake), fp32 row-major.
+ * Every comparison is made on SQUARED distances
+ *     d2(i,j) = max(nx[i] + ny[j] - 2 dot(x_i, y_j), 0),      nx / ny = the fp32 squared row norms,
+ * with the dot product on the fp32-input MFMA (one fp32 fma chain in a fixed order of k, so dot(a, b) == dot(b, a) bit for bit).  No
+ * N x M matrix is ever written: the reductions run in the epilogue of the 128 x 128 GEMM tile, per-tile partials go to the caller's
+ * workspace and a second fixed-order kernel combines them.  No atomics; bit-reproducible.  Any D >= 1 (the k tail is zero-filled; the
+ * 16-byte load path needs D % 4 == 0 and 16-byte aligned bases, anything else takes scalar loads), 1 <= k <= 15.
+ *   te_prdc_ws_bytes   : bytes of workspace that serve te_prdc_knn_f32 on N rows, on M rows, and te_prdc_counts_f32 on N x M:
+ *                        O((N + M) * number of 128-wide tile columns); negative on bad arguments
+ *   te_row_sqnorm_f32  : out[i] = sum_k x[i,k]^2
+ *   te_prdc_knn_f32    : r2[i] = element k of the ascending row {d2(i,j) : j < N} of the set against itself, the diagonal forced to
+ *                        exactly 0 (prdc.py:41-51: the k+1 smallest of pairwise_distances(X, X), whose diagonal sklearn zeroes);
+ *                        duplicates count separately.  N >= k + 1
+ *   te_prdc_counts_f32 : col_count[j] = #{i : d2(i,j) < rr2[i]}   (prdc.py:75-78 as > 0: precision; :85-88: density)
+ *                        row_any[i]   = any_j d2(i,j) < rf2[j]    (:80-83: recall)
+ *                        row_min[i]   = min_j d2(i,j)             (:90-93: coverage, against rr2[i])
+ *                        rr2 [N] / rf2 [M]: the squared radii of the real / fake set; both comparisons strict.  col_count and
+ *                        row_any are int32.
+ */
+int64_t te_prdc_ws_bytes(int N, int M, int D, int k);
+int te_row_sqnorm_f32(float* out, const float* x, int N, int D, te_stream_t stream);
+int te_prdc_knn_f32(float* r2, const float* x, const float* nx, int N, int D, int k, void* ws, te_stream_t stream);
+int te_prdc_counts_f32(int32_t* col_count, int32_t* row_any, float* row_min, const float* x, const float* nx, const float* rr2,
+                       const float* y, const float* ny, const float* rf2, int N, int M, int D, void* ws, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

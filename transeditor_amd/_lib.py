@@ -106,6 +106,10 @@ _SIGNATURES = {
     'te_noise_reg_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
     'te_noise_reg_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     'te_noise_normalize_f32': (C.c_int, [_P, _P, _I, _I, _P]),
+    'te_prdc_ws_bytes': (C.c_int64, [_I, _I, _I, _I]),
+    'te_row_sqnorm_f32': (C.c_int, [_P, _P, _I, _I, _P]),
+    'te_prdc_knn_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    'te_prdc_counts_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -896,6 +900,56 @@ def noise_normalize_(maps):
     _check(lib().te_noise_normalize_f32(ptrs, sizes, n, B, _stream()), 'te_noise_normalize_f32')
 
 
+# --------------------------------------------------------------------------------------------- M1 PRDC
+def _features(t, what):
+    if t.ndim != 2:
+        raise RuntimeError(f'te_hip: {what} expects [N,D] features, got {tuple(t.shape)}')
+    _ptr(t)
+    return t.shape
+
+
+def _prdc_ws(N, M, D, k, device):
+    nb = lib().te_prdc_ws_bytes(N, M, D, k)
+    if nb < 0:
+        raise RuntimeError(f'te_prdc_ws_bytes failed ({nb}) for N={N}, M={M}, D={D}, k={k}: 1 <= k <= 15 and at least k + 1 rows per set')
+    return torch.empty(nb // 4, device=device, dtype=torch.float32)
+
+
+def row_sqnorm(x):
+    """[N,D] -> the squared row norms [N]"""
+    N, D = _features(x, 'row_sqnorm')
+    out = torch.empty(N, device=x.device, dtype=torch.float32)
+    _check(lib().te_row_sqnorm_f32(_ptr(out), _ptr(x), N, D, _stream()), 'te_row_sqnorm_f32')
+    return out
+
+
+def prdc_knn(x, nx, k):
+    """squared distance of every row of x [N,D] to its k-th nearest other row (element k of the sorted row, diagonal 0) -> [N]"""
+    N, D = _features(x, 'prdc_knn')
+    if nx.shape != (N,):
+        raise RuntimeError(f'te_hip: prdc_knn expects {N} row norms, got {tuple(nx.shape)}')
+    ws = _prdc_ws(N, N, D, k, x.device)
+    r2 = torch.empty(N, device=x.device, dtype=torch.float32)
+    _check(lib().te_prdc_knn_f32(_ptr(r2), _ptr(x), _ptr(nx), N, D, k, _ptr(ws), _stream()), 'te_prdc_knn_f32')
+    return r2
+
+
+def prdc_counts(x, nx, rr2, y, ny, rf2):
+    """real x [N,D], fake y [M,D], their row norms and squared radii -> (col_count [M] int32, row_any [N] int32, row_min [N])"""
+    N, D = _features(x, 'prdc_counts')
+    M, Dy = _features(y, 'prdc_counts')
+    if Dy != D or nx.shape != (N,) or rr2.shape != (N,) or ny.shape != (M,) or rf2.shape != (M,):
+        raise RuntimeError(f'te_hip: prdc_counts: inconsistent shapes x {tuple(x.shape)}, y {tuple(y.shape)}, nx {tuple(nx.shape)}, '
+                           f'rr2 {tuple(rr2.shape)}, ny {tuple(ny.shape)}, rf2 {tuple(rf2.shape)}')
+    ws = _prdc_ws(N, M, D, 1, x.device)
+    col_count = torch.empty(M, device=x.device, dtype=torch.int32)
+    row_any = torch.empty(N, device=x.device, dtype=torch.int32)
+    row_min = torch.empty(N, device=x.device, dtype=torch.float32)
+    _check(lib().te_prdc_counts_f32(_ptr_as(col_count, torch.int32), _ptr_as(row_any, torch.int32), _ptr(row_min), _ptr(x), _ptr(nx),
+                                    _ptr(rr2), _ptr(y), _ptr(ny), _ptr(rf2), N, M, D, _ptr(ws), _stream()), 'te_prdc_counts_f32')
+    return col_count, row_any, row_min
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -909,7 +963,7 @@ def _install_roctx():
              'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd', 'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd',
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
-             'noise_reg_bwd', 'noise_normalize_']
+             'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts']
     g = globals()
 
     def wrap(fn, name):

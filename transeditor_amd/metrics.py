@@ -13,8 +13,8 @@ Differences from the reference, all deliberate:
   - the distances stay on the device until the run ends (no host synchronisation inside the loop);
   - the reference hard-codes 10000 samples in batches of 64 inside evaluate_ppl (:142-143) whatever the command line says; here they
     are arguments with those defaults (--ppl_n_sample, --batch);
-  - FID, PRDC and the AlexNet LPIPS diversity score are not built (they need networks and weights this library does not have):
-    --fid / --lpips exit with a message.
+  - FID and the AlexNet LPIPS diversity score are not built (they need networks and weights this library does not have):
+    --fid / --lpips exit with a message.  PRDC is built on given features: transeditor_amd.prdc.
 """
 import argparse
 import json
