@@ -1,10 +1,11 @@
-"""Compare the gfx950 machine code of the split-bf16 kernels between two source trees (a refactor's "same code" check; no GPU needed).
+"""Compare the gfx950 machine code of the library's kernels between two source trees (a refactor's "same code" check; no GPU needed).
 
-    python tools/isa_compare.py PARENT_TREE BRANCH_TREE [-o profiles/NAME.txt] [--keep DIR]
+    python tools/isa_compare.py PARENT_TREE BRANCH_TREE [-o profiles/NAME.txt] [--keep DIR] [-D NAME[=VALUE] ...]
 
-Both trees are compiled with build.py's flags plus --save-temps; for every kernel of wino6 / s2s6 / t2s6 / p1s6 / wgrad6 the table gives
-registers, scratch, LDS, occupancy, instruction counts by class (parent | branch) and whether the instruction streams are identical after
-dropping comments, directives and the function number inside local labels.  Exit status 1 if any kernel differs.
+Both trees are compiled with build.py's flags plus --save-temps (and every -D given, e.g. a profiler build of both); for every kernel of
+every source in build.py's SOURCES the table gives registers, scratch, LDS, occupancy, instruction counts by class (parent | branch) and
+whether the instruction streams are identical after dropping comments, directives and the function number inside local labels.  Exit
+status 1 if any kernel differs.
 """
 import argparse
 import os
@@ -14,9 +15,9 @@ import sys
 import tempfile
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-from transeditor_amd.build import EXTRA_FLAGS, FLAGS, _hipcc  # noqa: E402
+from transeditor_amd.build import EXTRA_FLAGS, FLAGS, SOURCES, _hipcc  # noqa: E402
 
-FILES = ['wino6', 's2s6', 't2s6', 'p1s6', 'wgrad6']
+FILES = [s[:-len('.hip')] for s in SOURCES]
 RES = [('VGPR', r'; NumVgprs: (\d+)'), ('AGPR', r'; NumAgprs: (\d+)'), ('SGPR', r'; TotalNumSgprs: (\d+)'),
        ('scratch', r'; ScratchSize: (\d+)'), ('LDS', r'; LDSByteSize: (\d+)'), ('occ', r'; Occupancy: (\d+)')]
 CLASSES = [('MFMA', r'v_mfma'), ('ds_read', r'ds_read|ds_load'), ('ds_write', r'ds_write|ds_store'), ('gload_lds', r'global_load_lds|buffer_load.* lds'),
@@ -24,12 +25,12 @@ CLASSES = [('MFMA', r'v_mfma'), ('ds_read', r'ds_read|ds_load'), ('ds_write', r'
            ('s_barrier', r's_barrier')]
 
 
-def compile_tree(tree, out):
+def compile_tree(tree, out, defines=()):
     os.makedirs(out, exist_ok=True)
     procs = []
     for f in FILES:
         src = os.path.join(os.path.abspath(tree), 'transeditor_amd', 'csrc', f + '.hip')
-        cmd = [_hipcc(), *FLAGS, *EXTRA_FLAGS.get(f + '.hip', []), '--save-temps', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', f + '.o']
+        cmd = [_hipcc(), *FLAGS, *EXTRA_FLAGS.get(f + '.hip', []), *('-D' + d for d in defines), '--save-temps', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', f + '.o']
         procs.append((f, subprocess.Popen(cmd, cwd=out, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     for f, p in procs:
         log, _ = p.communicate()
@@ -72,15 +73,16 @@ def main():
     ap.add_argument('branch')
     ap.add_argument('-o', '--output')
     ap.add_argument('--keep', help='directory for the compiler outputs (default: a temporary one)')
+    ap.add_argument('-D', dest='defines', action='append', default=[], metavar='NAME[=VALUE]', help='extra define for both trees')
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         base = a.keep or tmp
         sides = []
         for tag, tree in (('parent', a.parent), ('branch', a.branch)):
-            compile_tree(tree, os.path.join(base, tag))
+            compile_tree(tree, os.path.join(base, tag), a.defines)
             sides.append(kernels(os.path.join(base, tag)))
     par, br = sides
-    lines = ['machine code of the split-bf16 kernels, parent | branch (build.py flags + --save-temps, gfx950)', '']
+    lines = ['machine code of the library\'s kernels, parent | branch (build.py flags' + ''.join(' -D' + d for d in a.defines) + ' + --save-temps, gfx950)', '']
     ndiff = 0
     for name in sorted(set(par) | set(br)):
         if name not in par or name not in br:

@@ -7,7 +7,7 @@ per kernel: launches, HIP-event time per launch, algorithmic and executed TFLOP/
 clock, the power cap.
 
     python tools/power_probe.py                         # the product library
-    VARIANT=mfma_only python tools/power_probe.py       # tools/exp/libte_<name>.so (tools/exp_build.py mfma_only -DW6_SKIP_COMMIT)
+    VARIANT=name python tools/power_probe.py            # tools/exp/libte_<name>.so (a variant built by tools/exp_build.py)
 """
 import math
 import os

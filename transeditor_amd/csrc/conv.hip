@@ -30,6 +30,16 @@
 //        receives only the taps with ky = a (mod 2), kx = b (mod 2) -> 4+2+2+1 = 9 tap-GEMMs per cell,
 //        i.e. exactly the FLOPs of the zero-insertion-free transposed convolution.
 #include "conv_common.h"
+// experimental builds.  TE_CONV_PROF: per-phase cycle counts of every wave of the FAST kernels (tools/conv_phase_prof.py);
+// TE_CONV_PROF2: whole-block timeline of ANY kernel form on the 100 MHz s_memrealtime counter: entry, K loop start / end, exit
+// (tools/conv_timeline.py).  Both are read back with te_debug_conv_prof.
+#ifdef TE_CONV_PROF
+#define TE_PROF
+#endif
+#ifdef TE_CONV_PROF2
+#define TE_PROF2
+#endif
+#include "te_prof.h"
 
 namespace {
 
@@ -37,49 +47,15 @@ namespace {
 // 32-row M blocks and NBW 32-cell blocks; KC input channels per stage; NSP staging sweeps for the input tile.
 //   TC 0: M >= 96 -> block 128 (M) x 128 cells      TC 1: M ~ 64 -> 64 x 256 cells      TC 2: M <= 32 -> 32 x 256 cells
 // (narrow layers of the 512 / 1024 px generators, ToRGB fallbacks) so the MFMA rows are not padded 2-4x with zeros.
-#ifndef T2KC0
-#define T2KC0 16
-#endif
-// build knobs for A/B measurements (tools/exp_build.py); the defaults are the product
-#ifndef TE_CONV_FAST         // 0: never dispatch to the FAST kernels
-#define TE_CONV_FAST 1
-#endif
-#ifndef TE_CONV_XCD          // XCD-aware block -> (tile, M block) mapping (0: M block major, as the plain 2-D grid did)
-#define TE_CONV_XCD 1
-#endif
-#ifndef TE_CONV_FAST_NARROW  // FAST kernels for the 64- and 32-row tile classes too (narrow layers of the 512 / 1024 px models)
-#define TE_CONV_FAST_NARROW 1
-#endif
-#ifndef TE_CONV_DEEP1X1      // 0: never pick the deep-stage 1x1 class
-#define TE_CONV_DEEP1X1 1
-#endif
-#ifndef TE_FAST_PF           // LDS operands of step s+1 are read before the MFMAs of step s
-#define TE_FAST_PF 1
-#endif
-#ifndef TE_FAST_IL           // the global loads of the next stage are spread over the MFMA steps of this one
-#define TE_FAST_IL 1
-#endif
-#if defined(TE_CONV_PROF) || defined(TE_CONV_PROF2)
-// experimental builds: per-phase cycle counts of wave 0 of every block (s_memtime), read back with te_debug_conv_prof
-__device__ unsigned long long te_conv_prof_buf[8192 * 8];
-#endif
-#ifdef TE_CONV_PROF
-#define PROF_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#else
-#define PROF_T(v)
-#endif
-#ifdef TE_CONV_PROF2         // whole-block timeline of ANY kernel form (100 MHz s_memrealtime): entry, K loop start / end, exit
-#define PROF2_T(v) const unsigned long long v = __builtin_amdgcn_s_memrealtime()
-#else
-#define PROF2_T(v)
-#endif
+constexpr int T2_KC0 = 16;       // channels per stage of the transposed kind at the 64 x 128 tile class
+PROF_BUFFER(conv, 8192 * 8)
 template <int KIND, int TC> struct Cfg;
 template <int KIND> struct Cfg<KIND, 0> { static constexpr int WM = 2, MBW = 2, NBW = 2, KC = 8, NSP = (KIND == TE_CONV_S2) ? 3 : (KIND == TE_CONV_3X3 ? 2 : 1), NQ = (KIND == TE_CONV_S2) ? 5 : 2; };
 template <int KIND> struct Cfg<KIND, 1> { static constexpr int WM = 2, MBW = 1, NBW = (KIND == TE_CONV_S2) ? 2 : 4, KC = 8, NSP = (KIND == TE_CONV_S2) ? 3 : (KIND == TE_CONV_3X3 ? 2 : 1), NQ = (KIND == TE_CONV_S2) ? 5 : 4; };
 template <int KIND> struct Cfg<KIND, 2> { static constexpr int WM = 1, MBW = 1, NBW = 2, KC = 8, NSP = (KIND == TE_CONV_S2) ? 5 : (KIND == TE_CONV_3X3 ? 2 : 1), NQ = (KIND == TE_CONV_S2) ? 10 : 4; };
 // transposed conv: 4 phase accumulators per cell block -> 64 x 128 cells per block and 16 channels per stage keep the
 // MFMA work per staged weight byte equal to the plain 3x3 kernel; 32 x 128 cells for narrow outputs
-template <> struct Cfg<TE_CONV_T2, 0> { static constexpr int WM = 2, MBW = 1, NBW = 2, KC = T2KC0, NSP = 1, NQ = 3; };
+template <> struct Cfg<TE_CONV_T2, 0> { static constexpr int WM = 2, MBW = 1, NBW = 2, KC = T2_KC0, NSP = 1, NQ = 3; };
 template <> struct Cfg<TE_CONV_T2, 1> { static constexpr int WM = 2, MBW = 1, NBW = 1, KC = 16, NSP = 1, NQ = 2; };
 template <> struct Cfg<TE_CONV_T2, 2> { static constexpr int WM = 1, MBW = 1, NBW = 1, KC = 16, NSP = 1, NQ = 3; };
 // 1x1 with deep stages (FAST only: 64 channels per stage = 128 MFMAs per wave and stage instead of 16; the skip convolutions
@@ -177,7 +153,6 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
     // through one L2 - 1628 -> 664 MB read for the 128 -> 128 @256^2 launch, profiles/experiments/r04_xcd_band_ab.log), then
     // the short edge tiles of T2 interleaved (tile q * 8 + x: every XCD gets its share of the cheap tiles, and they come last
     // for every M block, which is what a greedy dispatcher wants at the tail); a tile id past the end exits.
-#if TE_CONV_XCD
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
     const int tq = jx / p.mblocks, mblk = jx % p.mblocks;
     int tile_id;
@@ -188,9 +163,6 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
         tile_id = p.nt8 ? p.nbody + (tq - p.nt8) * 8 + xcd : tq * 8 + xcd;
         if (tile_id >= p.ntiles) return;
     }
-#else
-    const int tile_id = blockIdx.x % p.ntiles, mblk = blockIdx.x / p.ntiles;
-#endif
     const int ridx = (p.nreg > 1 && tile_id >= p.reg[1].first_block) + (p.nreg > 2 && tile_id >= p.reg[2].first_block);
     const ConvArgs::Region g = p.reg[ridx];
     int t = tile_id - g.first_block;
@@ -433,7 +405,7 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
     // queues 25 loads at the texture addresser at once and the last of them has time to land before the commit
     auto compute_fast = [&](const float* wlb, const float* xlb, int kn) {
         constexpr int NSTEP = (KC / 2) * NTAP;
-        constexpr int SPAN = TE_FAST_IL ? (NSTEP * 3) / 4 : 1;     // steps that carry loads
+        constexpr int SPAN = (NSTEP * 3) / 4;                      // steps that carry loads
         auto pieces = [&](int st) {
 #pragma unroll
             for (int i = 0; i < NPIECE; ++i)
@@ -444,17 +416,13 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
             operands(wlb, xlb, 0, 0, a0, b0);
 #pragma unroll
             for (int st = 0; st < NSTEP; ++st) {
-                const int kk = (st / NTAP) * 2, tp = st % NTAP;
+                const int tp = st % NTAP;
                 float a1[MBW], b1[NBW];
-                if (TE_FAST_PF) {
-                    if (st + 1 < NSTEP) operands(wlb, xlb, ((st + 1) / NTAP) * 2, (st + 1) % NTAP, a1, b1);
-                } else {
-                    operands(wlb, xlb, kk, tp, a0, b0);
-                }
+                if (st + 1 < NSTEP) operands(wlb, xlb, ((st + 1) / NTAP) * 2, (st + 1) % NTAP, a1, b1);
                 pieces(st);
                 __builtin_amdgcn_sched_barrier(0);
                 mfmas(tp, a0, b0);
-                if (TE_FAST_PF && st + 1 < NSTEP) {
+                if (st + 1 < NSTEP) {
 #pragma unroll
                     for (int mb = 0; mb < MBW; ++mb) a0[mb] = a1[mb];
 #pragma unroll
@@ -517,53 +485,41 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
         // of the next one are dealt out (the last iteration re-requests its own stage: never committed, always in range)
 #pragma unroll
         for (int i = 0; i < NPIECE; ++i) load_piece(kbeg, i);
-#ifdef TE_CONV_PROF
-        unsigned long long pc[5] = {0, 0, 0, 0, 0};
-        const unsigned long long pstart = __builtin_readcyclecounter();
-        const unsigned long long rstart = __builtin_amdgcn_s_memrealtime();
-#endif
+        PROF_ONLY(unsigned long long pc[5] = {0, 0, 0, 0, 0};)
+        PROF_T(pstart);
+        PROF_ONLY(const unsigned long long rstart = __builtin_amdgcn_s_memrealtime();)
         for (int k0 = kbeg; k0 < kend; k0 += KC) {
             PROF_T(t0);
             __syncthreads();              // every wave finished reading the previous stage
             PROF_T(t1);
-#ifdef TE_CONV_PROF
-            __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): separate "waiting for the stage loads" from the LDS writes
-            const unsigned long long t1b = __builtin_readcyclecounter();
-            pc[4] += t1b - t1;
-#endif
+            PROF_ONLY(__builtin_amdgcn_s_waitcnt(0x0F70);)      // vmcnt(0): separate "waiting for the stage loads" from the LDS writes
+            PROF_T(t1b);
+            PROF_ACC(pc[4], t1, t1b);
             commit(wl, xl);
             PROF_T(t2);
             __syncthreads();
             PROF_T(t3);
             compute_fast(wl, xl, min(k0 + KC, kend - KC));
-#ifdef TE_CONV_PROF
-            const unsigned long long t4 = __builtin_readcyclecounter();
-            pc[0] += t1 - t0; pc[1] += t2 - t1; pc[2] += t3 - t2; pc[3] += t4 - t3;
-#endif
+            PROF_T(t4);
+            PROF_ACC(pc[0], t0, t1); PROF_ACC(pc[1], t1, t2); PROF_ACC(pc[2], t2, t3); PROF_ACC(pc[3], t3, t4);
         }
-#ifdef TE_CONV_PROF
-        const int lin = blockIdx.x + gridDim.x * blockIdx.z;
+        PROF_ONLY(const int lin = blockIdx.x + gridDim.x * blockIdx.z;
         if ((tid & 63) == 0 && lin < 8192 / 4) {
             unsigned long long* d = te_conv_prof_buf + ((size_t)lin * 4 + wid) * 8;
             d[0] = pc[0]; d[1] = pc[1]; d[2] = pc[2]; d[3] = pc[3]; d[4] = pstart; d[5] = __builtin_readcyclecounter();
             d[6] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
             d[7] = (kend - kbeg) / KC; d[6] = pc[4];
             d[0] = pc[0] + (((unsigned long long)(__builtin_amdgcn_s_memrealtime() - rstart)) << 32);   // high half: 100 MHz ticks of the K loop
-        }
-#endif
+        })
     } else {
         // software pipeline: iteration `k0` commits stage k0 (prefetched by the previous iteration) to LDS, issues the
         // global loads of stage k0+KC, then runs the MFMAs of stage k0 while those loads are in flight.
-#ifdef TE_CONV_PROF2
-        unsigned long long qa = 0, qb = 0, qc = 0, qw = 0;
-#endif
+        PROF2_ONLY(unsigned long long qa = 0, qb = 0, qc = 0, qw = 0;)
         for (int k0 = kbeg - KC; k0 < kend; k0 += KC) {
             PROF2_T(s0);
             if (k0 >= kbeg) {
                 __syncthreads();              // every wave finished reading the previous stage
-#ifdef TE_CONV_PROF2
-                { PROF2_T(w0); __builtin_amdgcn_s_waitcnt(0x0F70); qw += __builtin_amdgcn_s_memrealtime() - w0; }   // vmcnt(0): waiting for the stage loads
-#endif
+                PROF2_ONLY({ PROF2_T(w0); __builtin_amdgcn_s_waitcnt(0x0F70); qw += __builtin_amdgcn_s_memrealtime() - w0; })   // vmcnt(0): waiting for the stage loads
                 commit(wl, xl);
                 __syncthreads();
             }
@@ -571,21 +527,15 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
             const int kn = k0 + KC;
             if (kn < kend) issue(kn);
             PROF2_T(s2);
-#ifdef TE_CONV_PROF2
-            qa += s1 - s0; qb += s2 - s1;
-#endif
+            PROF2_ONLY(qa += s1 - s0; qb += s2 - s1;)
             if (k0 < kbeg) continue;
             compute(wl, xl);
-#ifdef TE_CONV_PROF2
-            qc += __builtin_amdgcn_s_memrealtime() - s2;
-#endif
+            PROF2_ONLY(qc += __builtin_amdgcn_s_memrealtime() - s2;)
         }
-#ifdef TE_CONV_PROF2
-        if (tid == 0) {
+        PROF2_ONLY(if (tid == 0) {
             const int lin = blockIdx.x + gridDim.x * blockIdx.z;
             if (lin < 8192) { unsigned long long* d = te_conv_prof_buf + (size_t)lin * 8; d[5] = qa | (qw << 32); d[6] = qb | (qc << 32); }
-        }
-#endif
+        })
     }
 
     PROF2_T(q2);
@@ -712,15 +662,13 @@ __global__ __launch_bounds__(NTHREADS, OCC) void conv_mfma_kernel(const ConvArgs
             }
         }
     }
-#ifdef TE_CONV_PROF2
-    {
+    PROF2_ONLY({
         const int lin = blockIdx.x + gridDim.x * blockIdx.z;
         if (tid == 0 && lin < 8192) {
             unsigned long long* d = te_conv_prof_buf + (size_t)lin * 8;
             d[0] = q0; d[1] = q1; d[2] = q2; d[3] = __builtin_amdgcn_s_memrealtime(); d[4] = (kend - kbeg) / KC; d[7] = 1;
         }
-    }
-#endif
+    })
 }
 
 // epilogue of the split-K path: out = act((sum_z ws[z] | out) * osc[b,m] + bias[m]); the slabs are summed in fixed order
@@ -980,11 +928,6 @@ int add_region(ConvArgs& a, int ri0, int rj0, int rh, int rw, int& nblocks, size
     return 0;
 }
 
-#ifndef TE_CONV_OCC
-#define TE_CONV_OCC 3
-#endif
-constexpr int conv_occ() { return TE_CONV_OCC; }      // waves per SIMD the plain 3x3 128-row tile is compiled for (2: 135.7 vs 140.1 TFLOP/s with the FAST kernel)
-
 template <int KIND, int TC, bool HAS_ISC, bool MS, int OCC, bool FAST, bool EPI>
 void launch_f(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s) {
     constexpr int BM = tile_bm<KIND, TC>();
@@ -995,15 +938,11 @@ void launch_f(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s) 
     b.nbody = (a.nreg > 1) ? a.reg[1].first_block : nblocks;
     b.nt8 = te::xcd_banded() ? (int)te::cdiv(b.nbody, 8) : 0;
     const int64_t per_xcd = b.nt8 ? b.nt8 + te::cdiv(nblocks - b.nbody, 8) : te::cdiv(nblocks, 8);
-#if TE_CONV_XCD
     dim3 grid((unsigned)(per_xcd * 8 * b.mblocks), 1u, (unsigned)a.ksplit);
-#else
-    dim3 grid((unsigned)(nblocks * b.mblocks), 1u, (unsigned)a.ksplit);
-#endif
     conv_mfma_kernel<KIND, TC, HAS_ISC, MS, OCC, FAST, EPI><<<grid, NTHREADS, lds_floats * sizeof(float), s>>>(b);
 }
 
-template <int KIND, int TC> constexpr bool have_fast() { return TE_CONV_FAST && (TC == 3 || ((TC == 0 || TE_CONV_FAST_NARROW) && KIND != TE_CONV_1X1)); }
+template <int KIND, int TC> constexpr bool have_fast() { return TC == 3 || KIND != TE_CONV_1X1; }
 
 template <int KIND, int TC, bool HAS_ISC, bool MS, int OCC, bool EPI>
 void launch_o(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s, bool fast) {
@@ -1015,9 +954,10 @@ void launch_o(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s, 
 template <int KIND, int TC, bool HAS_ISC, bool MS, bool EPI = false>
 void launch_t(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s, bool fast) {
     // 3 waves/SIMD variant only for the plain 3x3 at the 128-row tile (the only one whose register budget is near 168); the
-    // epilogue-stage variants take the 2-wave budget (their extra loads do not fit 168 registers)
+    // epilogue-stage variants take the 2-wave budget (their extra loads do not fit 168 registers).  (Compiled for 2 waves the plain 3x3
+    // 128-row tile measured 135.7 against 140.1 TFLOP/s with the FAST kernel.)
     constexpr bool CAN3 = ((KIND == TE_CONV_3X3 && TC == 0 && !MS) || (KIND == TE_CONV_T2 && TC == 1 && !MS));
-    if (CAN3 && conv_occ() == 3) launch_o<KIND, TC, HAS_ISC, MS, CAN3 ? 3 : 2, EPI>(a, nblocks, lds_floats, s, fast);
+    if (CAN3) launch_o<KIND, TC, HAS_ISC, MS, CAN3 ? 3 : 2, EPI>(a, nblocks, lds_floats, s, fast);
     else launch_o<KIND, TC, HAS_ISC, MS, 2, EPI>(a, nblocks, lds_floats, s, fast);
 }
 
@@ -1078,16 +1018,8 @@ int launch_regions(const ConvArgs& a, const int (*regions)[4], int n, hipStream_
 
 }  // namespace
 
-#if defined(TE_CONV_PROF) || defined(TE_CONV_PROF2)
-extern "C" int te_debug_conv_prof(void* host_dst, int64_t bytes) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(te_conv_prof_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int te_debug_conv_prof_clear() {
-    void* dptr = nullptr;
-    if (hipGetSymbolAddress(&dptr, HIP_SYMBOL(te_conv_prof_buf)) != hipSuccess) return -1;
-    return (int)hipMemset(dptr, 0, sizeof(te_conv_prof_buf));
-}
-#endif
+PROF_READBACK(conv)
+PROF_CLEAR(conv)
 
 extern "C" int64_t te_conv_packed_numel(int kind_pack, int Co, int Ci, int ksize) {
     const PackDims d = pack_dims(kind_pack, Co, Ci, ksize);
@@ -1159,18 +1091,11 @@ static int pack_launch(const char* what, int n, float* const* wp, const float* c
 }
 
 // transposed conv on images up to this many cells per side runs as ONE padded (H+1) x (W+1) region; larger ones as body +
-// last column + last row (build knob for A/B measurements; round 3: 16 -> 8, the 8x8 -> 17x17 layer filled 42 % of its
-// padded tiles: 152 -> 106 us at 512 -> 512, batch 16)
-#ifndef TE_T2_PAD_LIMIT
-#define TE_T2_PAD_LIMIT 8
-#endif
-
-#ifndef TE_SPLITK_MINSTAGES      // build knobs of the split-K plan: fewest stages a split keeps, blocks per CU it aims at
-#define TE_SPLITK_MINSTAGES 4
-#endif
-#ifndef TE_SPLITK_BLOCKS
-#define TE_SPLITK_BLOCKS 2
-#endif
+// last column + last row (round 3: 16 -> 8, the 8x8 -> 17x17 layer filled 42 % of its padded tiles: 152 -> 106 us at
+// 512 -> 512, batch 16)
+constexpr int T2_PAD_LIMIT = 8;
+// the split-K plan: fewest stages a split keeps, blocks per CU it aims at
+constexpr int SPLITK_MINSTAGES = 4, SPLITK_BLOCKS = 2;
 
 // tile class + split-K plan of a launch (shared by te_conv_splitk_count and the launch itself)
 struct ConvPlan { int tc, ksplit, kchunk; };
@@ -1181,30 +1106,28 @@ static ConvPlan conv_plan(int kind, int B, int K, int M, int H, int W) {
     int tc = tile_class(M);
     // transposed conv on small images (<= 1024 of the 64 x 128 tiles): the 64 x 64 tile class fits 3 waves per SIMD and
     // gives the chip more, shorter blocks (512->512 @32: 87 -> 100 TFLOP/s, @16: 57 -> 83)
-#ifndef TE_T2_TC1_LIMIT
-#define TE_T2_TC1_LIMIT (1024 * 128)
-#endif
-    if (t2k && tc == 0 && (int64_t)B * H * W * te::cdiv(M, 64) <= (int64_t)TE_T2_TC1_LIMIT) tc = 1;
+    constexpr int T2_TC1_LIMIT = 1024 * 128;
+    if (t2k && tc == 0 && (int64_t)B * H * W * te::cdiv(M, 64) <= (int64_t)T2_TC1_LIMIT) tc = 1;
     // (narrower tile classes for the 4x4 / 8x8 layers were measured and lose: 3x3 512->512 @4x4 65 -> 112 (64 rows) / 119 us (32 rows),
     // profiles/experiments/r03_tiny_tile_class.log)
     pl.tc = tc;
-    const int KC = t2k ? (tc == 0 ? T2KC0 : 16) : 8;
+    const int KC = t2k ? (tc == 0 ? T2_KC0 : 16) : 8;
     const int BM = t2k ? (tc == 2 ? 32 : 64) : (tc == 0 ? 128 : (tc == 1 ? 64 : 32));
     // split the channel loop when the image is too small to give every CU a tile (4x4 ... 16x16 layers); the
     // split count comes from the real tile geometry of the main region and is shared by every region of the launch
     const int ntile = t2k ? (tc == 1 ? 64 : 128) : ((tc == 0 || (kind == TE_CONV_S2 && tc == 1)) ? 128 : 256);      // cells per block tile of the chosen tile class
     int rh = H, rw = W;
-    if (t2k && (W + 1 <= TE_T2_PAD_LIMIT || H + 1 <= TE_T2_PAD_LIMIT)) { rh = H + 1; rw = W + 1; }
+    if (t2k && (W + 1 <= T2_PAD_LIMIT || H + 1 <= T2_PAD_LIMIT)) { rh = H + 1; rw = W + 1; }
     const int TW = std::min(32, pow2ceil(rw)), TH = std::min(pow2ceil(rh), ntile / TW), NS = ntile / (TW * TH);
     const int64_t base_blocks = (int64_t)te::cdiv(rw, TW) * te::cdiv(rh, TH) * te::cdiv(B, NS) * te::cdiv(M, BM);
     const int stages = Kp / KC;
     int ks = 1;
-    if (base_blocks < te::kNumCU) ks = (int)std::min<int64_t>(te::cdiv(TE_SPLITK_BLOCKS * te::kNumCU, base_blocks), std::max(1, stages / TE_SPLITK_MINSTAGES));
+    if (base_blocks < te::kNumCU) ks = (int)std::min<int64_t>(te::cdiv(SPLITK_BLOCKS * te::kNumCU, base_blocks), std::max(1, stages / SPLITK_MINSTAGES));
     pl.ksplit = std::max(1, ks);
     pl.kchunk = (int)te::cdiv(stages, pl.ksplit) * KC;
     pl.ksplit = (int)te::cdiv(Kp, pl.kchunk);
     // 1x1 on images that fill the chip, channel count a multiple of 64: the deep-stage FAST class
-    if (TE_CONV_FAST && TE_CONV_DEEP1X1 && kind == TE_CONV_1X1 && tc == 0 && pl.ksplit == 1 && NS == 1 && K % 64 == 0) pl.tc = 3;
+    if (kind == TE_CONV_1X1 && tc == 0 && pl.ksplit == 1 && NS == 1 && K % 64 == 0) pl.tc = 3;
     return pl;
 }
 
@@ -1275,7 +1198,7 @@ extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const flo
         } break;
         default: {      // TE_CONV_T2
             a.Hi = H; a.Wi = W; a.Ho = 2 * H + 1; a.Wo = 2 * W + 1;
-            if (W + 1 <= TE_T2_PAD_LIMIT || H + 1 <= TE_T2_PAD_LIMIT) {
+            if (W + 1 <= T2_PAD_LIMIT || H + 1 <= T2_PAD_LIMIT) {
                 const int r[1][4] = {{0, 0, H + 1, W + 1}};                       // small images: one padded region
                 rc = launch_regions<TE_CONV_T2>(a, r, 1, s, tc);
             } else {

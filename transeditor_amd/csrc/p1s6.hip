@@ -126,20 +126,16 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const int i = q * 2 + n;                             // MFMA index inside the k step (12)
-#ifndef P1_SKIP_MFMA
                     split6_product(q, av[ks & 1], bv[ks & 1][n], acc[MSET][n], acc[MSET][n]);
-#endif
                     if (ks + 1 < NKS && i < 9) {                         // operands of the next k step: 3 + 6 reads
                         if (i < 3) rd_a(ks + 1, i);
                         else rd_b(ks + 1, (i - 3) / 3, (i - 3) % 3);
                     }
-#ifndef P1_SKIP_ARITH
                     {
                         const int k = ks * 12 + i;                       // 0 .. 47
                         if (k < 32) arith(32 * MSET + k);
                         if (k == 34) fetch_half(MSET, fs);
                     }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
         }
@@ -153,9 +149,7 @@ __global__ __launch_bounds__(WT, 2) void p1s6_kernel(const P1Args p) {
         const int cs = (ph >> 1) + 1;
         if (cs < nimg) issue_u(ph & 1, cs);
         __builtin_amdgcn_sched_barrier(0);
-#ifndef P1_SKIP_ARITH
         if (write) write_res();
-#endif
         split6_wait_vm();     // (also waits for the fetch of the next stage issued in this group's last multiplying phase: long landed)
         split6_barrier();                                    // end of phase
     };

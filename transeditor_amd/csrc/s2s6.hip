@@ -21,6 +21,10 @@
 // Every input element of the tile is inside the image (2 (H - 1) + 2 = 2 H: no padding, no edge cases); the epilogue is the direct
 // kernel's (demodulation scale, bias, leaky ReLU, residual, mask).
 #include "split6_common.h"
+#ifdef S2_PROF       // experimental builds: per-wave cycle counts of the phases, read back with te_debug_s2s6_prof (tools/s2s6_phase_prof.py)
+#define TE_PROF
+#endif
+#include "te_prof.h"
 
 namespace {
 
@@ -39,18 +43,7 @@ constexpr int N_SLOT = P_IN + 16 * P_IN;                      // arithmetic slot
 constexpr int SLOT0 = NTAP * 6 - N_SLOT;                      // the program starts behind MFMA 3
 constexpr int UA_TAPS = 5;                                    // taps 0-4: weight half a (30 slots), taps 5-8: half b (24 slots)
 
-#ifdef S2_PROF       // experimental builds: per-wave cycle counts of the phases, read back with te_debug_s2s6_prof (tools/s2s6_phase_prof.py)
-__device__ unsigned long long te_s2s6_prof_buf[2048 * 8 * 8];
-#define S2_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define S2_ACC(i, a, b) pc[i] += (b) - (a)
-#else
-#define S2_T(v)
-#define S2_ACC(i, a, b)
-#endif
-
-#ifndef DMA_PRIO
-#define DMA_PRIO 0         // experiment: the staging wave raises its priority while it issues the weight DMA (wino6.hip)
-#endif
+PROF_BUFFER(s2s6, 2048 * 8 * 8)
 
 struct S2Args {
     float* out; const float* in; const u32x4* U; const float* isc; const float* osc; const float* bias; const float* res;
@@ -201,13 +194,11 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
     }
     split6_barrier();
     const int nphase = 2 * nstage;
-#ifdef S2_PROF
-    unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long pstart = __builtin_readcyclecounter(), rstart = __builtin_amdgcn_s_memrealtime();
-#endif
+    PROF_ONLY(unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};)
+    PROF_ONLY(const unsigned long long pstart = __builtin_readcyclecounter(), rstart = __builtin_amdgcn_s_memrealtime();)
     for (int ph = 0; ph < nphase; ++ph) {
         const bool last = ph == nphase - 1;
-        S2_T(t0);
+        PROF_T(t0);
         if ((ph & 1) == grp) {
             // ---- multiply this group's half of stage ph / 2; behind the MFMAs: the arithmetic of the stage after (rin -> res)
             bf16x8 av[2][3], bv[2][3];
@@ -223,22 +214,14 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
 #pragma unroll
             for (int t = 0; t < NTAP; ++t) {
                 const int slot = t & 1;
-#ifdef S2_PROF
-                if (t == UA_TAPS - 1) { S2_T(ta); split6_barrier(); S2_T(tb); S2_ACC(0, t0, ta); S2_ACC(1, ta, tb); pc[2] -= tb; }
-#else
-                if (t == UA_TAPS - 1) split6_barrier();    // mid-phase barrier: in front of tap 4's MFMAs (operands read) and of the first read of half b
-#endif
+                // mid-phase barrier: in front of tap 4's MFMAs (operands read) and of the first read of half b
+                if (t == UA_TAPS - 1) { PROF_T(ta); split6_barrier(); PROF_T(tb); PROF_ACC(pc[0], t0, ta); PROF_ACC(pc[1], ta, tb); PROF_ONLY(pc[2] -= tb;) }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < 6; ++q) {
-#ifndef ST_SKIP_MFMA     // (experiment switches ST_*: timing decomposition only, results are wrong)
                     split6_product(q, av[slot], bv[slot], acc, accl);
-#endif
                     if (t + 1 < NTAP && q < 3) { rd1(t + 1, slot ^ 1, 2 * q); rd1(t + 1, slot ^ 1, 2 * q + 1); }
-#ifndef ST_NO_ARITH
                     arith(t * 6 + q - SLOT0);
-#endif
-#ifndef ST_NO_FETCH
                     {   // the fetch of the stage after next: an item's loads right behind the last slot that reads its registers
                         const int k = t * 6 + q - SLOT0;
                         if (k == P_IN - 1) fetch_scales(fs2);
@@ -246,14 +229,11 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
                         for (int i = 0; i < P_IN; ++i)
                             if (k == P_IN + 16 * i + 12) fetch_item(i, fs2);
                     }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
-#ifdef S2_PROF
-            { asm volatile("s_nop 0" ::: "memory"); S2_T(tc); pc[2] += tc; }
-#endif
+            PROF_ONLY({ asm volatile("s_nop 0" ::: "memory"); PROF_T(tc); pc[2] += tc; })
         } else {
             // ---- stage: move this group's half of stage cs = (ph + 1) / 2 to LDS, fetch stage cs + 1, renew a half of the weight image
             const int cs = (ph + 1) >> 1;
@@ -262,44 +242,32 @@ __global__ __launch_bounds__(WT, 2) void s2s6_kernel(const S2Args p) {
             // writes of this half tile in its shadow, then the wait for the DMA; group 0 renews half a behind the barrier.  The LDS
             // writes are unconditional: in group 1's first phase they repeat what the prologue wrote, in group 0's last phase they
             // put stale results in a tile nobody reads any more.
-#ifndef ST_NO_DMA
-            if (DMA_PRIO) __builtin_amdgcn_s_setprio(DMA_PRIO);
             if (work && grp == 1) issue_u(1, cs);
-            if (DMA_PRIO) __builtin_amdgcn_s_setprio(0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
-#ifndef ST_NO_DSW
             write_res();
-#endif
             if (work && grp == 1) split6_wait_vm();
-            S2_T(ta);
+            PROF_T(ta);
             split6_barrier();
-            S2_T(tb);
-#ifndef ST_NO_DMA
+            PROF_T(tb);
             if (work && grp == 0) {
-                if (DMA_PRIO) __builtin_amdgcn_s_setprio(DMA_PRIO);
                 issue_u(0, cs);
-                if (DMA_PRIO) __builtin_amdgcn_s_setprio(0);
                 split6_wait_vm();
             }
-#endif
-            S2_T(tc);
-            S2_ACC(3, t0, ta); S2_ACC(4, ta, tb); S2_ACC(5, tb, tc);
+            PROF_T(tc);
+            PROF_ACC(pc[3], t0, ta); PROF_ACC(pc[4], ta, tb); PROF_ACC(pc[5], tb, tc);
         }
-        S2_T(t8);
+        PROF_T(t8);
         if (!last) split6_barrier();
-        S2_T(t9);
-        S2_ACC(6, t8, t9);
+        PROF_T(t9);
+        PROF_ACC(pc[6], t8, t9);
     }
-#ifdef S2_PROF
-    if (lane == 0 && blockIdx.x < 2048) {
+    PROF_ONLY(if (lane == 0 && blockIdx.x < 2048) {
         unsigned long long* d = te_s2s6_prof_buf + ((size_t)blockIdx.x * 8 + wid) * 8;
-#pragma unroll
+        _Pragma("unroll")
         for (int i = 0; i < 6; ++i) d[i] = pc[i];
         d[6] = pc[6] | ((__builtin_amdgcn_s_memrealtime() - rstart) << 40);
         d[7] = ((unsigned long long)nstage << 48) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFFFull);
-    }
-#endif
+    })
     // epilogue: the direct kernel's stages (demodulation scale, bias, leaky ReLU, residual, mask)
     const int mbase = mb * BM + wm * 32;
     const size_t off0 = ((size_t)b * p.M + mbase) * oplane + (size_t)(yh + 2 * wrl + rr) * p.W + x0 + jj;
@@ -568,11 +536,7 @@ __global__ __launch_bounds__(WT, 2) void s2s6q_kernel(const S2Args p) {
 
 }  // namespace
 
-#ifdef S2_PROF
-extern "C" int te_debug_s2s6_prof(void* host_dst, int64_t bytes) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(te_s2s6_prof_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-}
-#endif
+PROF_READBACK(s2s6)
 
 extern "C" int te_conv_s2s6_supported(int B, int K, int M, int H, int W) {
     if (!(B > 0 && K >= 32 && K % KC == 0 && M >= BM && M % BM == 0 && H >= TH && H % TH == 0 && W >= TWO && W % TWO == 0)) return 0;

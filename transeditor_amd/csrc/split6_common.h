@@ -1,7 +1,7 @@
 // Shared by the six-product split-bf16 kernels (wino6.hip, s2s6.hip, t2s6.hip, p1s6.hip, wgrad6.hip): what carries the
 // numeric contract of the family - the three-piece split and the order of the six piece products - and the pieces of
 // plumbing every file used to re-declare (vector types, barrier pair, XCD-banded tile decode, the big-LDS launch).  A kernel file keeps
-// its tile geometry, its LDS layout, its phase schedule and its experiment switches.
+// its tile geometry, its LDS layout and its phase schedule; the phase-profiler plumbing is te_prof.h.
 #pragma once
 #include "conv_common.h"
 

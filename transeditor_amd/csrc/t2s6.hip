@@ -30,6 +30,10 @@
 // r06_t2s6_check_double_buffered.log): the kernel sits at the part's power limit, the saved cycles came back as a lower clock.  Kept for
 // the simpler protocol.  (s2s6.hip keeps the half-by-half protocol: two of its 54 KB images do not fit beside its 61 KB of half tiles.)
 #include "split6_common.h"
+#ifdef T2_PROF       // experimental builds: per-wave cycle counts of the phases, read back with te_debug_t2s6_prof (tools/s2s6_phase_prof.py)
+#define TE_PROF
+#endif
+#include "te_prof.h"
 
 namespace {
 
@@ -47,18 +51,7 @@ constexpr int N_SLOT = 1 + 16;                                // arithmetic slot
 constexpr int SLOT0 = 24;                                     // MFMA behind which the program starts (54 per phase)
 constexpr int UA_TAPS = 5;                                    // taps 0-4: weight half a (30 slots), taps 5-8: half b (24 slots)
 
-#ifdef T2_PROF       // experimental builds: per-wave cycle counts of the phases, read back with te_debug_t2s6_prof (tools/s2s6_phase_prof.py)
-__device__ unsigned long long te_t2s6_prof_buf[2048 * 8 * 8];
-#define T2_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define T2_ACC(i, a, b) pc[i] += (b) - (a)
-#else
-#define T2_T(v)
-#define T2_ACC(i, a, b)
-#endif
-
-#ifndef DMA_PRIO
-#define DMA_PRIO 0         // experiment: the staging wave raises its priority while it issues the weight DMA (wino6.hip)
-#endif
+PROF_BUFFER(t2s6, 2048 * 8 * 8)
 
 struct T2Args {
     float* out; const float* in; const u32x4* U; const float* isc; const float* osc; const float* bias; int act;
@@ -200,13 +193,11 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
     }
     split6_barrier();
     const int nphase = 2 * nstage;
-#ifdef T2_PROF
-    unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long pstart = __builtin_readcyclecounter(), rstart = __builtin_amdgcn_s_memrealtime();
-#endif
+    PROF_ONLY(unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};)
+    PROF_ONLY(const unsigned long long pstart = __builtin_readcyclecounter(), rstart = __builtin_amdgcn_s_memrealtime();)
     for (int ph = 0; ph < nphase; ++ph) {
         const bool last = ph == nphase - 1;
-        T2_T(t0);
+        PROF_T(t0);
         if ((ph & 1) == grp) {
             // ---- multiply this group's half of stage ph / 2; behind the MFMAs: the arithmetic of the stage after (rin -> res)
             bf16x8 av[2][3], bv[2][3];
@@ -226,55 +217,41 @@ __global__ __launch_bounds__(WT, 2) void t2s6_kernel(const T2Args p) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int qq = 0; qq < 6; ++qq) {
-#ifndef ST_SKIP_MFMA     // (experiment switches ST_*: timing decomposition only, results are wrong)
                     split6_product(qq, av[slot], bv[slot], acc[c], acc[c]);
-#endif
                     if (t + 1 < NTAP && qq < 3) { rd1(t + 1, slot ^ 1, 2 * qq); rd1(t + 1, slot ^ 1, 2 * qq + 1); }
-#ifndef ST_NO_ARITH
                     arith(t * 6 + qq - SLOT0, sa);
-#endif
-#ifndef ST_NO_FETCH
                     if (t * 6 + qq - SLOT0 == 0) fetch_scales(fs2);          // the fetch of the stage after next (see fetch_item)
                     if (t * 6 + qq - SLOT0 == 13) fetch_item(fs2);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
-#ifdef T2_PROF
-            { asm volatile("s_nop 0" ::: "memory"); T2_T(tc); T2_ACC(0, t0, tc); }
-#endif
+            PROF_ONLY({ asm volatile("s_nop 0" ::: "memory"); PROF_T(tc); PROF_ACC(pc[0], t0, tc); })
         } else {
             // ---- stage: move this group's half of stage (ph + 1) / 2 to LDS; bring in this group's part (ph & 1: group 1 part 0 in even
             // phases, group 0 part 1 in odd ones) of the weights of stage (ph >> 1) + 1, into the buffer stage (ph >> 1) - 1 was read
             // from (last read in phase ph - 1 / ph - 2); waited for at the end of THIS phase.  The LDS writes are unconditional (s2s6.hip).
             const int cw = (ph >> 1) + 1;
-#ifndef ST_NO_DMA
             if (cw < nstage) issue_u(ph & 1, cw);
-#endif
             __builtin_amdgcn_sched_barrier(0);
-#ifndef ST_NO_DSW
             write_res();
-#endif
-            T2_T(ta);
+            PROF_T(ta);
             split6_wait_vm();
-            T2_T(tb);
-            T2_ACC(3, t0, ta); T2_ACC(4, ta, tb);
+            PROF_T(tb);
+            PROF_ACC(pc[3], t0, ta); PROF_ACC(pc[4], ta, tb);
         }
-        T2_T(t8);
+        PROF_T(t8);
         if (!last) split6_barrier();
-        T2_T(t9);
-        T2_ACC(6, t8, t9);
+        PROF_T(t9);
+        PROF_ACC(pc[6], t8, t9);
     }
-#ifdef T2_PROF
-    if (lane == 0 && blockIdx.x < 2048) {
+    PROF_ONLY(if (lane == 0 && blockIdx.x < 2048) {
         unsigned long long* d = te_t2s6_prof_buf + ((size_t)blockIdx.x * 8 + wid) * 8;
-#pragma unroll
+        _Pragma("unroll")
         for (int i = 0; i < 6; ++i) d[i] = pc[i];
         d[6] = pc[6] | ((__builtin_amdgcn_s_memrealtime() - rstart) << 40);
         d[7] = ((unsigned long long)nstage << 48) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFFFull);
-    }
-#endif
+    })
     // epilogue: demodulation scale, bias, leaky ReLU; phases (a, 0) and (a, 1) of a cell are adjacent output columns: one 8-byte store
     const int mbase = mb * BM + wm * 32;
     const int ci = yh + 2 * wrl + rr, cj = x0 + jj;
@@ -670,11 +647,7 @@ __global__ __launch_bounds__(ET) void t2_edge_kernel(const T2EdgeArgs p) {
 
 }  // namespace
 
-#ifdef T2_PROF
-extern "C" int te_debug_t2s6_prof(void* host_dst, int64_t bytes) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(te_t2s6_prof_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-}
-#endif
+PROF_READBACK(t2s6)
 
 extern "C" int te_conv_t2s6_supported(int B, int K, int M, int H, int W) {
     if (!(B > 0 && K >= 32 && K % KC == 0 && M >= BM && M % BM == 0 && H >= TH && H % TH == 0 && W >= TWC && W % TWC == 0)) return 0;

@@ -36,20 +36,12 @@ struct FirParams {
 // every shared line crosses the fabric twice (measured round 2: 1.38x - 1.66x the algorithmic traffic).  Here the j-th
 // block of XCD x takes tile j % T of plane group x + 8 * (j / T): all tiles of a plane run on ONE XCD at about the same
 // time and share those lines through its L2; a block then walks the planes pg, pg + zgroups, ... as before.
-#ifndef TE_FIR_XCD          // build knob for A/B measurements (tools/exp_build.py): 0 = tile-major ids, as the 3-D grid had them
-#define TE_FIR_XCD 1
-#endif
 struct TileId { int bx, by, pg; };
 __device__ __forceinline__ TileId xcd_tile(const FirParams& p) {
     const int T = p.tiles_x * p.tiles_y;
-#if TE_FIR_XCD
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
     const int t = j % T;
     return TileId{t % p.tiles_x, t / p.tiles_x, xcd + 8 * (j / T)};
-#else
-    const int t = blockIdx.x % T;
-    return TileId{t % p.tiles_x, t / p.tiles_x, (int)(blockIdx.x / T)};
-#endif
 }
 inline unsigned xcd_grid(FirParams& p, int tiles_x, int tiles_y, int64_t z) {
     p.tiles_x = tiles_x; p.tiles_y = tiles_y;

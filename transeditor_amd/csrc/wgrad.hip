@@ -17,6 +17,10 @@
 // (32 different channels, same position) hit 32 different banks.
 #include "te_common.h"
 #include <stdlib.h>
+#ifdef TE_CONV_PROF  // experimental builds: per-phase cycle counts of every wave, read back with te_debug_wgrad_prof (tools/conv_phase_prof.py)
+#define TE_PROF
+#endif
+#include "te_prof.h"
 
 namespace {
 
@@ -61,13 +65,7 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned of
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 
-#ifdef TE_CONV_PROF
-// experimental builds: per-phase cycle counts (s_memtime) of every wave, read back with te_debug_wgrad_prof
-__device__ unsigned long long te_wgrad_prof_buf[8192 * 8];
-#define WPROF(i) { const unsigned long long t_ = __builtin_readcyclecounter(); pc[i] += t_ - tlast; tlast = t_; }
-#else
-#define WPROF(i)
-#endif
+PROF_BUFFER(wgrad, 8192 * 8)
 
 // WINO (3x3 only): the cells of a stage are taken as horizontal PAIRS and the three taps of a kernel row come out of FOUR
 // products per pair instead of six - the 1-D Winograd form F(3,2), the transpose of the F(2,3) the forward kernel (wino.hip)
@@ -145,11 +143,9 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
     const int t_begin = (int)((int64_t)n_tiles * s_chunk / p.S), t_end = (int)((int64_t)n_tiles * (s_chunk + 1) / p.S);
 
     float preg[NP], qreg[NQ];
-#ifdef TE_CONV_PROF
-    unsigned long long pc[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long tlast = __builtin_readcyclecounter();
-    const unsigned long long pstart = tlast;
-#endif
+    PROF_ONLY(unsigned long long pc[6] = {0, 0, 0, 0, 0, 0};)
+    PROF_ONLY(unsigned long long tlast = __builtin_readcyclecounter();)
+    PROF_ONLY(const unsigned long long pstart = tlast;)
     // ---- tile loop, double-buffered LDS (two [plain | shifted] operand images, <= 2 x 68 KB): while the MFMAs of tile t run
     // on one image, tile t+1 (already in registers) is written to the other and the loads of tile t+2 are issued, so a
     // tile costs ONE workgroup barrier and no phase in which the matrix pipe waits for staging.
@@ -407,7 +403,7 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
     // two barriers per tile, so that several blocks share a CU instead
     constexpr bool DB = (KIND != TE_CONV_1X1) && (NWP == 4);
     for (int tl = t_begin; tl < t_end; ++tl) {
-        WPROF(5)
+        PROF_LAP(pc[5]);
         float* cur = smem + (DB ? ((tl - t_begin) & 1) * bufsz : 0);
         float* nxt = smem + (DB ? (((tl - t_begin) & 1) ^ 1) * bufsz : 0);
         const float* g_l = cur + g_off;
@@ -415,15 +411,15 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
         first_operands(g_l, x_l);
         if (DB) {
             steps(g_l, x_l, kw, ks1);
-            WPROF(4)
+            PROF_LAP(pc[4]);
             if (tl + 1 < t_end) commit(nxt, nxt + PCH * p.PS);      // tile tl+1: loaded while tile tl-1 was multiplied
-            WPROF(1)
+            PROF_LAP(pc[1]);
             steps(g_l, x_l, ks1, ks2);
-            WPROF(4)
+            PROF_LAP(pc[4]);
             if (tl + 2 < t_end) issue(tl + 2);
-            WPROF(3)
+            PROF_LAP(pc[3]);
             steps(g_l, x_l, ks2, nks);
-            WPROF(4)
+            PROF_LAP(pc[4]);
         } else {
             steps(g_l, x_l, kw, nks);
             __syncthreads();                // everyone is done reading the image
@@ -431,10 +427,9 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
             if (tl + 2 < t_end) issue(tl + 2);
         }
         __syncthreads();                    // everyone is done reading `cur` and writing `nxt`
-        WPROF(0)
+        PROF_LAP(pc[0]);
     }
-#ifdef TE_CONV_PROF
-    {
+    PROF_ONLY({
         const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
         if (lane == 0 && lin * (NTHREADS / 64) + wid < 8192) {
             unsigned long long* d = te_wgrad_prof_buf + ((size_t)lin * (NTHREADS / 64) + wid) * 8;
@@ -442,8 +437,7 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
             d[6] = __builtin_readcyclecounter() - pstart;
             d[7] = t_end - t_begin;
         }
-    }
-#endif
+    })
 
     if constexpr (NWP == 2) {
         if (kstride > 1) {        // block-uniform: combine the K-split partial tiles, one round per extra share
@@ -893,11 +887,7 @@ inline int reduce_w_nchunk(int B, int S, int64_t E, bool vec) {
 
 }  // namespace
 
-#ifdef TE_CONV_PROF
-extern "C" int te_debug_wgrad_prof(void* host_dst, int64_t bytes) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(te_wgrad_prof_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-}
-#endif
+PROF_READBACK(wgrad)
 
 extern "C" int te_wgrad_split_bf16(int on);
 extern "C" int te_wgrad_split_supported(int kind, int Co, int Ci, int H, int W);
@@ -919,10 +909,8 @@ extern "C" int te_wgrad_slab_count(int kind, int B, int Co, int Ci, int H, int W
     // blocks per CU the split aims at: the 8-wave 3x3 / T2 blocks own a CU (two 68 KB operand images), so ONE round of them
     // does the same work as two with half the slab bytes for the reducer (same-box A/B, round 3: +0.8 % / +1.2 % on the
     // kernels, half the te_wgrad_reduce traffic of the narrow layers); the light 1x1 blocks share a CU and want two
-#ifndef TE_WGRAD_ROUNDS
-#define TE_WGRAD_ROUNDS ((kind == TE_CONV_1X1) ? 2 : 1)
-#endif
-    int64_t S = te::cdiv((int64_t)TE_WGRAD_ROUNDS * te::kNumCU, mn);
+    const int rounds = (kind == TE_CONV_1X1) ? 2 : 1;
+    int64_t S = te::cdiv((int64_t)rounds * te::kNumCU, mn);
     S = std::max<int64_t>(1, std::min<int64_t>(S, tiles));
     return (int)S;
 }

@@ -25,6 +25,10 @@
 // registers loaded during step y - 1, and the loads of the rows after that are issued at the head of the step: every global load
 // has a whole step (>= 2 300 cycles) to land.  One workgroup barrier per step.
 #include "split6_common.h"
+#ifdef WG6_PROF      // experimental builds: cycle counts per wave, read back with te_debug_wgrad6_prof (tools/wgrad6_check.py prof)
+#define TE_PROF
+#endif
+#include "te_prof.h"
 
 namespace {
 
@@ -73,15 +77,8 @@ __device__ __forceinline__ void wg6_segment(const Wg6Chunk& c, int k, int S, int
     } else { t0 = (int)((int64_t)n_steps * c.s / S); t1 = (int)((int64_t)n_steps * (c.s + 1) / S); }
 }
 
-#ifndef WG6_ILV
-#define WG6_ILV 1    // 1: consecutive MFMAs on different accumulators (see the MFMA loop); 0: six in a row per accumulator (A/B: same time)
-#endif
-#ifndef WG6_SLOT0
-#define WG6_SLOT0 0  // MFMA behind which the 64-slot staging program starts (72 MFMAs per step)
-#endif
-#ifdef WG6_PROF      // experimental builds: cycle counts per wave (tools/wgrad6_check.py prof)
-__device__ unsigned long long te_wgrad6_prof_buf[2048 * 4 * 4];
-#endif
+constexpr int SLOT0 = 0;  // MFMA behind which the 64-slot staging program of wgrad6_kernel starts (72 MFMAs per step)
+PROF_BUFFER(wgrad6, 2048 * 4 * 4)
 
 // PAIR (round 6; Co == Ci == 32, NB == 1, B even - the 32-channel 3x3 layer at 1024^2 of the FFHQ-1024 generator, reference channel table
 // model_spatial_query.py:473-483): the 64 lanes of a staging wave are the 32 channels of sample 2 k (lanes 0-31) and the 32 channels of
@@ -200,11 +197,9 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
     const int n_steps = sps * (PAIR ? 1 : p.NB);
     const int a_elem = half * TC + wco * 32 + l31;            // + ((piece * 4 + j) * 2) * 64 + image * IMG
     const int b_elem = half * TC + wci * 32 + l31;
-#ifdef WG6_PROF
-    unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;
-    const unsigned long long pstart = __builtin_readcyclecounter();
-    int nstep_done = 0;
-#endif
+    PROF_ONLY(unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;)
+    PROF_T(pstart);
+    PROF_ONLY(int nstep_done = 0;)
 
     float rw[NRAW], rn[NRAW];
     for (int sg = 0; sg < ck.nseg; ++sg) {
@@ -214,9 +209,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
         const int bb = t / sps, rem = t - bb * sps, cx = rem / p.H, ya = rem - cx * p.H;
         const int n = min(p.H - ya, t_end - t), yb = ya + n;
         t += n;
-#ifdef WG6_PROF
-        const unsigned long long th0 = __builtin_readcyclecounter();
-#endif
+        PROF_T(th0);
         // ---- head of a sweep: input rows ya - 1, ya, ya + 1 and gradient row ya, then the registers of the first step
         {
             float r0[NRAW], r1[NRAW];
@@ -234,13 +227,10 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
             for (int i = 0; i < NRAW; ++i) asm volatile("" :: "v"(rw[i]));
         }
         split6_barrier();
-#ifdef WG6_PROF
-        pc_head += __builtin_readcyclecounter() - th0;
-#endif
+        PROF_T(th1);
+        PROF_ACC(pc_head, th0, th1);
         for (int y = ya; y < yb; ++y) {
-#ifdef WG6_PROF
-            const unsigned long long tm0 = __builtin_readcyclecounter();
-#endif
+            PROF_T(tm0);
             // registers of the step after next: input row y + 3 / gradient row y + 2 (a whole step to land)
             load_raw(rn, bb, cx, role ? y + 3 : y + 2);
             const int w_img = role ? x_img(y + 2) : g_img(y + 1);           // image this lane's results of the step go to
@@ -248,10 +238,9 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
             int b_base[3];
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) b_base[ky] = x_img(y - 1 + ky) * IMG + b_elem;
-#if WG6_ILV
             // MFMA order inside a component: product q of the three tap rows in turn, so that consecutive MFMAs write DIFFERENT
             // accumulators (an accumulator is touched every third instruction; each one still sees its six products in the order
-            // mm, hl, lh, hm, mh, hh).  Measured against six in a row into one accumulator (WG6_ILV=0): 3 419 against 3 465 cycles per
+            // mm, hl, lh, hm, mh, hh).  Measured against six in a row into one accumulator: 3 419 against 3 465 cycles per
             // step - the dependent accumulate chain is not what holds the stream at ~48 cycles per MFMA (the staging program is).
             bf16x8 av[2][3], bv[2][3][3];
             auto rd_a = [&](int j, int pc) { av[j & 1][pc] = __builtin_bit_cast(bf16x8, lds[a_base + (pc * 4 + j) * 2 * TC]); };
@@ -269,77 +258,35 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
 #pragma unroll
                 for (int m = 0; m < 18; ++m) {
                     const int q = m / 3, ky = m % 3;
-#ifndef WG6_SKIP_MFMA
                     if (active) acc[ky * 4 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[j & 1][PA[q]], bv[j & 1][ky][PB[q]], acc[ky * 4 + j], 0, 0, 0);
-#endif
                     if (j + 1 < 4 && m < 12) {                                            // operands of the next component: 12 reads
                         if (m < 3) rd_a(j + 1, m);
                         else rd_b(j + 1, (m - 3) / 3, (m - 3) % 3);
                     }
-#ifndef WG6_SKIP_ARITH
                     {   // the staging program: slot k = unit (k >> 2), step (k & 3); a component's three elements go to LDS behind its last step
-                        const int k = j * 18 + m - WG6_SLOT0;
+                        const int k = j * 18 + m - SLOT0;
                         if (k >= 0 && k < 64) stage_slot(rw, k, w_img);
                     }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#else
-            bf16x8 av[2][3], bv[2][3];
-            auto rd_a = [&](int j, int pc) { av[j & 1][pc] = __builtin_bit_cast(bf16x8, lds[a_base + (pc * 4 + j) * 2 * TC]); };
-            auto rd_b = [&](int gi, int pc) {
-                const int j = gi / 3, ky = gi % 3;
-                bv[gi & 1][pc] = __builtin_bit_cast(bf16x8, lds[b_base[ky] + (pc * 4 + j) * 2 * TC]);
-            };
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) { rd_a(0, pc); rd_b(0, pc); }
-#pragma unroll
-            for (int gi = 0; gi < 12; ++gi) {                                            // group = (component j, tap row ky)
-                const int j = gi / 3, ky = gi % 3;
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < 6; ++q) {
-#ifndef WG6_SKIP_MFMA
-                    if (active) acc[ky * 4 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[j & 1][PA[q]], bv[gi & 1][PB[q]], acc[ky * 4 + j], 0, 0, 0);
-#endif
-                    if (gi + 1 < 12 && q < 3) {                                           // operands of the next group
-                        rd_b(gi + 1, q);
-                        if ((gi + 1) % 3 == 0) rd_a((gi + 1) / 3, q);
-                    }
-#ifndef WG6_SKIP_ARITH
-                    {   // the staging program: slot k = unit (k >> 2), step (k & 3); a component's three elements go to LDS behind its last step
-                        const int k = gi * 6 + q - WG6_SLOT0;
-                        if (k >= 0 && k < 64) stage_slot(rw, k, w_img);
-                    }
-#endif
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#endif
-#ifdef WG6_PROF
-            const unsigned long long tm1 = __builtin_readcyclecounter();
-#endif
+            PROF_T(tm1);
 #pragma unroll
             for (int i = 0; i < NRAW; ++i) rw[i] = rn[i];
             split6_barrier();
-#ifdef WG6_PROF
-            { const unsigned long long tm2 = __builtin_readcyclecounter(); pc_mult += tm1 - tm0; pc_bar += tm2 - tm1; ++nstep_done; }
-#endif
+            PROF_T(tm2);
+            PROF_ACC(pc_mult, tm0, tm1); PROF_ACC(pc_bar, tm1, tm2); PROF_ONLY(++nstep_done;)
         }
     }
     }
-#ifdef WG6_PROF
-    {
+    PROF_ONLY({
         const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
         if (lane == 0 && lin < 2048) {
             unsigned long long* d = te_wgrad6_prof_buf + ((size_t)lin * 4 + wid) * 4;
             d[0] = pc_mult; d[1] = pc_head; d[2] = pc_bar;
             d[3] = ((unsigned long long)nstep_done << 40) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFull);
         }
-    }
-#endif
+    })
 
     // ---- fold the twelve accumulators to the nine taps and write the slab tile: slab[b][s][co][ci][tap]
     if (!active) return;
@@ -472,11 +419,9 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
     const int a_elem = half * TC + wco * 32 + l31;
     const int b_elem = NGR * GI + half * TC + wci * 32 + l31;
 
-#ifdef WG6_PROF
-    unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;
-    const unsigned long long pstart = __builtin_readcyclecounter();
-    int nstep_done = 0;
-#endif
+    PROF_ONLY(unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;)
+    PROF_T(pstart);
+    PROF_ONLY(int nstep_done = 0;)
     float rg[17], rx[8], ng[17], nx[8];
     for (int sg = 0; sg < ck.nseg; ++sg) {
     int t, t_end;
@@ -485,9 +430,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
         const int bb = t / sps, rem = t - bb * sps, cx = rem / p.H, ya = rem - cx * p.H;
         const int n = min(p.H - ya, t_end - t), yb = ya + n;
         t += n;
-#ifdef WG6_PROF
-        const unsigned long long th0 = __builtin_readcyclecounter();
-#endif
+        PROF_T(th0);
         // ---- head of a sweep: g rows 2 ya .. 2 ya + 3 into ring slots 0..3, x row ya into buffer ya & 1, registers of the first step
         {
             float g0[17], g1[17];
@@ -506,14 +449,11 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
             for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(rx[i]));
         }
         split6_barrier();
-#ifdef WG6_PROF
-        pc_head += __builtin_readcyclecounter() - th0;
-#endif
+        PROF_T(th1);
+        PROF_ACC(pc_head, th0, th1);
         int s0 = 0;                                           // ring slot of g row 2 y
         for (int y = ya; y < yb; ++y) {
-#ifdef WG6_PROF
-            const unsigned long long tm0 = __builtin_readcyclecounter();
-#endif
+            PROF_T(tm0);
             load_g(ng, bb, cx, 2 * y + 5 + rsel);             // registers of the step after next
             load_x(nx, bb, cx, y + 2);
             int wslot = s0 + 3 + rsel; wslot -= wslot >= NGR ? NGR : 0;
@@ -534,41 +474,32 @@ __global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int qq = 0; qq < 6; ++qq) {
-#ifndef WG6_SKIP_MFMA
                     if (active) acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[tp & 1][PA[qq]], bx[PB[qq]], acc[tp], 0, 0, 0);
-#endif
                     if (tp + 1 < 9 && qq < 3) rd_a(tp + 1, qq);
-#ifndef WG6_SKIP_ARITH
                     stage_slot(rg, rx, tp * 6 + qq, wslot, (y + 1) & 1);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#ifdef WG6_PROF
-            const unsigned long long tm1 = __builtin_readcyclecounter();
-#endif
+            PROF_T(tm1);
 #pragma unroll
             for (int i = 0; i < 17; ++i) rg[i] = ng[i];
 #pragma unroll
             for (int i = 0; i < 8; ++i) rx[i] = nx[i];
             s0 += 2; s0 -= s0 >= NGR ? NGR : 0;
             split6_barrier();
-#ifdef WG6_PROF
-            { const unsigned long long tm2 = __builtin_readcyclecounter(); pc_mult += tm1 - tm0; pc_bar += tm2 - tm1; ++nstep_done; }
-#endif
+            PROF_T(tm2);
+            PROF_ACC(pc_mult, tm0, tm1); PROF_ACC(pc_bar, tm1, tm2); PROF_ONLY(++nstep_done;)
         }
     }
     }
-#ifdef WG6_PROF
-    {
+    PROF_ONLY({
         const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
         if (lane == 0 && lin < 2048) {
             unsigned long long* d = te_wgrad6_prof_buf + ((size_t)lin * 4 + wid) * 4;
             d[0] = pc_mult; d[1] = pc_head; d[2] = pc_bar;
             d[3] = ((unsigned long long)nstep_done << 40) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFull);
         }
-    }
-#endif
+    })
 
     if (!active) return;
     float* sl = p.slabs + ((size_t)bgrp * p.S + s_chunk) * p.Co * p.Ci * 9;
@@ -684,11 +615,9 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
     const int a_elem = half * TC + wco * 32 + l31;
     const int b_elem = NGR * GI + half * TC + wci * 32 + l31;
 
-#ifdef WG6_PROF
-    unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;
-    const unsigned long long pstart = __builtin_readcyclecounter();
-    int nstep_done = 0;
-#endif
+    PROF_ONLY(unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;)
+    PROF_T(pstart);
+    PROF_ONLY(int nstep_done = 0;)
     float rg[17], rx[8], ng[17], nx[8];
     for (int sg = 0; sg < ck.nseg; ++sg) {
     int t, t_end;
@@ -697,9 +626,7 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
         const int bb = t / sps, rem = t - bb * sps, cx = rem / p.H, ya = rem - cx * p.H;
         const int n = min(p.H - ya, t_end - t), yb = ya + n;
         t += n;
-#ifdef WG6_PROF
-        const unsigned long long th0 = __builtin_readcyclecounter();
-#endif
+        PROF_T(th0);
         // ---- head of a sweep: g rows 2 ya .. 2 ya + 3 into ring slots 0..3, x row ya into buffer ya & 1, registers of the first step
         {
             float g0[17], g1[17];
@@ -718,14 +645,11 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
             for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(rx[i]));
         }
         split6_barrier();
-#ifdef WG6_PROF
-        pc_head += __builtin_readcyclecounter() - th0;
-#endif
+        PROF_T(th1);
+        PROF_ACC(pc_head, th0, th1);
         int s0 = 0;                                           // ring slot of g row 2 y
         for (int y = ya; y < yb; ++y) {
-#ifdef WG6_PROF
-            const unsigned long long tm0 = __builtin_readcyclecounter();
-#endif
+            PROF_T(tm0);
             load_g(ng, bb, cx, 2 * y + 5 + rsel);             // registers of the step after next
             load_x(nx, bb, cx, y + 2);
             int wslot = s0 + 3 + rsel; wslot -= wslot >= NGR ? NGR : 0;
@@ -760,31 +684,26 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
                         __builtin_amdgcn_sched_barrier(0);
                     }
             }
-#ifdef WG6_PROF
-            const unsigned long long tm1 = __builtin_readcyclecounter();
-#endif
+            PROF_T(tm1);
 #pragma unroll
             for (int i = 0; i < 17; ++i) rg[i] = ng[i];
 #pragma unroll
             for (int i = 0; i < 8; ++i) rx[i] = nx[i];
             s0 += 2; s0 -= s0 >= NGR ? NGR : 0;
             split6_barrier();
-#ifdef WG6_PROF
-            { const unsigned long long tm2 = __builtin_readcyclecounter(); pc_mult += tm1 - tm0; pc_bar += tm2 - tm1; ++nstep_done; }
-#endif
+            PROF_T(tm2);
+            PROF_ACC(pc_mult, tm0, tm1); PROF_ACC(pc_bar, tm1, tm2); PROF_ONLY(++nstep_done;)
         }
     }
     }
-#ifdef WG6_PROF
-    {
+    PROF_ONLY({
         const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
         if (lane == 0 && lin < 2048) {
             unsigned long long* d = te_wgrad6_prof_buf + ((size_t)lin * 4 + wid) * 4;
             d[0] = pc_mult; d[1] = pc_head; d[2] = pc_bar;
             d[3] = ((unsigned long long)nstep_done << 40) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFull);
         }
-    }
-#endif
+    })
 
     float* sl = p.slabs + ((size_t)bgrp * p.S + s_chunk) * p.Co * p.Ci * 9;
 #pragma unroll
@@ -970,11 +889,7 @@ std::atomic<int> g_wg6_on{[] { const char* e = getenv("TE_SPLIT_BF16"); return (
 
 }  // namespace
 
-#ifdef WG6_PROF
-extern "C" int te_debug_wgrad6_prof(void* host_dst, int64_t bytes) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(te_wgrad6_prof_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-}
-#endif
+PROF_READBACK(wgrad6)
 
 // process-wide switch (0 / 1; anything else only queries): does te_wgrad_f32 / te_wgrad_group_f32 take this kernel where it applies?
 extern "C" int te_wgrad_split_bf16(int on) {

@@ -21,6 +21,10 @@
 // Block: 512 threads, tile 64 output channels x 8 rows x 32 columns.  Epilogue = wino.hip's (output transform, demodulation scale, bias,
 // leaky ReLU, residual, mask).
 #include "split6_common.h"
+#ifdef W6P_PROF      // experimental builds: per-wave cycle counts of the phases, read back with te_debug_w6p_prof (tools/w6p_phase_prof.py)
+#define TE_PROF
+#endif
+#include "te_prof.h"
 
 namespace {
 
@@ -63,23 +67,9 @@ constexpr int GT = WT / 2;                                // threads of a group
 constexpr int P_IN = (PR * NP * 8) / GT;                  // (row, pair, channel pair) items per thread and stage: 768 / 256 = 3
 static_assert(PR * NP * 8 == P_IN * GT, "items must divide over the group");
 
-#ifdef W6P_PROF      // experimental builds: per-wave cycle counts of the phases (s_memtime), read back with te_debug_w6p_prof
-__device__ unsigned long long te_w6p_prof_buf[2048 * 8 * 8];
-#define W6P_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define W6P_ACC(i, a, b) pc[i] += (b) - (a)
-#else
-#define W6P_T(v)
-#define W6P_ACC(i, a, b)
-#endif
-#ifndef W6P_SLOT0
-#define W6P_SLOT0 21         // MFMA slot behind which the staging arithmetic starts (72 slots, the program has 51): the fetch it
-#endif                       // consumes is issued half a phase earlier by group 1
-#ifndef DMA_PRIO
-#define DMA_PRIO 0         // experiment: the staging wave raises its priority while it issues the weight DMA
-#endif
-#ifndef W6P_PRIO
-#define W6P_PRIO 1           // 1: a wave raises its priority while it multiplies (+1 - 1.5 % over 0); 3: static priority for group 1 (-3 %)
-#endif
+PROF_BUFFER(w6p, 2048 * 8 * 8)
+constexpr int SLOT0 = 21;    // MFMA slot behind which the staging arithmetic starts (72 slots, the program has 51): the fetch it
+                             // consumes is issued half a phase earlier by group 1
 
 // ISC: the launch carries style scales.  A template parameter, and the fetch of the staging role is unconditional (clamped to the last
 // stage): with `if (iscb)` / `if (fetch)` around the loads the compiler kept two copies of the 26 fetch registers and moved them twice per
@@ -244,14 +234,11 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
     }
     split6_barrier();
     const int nphase = 2 * nstage;
-    if (W6P_PRIO == 3 && grp == 1) __builtin_amdgcn_s_setprio(1);
-#ifdef W6P_PROF
-    unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long pstart = __builtin_readcyclecounter(), rstart = __builtin_amdgcn_s_memrealtime();
-#endif
+    PROF_ONLY(unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};)
+    PROF_ONLY(const unsigned long long pstart = __builtin_readcyclecounter(), rstart = __builtin_amdgcn_s_memrealtime();)
     for (int ph = 0; ph < nphase; ++ph) {
         const bool last = ph == nphase - 1;
-        W6P_T(t0);
+        PROF_T(t0);
         if ((ph & 1) == grp) {
             // ---- multiply this group's half of stage ph / 2; behind the MFMAs: the arithmetic of stage ph / 2 + 1 (rin -> res)
             // (in a group's last multiplying phase the arithmetic runs on the stale registers of the last fetch and its results are never
@@ -265,28 +252,22 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
             };
 #pragma unroll
             for (int q = 0; q < 6; ++q) rd1(0, 0, q);
-            if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+            // a wave raises its priority while it multiplies (+1 - 1.5 % over none; a static priority for group 1 instead: -3 %)
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int g = 0; g < 12; ++g) {
                 const int slot = g & 1, c = g & 3;
-#ifdef W6P_PROF
-                if (g == 5) { W6P_T(ta); split6_barrier(); W6P_T(tb); W6P_ACC(0, t0, ta); W6P_ACC(1, ta, tb); pc[2] -= tb; }
-#else
-                if (g == 5) split6_barrier();             // mid-phase barrier (every phase, the last one too: no branch in the MFMA stream)
-#endif
+                // mid-phase barrier (every phase, the last one too: no branch in the MFMA stream)
+                if (g == 5) { PROF_T(ta); split6_barrier(); PROF_T(tb); PROF_ACC(pc[0], t0, ta); PROF_ACC(pc[1], ta, tb); PROF_ONLY(pc[2] -= tb;) }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < 6; ++q) {
-#ifndef W6_SKIP_MFMA
                     split6_product(q, av[slot], bv[slot], acc[c], acc[c]);
-#endif
                     if (g + 1 < 12 && q < 3) { rd1(g + 1, slot ^ 1, 2 * q); rd1(g + 1, slot ^ 1, 2 * q + 1); }
-#ifndef W6_SKIP_COMMIT
-                    arith(g * 6 + q - W6P_SLOT0);
-#endif
+                    arith(g * 6 + q - SLOT0);
                     {   // the fetch of the stage after next, item by item behind the last slot that reads the item's registers
-                        constexpr int LASTQ = 71 - W6P_SLOT0;                      // slot of the last MFMA
-                        const int k = g * 6 + q - W6P_SLOT0;
+                        constexpr int LASTQ = 71 - SLOT0;                      // slot of the last MFMA
+                        const int k = g * 6 + q - SLOT0;
                         if (k == P_IN - 1) fetch_scales(fs2);
 #pragma unroll
                         for (int i = 0; i < P_IN; ++i)
@@ -295,10 +276,8 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-#ifdef W6P_PROF
-            { asm volatile("s_nop 0" ::: "memory"); W6P_T(tc); pc[2] += tc; }
-#endif
+            __builtin_amdgcn_s_setprio(0);
+            PROF_ONLY({ asm volatile("s_nop 0" ::: "memory"); PROF_T(tc); pc[2] += tc; })
         } else {
             // ---- stage: move this group's half of stage cs = (ph + 1) / 2 to LDS, fetch stage cs + 1, renew a half of the weight image
             const int cs = (ph + 1) >> 1;
@@ -307,40 +286,32 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
             // this half tile in its shadow, then the wait for the DMA; group 0 renews Ua behind the barrier.  (The fetch of the next
             // stage is not issued here any more: see fetch_item.)  The LDS writes are unconditional: in group 1's first phase they
             // repeat what the prologue wrote, in group 0's last phase they put stale results in a tile nobody reads any more.
-            if (DMA_PRIO) __builtin_amdgcn_s_setprio(DMA_PRIO);
             if (grp == 1 && work) issue_u(1, cs);
-            if (DMA_PRIO) __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-#ifndef W6_SKIP_COMMIT
             write_res();
-#endif
             if (grp == 1 && work) split6_wait_vm();
-            W6P_T(ta);
+            PROF_T(ta);
             split6_barrier();
-            W6P_T(tb);
+            PROF_T(tb);
             if (grp == 0 && work) {
-                if (DMA_PRIO) __builtin_amdgcn_s_setprio(DMA_PRIO);
                 issue_u(0, cs);
-                if (DMA_PRIO) __builtin_amdgcn_s_setprio(0);
                 split6_wait_vm();
             }
-            W6P_T(tc);
-            W6P_ACC(3, t0, ta); W6P_ACC(4, ta, tb); W6P_ACC(5, tb, tc);
+            PROF_T(tc);
+            PROF_ACC(pc[3], t0, ta); PROF_ACC(pc[4], ta, tb); PROF_ACC(pc[5], tb, tc);
         }
-        W6P_T(t8);
+        PROF_T(t8);
         if (!last) split6_barrier();
-        W6P_T(t9);
-        W6P_ACC(6, t8, t9);
+        PROF_T(t9);
+        PROF_ACC(pc[6], t8, t9);
     }
-#ifdef W6P_PROF
-    if (lane == 0 && blockIdx.x < 2048) {
+    PROF_ONLY(if (lane == 0 && blockIdx.x < 2048) {
         unsigned long long* d = te_w6p_prof_buf + ((size_t)blockIdx.x * 8 + wid) * 8;
-#pragma unroll
+        _Pragma("unroll")
         for (int i = 0; i < 6; ++i) d[i] = pc[i];
         d[6] = pc[6] | ((__builtin_amdgcn_s_memrealtime() - rstart) << 40);          // (100 MHz counter: the shader clock follows)
         d[7] = ((unsigned long long)nstage << 48) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFFFull);
-    }
-#endif
+    })
     // epilogue: as wino.hip (output transform, demodulation scale, bias, leaky ReLU, residual, mask); group 0 is here one phase early
     const int wr = grp * 2 + wrl;
     const int mbase = mb * BM + wm * 32;
@@ -537,7 +508,7 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
         };
 #pragma unroll
         for (int q = 0; q < 6; ++q) rd1(0, 0, q);
-        if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int g = 0; g < 12; ++g) {
             const int slot = g & 1, c = g & 3;
@@ -545,9 +516,7 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
-#ifndef W6_SKIP_MFMA
                 split6_product(q, av[slot], bv[slot], acc[MSET][c], acc[MSET][c]);
-#endif
                 if (g + 1 < 12 && q < 3) { rd1(g + 1, slot ^ 1, 2 * q); rd1(g + 1, slot ^ 1, 2 * q + 1); }
                 const int k = g * 6 + q;
                 if (MSET == 0) {
@@ -557,14 +526,12 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
                     for (int i = 0; i < P_IN; ++i)
                         if (k == 6 + 12 * i) fetch_item(i, fs);
                 } else {
-#ifndef W6_SKIP_COMMIT
-                    arith(k - W6P_SLOT0);
-#endif
+                    arith(k - SLOT0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (W6P_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         split6_barrier();                             // end of phase
     };
     // one phase in the staging role.  p = global phase index; image cs = (p + 1) >> 1 is the one whose half this phase renews:
@@ -576,9 +543,7 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
         const bool work = cs >= 1 && cs < nimg;
         if (grp == 1 && work) issue_u(1, cs);
         __builtin_amdgcn_sched_barrier(0);
-#ifndef W6_SKIP_COMMIT
         if (write) write_res();
-#endif
         if (grp == 1 && work) split6_wait_vm();
         split6_barrier();                             // mid-phase
         if (grp == 0 && work) {
@@ -672,11 +637,7 @@ extern "C" int te_conv_wino6_form(int form) {
     return old;
 }
 
-#ifdef W6P_PROF
-extern "C" int te_debug_w6p_prof(void* host_dst, int64_t bytes) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(te_w6p_prof_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-}
-#endif
+PROF_READBACK(w6p)
 
 extern "C" int te_conv_wino6_supported(int B, int K, int M, int H, int W) {
     if (!(B > 0 && K >= 32 && K % 32 == 0 && M >= BM && M % BM == 0 && H >= TH && H % TH == 0)) return 0;
