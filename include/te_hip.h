@@ -583,6 +583,38 @@ int te_prdc_knn_f32(float* r2, const float* x, const float* nx, int N, int D, in
 int te_prdc_counts_f32(int32_t* col_count, int32_t* row_any, float* row_min, const float* x, const float* nx, const float* rr2,
                        const float* y, const float* ny, const float* rf2, int N, int M, int D, void* ws, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M2  the VGG16 fc7 feature extractor of the PRDC metric (metrics/calc_prdc.py:101-104: torchvision vgg16 with classifier[:-1] on the
+ * generator's [-1, 1] image, i.e. the 4096-d output of fc7 after its ReLU).  conv1_2 ... conv5_3 and the max-pools are L1's; here the
+ * three pieces L1 does not have.  Forward only (the metric runs under no_grad in eval mode: Dropout is the identity).
+ *
+ * te_vgg_stem_fwd_f32 (calc_prdc.py:101-104; replaces torchvision vgg16.features[0:2] = Conv2d(3, 64, 3, padding=1) + ReLU): the kernel
+ * of te_lpips_stem_fwd_f32 without the ScalingLayer, the raw input straight into conv1_1:
+ *     out[n,o] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * x[n,c,y+ky-1,x+kx-1])            w [64,3,3,3], b [64], x zero outside the image
+ *
+ * te_adaptive_avgpool_f32 (calc_prdc.py:101-104; replaces torchvision vgg16.avgpool = AdaptiveAvgPool2d((7, 7)) and the flatten
+ * behind it): over `planes` = N * C planes of H x W, torch's rule per axis: output o averages the window
+ * [floor(o * H / OH), ceil((o + 1) * H / OH)), summed row-major in fp32 and divided by the window's element count.  out is
+ * [planes, OH * OW] contiguous: for N x 512 planes and 7 x 7 that IS the flattened [N, 25088] layout fc6 reads.  Any H, W >= 1
+ * (H < OH: windows repeat; H == OH: a bit-exact copy).
+ *
+ * te_fc_stream_f32 (calc_prdc.py:101-104; replaces torchvision vgg16.classifier[0:2] and [3:5] = Linear + ReLU): a weight-streaming
+ * dense layer for FEW rows against a weight far larger than the caches (fc6: 25088 -> 4096, 411 MB):
+ *     C[i,j] = act(sum_k A[i,k] * W[j,k] + bias[j])     A [I,K], W [J,K] (torch Linear layout), C [I,J] row-major; act 0 none, 1 ReLU
+ * on the fp32-input MFMA (exact fp32).  A workgroup owns 64 output columns, up to 64 rows and one of S chunks of K: every weight
+ * element is loaded once per 64-row block, 16 bytes at a time along K; A is re-read from cache.  The partial tiles go to the caller's
+ * workspace ws[S][I][J] (te_fc_stream_ws_bytes), a second kernel sums them over s ascending and applies bias and activation: no
+ * atomics, bit-reproducible.  S = te_fc_stream_splits(J, K) depends on (J, K) ONLY and a row's summation order does not depend on I,
+ * so a row's result is bitwise the same whatever batch it is in.  Any I >= 1, J >= 1; K >= 4, K % 4 == 0 and 16-byte aligned a / w,
+ * anything else is TE_ERR_SHAPE.  te_fc_stream_splits / te_fc_stream_ws_bytes return a negative TE_ERR_* on bad arguments.
+ */
+int te_vgg_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, te_stream_t stream);
+int te_adaptive_avgpool_f32(float* out, const float* x, int64_t planes, int H, int W, int OH, int OW, te_stream_t stream);
+int te_fc_stream_splits(int J, int K);
+int64_t te_fc_stream_ws_bytes(int64_t I, int J, int K);
+int te_fc_stream_f32(float* c, float* ws, const float* a, const float* w, const float* bias, int64_t I, int J, int K, int act,
+                     te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,11 @@ _SIGNATURES = {
     'te_row_sqnorm_f32': (C.c_int, [_P, _P, _I, _I, _P]),
     'te_prdc_knn_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'te_prdc_counts_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    'te_vgg_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    'te_adaptive_avgpool_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
+    'te_fc_stream_splits': (C.c_int, [_I, _I]),
+    'te_fc_stream_ws_bytes': (C.c_int64, [_L, _I, _I]),
+    'te_fc_stream_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -950,6 +955,46 @@ def prdc_counts(x, nx, rr2, y, ny, rf2):
     return col_count, row_any, row_min
 
 
+# --------------------------------------------------------------------------------------------- M2 VGG16 fc7 features
+def vgg_stem_fwd(x, w, b):
+    """conv1_1 -> bias -> ReLU on the raw input (no ScalingLayer): x [N,3,H,W] -> [N,64,H,W]"""
+    x = x.contiguous()
+    N, _, H, W = x.shape
+    out = torch.empty(N, 64, H, W, device=x.device, dtype=x.dtype)
+    _check(lib().te_vgg_stem_fwd_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(b), N, H, W, _stream()), 'te_vgg_stem_fwd_f32')
+    return out
+
+
+def adaptive_avgpool(x, OH=7, OW=7):
+    """torch's adaptive_avg_pool2d: x [N,C,H,W] -> [N,C,OH,OW] (contiguous: .view(N, -1) is the flattened layout)"""
+    x = x.contiguous()
+    N, Cn, H, W = x.shape
+    out = torch.empty(N, Cn, OH, OW, device=x.device, dtype=x.dtype)
+    _check(lib().te_adaptive_avgpool_f32(_ptr(out), _ptr(x), N * Cn, H, W, OH, OW, _stream()), 'te_adaptive_avgpool_f32')
+    return out
+
+
+def fc_stream_splits(J, K):
+    """the number of K chunks te_fc_stream_f32 uses for a [J,K] weight (no batch size enters)"""
+    S = lib().te_fc_stream_splits(J, K)
+    if S < 0:
+        raise RuntimeError(f'te_fc_stream_splits failed ({S}) for J={J}, K={K}: J >= 1, K a positive multiple of 4')
+    return S
+
+
+def fc_stream(a, w, bias, act=0):
+    """act(a @ w.T + bias): a [I,K], w [J,K] (torch Linear layout), bias [J] -> [I,J]; act 0 none, 1 ReLU.  The ABI refuses bad shapes
+    and misaligned operands; nothing is launched then."""
+    if a.ndim != 2 or w.ndim != 2 or bias.ndim != 1 or a.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0]:
+        raise RuntimeError(f'te_hip: fc_stream: inconsistent shapes a {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
+    (I, K), J = a.shape, w.shape[0]
+    nb = lib().te_fc_stream_ws_bytes(I, J, K)
+    c = torch.empty(I, J, device=a.device, dtype=a.dtype)
+    ws = torch.empty(max(nb, 4) // 4, device=a.device, dtype=a.dtype)        # (nb < 0: the call below names what is wrong)
+    _check(lib().te_fc_stream_f32(_ptr(c), _ptr(ws), _ptr(a), _ptr(w), _ptr(bias), I, J, K, act, _stream()), 'te_fc_stream_f32')
+    return c
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -963,7 +1008,7 @@ def _install_roctx():
              'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd', 'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd',
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
-             'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts']
+             'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream']
     g = globals()
 
     def wrap(fn, name):

@@ -21,6 +21,8 @@ constexpr float kEps = 1e-10f;   // normalize_tensor eps (utils/lpips/__init__.p
 
 // out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * s(x)[n,c,y+ky-1,x+kx-1]); s(x) is zero outside the image (the scaling
 // happens BEFORE nn.Conv2d's zero padding).  w: [64,3,3,3] in LDS, 27 scaled inputs per thread in registers.
+// SCALED = false: s is the identity (torchvision's vgg16.features[0] on the raw input: te_vgg_stem_fwd_f32).
+template <bool SCALED>
 __global__ __launch_bounds__(256) void stem_fwd_kernel(float* __restrict__ out, const float* __restrict__ x,
                                                        const float* __restrict__ w, const float* __restrict__ b, int H, int W) {
     __shared__ float ws[64 * 27];
@@ -43,7 +45,8 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(float* __restrict__ out, 
             for (int kx = 0; kx < 3; ++kx) {
                 const int iy = yy + ky - 1, ix = xx + kx - 1;
                 const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-                in[c * 9 + ky * 3 + kx] = ok ? (xc[(int64_t)iy * W + ix] - kShift[c]) / kScale[c] : 0.f;
+                const float v = ok ? xc[(int64_t)iy * W + ix] : 0.f;
+                in[c * 9 + ky * 3 + kx] = SCALED ? (ok ? (v - kShift[c]) / kScale[c] : 0.f) : v;
             }
         }
     }
@@ -357,8 +360,16 @@ extern "C" int te_lpips_stem_fwd_f32(float* out, const float* x, const float* w,
     TE_REQUIRE(out && x && w && b, TE_ERR_NULL, "te_lpips_stem_fwd_f32: NULL pointer");
     TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_lpips_stem_fwd_f32: bad dims");
     const int64_t HW = (int64_t)H * W;
-    stem_fwd_kernel<<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, w, b, H, W);
+    stem_fwd_kernel<true><<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, w, b, H, W);
     return te::launch_status("te_lpips_stem_fwd_f32");
+}
+
+extern "C" int te_vgg_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, te_stream_t stream) {
+    TE_REQUIRE(out && x && w && b, TE_ERR_NULL, "te_vgg_stem_fwd_f32: NULL pointer");
+    TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_vgg_stem_fwd_f32: bad dims");
+    const int64_t HW = (int64_t)H * W;
+    stem_fwd_kernel<false><<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, w, b, H, W);
+    return te::launch_status("te_vgg_stem_fwd_f32");
 }
 
 extern "C" int te_lpips_stem_dgrad_f32(float* gx, const float* g, const float* y1, const float* w, int N, int H, int W,

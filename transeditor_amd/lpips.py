@@ -35,29 +35,33 @@ def default_vgg_path():
     return os.path.join(torch.hub.get_dir(), 'checkpoints', 'vgg16-397923af.pth')
 
 
-def _load(path, what):
+def _load(path, what, who='LPIPS'):
     if path is None or not os.path.isfile(path):
-        raise FileNotFoundError(f'LPIPS: {what} file not found: {path}')
+        raise FileNotFoundError(f'{who}: {what} file not found: {path}')
     sd = torch.load(path, map_location='cpu')
     if not isinstance(sd, dict):
-        raise ValueError(f'LPIPS: {what} file {path} does not hold a state dict')
+        raise ValueError(f'{who}: {what} file {path} does not hold a state dict')
     return sd
 
 
-def load_vgg16(path):
-    """[(weight [Co,Ci,3,3], bias [Co])] * 13 from a torchvision vgg16 state dict (other keys ignored)"""
-    sd = _load(path, 'vgg16')
+def vgg16_convs(sd, path, who='LPIPS'):
+    """[(weight [Co,Ci,3,3], bias [Co])] * 13 from a torchvision vgg16 state dict (other keys ignored); `path` names it in messages"""
     out, ci = [], 3
     for idx, co in zip(VGG_CONV_INDEX, VGG_CHANNELS):
         kw, kb = f'features.{idx}.weight', f'features.{idx}.bias'
         if kw not in sd or kb not in sd:
-            raise ValueError(f'LPIPS: {path} has no {kw} / {kb} (not a torchvision vgg16 state dict)')
+            raise ValueError(f'{who}: {path} has no {kw} / {kb} (not a torchvision vgg16 state dict)')
         w, b = sd[kw], sd[kb]
         if tuple(w.shape) != (co, ci, 3, 3) or tuple(b.shape) != (co,):
-            raise ValueError(f'LPIPS: {kw} is {tuple(w.shape)} / bias {tuple(b.shape)}, expected {(co, ci, 3, 3)} / {(co,)}')
+            raise ValueError(f'{who}: {kw} is {tuple(w.shape)} / bias {tuple(b.shape)}, expected {(co, ci, 3, 3)} / {(co,)}')
         out.append((w.detach().float().contiguous(), b.detach().float().contiguous()))
         ci = co
     return out
+
+
+def load_vgg16(path):
+    """vgg16_convs of the state dict in the file `path`"""
+    return vgg16_convs(_load(path, 'vgg16'), path)
 
 
 def load_lin(path):
@@ -116,7 +120,30 @@ class _Distance(Function):
         return _lib.lpips_stem_dgrad(g, acts[0], net._w(0)), None, None
 
 
-class PerceptualLoss(torch.nn.Module):
+class VGGTrunk:
+    """conv1_2 ... conv5_3 of a frozen vgg16 on the project's 3x3 convolution: shared by PerceptualLoss and
+    vgg_features.VGG16Features.  The module keeps conv i's weight / bias as the buffers w{i} / b{i} and a dict `_packs`."""
+
+    def _w(self, i):
+        return getattr(self, f'w{i}')
+
+    def _packed(self, i, pack_kind):
+        """packed layout of conv i (the trunk is frozen: kept as long as the buffer's version and address are unchanged)"""
+        w = self._w(i)
+        key = (i, pack_kind)
+        ent = self._packs.get(key)
+        if ent is None or ent[0] != (w._version, w.data_ptr()):
+            ent = self._packs[key] = ((w._version, w.data_ptr()), _lib.conv_pack(w, pack_kind))
+        return ent[1]
+
+    def _conv_fwd(self, i, x):
+        w = self._w(i)
+        B, _, H, W = x.shape
+        pk, ck = modconv.fwd_kinds('3x3', B, w, H, W)
+        return _relu_(_lib.conv(x, self._packed(i, pk), ck, w.shape[0], H, W, bias=getattr(self, f'b{i}')))
+
+
+class PerceptualLoss(VGGTrunk, torch.nn.Module):
     def __init__(self, model='net-lin', net='vgg', colorspace='rgb', spatial=False, use_gpu=True, gpu_ids=[0], vgg_path=None,
                  lin_path=None):
         super().__init__()
@@ -140,26 +167,8 @@ class PerceptualLoss(torch.nn.Module):
         if use_gpu and torch.cuda.is_available():
             self.to(f'cuda:{gpu_ids[0]}')
 
-    def _w(self, i):
-        return getattr(self, f'w{i}')
-
     def _lin(self, l):
         return getattr(self, f'lin{l}')
-
-    def _packed(self, i, pack_kind):
-        """packed layout of conv i (the trunk is frozen: kept as long as the buffer's version and address are unchanged)"""
-        w = self._w(i)
-        key = (i, pack_kind)
-        ent = self._packs.get(key)
-        if ent is None or ent[0] != (w._version, w.data_ptr()):
-            ent = self._packs[key] = ((w._version, w.data_ptr()), _lib.conv_pack(w, pack_kind))
-        return ent[1]
-
-    def _conv_fwd(self, i, x):
-        w = self._w(i)
-        B, _, H, W = x.shape
-        pk, ck = modconv.fwd_kinds('3x3', B, w, H, W)
-        return _relu_(_lib.conv(x, self._packed(i, pk), ck, w.shape[0], H, W, bias=getattr(self, f'b{i}')))
 
     def _conv_dgrad(self, i, g):
         w = self._w(i)
