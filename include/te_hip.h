@@ -615,6 +615,31 @@ int64_t te_fc_stream_ws_bytes(int64_t I, int J, int K);
 int te_fc_stream_f32(float* c, float* ws, const float* a, const float* w, const float* bias, int64_t I, int J, int K, int act,
                      te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M3  the feature moments behind the Frechet inception distance, streamed in fp64 on the device.  The FID needs no features, only
+ * n, s = sum_k x_k and S = sum_k x_k x_k^T, which add across batches, calls and ranks.
+ *
+ * te_fid_moments_f64 (metrics/fid_query.py:38-40 and :162-163, metrics/calc_inception.py:69-71 and :110-111; replaces the per-batch
+ * feat.to('cpu'), the torch.cat of all features on the host and the sums inside np.mean / np.cov): x [N,D] fp32 row-major on the
+ * device (4-byte alignment suffices: the 16-byte load path needs D % 4 == 0 and a 16-byte aligned base, anything else takes scalar
+ * loads), S [D,D] and s [D] fp64:
+ *     S[i][j] (+)= sum_k x[k][i] * x[k][j]   for j >= i        s[j] (+)= sum_k x[k][j]
+ * accumulate 0 overwrites, 1 adds to what is there.  ONLY THE UPPER TRIANGLE (j >= i) of S is defined afterwards.  The products run
+ * on v_mfma_f64_16x16x4_f64 over 64 x 64 tiles with tj >= ti; every fp32 x fp32 product is exact in fp64, only the sums round.  For
+ * small D the sample index is split and the partial tiles go to ws, combined in split order by a second kernel: no atomics, one
+ * owner and one summation order per element, bit-reproducible.  1 <= D <= 8192, N >= 1.
+ *
+ * te_fid_moments_ws_bytes: the bytes of ws for (N, D); 0 where the sample index is not split (ws may then be NULL); negative on
+ * bad arguments.  At most (2048 + T) * 32 KiB + 64 * (D + 63) bytes with T = the number of upper 64 x 64 tiles.
+ *
+ * te_fid_finalize_f64 (fid_query.py:162-163, calc_inception.py:110-111; replaces np.mean(features, 0) and
+ * np.cov(features, rowvar=False)): mean = s / n, cov[i][j] = cov[j][i] = (S[i][j] - s[i] s[j] / n) / (n - 1) read from the upper
+ * triangle of S (ddof = 1); both triangles of cov are written.  TE_ERR_SHAPE for n < 2.
+ */
+int64_t te_fid_moments_ws_bytes(int64_t N, int D);
+int te_fid_moments_f64(double* S, double* s, void* ws, const float* x, int64_t N, int D, int accumulate, te_stream_t stream);
+int te_fid_finalize_f64(double* mean, double* cov, const double* S, const double* s, int64_t n, int D, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,9 @@ _SIGNATURES = {
     'te_fc_stream_splits': (C.c_int, [_I, _I]),
     'te_fc_stream_ws_bytes': (C.c_int64, [_L, _I, _I]),
     'te_fc_stream_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'te_fid_moments_ws_bytes': (C.c_int64, [_L, _I]),
+    'te_fid_moments_f64': (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
+    'te_fid_finalize_f64': (C.c_int, [_P, _P, _P, _P, _L, _I, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -995,6 +998,37 @@ def fc_stream(a, w, bias, act=0):
     return c
 
 
+# --------------------------------------------------------------------------------------------- M3 FID feature moments
+def fid_moments_ws_bytes(N, D):
+    nb = lib().te_fid_moments_ws_bytes(N, D)
+    if nb < 0:
+        raise RuntimeError(f'te_fid_moments_ws_bytes failed ({nb}) for N={N}, D={D}: N >= 1 and 1 <= D <= 8192')
+    return nb
+
+
+def fid_moments(S, s, x, accumulate):
+    """S [D,D] fp64 (upper triangle) and s [D] fp64 (+)= the second and first moments of the rows of x [N,D] fp32; in place"""
+    N, D = _features(x, 'fid_moments')
+    if S.shape != (D, D) or s.shape != (D,):
+        raise RuntimeError(f'te_hip: fid_moments: x {tuple(x.shape)} needs S [{D},{D}] and s [{D}], got {tuple(S.shape)} and {tuple(s.shape)}')
+    nb = fid_moments_ws_bytes(N, D)
+    ws = torch.empty(nb // 8, device=x.device, dtype=torch.float64) if nb else None
+    _check(lib().te_fid_moments_f64(_ptr_as(S, torch.float64), _ptr_as(s, torch.float64), _ptr_as(ws, torch.float64), _ptr(x), N, D,
+                                    1 if accumulate else 0, _stream()), 'te_fid_moments_f64')
+
+
+def fid_finalize(S, s, n):
+    """the moments of n samples -> (mean [D], cov [D,D]) fp64 on the device: np.mean / np.cov(rowvar=False)"""
+    if S.ndim != 2 or S.shape[0] != S.shape[1] or s.shape != (S.shape[0],):
+        raise RuntimeError(f'te_hip: fid_finalize expects S [D,D] and s [D], got {tuple(S.shape)} and {tuple(s.shape)}')
+    D = S.shape[0]
+    mean = torch.empty(D, device=S.device, dtype=torch.float64)
+    cov = torch.empty(D, D, device=S.device, dtype=torch.float64)
+    _check(lib().te_fid_finalize_f64(_ptr_as(mean, torch.float64), _ptr_as(cov, torch.float64), _ptr_as(S, torch.float64),
+                                     _ptr_as(s, torch.float64), int(n), D, _stream()), 'te_fid_finalize_f64')
+    return mean, cov
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1008,7 +1042,8 @@ def _install_roctx():
              'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd', 'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd',
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
-             'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream']
+             'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
+             'fid_moments', 'fid_finalize']
     g = globals()
 
     def wrap(fn, name):
