@@ -640,6 +640,41 @@ int64_t te_fid_moments_ws_bytes(int64_t N, int D);
 int te_fid_moments_f64(double* S, double* s, void* ws, const float* x, int64_t N, int D, int accumulate, te_stream_t stream);
 int te_fid_finalize_f64(double* mean, double* cov, const double* S, const double* s, int64_t n, int D, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * E1  the linear C-SVC behind an editing boundary (our_interfaceGAN/train_boundary.py), from the training rows on.  The reference
+ * copies the rows to the host and calls sklearn's SVC(kernel='linear'), which is libsvm's SMO on the CPU; here the Gram matrix, the
+ * solve and the weight vector stay on the device.
+ *
+ * te_gram_f32 (train_boundary.py:113-114; replaces libsvm's Kernel::k_function / SVC_Q::get_Q rows behind clf.fit): K [n,n] = x x^T
+ * for row-major x [n,D], on the fp32-input MFMA with fp32 accumulation (libsvm's kernel cache, Qfloat, is fp32 too).  Only the
+ * 128 x 128 tiles with tj >= ti are computed and every element is written to both triangles, so K[i][j] and K[j][i] are the same
+ * bits.  One owner and one summation order per element, no atomics.  1 <= n <= 4194304, any D >= 1 (the k tail is zero-filled; the
+ * 16-byte load path needs D % 4 == 0 and a 16-byte aligned base, anything else takes scalar loads).
+ *
+ * te_svm_smo_f64 (train_boundary.py:113-114; replaces libsvm's Solver::Solve behind clf.fit): the C-SVC dual
+ *     min 1/2 a^T Q a - e^T a,   0 <= a_t <= C,   y^T a = 0,   Q_ij = y_i y_j K_ij
+ * by libsvm's SMO WITHOUT shrinking: second-order working-set selection (i = argmax of -y_t G_t over I_up; j = argmin over I_low
+ * with b = Gmax + y_t G_t > 0 of -b^2 / a, a = K_ii + K_tt - 2 K_it, a <= 0 replaced by 1e-12), libsvm's two-variable update with
+ * its clipping order for y_i != y_j and y_i == y_j, G += Q_i da_i + Q_j da_j, stop when Gmax - Gmin < eps.  rho is libsvm's
+ * calculate_rho on the final state: the mean of y_t G_t over the free variables (0 < a_t < C), or (ub + lb) / 2 of the two bound
+ * sets where there is none; the decision function is sum_t a_t y_t K(x_t, x) - rho.  K [n,n] fp32 (te_gram_f32's; only rows are
+ * read), alpha [n] and rho [1] fp64, info [2] int32: info[0] = the iterations (updates) run, info[1] = 1 if the stop criterion was
+ * met, 0 if max_iter ended the solve (alpha is feasible either way).
+ * y is a HOST array of n labels, each +1 or -1: it is validated on the host and reaches the kernel as kernel arguments.
+ * ONE workgroup: gradient and alpha in fp64 registers of fixed owner threads, labels and the fp32 diagonal in LDS, two rows of K read
+ * per iteration.  Ties in both selections go to the lowest index (libsvm keeps the highest), so the result is bit-reproducible.
+ * LIMIT: 2 <= n <= 8192 (the reference's default, 150 000 samples at ratio 0.02 and split 0.7, needs n = 4200) with both labels
+ * present, C > 0, eps > 0, max_iter >= 0; anything else is TE_ERR_SHAPE and nothing is launched.
+ *
+ * te_svm_coef_f32 (train_boundary.py:138; replaces classifier.coef_): w[d] = sum_i alpha_i y_i x[i,d], accumulated in fp64 over i
+ * ascending by one owner thread per d and rounded once to fp32 (rows with alpha_i == 0 are passed over: they add an exact zero).
+ * y as above (HOST); 1 <= n <= 8192, D >= 1.  The un-normalised coef_; the caller divides by its norm.
+ */
+int te_gram_f32(float* K, const float* x, int n, int D, te_stream_t stream);
+int te_svm_smo_f64(double* alpha, double* rho, int32_t* info, const float* K, const int8_t* y, int n, double C, double eps,
+                   int64_t max_iter, te_stream_t stream);
+int te_svm_coef_f32(float* w, const float* x, const double* alpha, const int8_t* y, int n, int D, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,9 @@ _SIGNATURES = {
     'te_fid_moments_ws_bytes': (C.c_int64, [_L, _I]),
     'te_fid_moments_f64': (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
     'te_fid_finalize_f64': (C.c_int, [_P, _P, _P, _P, _L, _I, _P]),
+    'te_gram_f32': (C.c_int, [_P, _P, _I, _I, _P]),
+    'te_svm_smo_f64': (C.c_int, [_P, _P, _P, _P, _P, _I, C.c_double, C.c_double, _L, _P]),
+    'te_svm_coef_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1029,6 +1032,54 @@ def fid_finalize(S, s, n):
     return mean, cov
 
 
+# --------------------------------------------------------------------------------------------- E1 linear SVM of an editing boundary
+def _labels(y, n, what):
+    """n labels +1 / -1 on the HOST (a numpy array, a CPU tensor or a sequence) -> a contiguous int8 ctypes array"""
+    import numpy as np
+    if torch.is_tensor(y):
+        if y.is_cuda:
+            raise RuntimeError(f'te_hip: {what}: the labels are a host array (the ABI validates them before it launches), got {y.device}')
+        y = y.numpy()
+    y = np.ascontiguousarray(y, dtype=np.int8)
+    if y.shape != (n,):
+        raise RuntimeError(f'te_hip: {what} expects {n} labels, got {tuple(y.shape)}')
+    return y
+
+
+def gram(x):
+    """x [n,D] -> K = x x^T [n,n], bitwise symmetric"""
+    n, D = _features(x, 'gram')
+    K = torch.empty(n, n, device=x.device, dtype=torch.float32)
+    _check(lib().te_gram_f32(_ptr(K), _ptr(x), n, D, _stream()), 'te_gram_f32')
+    return K
+
+
+def svm_smo(K, y, C_=1.0, eps=1e-3, max_iter=1_000_000):
+    """the C-SVC dual on the Gram matrix K [n,n] with HOST labels y (+1 / -1) -> (alpha [n] fp64, rho [1] fp64, info [2] int32 =
+    (iterations, converged)), all on the device; nothing synchronises"""
+    if K.ndim != 2 or K.shape[0] != K.shape[1]:
+        raise RuntimeError(f'te_hip: svm_smo expects a square Gram matrix, got {tuple(K.shape)}')
+    n = K.shape[0]
+    y = _labels(y, n, 'svm_smo')
+    alpha = torch.empty(n, device=K.device, dtype=torch.float64)
+    rho = torch.empty(1, device=K.device, dtype=torch.float64)
+    info = torch.empty(2, device=K.device, dtype=torch.int32)
+    _check(lib().te_svm_smo_f64(_ptr_as(alpha, torch.float64), _ptr_as(rho, torch.float64), _ptr_as(info, torch.int32), _ptr(K),
+                                y.ctypes.data, n, float(C_), float(eps), int(max_iter), _stream()), 'te_svm_smo_f64')
+    return alpha, rho, info
+
+
+def svm_coef(x, alpha, y):
+    """w [D] = sum_i alpha_i y_i x[i,:] (fp64 accumulation, one rounding): x [n,D] fp32, alpha [n] fp64, HOST labels y"""
+    n, D = _features(x, 'svm_coef')
+    if alpha.shape != (n,):
+        raise RuntimeError(f'te_hip: svm_coef expects {n} alphas, got {tuple(alpha.shape)}')
+    y = _labels(y, n, 'svm_coef')
+    w = torch.empty(D, device=x.device, dtype=torch.float32)
+    _check(lib().te_svm_coef_f32(_ptr(w), _ptr(x), _ptr_as(alpha, torch.float64), y.ctypes.data, n, D, _stream()), 'te_svm_coef_f32')
+    return w
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1043,7 +1094,7 @@ def _install_roctx():
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
-             'fid_moments', 'fid_finalize']
+             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef']
     g = globals()
 
     def wrap(fn, name):
