@@ -675,6 +675,42 @@ int te_svm_smo_f64(double* alpha, double* rho, int32_t* info, const float* K, co
                    int64_t max_iter, te_stream_t stream);
 int te_svm_coef_f32(float* w, const float* x, const double* alpha, const int8_t* y, int n, int D, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M4  the Inception-v3 pool3 extractor of the FID (metrics/inception.py:16-163 InceptionV3 with use_fid_inception=True and
+ * output_blocks=[3], built by metrics/calc_inception.py:55 and metrics/fid_query.py:86): a general forward convolution and the small
+ * layers around it.  Forward only, NCHW fp32.  The final global average is te_adaptive_avgpool_f32 with OH = OW = 1.
+ *
+ * te_conv2d_f32 (inception.py:175-190; replaces every torchvision BasicConv2d of the network = Conv2d(bias=False) +
+ * BatchNorm2d(eps=0.001) in eval mode + ReLU, the batch norm folded into w and bias by the caller, and the torch.cat at
+ * inception.py:215, :243, :259, :267, :276, :292, :300, :310 and in torchvision's InceptionB / InceptionD):
+ *     out[b, c0 + m, oy, ox] = act(bias[m] + sum_{c,ky,kx} w[m,c,ky,kx] * x[b, c, oy*s + ky - py, ox*s + kx - px])      x = 0 outside
+ * x [B,Ci,H,W]; w [Co,Ci,kh,kw] (torch layout, read as it is: no packed form); bias [Co]; out is the channel slice [c0, c0 + Co) of a
+ * contiguous [B,Ctot,Ho,Wo] tensor, Ho = (H + 2 py - kh) / s + 1 (floor), Wo likewise; act 0 none, 1 ReLU (a NaN propagates).
+ * s = 1 or 2 and act = 0 or 1 (else TE_ERR_UNSUPPORTED), 1 <= kh, kw <= 7 (else TE_ERR_UNSUPPORTED), 0 <= py < kh, 0 <= px < kw,
+ * Ho, Wo >= 1, 0 <= c0, c0 + Co <= Ctot, any B, Ci, Co, H, W >= 1 with Ci * H * W, Ci * kh * kw and Ho * Wo below 2^31 (else
+ * TE_ERR_SHAPE); nothing is launched on a refusal.  An implicit GEMM on v_mfma_f32_32x32x2_f32, exact fp32: M = Co, N = the
+ * B * Ho * Wo pixels flattened across the batch, K = Ci * kh * kw; the patch is gathered into LDS on the fly (no im2col tensor, no
+ * workspace).  K is NOT split: each output element has one owner and is one fp32 fma chain over k in a fixed permutation that
+ * depends on K only, never on B or on the tile, so an image's outputs are bitwise the same whatever batch it is in.  No atomics.
+ *
+ * te_pool3_f32 (inception.py:89, :98 nn.MaxPool2d(3, 2) and torchvision's InceptionB / InceptionD pool branch; inception.py:306
+ * F.max_pool2d(x, 3, 1, 1); inception.py:210, :238, :271 F.avg_pool2d(x, 3, 1, 1, count_include_pad=False)): 3 x 3 windows over
+ * x [B,C,H,W] into the slice [c0, c0 + C) of a contiguous [B,Ctot,Ho,Wo] tensor.  mode 0: max, stride 2, no padding, floor
+ * (Ho = (H - 3) / 2 + 1; H, W >= 3); mode 1: max, stride 1, pad 1, the padding never wins; mode 2: average, stride 1, pad 1, summed
+ * row-major in fp32 and divided by the number of taps inside the image.  Max follows te_maxpool2_fwd_f32's rule: a greater value or
+ * a NaN replaces.
+ *
+ * te_resize_bilinear_f32 (inception.py:147-150; replaces F.interpolate(size, mode='bilinear', align_corners=False)): planes of H x W
+ * to OH x OW, any sizes up to 2^22, up- and downscaling, no antialiasing.  Per axis src = max((in / out) * (o + 0.5) - 0.5, 0), taps
+ * floor(src) and the next sample inside the image, weights l1 = src - floor(src), l0 = 1 - l1; x is mixed first, then y, as
+ * te_crop_resize_bilinear_f32 does.  src is evaluated exactly, as (in * (2 o + 1) - out) / (2 out) in integers (torch's fp32
+ * coordinate is off by up to in * 2^-23 of a sample); equal sizes give a bit-exact copy.  1 <= planes <= 65535.
+ */
+int te_conv2d_f32(float* out, const float* x, const float* w, const float* bias, int B, int Ci, int Co, int H, int W, int kh, int kw,
+                  int s, int py, int px, int Ctot, int c0, int act, te_stream_t stream);
+int te_pool3_f32(float* out, const float* x, int B, int C, int H, int W, int mode, int Ctot, int c0, te_stream_t stream);
+int te_resize_bilinear_f32(float* out, const float* x, int64_t planes, int H, int W, int OH, int OW, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

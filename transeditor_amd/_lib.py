@@ -121,6 +121,9 @@ _SIGNATURES = {
     'te_gram_f32': (C.c_int, [_P, _P, _I, _I, _P]),
     'te_svm_smo_f64': (C.c_int, [_P, _P, _P, _P, _P, _I, C.c_double, C.c_double, _L, _P]),
     'te_svm_coef_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    'te_conv2d_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 13 + [_P]),
+    'te_pool3_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'te_resize_bilinear_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1080,6 +1083,63 @@ def svm_coef(x, alpha, y):
     return w
 
 
+# --------------------------------------------------------------------------------------------- M4 Inception-v3 pool3 features
+POOL3_MAX_S2, POOL3_MAX_S1, POOL3_AVG_S1 = 0, 1, 2
+
+
+def conv2d_out_hw(H, W, kh, kw, stride=1, pad=(0, 0)):
+    return (H + 2 * pad[0] - kh) // stride + 1, (W + 2 * pad[1] - kw) // stride + 1
+
+
+def _slice_out(out, c0, B, Cn, Ho, Wo, like, what):
+    """the [B,Ctot,Ho,Wo] tensor a slice [c0, c0 + Cn) is written into: a new [B,Cn,Ho,Wo] one where none is given"""
+    if out is None:
+        if c0 != 0:
+            raise RuntimeError(f'te_hip: {what}: c0 = {c0} needs the output tensor it indexes')
+        return torch.empty(B, Cn, Ho, Wo, device=like.device, dtype=like.dtype)
+    if out.ndim != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (Ho, Wo):
+        raise RuntimeError(f'te_hip: {what}: the output must be [{B},Ctot,{Ho},{Wo}], got {tuple(out.shape)}')
+    return out
+
+
+def conv2d(x, w, bias, stride=1, pad=(0, 0), act=0, out=None, c0=0):
+    """act(conv2d(x, w, stride, pad) + bias) written into channels [c0, c0 + Co) of `out` [B,Ctot,Ho,Wo] (a new [B,Co,Ho,Wo] tensor
+    where out is None): x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co]; act 0 none, 1 ReLU.  The ABI refuses what it does not cover (a
+    stride above 2, a kernel above 7 x 7, padding >= the kernel, an empty output, a slice past Ctot); nothing is launched then.
+    Returns out."""
+    if x.ndim != 4 or w.ndim != 4 or bias.ndim != 1 or x.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0]:
+        raise RuntimeError(f'te_hip: conv2d: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
+    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    out = _slice_out(out, c0, B, Co, max(Ho, 0), max(Wo, 0), x, 'conv2d')
+    _check(lib().te_conv2d_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(bias), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], out.shape[1],
+                               c0, act, _stream()), 'te_conv2d_f32')
+    return out
+
+
+def pool3(x, mode, out=None, c0=0):
+    """3 x 3 pooling of x [B,C,H,W] into channels [c0, c0 + C) of `out`: POOL3_MAX_S2 (max, stride 2, no padding), POOL3_MAX_S1 (max,
+    stride 1, pad 1) or POOL3_AVG_S1 (average, stride 1, pad 1, over the taps inside the image).  Returns out."""
+    if x.ndim != 4:
+        raise RuntimeError(f'te_hip: pool3 expects [B,C,H,W], got {tuple(x.shape)}')
+    B, Cn, H, W = x.shape
+    Ho, Wo = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == POOL3_MAX_S2 else (H, W)
+    out = _slice_out(out, c0, B, Cn, max(Ho, 0), max(Wo, 0), x, 'pool3')
+    _check(lib().te_pool3_f32(_ptr(out), _ptr(x), B, Cn, H, W, mode, out.shape[1], c0, _stream()), 'te_pool3_f32')
+    return out
+
+
+def resize_bilinear(x, OH, OW):
+    """F.interpolate(x, (OH, OW), mode='bilinear', align_corners=False) of x [B,C,H,W]"""
+    if x.ndim != 4:
+        raise RuntimeError(f'te_hip: resize_bilinear expects [B,C,H,W], got {tuple(x.shape)}')
+    x = x.contiguous()
+    B, Cn, H, W = x.shape
+    out = torch.empty(B, Cn, OH, OW, device=x.device, dtype=x.dtype)
+    _check(lib().te_resize_bilinear_f32(_ptr(out), _ptr(x), B * Cn, H, W, OH, OW, _stream()), 'te_resize_bilinear_f32')
+    return out
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1094,7 +1154,7 @@ def _install_roctx():
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
-             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef']
+             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear']
     g = globals()
 
     def wrap(fn, name):

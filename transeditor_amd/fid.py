@@ -1,9 +1,12 @@
-"""The Frechet inception distance (FID): the reference's metrics/fid_query.py and metrics/calc_inception.py from the features on, with the
-feature moments on the gfx950 kernels of csrc/fid.hip.
+"""The Frechet inception distance (FID): the reference's metrics/fid_query.py and metrics/calc_inception.py, with the feature moments on
+the gfx950 kernels of csrc/fid.hip and the Inception-v3 pool3 features of transeditor_amd.inception_features.
 
     python -m transeditor_amd.fid --real real.npy --fake fake.npy                    (two feature files, float32 [N,D])
     python -m transeditor_amd.fid --stats inception_ffhq.pkl --fake fake.npy         (the reference's statistics file against features)
-    python -m transeditor_amd.fid --features real.npy --write_stats inception_x.pkl  (calc_inception.py's output; .pkl or .npz)
+    python -m transeditor_amd.fid --features real.npy --write_stats inception_x.pkl  (statistics of a feature file; .pkl or .npz)
+    python -m transeditor_amd.fid --dataset lmdb --inception W.pth --write_stats inception_x.pkl     (calc_inception.py end to end)
+    python -m transeditor_amd.fid --ckpt C --stats inception_x.pkl --inception W.pth                 (fid_query.py end to end;
+                                                                  --dataset lmdb in place of --stats: real statistics on the fly)
 
 The FID needs no features, only n, s = sum x and S = sum x x^T, and these add across batches, calls and ranks.  FeatureStats holds them
 on the device in fp64 and folds every full staging buffer in with one te_fid_moments_f64 call (a symmetric rank-N update on the fp64
@@ -20,7 +23,9 @@ Differences from the reference, all deliberate:
   - no feature is copied to the host: the reference synchronises device and host once per batch (feat.to('cpu')), here finalize() is
     the one synchronisation.
 The count n is known on the host from the shapes of the batches, so FeatureStats keeps it as a Python int and reading it never
-synchronises.  The Inception-v3 network is not part of this module: `feature_fn` is any callable images [B,3,S,S] -> [B,D] fp32.
+synchronises.  `feature_fn` is any callable images [B,3,S,S] -> [B,D] fp32; the reference's network is
+transeditor_amd.inception_features.InceptionV3Features (the TensorFlow-FID Inception-v3 up to pool3, on te_conv2d_f32), which the
+--dataset and --ckpt modes of the command line build from a local weight file.
 """
 import argparse
 import json
@@ -270,10 +275,29 @@ def evaluate_fid(generator, feature_fn, real_stats, **kw):
 
 # ------------------------------------------------------------------------------------------------------------------------ CLI
 class _Parser(argparse.ArgumentParser):
-    """three modes that exclude each other; parse_args sets args.mode = 'files' | 'stats' | 'write'"""
+    """five modes that exclude each other; parse_args sets args.mode = 'files' | 'stats' | 'write' (from feature files) |
+    'dataset' (a dataset through the Inception network into a statistics file) | 'model' (a checkpoint against statistics)"""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
+        if a.ckpt is not None:
+            if any(v is not None for v in (a.real, a.fake, a.features, a.write_stats)):
+                self.error('--ckpt (a checkpoint through the Inception network) excludes --real, --fake, --features and --write_stats')
+            if (a.stats is None) == (a.dataset is None):
+                self.error('--ckpt needs the real statistics: exactly one of --stats (a file) and --dataset (computed on the fly)')
+            if a.size < 32 or a.size & (a.size - 1):
+                self.error(f'--size must be a power of two >= 32, got {a.size}')
+            a.mode = 'model'
+            return a
+        if a.dataset is not None:
+            if a.write_stats is None:
+                self.error('--dataset needs --write_stats (the statistics file to write) or --ckpt (a checkpoint to evaluate)')
+            if any(v is not None for v in (a.real, a.fake, a.stats, a.features)):
+                self.error('--dataset / --write_stats (write a statistics file) exclude --real, --stats, --fake and --features')
+            a.mode = 'dataset'
+            return a
+        if a.inception is not None:
+            self.error('--inception (the network weights) goes with --dataset or --ckpt; the other modes start from features')
         if (a.features is None) != (a.write_stats is None):
             self.error('--features and --write_stats go together')
         if a.features is not None:
@@ -284,7 +308,7 @@ class _Parser(argparse.ArgumentParser):
         if a.real is not None and a.stats is not None:
             self.error('--real (a feature file) and --stats (a statistics file) exclude each other')
         if a.real is None and a.stats is None:
-            self.error('give --real and --fake, --stats and --fake, or --features and --write_stats')
+            self.error('give --real and --fake, --stats and --fake, --features and --write_stats, --dataset and --write_stats, or --ckpt')
         if a.fake is None:
             self.error('--real / --stats need --fake')
         a.mode = 'files' if a.real is not None else 'stats'
@@ -293,20 +317,74 @@ class _Parser(argparse.ArgumentParser):
 
 def build_parser():
     parser = _Parser(description='Frechet inception distance (metrics/fid_query.py) of two feature files (--real, --fake) or of a '
-                                 'statistics file against a feature file (--stats, --fake); or write the statistics file of a feature '
-                                 'file (--features, --write_stats: metrics/calc_inception.py)')
+                                 'statistics file against a feature file (--stats, --fake); write the statistics file of a feature '
+                                 'file (--features, --write_stats) or of a dataset through the Inception network (--dataset, '
+                                 '--write_stats: metrics/calc_inception.py); or evaluate a checkpoint (--ckpt with --stats or --dataset)')
     parser.add_argument('--real', help='.npy file of the real features [N,D], float32')
     parser.add_argument('--fake', help='.npy file of the generated features [M,D], float32')
     parser.add_argument('--stats', help="statistics of the real set: calc_inception.py's pickle, or an .npz with mean and cov")
     parser.add_argument('--features', help='.npy file of features [N,D], float32, whose statistics are written')
     parser.add_argument('--write_stats', help='output statistics file (.pkl as calc_inception.py writes it, or .npz)')
+    parser.add_argument('--ckpt', help='a checkpoint file, or a directory of <iteration>.pt files')
+    parser.add_argument('--dataset', help='LMDB directory of the real images (utils/dataset.py MultiResolutionDataset)')
+    parser.add_argument('--inception', default=None, help='pytorch-fid Inception-v3 state dict (default: the torch hub cache path)')
+    parser.add_argument('--size', type=int, default=256)
+    parser.add_argument('--n_sample', type=int, default=50000)
+    parser.add_argument('--batch', type=int, default=64)
+    parser.add_argument('--start_num', type=int, default=0)
+    parser.add_argument('--truncation', type=float, default=1.0)
+    parser.add_argument('--seed', type=int, default=None, help='seed of the generated codes and of the choice of real images')
+    parser.add_argument('--flip', action='store_true', help='random horizontal flips of the real images (calc_inception.py --flip)')
+    parser.add_argument('--para_num', type=int, default=16)
+    parser.add_argument('--channel_multiplier', type=int, default=2)
+    parser.add_argument('--num_trans', type=int, default=8)
     return parser
+
+
+def _dataset_stats_of(args, net):
+    """calc_inception.py:93-111: the statistics of min(n_sample, len) images of the LMDB dataset at --size"""
+    from .utils.dataset import MultiResolutionDataset, image_transform
+    dataset = MultiResolutionDataset(args.dataset, image_transform(flip_probability=0.5 if args.flip else 0), args.size)
+    n = min(args.n_sample, len(dataset))
+    return dataset_stats(dataset, net, n_sample=n, batch=args.batch, seed=args.seed), n
+
+
+def _network_modes(args):
+    import math
+    from .inception_features import InceptionV3Features
+    net = InceptionV3Features(args.inception)
+    if args.mode == 'dataset':
+        stats, n = _dataset_stats_of(args, net)
+        mean, cov = stats.finalize()
+        save_stats(args.write_stats, mean, cov, size=args.size, path=args.dataset)              # calc_inception.py:115-116's keys
+        res = {'metric': 'fid_stats', 'dataset': args.dataset, 'n': n, 'dim': int(mean.shape[0]), 'wrote': args.write_stats}
+        print(json.dumps(res), flush=True)
+        return res
+    from .inference import GeneratorSampler
+    from .metrics import checkpoints
+    from .model_spatial_query import Generator
+    from .train_step import load_checkpoint_into
+    real = load_stats(args.stats) if args.stats is not None else _dataset_stats_of(args, net)[0].finalize()
+    results = []
+    for model_path in checkpoints(args.ckpt, args.start_num):
+        g = Generator(args.size, 512, 512, 2 * (int(math.log(args.size, 2)) - 1), channel_multiplier=args.channel_multiplier,
+                      n_trans=args.num_trans, pixel_norm_op_dim=1).to('cuda')
+        load_checkpoint_into(model_path, g, device='cuda', g_ema_only_ok=True)
+        res = {'metric': 'fid', 'ckpt': model_path, 'stats': args.stats, 'dataset': args.dataset, 'n_fake': args.n_sample,
+               'truncation': args.truncation}
+        res['fid'] = evaluate_fid(GeneratorSampler(g), net, real, n_sample=args.n_sample, batch=args.batch, truncation=args.truncation,
+                                  seed=args.seed, para_num=args.para_num)
+        print(json.dumps(res), flush=True)
+        results.append(res)
+    return results
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError(_NO_GPU)
+    if args.mode in ('dataset', 'model'):
+        return _network_modes(args)
     if args.mode == 'write':
         f = np.load(args.features, allow_pickle=False)
         mean, cov = _stats_of(f, '--features')
