@@ -1,5 +1,6 @@
 """transeditor_amd.edit without a GPU: the numpy restatement of the SMO solve (tests/svm_restated.py) against the reference's own
-boundaries (tests/golden/boundary_ref.npz, tools/gen_boundary_golden.py), linear_interpolate against the reference's outputs,
+boundaries (tests/golden/boundary_ref.npz and boundary_ref_large.npz, tools/gen_boundary_golden.py), the hand-placed tie problems of
+the GPU tests against their hand-derived answer, linear_interpolate against the reference's outputs,
 select_extremes' rules, the three ValueErrors, the command line's exclusions and the host-side argument checks of the ABI."""
 import os
 
@@ -17,6 +18,9 @@ CASES = ['a', 'b', 'c']
 # shuffle (3.4e-6 .. 3.8e-6 seen on case c), the restatement's with the BLAS behind its Gram matrix.  Kept below 1e-4.
 RESTATED_BAR = 8 * 3.45e-6
 assert RESTATED_BAR < 1e-4
+# The same rule for case d (n = 4200, boundary_ref_large.npz): 8 x the 7.36e-7 the tool printed when that fixture was written
+# (BOUNDARY_REPORT.txt; 5.1e-7 .. 7.4e-7 over three runs of the reference's unseeded shuffle).
+RESTATED_BAR_LARGE = 8 * 7.36e-7
 
 
 @pytest.fixture(scope='module')
@@ -46,6 +50,49 @@ def test_restatement_reproduces_the_reference_boundary(golden, case):
           f'{R.one_minus_cos(w, golden[f"{case}_optimum"]):.2e}')
     assert gap <= RESTATED_BAR
     assert float(w @ golden[f'{case}_boundary'][0]) > 0                                    # toward high scores
+
+
+def test_restatement_reproduces_the_reference_boundary_at_the_default_size():
+    """case d: 4200 training rows, what the reference's default run trains on; five rows per thread of the GPU solver"""
+    with np.load(os.path.join(GOLDEN, 'boundary_ref_large.npz'), allow_pickle=False) as z:
+        golden = {k: z[k] for k in z.files}
+    codes, scores = R.draw('d')
+    assert np.array_equal(codes, golden['d_codes']) and np.array_equal(scores, golden['d_scores'])
+    x, y = R.training_set(codes, scores, R.CASES['d'][2])
+    assert x.shape == (4200, 12) and int((y > 0).sum()) == 2100
+    K = R.gram32(x)
+    alpha, rho, it, converged = R.smo(K, y)
+    assert converged and it == int(golden['d_iterations'])
+    assert alpha.min() >= 0.0 and alpha.max() <= 1.0 and abs(float(alpha @ y)) <= len(y) * 2.0 ** -52
+    assert R.violation(K, y, alpha, 1.0) < 1e-3 * (1 + 1e-6)
+    assert (alpha >= 1.0).sum() > 1000 and ((alpha > 0) & (alpha < 1.0)).sum() > 0           # not separable
+    assert R.slots(np.nonzero(alpha > 0)[0]) == [0, 1, 2, 3, 4]                              # support vectors in every slot
+    w = R.direction(x, y, alpha)
+    gap = R.one_minus_cos(w, golden['d_boundary'])
+    print(f'case d: {it} iterations, 1 - cos restatement to reference {gap:.2e} (bar {RESTATED_BAR_LARGE:.2e}), to the optimum '
+          f'{R.one_minus_cos(w, golden["d_optimum"]):.2e}')
+    assert gap <= RESTATED_BAR_LARGE
+    assert float(w @ golden['d_boundary'][0]) > 0
+
+
+@pytest.mark.parametrize('C', [1.0, 0.125])
+@pytest.mark.parametrize('flip', [False, True])
+@pytest.mark.parametrize('layout', list(R.TIE_LAYOUTS))
+def test_restatement_on_the_tie_problems_gives_the_hand_derived_answer(layout, flip, C):
+    """All rows of a class are one vector, so every selection is a tie and np.argmax takes the lowest row: the support is the k lowest
+    rows of each class, after k iterations (svm_restated.tie_support).  The GPU tests hold the kernel to this restatement."""
+    K, y = R.tie_problem(layout, flip)
+    assert K.dtype == np.float32 and K.shape == (R.TIE_N, R.TIE_N) and np.array_equal(K, K.T) and sorted(np.unique(K)) == [-1.0, 1.0625, 1.25]
+    placed = np.nonzero(y < 0 if flip else y > 0)[0].tolist()
+    assert placed == sorted(R.TIE_LAYOUTS[layout]) and len(placed) >= 5
+    alpha, rho, it, converged = R.smo(K, y, C, 1e-3)
+    support, k = R.tie_support(y, C)
+    assert converged and it == k and np.nonzero(alpha > 0)[0].tolist() == support
+    step = 2.0 / 4.3125                                                                       # the unconstrained step of one pair
+    want = [C] * (k - 1) + [step - (k - 1) * C]
+    for cls in (1, -1):
+        assert np.allclose(alpha[[i for i in support if y[i] == cls]], want, rtol=0, atol=1e-15)
+    assert abs(rho - (1.25 - 1.0625) / 4.3125) <= 1e-15                                          # the midplane of the two rows
 
 
 def test_restatement_stops_at_max_iter_with_a_feasible_iterate(golden):

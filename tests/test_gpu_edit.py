@@ -1,6 +1,8 @@
 """transeditor_amd.edit on the GPU: the three kernels of csrc/svm.hip at the binding level against float64, the solver's result
 against the optimality conditions of the problem it was given (path-independent), train_boundary end to end against the reference's own
-boundaries (tests/golden/boundary_ref.npz), edit_sweep / sample_codes against the GeneratorSampler, and the command line."""
+boundaries (tests/golden/boundary_ref.npz, boundary_ref_large.npz), edit_sweep / sample_codes against the GeneratorSampler, and the
+command line.  Above 1024 rows a thread of the one-workgroup solver owns several rows (smo_kernel<R>, R = 2 .. 8; the default run
+is R = 5): every R against the optimality conditions, and the lowest-index tie rule at each of its three levels on hand-placed ties."""
 import json
 import os
 import warnings
@@ -20,8 +22,11 @@ C, EPS = 1.0, 1e-3
 
 @pytest.fixture(scope='module')
 def golden():
-    with np.load(os.path.join(GOLDEN, 'boundary_ref.npz'), allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    out = {}
+    for name in ('boundary_ref.npz', 'boundary_ref_large.npz'):                  # cases a, b, c and li_*; case d
+        with np.load(os.path.join(GOLDEN, name), allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 @pytest.fixture(scope='module')
@@ -143,6 +148,124 @@ def test_smo_refuses_bad_arguments_before_any_launch(solved):
         _lib.svm_smo(Kd, np.ones(n, np.int8), C, EPS)
 
 
+# ---------------------------------------------------------------------------------------------------------- above 1024 rows
+# (n, hardest rows last): every instantiation R = ceil(n / 1024) = 2 .. 8, the edges 1025 / 2048 / 2049 / 8192 and the default run's
+# 4200.  Hardest last: every support vector, so every selected i and j, lies in the last slots; the random order puts them in all.
+LARGE = [(1025, True), (2048, True), (2049, True), (4096, True), (4200, True), (4200, False), (5121, True), (7000, True), (8192, True)]
+
+
+@pytest.mark.parametrize('n,hardest_last', LARGE)
+def test_smo_above_1024_rows_meets_the_optimality_conditions_of_its_problem(n, hardest_last):
+    """test_smo_meets_the_optimality_conditions_of_its_problem where thread t owns the rows t, t + 1024, ...: D = 16, margin 0.5, label
+    noise 0.3 (svm_restated.margin_problem), C = 1, eps = 1e-3.  The restatement runs on the Gram matrix the kernel was given."""
+    from transeditor_amd import _lib
+    x, y = R.margin_problem(n, hardest_last=hardest_last)
+    Kd = _lib.gram(torch.from_numpy(x).to(DEV))
+    alpha, rho, info = _lib.svm_smo(Kd, y, C, EPS)
+    alpha, rho, info = alpha.cpu().numpy(), float(rho.item()), info.cpu().numpy()
+    K = Kd.cpu().numpy().astype(np.float64)                                      # the one float64 copy of this case
+    del Kd
+    slots = (n + R.SLOT - 1) // R.SLOT
+    assert alpha.dtype == np.float64 and alpha.shape == (n,)
+    assert alpha.min() >= 0.0 and alpha.max() <= C
+    assert abs(float(alpha @ y.astype(np.float64))) <= n * C * 2.0 ** -52
+    viol = R.violation(K, y, alpha, C)
+    want_alpha, want_rho, want_it, conv = R.smo(K, y, C, EPS)
+    sv, want_sv = np.nonzero(alpha > 0)[0], np.nonzero(want_alpha > 0)[0]
+    print(f'n {n} R {slots} {"hardest last" if hardest_last else "random order"}: {info[0]} iterations (restatement on the same Gram: '
+          f'{want_it}), violation {viol:.6e}, rho {rho:.6f} (restatement {want_rho:.6f}), {int((alpha >= C).sum())} alphas at C, '
+          f'{len(sv)} support vectors in slots {R.slots(sv)} (restatement {len(want_sv)} in {R.slots(want_sv)})')
+    assert viol < EPS * (1 + 1e-6)
+    assert info[1] == 1 and conv
+    assert want_it / 2 <= info[0] <= want_it * 2
+    gmax, gmin = R.extremes(K, y, alpha, C)
+    assert -gmax - 1e-9 <= rho <= -gmin + 1e-9
+    if hardest_last:                                                             # a property of the input: the top slot is in use
+        assert want_sv.max() >= R.SLOT * (slots - 1) and sv.max() >= R.SLOT * (slots - 1)
+    else:
+        assert R.slots(want_sv) == list(range(slots)) and R.slots(sv) == list(range(slots))
+    del K
+
+
+@pytest.mark.parametrize('C_', [1.0, 0.125])
+@pytest.mark.parametrize('flip', [False, True])
+@pytest.mark.parametrize('layout', list(R.TIE_LAYOUTS))
+def test_smo_ties_go_to_the_lowest_index_at_every_level(layout, flip, C_):
+    """svm_restated.tie_problem: K is built on the host from two rows, so all rows of a class are the same bits and every selection is a
+    tie among all candidates of a class; the layouts put the two lowest candidates where a wrong preference per thread, across lanes
+    or across waves would pick the other (flip: the placed class is -1, so selection B meets the tie that selection A met).  C = 1:
+    one iteration, two support vectors; C = 0.125: the box fills the four lowest rows of each class in order."""
+    from transeditor_amd import _lib
+    K, y = R.tie_problem(layout, flip)
+    Kd = torch.from_numpy(K).to(DEV)
+    runs = []
+    for _ in range(2):
+        alpha, rho, info = _lib.svm_smo(Kd, y, C_, EPS)
+        runs.append((alpha.cpu().numpy(), float(rho.item()), info.cpu().numpy()))
+    alpha, rho, info = runs[0]
+    want_alpha, want_rho, want_it, conv = R.smo(K, y, C_, EPS)
+    support, k = R.tie_support(y, C_)
+    assert conv and want_it == k and np.nonzero(want_alpha > 0)[0].tolist() == support   # the restatement gives the hand-derived answer
+    print(f'{layout} flip {flip} C {C_}: support {np.nonzero(alpha > 0)[0].tolist()} (restatement {support}), {info[0]} iterations '
+          f'({want_it}), max |alpha - restatement| {np.abs(alpha - want_alpha).max():.2e}, rho {rho!r} ({want_rho!r})')
+    assert np.nonzero(alpha > 0)[0].tolist() == support
+    assert info.tolist() == [want_it, 1]
+    assert np.abs(alpha - want_alpha).max() <= 1e-12 and abs(rho - want_rho) <= 1e-12
+    assert runs[1][0].tobytes() == alpha.tobytes() and runs[1][1] == rho and np.array_equal(runs[1][2], info)
+
+
+def test_smo_at_4200_rows_is_bit_reproducible_and_stops_at_max_iter():
+    from transeditor_amd import _lib
+    x, y = R.margin_problem(4200, hardest_last=False)
+    Kd = _lib.gram(torch.from_numpy(x).to(DEV))
+    a1, r1, i1 = _lib.svm_smo(Kd, y, C, EPS)
+    a2, r2, i2 = _lib.svm_smo(Kd, y, C, EPS)
+    assert i1.tolist()[1] == 1 and i1.tolist()[0] > 1000
+    assert a1.cpu().numpy().tobytes() == a2.cpu().numpy().tobytes() and r1.cpu().numpy().tobytes() == r2.cpu().numpy().tobytes()
+    assert i1.cpu().numpy().tobytes() == i2.cpu().numpy().tobytes()
+    alpha, rho, info = _lib.svm_smo(Kd, y, C, EPS, max_iter=7)
+    alpha = alpha.cpu().numpy()
+    assert info.tolist() == [7, 0] and np.isfinite(float(rho.item()))
+    assert alpha.min() >= 0.0 and alpha.max() <= C and abs(float(alpha @ y.astype(np.float64))) <= len(y) * C * 2.0 ** -52
+    assert (alpha > 0).sum() >= 2
+
+
+@pytest.mark.parametrize('D', [16, 33])
+@pytest.mark.parametrize('n', [1025, 4200])
+def test_gram_above_1024_rows_against_fp64_symmetric_and_reproducible(n, D):
+    """9 and 33 tiles per side, the 16-byte (D = 16) and the scalar (D = 33) loads; the bar of
+    test_gram_against_fp64_symmetric_and_reproducible."""
+    from transeditor_amd import _lib
+    x = np.random.default_rng(100 * n + D).standard_normal((n, D)).astype(np.float32)
+    xd = torch.from_numpy(x).to(DEV)
+    K = _lib.gram(xd)
+    again = _lib.gram(xd)
+    assert K.shape == (n, n) and K.dtype == torch.float32
+    assert torch.equal(K, K.T)
+    assert torch.equal(K, again)
+    x64 = x.astype(np.float64)
+    nx = (x64 ** 2).sum(1)
+    bar = 2e-6 * (nx[:, None] + nx[None, :])
+    err = np.abs(K.cpu().numpy().astype(np.float64) - x64 @ x64.T)
+    print(f'gram n {n} D {D}: max |gpu - fp64| / bar {float((err / bar).max()):.3f}')
+    assert np.all(err <= bar)
+
+
+def test_coef_at_8192_rows_within_one_ulp_of_the_fp64_sum():
+    from transeditor_amd import _lib
+    rng = np.random.default_rng(9)
+    n, D = 8192, 65
+    x = rng.standard_normal((n, D)).astype(np.float32)
+    kind = rng.random(n)                                                         # as a solve leaves them: most 0, some at C, a few free
+    alpha = np.where(kind < 0.8, 0.0, np.where(kind < 0.95, 1.0, rng.random(n)))
+    assert (alpha == 0).sum() > 6000 and (alpha == 1).sum() > 1000 and alpha[-1024:].any()
+    y = np.where(rng.random(n) < 0.5, 1, -1).astype(np.int8)
+    w = _lib.svm_coef(torch.from_numpy(x).to(DEV), torch.from_numpy(alpha).to(DEV), y).cpu().numpy()
+    want = ((alpha * y) @ x.astype(np.float64)).astype(np.float32)
+    assert w.dtype == np.float32 and w.shape == (D,)
+    assert np.all(np.abs(w.astype(np.float64) - want.astype(np.float64)) <= np.spacing(np.abs(want)).astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------------- te_svm_coef_f32
 def test_coef_within_one_ulp_of_the_fp64_sum():
     from transeditor_amd import _lib
@@ -158,7 +281,7 @@ def test_coef_within_one_ulp_of_the_fp64_sum():
 
 
 # ---------------------------------------------------------------------------------------------------------- train_boundary
-@pytest.mark.parametrize('case', CASES)
+@pytest.mark.parametrize('case', CASES + ['d'])
 def test_train_boundary_end_to_end(golden, case):
     """1 - cos to the stored float64 optimum: at most 4x the larger of the reference's and the restatement's own value on this case.
     All three are eps = 1e-3 solutions of one strictly convex problem; 4x in 1 - cos is 2x in angle, the room for two eps-optimal
@@ -179,7 +302,7 @@ def test_train_boundary_end_to_end(golden, case):
     assert report['train_accuracy'] == float(((f > 0) == (y > 0)).mean()) and report['val_accuracy'] is None
     assert report['converged'] is True and report['n_train'] == len(y) and report['n_val'] == 0
     assert 0 < report['n_support'] <= len(y) and report['iterations'] > 0
-    if case != 'b':
+    if case in ('a', 'c'):                                                       # b and d are not separable
         assert report['train_accuracy'] == 1.0
     # a validation split, and device tensors in place of numpy: the same bits
     b1, r1 = edit.train_boundary(codes, scores, ratio, split_ratio=0.7, seed=4)

@@ -1,8 +1,9 @@
-"""Writes tests/golden/boundary_ref.npz: what the reference's own train_boundary (our_interfaceGAN/train_boundary.py: sklearn's
+"""Writes tests/golden/boundary_ref.npz (and with --large tests/golden/boundary_ref_large.npz): what the reference's own train_boundary (our_interfaceGAN/train_boundary.py: sklearn's
 SVC(kernel='linear')) and linear_interpolate (our_interfaceGAN/linear_interpolation.py) return on seeded inputs, with the inputs.
 CPU only, seconds; needs scikit-learn.
 
     python tools/gen_boundary_golden.py --reference /path/to/TransEditor [--out tests/golden/boundary_ref.npz]
+    python tools/gen_boundary_golden.py --reference /path/to/TransEditor --large [--out tests/golden/boundary_ref_large.npz]
 
 Both functions are executed from the reference's own files; nothing is copied.  One shim: np.int = int (numpy 2 dropped the alias that
 train_boundary.py:81 uses).  The cases are tests/svm_restated.py's CASES / draw(): standard normal float32 codes, scores = a random unit
@@ -15,6 +16,9 @@ rows, which the optimum does not depend on.  Stored per case: <case>_codes, _sco
 direction of tests/svm_restated.py at eps = 1e-9 on the float64 Gram matrix), _gap_ref / _gap_restated (1 - cos of the reference's and
 of the restatement's eps = 1e-3 boundary to that optimum), _gap (1 - cos restatement to reference), _iterations (the restatement's).
 li_*: the inputs and outputs of linear_interpolate in its 2-D and its W+ form.
+--large writes svm_restated.LARGE_CASES to a file of their own, without the li_* entries; the small file is left alone:
+    d: N 6000, D 12, ratio 0.35, noise 1.0  -> n = 4200, the training rows of the reference's default run (150 000 samples, ratio 0.02,
+       split 0.7), NOT separable: five rows per thread of the one-workgroup solver of csrc/svm.hip
 """
 import argparse
 import contextlib
@@ -39,15 +43,19 @@ def load_reference(root, name):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reference', required=True, help='root of the reference repository')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'tests', 'golden', 'boundary_ref.npz'))
+    ap.add_argument('--large', action='store_true', help='the cases above 1024 training rows, to boundary_ref_large.npz')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'tests', 'golden', 'boundary_ref_large.npz' if a.large else 'boundary_ref.npz')
     if not hasattr(np, 'int'):
         np.int = int
     tb = load_reference(a.reference, 'train_boundary')
     li = load_reference(a.reference, 'linear_interpolation')
     import svm_restated as R
     out = {}
-    for case, (N, D, ratio, noise, seed) in R.CASES.items():
+    for case in (R.LARGE_CASES if a.large else R.SMALL_CASES):
+        N, D, ratio, noise, seed = R.CASES[case]
         codes, scores = R.draw(case)
         with contextlib.redirect_stdout(io.StringIO()):
             boundary = tb.train_boundary(codes, scores, chosen_num_or_ratio=ratio, split_ratio=1.0)
@@ -59,19 +67,21 @@ def main():
         w, w9 = R.direction(x, y, alpha), R.direction(x, y, alpha9)
         gap, gap_ref, gap_rest = R.one_minus_cos(w, boundary), R.one_minus_cos(boundary, w9), R.one_minus_cos(w, w9)
         print(f'case {case}: N {N} D {D} n {len(y)}  restatement: {it} iterations, {int((alpha >= 1.0).sum())} alphas at C, '
-              f'{int((alpha > 0).sum())} support vectors, rho {rho:.6f};  1 - cos restatement to reference {gap:.2e}, reference to the '
+              f'{int((alpha > 0).sum())} support vectors' + (f' in slots {R.slots(np.nonzero(alpha > 0)[0])}' if a.large else '')
+              + f', rho {rho:.6f};  1 - cos restatement to reference {gap:.2e}, reference to the '
               f'eps=1e-9 optimum {gap_ref:.2e}, restatement to the optimum {gap_rest:.2e}')
         out.update({f'{case}_codes': codes, f'{case}_scores': scores, f'{case}_boundary': boundary.astype(np.float32),
                     f'{case}_optimum': w9, f'{case}_gap': np.float64(gap), f'{case}_gap_ref': np.float64(gap_ref),
                     f'{case}_gap_restated': np.float64(gap_rest), f'{case}_iterations': np.int64(it)})
-    rng = np.random.default_rng(11)
-    b = out['a_boundary']
-    code2 = rng.standard_normal((1, b.shape[1])).astype(np.float32)
-    code3 = rng.standard_normal((1, 5, b.shape[1])).astype(np.float32)
-    out.update(li_boundary=b, li_code2=code2, li_code3=code3, li_start=np.float64(-3.0), li_end=np.float64(2.5), li_steps=np.int64(7),
-               li_out2=li.linear_interpolate(code2, b, start_distance=-3.0, end_distance=2.5, steps=7),
-               li_out3=li.linear_interpolate(code3, b, start_distance=-3.0, end_distance=2.5, steps=7))
-    assert out['li_out2'].dtype == np.float32 and out['li_out3'].dtype == np.float32
+    if not a.large:
+        rng = np.random.default_rng(11)
+        b = out['a_boundary']
+        code2 = rng.standard_normal((1, b.shape[1])).astype(np.float32)
+        code3 = rng.standard_normal((1, 5, b.shape[1])).astype(np.float32)
+        out.update(li_boundary=b, li_code2=code2, li_code3=code3, li_start=np.float64(-3.0), li_end=np.float64(2.5), li_steps=np.int64(7),
+                   li_out2=li.linear_interpolate(code2, b, start_distance=-3.0, end_distance=2.5, steps=7),
+                   li_out3=li.linear_interpolate(code3, b, start_distance=-3.0, end_distance=2.5, steps=7))
+        assert out['li_out2'].dtype == np.float32 and out['li_out3'].dtype == np.float32
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.savez_compressed(a.out, **out)
     print(f'wrote {a.out} ({os.path.getsize(a.out)} bytes)')
