@@ -9,8 +9,9 @@
  *     no synchronisation; safe to call from several host threads.  The process-wide mutable state behind this ABI is:
  *       - te_wgrad_split_bf16 (initialised from TE_SPLIT_BF16; the Python layer writes it): selects the split bf16 or the fp32
  *         weight-gradient kernel and with it the slab partition - results are fp32-equivalent, not bit-identical, across its values;
- *       - four test and tool hooks, te_conv_wino6_form, te_conv_s2s6_form, te_conv_t2s6_form and te_wgrad_t2_wide, which select
- *         between kernels of one kind with bit-identical results (tests compare the two live kernels of a kind on one input);
+ *       - five test and tool hooks, te_conv_wino6_form, te_conv_wino6_tiles_per_block, te_conv_s2s6_form, te_conv_t2s6_form and
+ *         te_wgrad_t2_wide, which select between kernels of one kind, or between grids of one kernel, with bit-identical results
+ *         (tests compare the two live kernels of a kind on one input);
  *       - TE_XCD_INTERLEAVED, read once from the environment: the order in which the convolution launches hand tiles to the XCDs
  *         (te_common.h); results are bit-identical;
  *       - the per-thread last-error string;
@@ -243,6 +244,16 @@ int te_conv_p1s6_supported(int B, int K, int M, int H, int W);
  *       half tile while the other transforms / splits / writes the next half tile and renews half of the weight image.
  * All forms issue the same products in the same order per output element: results are bit-identical. */
 int te_conv_wino6_form(int form);
+/* Tiles per block of the two-image form of TE_CONV_3X3W6 (a test and tool hook, process-wide; returns the previous value; anything
+ * but 0 .. 4096 only queries).  A block of that form walks a run of consecutive tiles of its XCD with one M block and carries its
+ * pipeline across them: the fetch, the split arithmetic and the weight DMA of a tile's first stage run in the shadow of the previous
+ * tile's last stage; only the epilogue stands between two tiles.
+ *   0 = automatic (default): runs of at most four tiles, fewer (three, two) where four would leave CUs without a block or cost the
+ *       launch more rounds of tile times over the CUs than one-tile blocks do; one tile per block where even two would;
+ *   1 = one tile per block;
+ *   n >= 2 = runs of at most n tiles (lengths differ by at most one within an XCD).
+ * Every output element sees the same products in the same order whatever the value: results are bit-identical. */
+int te_conv_wino6_tiles_per_block(int n);
 /* Kernel form of TE_CONV_S2S6 (returns the previous value; anything but 0 .. 2 only queries), a test and tool hook like the one above:
  *   1 = (round 6, default) the two-image form: a block owns 128 output channels and multiplies every staged half tile by two
  *       64-channel weight images (half the fetches, split arithmetic and LDS writes per MFMA) where M % 128 == 0 and the grid

@@ -42,6 +42,7 @@ _SIGNATURES = {
     'te_conv_wino_supported': (C.c_int, [_I, _I, _I, _I, _I]),
     'te_conv_wino6_supported': (C.c_int, [_I, _I, _I, _I, _I]),
     'te_conv_wino6_form': (C.c_int, [_I]),
+    'te_conv_wino6_tiles_per_block': (C.c_int, [_I]),
     'te_conv_s2s6_form': (C.c_int, [_I]),
     'te_conv_t2s6_form': (C.c_int, [_I]),
     'te_conv_t2s6_ws_floats': (C.c_int64, [_I, _I, _I]),
@@ -398,6 +399,12 @@ def wino6_form(form=-1):
     """test and tool hook: kernel form of TE_CONV_3X3W6 - 2 = two-image (default; M % 128 == 0 and a block per CU, else ping-pong),
     3 = two-image wherever M % 128 == 0, 1 = ping-pong (bit-identical results); returns the previous value (any other value: query only)"""
     return int(lib().te_conv_wino6_form(form))
+
+
+def wino6_tiles_per_block(n=-1):
+    """test and tool hook: tiles a block of the two-image form of TE_CONV_3X3W6 walks - 0 = automatic (default), 1 = one tile per block,
+    n >= 2 = runs of at most n tiles (bit-identical results); returns the previous value (anything but 0 .. 4096: query only)"""
+    return int(lib().te_conv_wino6_tiles_per_block(n))
 
 
 def s2s6_form(form=-1):

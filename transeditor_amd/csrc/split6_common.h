@@ -91,6 +91,28 @@ __device__ __forceinline__ bool split6_tile(int ntiles, int nt8, int mblocks, in
     return tile < (nt8 ? (int)(((int64_t)(xcd + 1) * ntiles) >> 3) : ntiles);
 }
 
+// ---- a LIST of consecutive tiles for a workgroup that walks several (wino6q_kernel).  The tiles of an XCD, in the order split6_tile
+// defines (so that neighbouring tiles keep sharing halo rows in one L2), are cut into `lists` runs whose lengths differ by at most one;
+// the grid is 8 lists mblocks.  The run is tile, tile + step, ... < end (step 1 in banded order, 8 in interleaved order); false = an empty
+// run.  lists == 0: one tile per workgroup, exactly split6_tile's assignment.
+__device__ __forceinline__ bool split6_tile_list(int ntiles, int nt8, int mblocks, int lists, int& tile, int& end, int& step, int& mb) {
+    step = nt8 ? 1 : 8;
+    if (lists == 0) {
+        const bool has = split6_tile(ntiles, nt8, mblocks, tile, mb);
+        end = tile + step;
+        return has;
+    }
+    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
+    const int lq = jx / mblocks;
+    mb = jx % mblocks;
+    const int first = nt8 ? (int)(((int64_t)xcd * ntiles) >> 3) : xcd;
+    const int nb = nt8 ? (int)(((int64_t)(xcd + 1) * ntiles) >> 3) - first : (ntiles - xcd + 7) >> 3;          // tiles of this XCD
+    const int lo = (int)((int64_t)lq * nb / lists), hi = (int)((int64_t)(lq + 1) * nb / lists);
+    tile = first + step * lo;
+    end = first + step * hi;
+    return lo < hi;
+}
+
 // ---- host: one launch of a kernel that needs more than 64 KB of dynamic LDS.  hipFuncSetAttribute is done once per (kernel, device):
 // one flag per instantiation of this template, i.e. per kernel.
 template <auto KERNEL, class Args>

@@ -21,6 +21,7 @@
 // Block: 512 threads, tile 64 output channels x 8 rows x 32 columns.  Epilogue = wino.hip's (output transform, demodulation scale, bias,
 // leaky ReLU, residual, mask).
 #include "split6_common.h"
+#include "wino6_schedule.h"
 #ifdef W6P_PROF      // experimental builds: per-wave cycle counts of the phases, read back with te_debug_w6p_prof (tools/w6p_phase_prof.py)
 #define TE_PROF
 #endif
@@ -35,6 +36,7 @@ struct Wino6Args {
     float* out; const float* in; const u32x4* U; const float* isc; const float* osc; const float* bias; const float* res;
     const float* mref; float mgain; int act;
     int B, K, M, H, W, ntiles, mblocks, tiles_x, tiles_y, nt8;
+    int lists;     // wino6q_kernel: runs per XCD the tile list is cut into (0 = one tile per block: split6_tile)
     int lgpw;      // log2 of the column PAIRS one sample contributes to a tile row: 4 (W >= 32); 3 (W == 16: two samples side by side, round 6)
 };
 
@@ -78,7 +80,8 @@ constexpr int SLOT0 = 21;    // MFMA slot behind which the staging arithmetic st
 // (Round 6, tried and NOT taken: a NARROW form for M == 32 - the 32 -> 32 layer at 1024^2 of the FFHQ-1024 generator - in which the block's
 //  second 32-channel tile is padding, its weight slots are not fetched and the waves that own it skip MFMAs and stores.  Correct at the
 //  5e-6 bar, but 1 121 us against the 769 us of the fp32 Winograd kernel wino3x3_kernel<32>: with K = 32 a block lives for two stages, one
-//  block per CU (144 KB of LDS), so the prologue's HBM latency and the epilogue are not overlapped by anything;
+//  block per CU (144 KB of LDS), so in this kernel - which has no tile walk, unlike wino6q_kernel - the prologue's HBM latency and the
+//  epilogue are not overlapped by anything;
 //  profiles/experiments/r06_g1024_kernel_stats_with_wino6p_narrow.txt, r06_wino6p_narrow.patch.)
 template <bool ISC>
 __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
@@ -379,6 +382,24 @@ __global__ __launch_bounds__(WT, 2) void wino6p_kernel(const Wino6Args p) {
 //     M1: 72 MFMAs + the staging arithmetic (rin -> res) behind them                       SB: weight DMA + res -> T_g(s + 1)
 // Both groups run the SAME straight-line loop body (M0 SA M1 SB), group 1 one staging phase late: no role branch around the MFMA streams, two
 // copies of the stream (one per accumulator set).  Same products in the same order per output element as wino6p: bit-identical.
+//
+// THE TILE WALK.  One block owns a CU (144 KB of LDS), and outside its channel stages the matrix pipe of that CU idles: a launch whose
+// blocks live for 8 stages (K = 128) spent 14.7 % of its time there, one with 32 stages 4.1 % (tools/block_overhead_probe.py,
+// profiles/experiments/r05_w6p_phase_profile.log step 5).  A block therefore takes a RUN of consecutive tiles of its XCD with one M block
+// (split6_tile_list: the order split6_tile defines, so neighbours keep sharing halo rows in one L2) and carries the pipeline across them:
+//   * at a tile's last stage the fetch of the M0 phase - which used to fetch the last stage a second time and drop it - fetches stage 0
+//     of the NEXT tile (the staging geometry, one set of registers, is switched to the next tile in front of that phase: its last user
+//     was the M1 phase before); the M1 phase splits it, the SB phase writes the next tile's T_g(0) (group 1 runs its last SB then);
+//   * the weight hand-over simply goes on: the image behind the tile's last one is image 0 again (same M block), Ua renewed by group 0
+//     in its last SB, Ub by group 1 in its last SB, beside which group 0 only executes the phase's two barriers;
+//   * between two tiles stands the epilogue alone, OUTSIDE the phase loop, with pointers and geometry live beside the accumulators, which
+//     are zeroed behind it.  Its stores drain under the next tile's stages.  A run's last tile ends, its first tile begins as before.
+// The phase body exists once.  The schedule - who multiplies, who stages, which weight half is renewed, the barriers - is written down in
+// wino6_schedule.h, from which this kernel takes every such decision and which tests/test_wino6_schedule.py replays on the host: equal
+// barrier counts of the two groups for every run length are checked THERE, not by a GPU run.  (The fully persistent form of round 5 put
+// the epilogue inside the phase loop: 256 VGPRs, 51 - 60 spilled, 1.4 - 1.7x slower; profiles/experiments/r05_w6p_phase_profile.log.)
+// To fit beside what the next tile keeps live, the epilogue addresses through a block-uniform base per channel plus one 32-bit lane
+// offset and handles four of a lane's sixteen rows at a time.
 template <bool ISC>
 __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -388,13 +409,13 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
     const int grp = wid >> 2, wq = wid & 3, wm = wq >> 1, wrl = wq & 1, gt = tid & (GT - 1);
     unsigned* tl = reinterpret_cast<unsigned*>(smem_raw + U_CHUNKS * 16) + grp * TP_DWORDS;      // this group's half tile
     const u32x4* tl4 = reinterpret_cast<const u32x4*>(tl);
-    int tile, mbq;               // (mblocks = M / 128 for this form)
-    if (!split6_tile(p.ntiles, p.nt8, p.mblocks, tile, mbq)) return;
-    const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, b = tile / (p.tiles_x * p.tiles_y);
-    const int x0 = tx * TW, y0 = ty * TH, yh = y0 + PH * grp;
-    const float* inb = p.in + (size_t)b * p.K * p.H * p.W;
-    const float* iscb = ISC ? p.isc + (size_t)b * p.K : nullptr;
-    const bool has_left = x0 == 0, has_right = x0 + TW == p.W, has_rowout = (yh == 0) || (yh + PH == p.H);
+    int tile, tile_end, tile_step, mbq;               // (mblocks = M / 128 for this form)
+    if (!split6_tile_list(p.ntiles, p.nt8, p.mblocks, p.lists, tile, tile_end, tile_step, mbq)) return;
+    // staging geometry of ONE tile: the current one, and from the top of a tile's last stage on (whose M0 phase fetches stage 0 of the
+    // next tile) the next one - set_tile.  Block-uniform parts are scalars; the epilogue decodes `tile` again for its own addresses.
+    const float* inb;
+    const float* iscb = nullptr;
+    bool has_left, has_right, has_rowout;
 
     f32x16 acc[2][4];
 #pragma unroll
@@ -406,15 +427,43 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
 
     unsigned g_off[P_IN];
     int l_off[P_IN], e_flag[P_IN];
+    // What only the switch to a tile (set_tile) and the epilogue need of the launch arguments - pointers, image and tile-grid sizes - is
+    // read there from the kernel-argument segment (scalar loads that hit the constant cache), through a pointer the compiler cannot see
+    // through: held in scalar registers from the kernel's entry they do not fit beside what the phase loop keeps, and spill to lanes.
+    typedef const __attribute__((address_space(4))) Wino6Args* KArgs;
+    auto kargs = [&]() {
+        KArgs k = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();                                  // (the kernel's only argument: offset 0)
+        asm volatile("" : "+s"(k));
+        return k;
+    };
+    auto set_tile = [&](int t) {
+        const KArgs a = kargs();
+        const int aH = a->H, aW = a->W, atx = a->tiles_x, aty = a->tiles_y, aK = a->K;
+        const int tx = t % atx, ty = (t / atx) % aty, b = t / (atx * aty);
+        const int x0 = tx * TW, yh = ty * TH + PH * grp;
+        inb = a->in + (size_t)b * aK * aH * aW;
+        if (ISC) iscb = a->isc + (size_t)b * aK;
+        has_left = x0 == 0; has_right = x0 + TW == aW; has_rowout = (yh == 0) || (yh + PH == aH);
+        // (opaque, as the epilogue's lane index: the tile-independent parts of the offsets are recomputed per tile, not kept - and spilled -
+        //  across the phase loop)
+        int gto = gt;
+        asm volatile("" : "+v"(gto));
+#pragma unroll
+        for (int i = 0; i < P_IN; ++i) {
+            const int e = gto + GT * i;
+            const int jj = e & 15, q = (e >> 4) & 7, row = e >> 7;
+            const int gy = yh - 1 + row;
+            const bool left = x0 == 0 && jj == 0, right = x0 + TW == aW && jj == NP - 1, rowout = gy < 0 || gy >= aH;
+            e_flag[i] = (left ? 1 : 0) | (right ? 2 : 0) | (rowout ? 4 : 0);
+            const int gyc = gy < 0 ? 0 : (gy >= aH ? aH - 1 : gy);
+            g_off[i] = (unsigned)((2 * q * aH + gyc) * aW + x0 + 2 * jj - 1 + (left ? 1 : 0) - (right ? 1 : 0));
+        }
+    };
+    set_tile(tile);
 #pragma unroll
     for (int i = 0; i < P_IN; ++i) {
         const int e = gt + GT * i;
         const int jj = e & 15, q = (e >> 4) & 7, row = e >> 7;
-        const int gy = yh - 1 + row;
-        const bool left = x0 == 0 && jj == 0, right = x0 + TW == p.W && jj == NP - 1, rowout = gy < 0 || gy >= p.H;
-        e_flag[i] = (left ? 1 : 0) | (right ? 2 : 0) | (rowout ? 4 : 0);
-        const int gyc = gy < 0 ? 0 : (gy >= p.H ? p.H - 1 : gy);
-        g_off[i] = (unsigned)((2 * q * p.H + gyc) * p.W + x0 + 2 * jj - 1 + (left ? 1 : 0) - (right ? 1 : 0));
         l_off[i] = ((row * 2 + (q >> 2)) * NP + jj) * 4 + (q & 3);                        // + (piece * 4 + c) * TP_PLANE
     }
     const unsigned q2 = 2u * ((gt >> 4) & 7);
@@ -431,17 +480,27 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
         for (int h2 = 0; h2 < 2; ++h2)
             rin[i][h2] = *reinterpret_cast<const f32x4u*>(inb + ((size_t)s * KC + h2) * plane + g_off[i]);
     };
-    // weight half `uh` of image j = 2 s + m: 36 fragment slots (3 pieces x 6 (tap row, component) groups x 2 M tiles), 9 per wave
+    // weight half `uh` of image j = 2 s + m: 36 fragment slots (3 pieces x 6 (tap row, component) groups x 2 M tiles), 9 per wave: wave wq
+    // takes slots 3 wq .. 3 wq + 2 of the twelve of EVERY piece, so that a slot's global and LDS addresses are one of three wave-dependent
+    // bases plus a compile-time multiple of the piece stride.  The wave index is made opaque per call: with wino6p_kernel's assignment
+    // (nine consecutive slots, piece and slot by division) the eighteen 64-bit slot offsets were hoisted out of the phase loop and, beside
+    // the tile walk's scalars, spilled to lanes.
     auto issue_u = [&](int uh, int j) {
-        const u32x4* us = p.U + (size_t)(j >> 1) * 36 * MT * 64;
-        const int mb = 2 * mbq + (j & 1);
+        int wqo = wq;
+        asm volatile("" : "+s"(wqo));
+        const u32x4* us = p.U + ((size_t)(j >> 1) * 36 * MT + 2 * (2 * mbq + (j & 1))) * 64;
+        const unsigned pstride = 12u * (unsigned)MT * 64u;                     // chunks from piece to piece
 #pragma unroll
-        for (int r = 0; r < 9; ++r) {
-            const int jw = wq * 9 + r, piece = jw / 12, rem = jw % 12, kc = (rem >> 1) + 6 * uh, mt = rem & 1;
-            const int pk = piece * 12 + kc;                                   // == (piece * 3 + ky) * 4 + c
-            const u32x4* g = us + ((size_t)pk * MT + 2 * mb + mt) * 64 + (unsigned)lane;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                             (__attribute__((address_space(3))) void*)(ul + (pk * 2 + mt) * 64), 16, 0, 0);
+        for (int t = 0; t < 3; ++t) {
+            const int rem = wqo * 3 + t, kc = (rem >> 1) + 6 * uh, mt = rem & 1;
+            const u32x4* g0 = us + (unsigned)(kc * MT + mt) * 64u;              // uniform base of slot (piece 0, kc, mt)
+            u32x4* l0 = ul + (kc * 2 + mt) * 64;
+#pragma unroll
+            for (int piece = 0; piece < 3; ++piece) {
+                const u32x4* g = g0 + piece * pstride + (unsigned)lane;         // uniform base + 32-bit lane offset
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                                 (__attribute__((address_space(3))) void*)(l0 + piece * 24 * 64), 16, 0, 0);
+            }
         }
     };
     // the staging arithmetic as a program of 51 slots (wino6p_kernel: arith), run behind the MFMAs of the m = 1 phase
@@ -498,6 +557,8 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
     const int a_chunk = wm * 64 + lane;
 
     // one multiplying phase with accumulator set MSET; behind the MFMAs: MSET 0 the fetch of stage `fs`, MSET 1 the staging arithmetic
+    // (wino6_sched::replay restates this phase as events - reads of the first weight half and the half tile, the mid barrier, reads of
+    //  the second half, the end barrier: a barrier or a first read of either weight half moved here must move THERE in the same change)
     auto multiply = [&](auto mset_tag, int fs) {
         constexpr int MSET = decltype(mset_tag)::value;
         bf16x8 av[2][3], bv[2][3];
@@ -534,20 +595,23 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
         __builtin_amdgcn_s_setprio(0);
         split6_barrier();                             // end of phase
     };
-    // one phase in the staging role.  p = global phase index; image cs = (p + 1) >> 1 is the one whose half this phase renews:
-    // group 1 (even p) renews Ub(cs) in FRONT of the mid-phase barrier (its partner reads it right behind), group 0 (odd p) renews
-    // Ua(cs) BEHIND it (the partner is past the last read of Ua(cs - 1) there).  WRITE: this is the phase behind the group's m = 1
-    // multiply: the parked results go to the half tile (nobody reads it until the group's next m = 0 phase).
-    auto stage = [&](int ph, bool write) {
-        const int cs = (ph + 1) >> 1;
-        const bool work = cs >= 1 && cs < nimg;
-        if (grp == 1 && work) issue_u(1, cs);
+    // one phase in the staging role.  ph = phase index inside the tile; image cs = (ph + 1) >> 1 is the one whose half this phase renews
+    // (cs == nimg: image 0 of the next tile, where the list has one): group 1 (even ph) renews Ub(cs) in FRONT of the mid-phase barrier
+    // (its partner reads it right behind), group 0 (odd ph) renews Ua(cs) BEHIND it (the partner is past the last read of Ua(cs - 1)
+    // there).  WRITE: this is the phase behind the group's m = 1 multiply: the parked results go to the half tile (nobody reads it until
+    // the group's next m = 0 phase).  (wino6_sched::replay's `stage` restates this order - DMA, write, wait, barrier, DMA, wait, barrier -
+    // and must be changed in the same change as this lambda: the host test sees the kernel only through it.)
+    auto stage = [&](int ph, bool write, bool has_next) {
+        const int cs = wino6_sched::renew_image(ph);
+        const bool work = wino6_sched::renew_work(cs, nimg, has_next);
+        const int ci = cs == nimg ? 0 : cs;
+        if (grp == 1 && work) issue_u(1, ci);
         __builtin_amdgcn_sched_barrier(0);
         if (write) write_res();
         if (grp == 1 && work) split6_wait_vm();
         split6_barrier();                             // mid-phase
         if (grp == 0 && work) {
-            issue_u(0, cs);
+            issue_u(0, ci);
             split6_wait_vm();
         }
         split6_barrier();                             // end of phase
@@ -563,63 +627,99 @@ __global__ __launch_bounds__(WT, 2) void wino6q_kernel(const Wino6Args p) {
     write_res();
     split6_wait_vm();
     split6_barrier();
-    int ph = 0;
-    if (grp == 1) { stage(0, false); ph = 1; }
-    for (int s = 0; s < nstage; ++s) {
-        const int fs = min(s + 1, nstage - 1);
-        multiply(std::integral_constant<int, 0>{}, fs);
-        stage(ph + 1, false);
-        multiply(std::integral_constant<int, 1>{}, fs);
-        if (!(grp == 1 && s == nstage - 1)) stage(ph + 3, true);
-        ph += 4;
-    }
+    // the tile walk (wino6_schedule.h holds the schedule; tests/test_wino6_schedule.py replays it).  ONE phase loop for every tile of the
+    // list; between two tiles only the epilogue, with nothing but pointers and geometry live beside the accumulators.
+    for (;;) {
+        const bool has_next = tile + tile_step < tile_end;
+        int ph = 0;
+        if (wino6_sched::lead_phase(grp)) { stage(0, false, has_next); ph = 1; }
+        for (int s = 0; s < nstage; ++s) {
+            bool next_tile;
+            const int fs = wino6_sched::fetch_stage(s, nstage, has_next, next_tile);
+            if (next_tile) set_tile(tile + tile_step);      // (rin, res and the old geometry are dead here: M1 of stage s - 1 used them last)
+            multiply(std::integral_constant<int, 0>{}, fs);
+            stage(ph + 1, false, has_next);
+            multiply(std::integral_constant<int, 1>{}, fs);
+            if (wino6_sched::runs_sb(grp, s, nstage, has_next)) stage(ph + 3, true, has_next);
+            ph += 4;
+        }
+        for (int i = 0; i < wino6_sched::tail_barriers(grp, has_next); ++i) split6_barrier();
 
-    // epilogue: as wino6p_kernel, once per accumulator set
-    const int wr = grp * 2 + wrl;
-    const float g_pos = p.act == 3 ? 1.4142135623730951f : 1.f;
+        // epilogue: as wino6p_kernel, once per accumulator set
+        const KArgs e = kargs();
+        const int tx = tile % e->tiles_x, ty = (tile / e->tiles_x) % e->tiles_y, b = tile / (e->tiles_x * e->tiles_y);
+        const int x0 = tx * TW, y0 = ty * TH;
+        // (the lane index is made opaque for every tile: everything per-lane the epilogue derives from it - output offsets, the bias values -
+        //  would otherwise be hoisted out of the tile loop and stay live, in ~100 registers, through the phase loop)
+        int elane = lane;
+        asm volatile("" : "+v"(elane));
+        const int ehalf = elane >> 5, err = (elane & 31) >> 4, ejj = elane & 15;
+        const int wr = grp * 2 + wrl;
+        // (the plane size too is taken from there: of `plane` the 32 block-uniform channel offsets (channel x plane, 64 bits each) are
+        //  computed once in front of the tile loop and kept, spilled to lanes, through it)
+        const int eM = e->M, eW = e->W, eact = e->act;
+        const size_t eplane = (size_t)e->H * eW;
+        const float emgain = e->mgain;
+        const float g_pos = eact == 3 ? 1.4142135623730951f : 1.f;
+        float* const eout = e->out;
+        const float* const eosc = e->osc; const float* const ebias = e->bias; const float* const eres = e->res; const float* const emref = e->mref;
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int mbase = (2 * mbq + m) * BM + wm * 32;
-        const size_t off0 = ((size_t)b * p.M + mbase) * plane + (size_t)(y0 + 2 * wr + rr) * p.W + x0 + 2 * jj;
-        float scv[16], biv[16];
+        for (int m = 0; m < 2; ++m) {
+            const int mbase = (2 * mbq + m) * BM + wm * 32;
+            // addresses = a block-uniform base per output channel (scalar registers) + ONE 32-bit per-lane offset, fetch_item's form: the
+            // 64-bit per-lane addresses of 48 loads and stores do not fit beside the accumulators and what the next tile keeps live
+            const size_t off0 = ((size_t)b * eM + mbase) * eplane + (size_t)(y0 + 2 * wr) * eW + x0;
+            const unsigned lo = (unsigned)(err * eW + 2 * ejj) + 4u * (unsigned)ehalf * (unsigned)eplane;
+            // (four of the sixteen rows at a time: scales, biases, residuals and mask references of all sixteen are 96 registers)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int mm = mbase + (r & 3) + 8 * (r >> 2) + 4 * half;
-            scv[r] = p.osc ? p.osc[(size_t)b * p.M + mm] : 1.f;
-            biv[r] = p.bias ? p.bias[mm] : 0.f;
-        }
-        f32x2 resv[16], mrefv[16];
-        if (p.res) {
+            for (int r0 = 0; r0 < 16; r0 += 4) {
+                float scv[4], biv[4];
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                resv[r] = *reinterpret_cast<const f32x2*>(p.res + off0 + (size_t)((r & 3) + 8 * (r >> 2) + 4 * half) * plane);
-        }
-        if (p.mref) {
+                for (int r = r0; r < r0 + 4; ++r) {
+                    const int mm = mbase + (r & 3) + 8 * (r >> 2) + 4 * ehalf;
+                    scv[r - r0] = eosc ? eosc[(size_t)b * eM + mm] : 1.f;
+                    biv[r - r0] = ebias ? ebias[mm] : 0.f;
+                }
+                f32x2 resv[4], mrefv[4];
+                if (eres) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                mrefv[r] = *reinterpret_cast<const f32x2*>(p.mref + off0 + (size_t)((r & 3) + 8 * (r >> 2) + 4 * half) * plane);
-        }
+                    for (int r = r0; r < r0 + 4; ++r)
+                        resv[r - r0] = *reinterpret_cast<const f32x2*>(eres + off0 + (size_t)((r & 3) + 8 * (r >> 2)) * eplane + lo);
+                }
+                if (emref) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dm = (r & 3) + 8 * (r >> 2) + 4 * half;
-            float v0 = acc[m][0][r] + acc[m][1][r] + acc[m][2][r];
-            float v1 = acc[m][1][r] - acc[m][2][r] - acc[m][3][r];
-            const float sc = scv[r], bi = biv[r];
-            v0 = v0 * sc + bi;
-            v1 = v1 * sc + bi;
-            if (p.act >= 3) {
-                v0 = (v0 > 0.f ? v0 : v0 * 0.2f) * g_pos;
-                v1 = (v1 > 0.f ? v1 : v1 * 0.2f) * g_pos;
+                    for (int r = r0; r < r0 + 4; ++r)
+                        mrefv[r - r0] = *reinterpret_cast<const f32x2*>(emref + off0 + (size_t)((r & 3) + 8 * (r >> 2)) * eplane + lo);
+                }
+#pragma unroll
+                for (int r = r0; r < r0 + 4; ++r) {
+                    float v0 = acc[m][0][r] + acc[m][1][r] + acc[m][2][r];
+                    float v1 = acc[m][1][r] - acc[m][2][r] - acc[m][3][r];
+                    const float sc = scv[r - r0], bi = biv[r - r0];
+                    v0 = v0 * sc + bi;
+                    v1 = v1 * sc + bi;
+                    if (eact >= 3) {
+                        v0 = (v0 > 0.f ? v0 : v0 * 0.2f) * g_pos;
+                        v1 = (v1 > 0.f ? v1 : v1 * 0.2f) * g_pos;
+                    }
+                    if (eres) { v0 += resv[r - r0][0]; v1 += resv[r - r0][1]; }
+                    if (emref) {
+                        v0 *= mrefv[r - r0][0] > 0.f ? emgain : 0.2f * emgain;
+                        v1 *= mrefv[r - r0][1] > 0.f ? emgain : 0.2f * emgain;
+                    }
+                    f32x2 v; v[0] = v0; v[1] = v1;
+                    *reinterpret_cast<f32x2*>(eout + off0 + (size_t)((r & 3) + 8 * (r >> 2)) * eplane + lo) = v;
+                }
             }
-            const size_t o = off0 + (size_t)dm * plane;
-            if (p.res) { v0 += resv[r][0]; v1 += resv[r][1]; }
-            if (p.mref) {
-                v0 *= mrefv[r][0] > 0.f ? p.mgain : 0.2f * p.mgain;
-                v1 *= mrefv[r][1] > 0.f ? p.mgain : 0.2f * p.mgain;
-            }
-            f32x2 v; v[0] = v0; v[1] = v1;
-            *reinterpret_cast<f32x2*>(p.out + o) = v;
         }
+        if (!has_next) break;
+        tile += tile_step;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[m][c][r] = 0.f;
     }
 }
 
@@ -635,6 +735,42 @@ extern "C" int te_conv_wino6_form(int form) {
     const int old = g_w6_form.load(std::memory_order_relaxed);
     if (form >= 1 && form <= 3) g_w6_form.store(form, std::memory_order_relaxed);
     return old;
+}
+
+// tiles per block of wino6q_kernel, a test and tool hook (te_hip.h): 0 = automatic (te_wino6_launch), 1 = one tile per block, n >= 2 =
+// lists of at most n tiles.  Results are bit-identical across its values.
+constexpr int W6_MAX_TPB = 4096;
+static std::atomic<int> g_w6_tpb{0};
+extern "C" int te_conv_wino6_tiles_per_block(int n) {
+    const int old = g_w6_tpb.load(std::memory_order_relaxed);
+    if (n >= 0 && n <= W6_MAX_TPB) g_w6_tpb.store(n, std::memory_order_relaxed);
+    return old;
+}
+
+// automatic choice: runs of at most FOUR tiles, fewer where four would leave CUs without a block, one tile per block where even two would.
+// Measured per launch with style scales, us, 20 launches per sample, fastest / slowest of 10 samples in two alternating visits per build on
+// one machine (profiles/r07_w6_tile_walk_launch.jsonl; "before" = the kernel before the tile walk, n = tiles per block):
+//     shape (K -> M @ H^2, batch)   before          n = 1           n = 2           n = 3           n = 4 (= automatic here)
+//     128 -> 128 @ 256^2, 16        1191 / 1243     1096 / 1123     1104 / 1119     1181 / 1186     1100 / 1106
+//     128 -> 128 @ 256^2, 32        2399 / 2440     2220 / 2244     2198 / 2214     2228 / 2251     2182 / 2202
+//     256 -> 256 @ 128^2, 16        1104 / 1120     1036 / 1053     1020 / 1037     1078 / 1094     1020 / 1036
+//     256 -> 256 @ 128^2, 32        2210 / 2240     2081 / 2105     2050 / 2063     2210 / 2225     2048 / 2062
+//     512 -> 512 @ 64^2,  16        1060 / 1092      994 / 1015      992 / 1011     1298 / 1300      989 / 1010
+//     512 -> 512 @ 64^2,  32        2145 / 2171     2004 / 2028     2018 / 2037     2141 / 2195     2014 / 2028
+// (n = 1 against "before" is the epilogue's new addressing and its four-row batches: most of the gain; the walk itself adds 1 - 2 % at
+// 256 channels and at 128 channels at batch 32, and nothing at 512, where a block lives for 32 stages.)  n = 3 shows what the second condition below is for: its
+// runs do not divide the XCD's tiles into whole rounds over the CUs (352 blocks of three tile times against 256 of four at 512 -> 512 @64^2).
+// A resident walk - one block per CU walking its whole share - was measured on an earlier state of this kernel and lost 1 - 3 % against
+// n = 4 at the 256^2 shapes: the hardware hands a free CU the next run, and blocks drift apart instead of storing in lock step.
+static int w6_auto_tpb(int nt8c, int mblocks) {
+    // (a run of n tiles occupies its CU n tile times: where the blocks of the walk need more tile times in all - rounds over the CUs times n -
+    //  than one-tile blocks need rounds, the coarser grain loses more at the launch's tail than the walk wins inside a block)
+    const int64_t rounds1 = te::cdiv((int64_t)8 * nt8c * mblocks, te::kNumCU);
+    for (int n = 4; n >= 2; --n) {
+        const int64_t blocks = (int64_t)8 * te::cdiv(nt8c, n) * mblocks;
+        if (blocks >= te::kNumCU && te::cdiv(blocks, te::kNumCU) * n <= rounds1) return n;
+    }
+    return 1;
 }
 
 PROF_READBACK(w6p)
@@ -672,7 +808,12 @@ int te_wino6_launch(float* out, const float* in, const float* U, const float* is
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
     if (form >= 2 && M % (2 * BM) == 0 && W >= TW && (form == 3 || blocks_q >= te::kNumCU)) {     // (W == 16: the ping-pong kernel only)
         a.mblocks = M / (2 * BM);
-        const int64_t blocks2 = blocks_q;
+        // the tile walk: a block takes a run of consecutive tiles of its XCD and carries the pipeline across them (wino6q_kernel).
+        const int nt8c = (int)te::cdiv(a.ntiles, 8);                   // tiles of the fullest XCD
+        int tpb = g_w6_tpb.load(std::memory_order_relaxed);
+        if (tpb == 0) tpb = w6_auto_tpb(nt8c, a.mblocks);
+        a.lists = tpb >= 2 ? (int)te::cdiv(nt8c, tpb) : 0;
+        const int64_t blocks2 = a.lists ? (int64_t)8 * a.lists * a.mblocks : blocks_q;
         const size_t lds = (size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4;
         SPLIT6_LAUNCH_ISC(wino6q_kernel, isc, dim3((unsigned)blocks2), WT, lds, s, a);
     } else {
