@@ -392,6 +392,39 @@ int te_blur_gradact_f32(float* gx, float* partial, const float* g, const float* 
                         te_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Loop-trip queries (host only, nothing is launched; each calls the grid function of the launch it describes).  Many kernels
+ * launch fewer blocks than they have work and loop inside the block; these say how often, so that a test can assert the trips
+ * it relies on (tests/loop_trips.py).
+ *   te_upfirdn2d_plan / te_blur_actgrad_plan / te_blur_gradact_plan: what te_upfirdn2d_f32 / te_blur_actgrad_f32 /
+ *     te_blur_gradact_f32 launch for the same arguments.  *zgroups = plane groups of the plane-walking kernels (blur44_kernel,
+ *     fir_tile_kernel: the block of group pg filters the planes pg, pg + zgroups, ... < major), *tiles = tiles per plane; both 0
+ *     where the direct kernel runs.
+ *   te_*_cover: elements (outputs) that ONE trip of the kernel's full grid covers; a launch with more elements strides.
+ *     te_upfirdn2d_direct_cover: fir_direct_kernel and the f16 / f64 entry points.  te_chan_scale_cover(rows, hw, aligned16).
+ *     te_bias_act_f32_cover(size_x, step_b (0: no bias), aligned16, *vec = 1 on the 16-byte path); te_bias_act_any_cover: f16 /
+ *     f64.  te_conv_finalize_cover: the split-K epilogue of te_conv_ws_f32 / te_conv_res_f32 over B M Ho Wo outputs.
+ *     te_small_gemm_splitk_finish_cover: the second kernel of te_small_gemm_splitk_f32.
+ *   te_conv_pack_plan: *blocks along x of a single-job te_conv_pack_weights_f32 launch, *tiles = 32 x 32 tiles of the job (a block
+ *     walks the tiles blockIdx.x, blockIdx.x + *blocks, ...).
+ *   te_wgrad_reduce_plan: second pass of the dW output of te_wgrad_reduce_f32 (16-byte aligned tensors): *parts partial tensors
+ *     (1: no second pass), *cover elements per trip of its grid.
+ * Negative TE_ERR_* on bad arguments. */
+int te_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                      int pad_x0, int pad_x1, int pad_y0, int pad_y1, int* zgroups, int* tiles);
+int te_blur_actgrad_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                         int* zgroups, int* tiles);
+int te_blur_gradact_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                         int* zgroups, int* tiles);
+int64_t te_upfirdn2d_direct_cover(int64_t outputs);
+int64_t te_chan_scale_cover(int64_t rows, int64_t hw, int aligned16);
+int64_t te_bias_act_f32_cover(int64_t size_x, int64_t step_b, int aligned16, int* vec);
+int64_t te_bias_act_any_cover(int64_t size_x);
+int64_t te_conv_finalize_cover(int64_t outputs);
+int64_t te_small_gemm_splitk_finish_cover(int I, int J);
+int te_conv_pack_plan(int kind_pack, int Co, int Ci, int ksize, int* blocks, int* tiles);
+int te_wgrad_reduce_plan(int B, int S, int Co, int Ci, int taps, int* parts, int64_t* cover);
+
+/* ---------------------------------------------------------------------------------------------
  * G2/A2  small dense layers (reference: EqualLinear.forward, model_spatial_query.py:213-221 — F.linear on
  * weight * scale with bias * lr_mul, optional activation).  One fused launch on fp32 MFMA:
  *     C[i,j] = act( alpha * sum_k A(i,k) * B(k,j) + beta * bias[j] ) + residual[i,j]      C, residual, pre: [I,J] row-major

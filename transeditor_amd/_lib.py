@@ -125,6 +125,18 @@ _SIGNATURES = {
     'te_conv2d_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 13 + [_P]),
     'te_pool3_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'te_resize_bilinear_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
+    # loop-trip queries (host only)
+    'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
+    'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
+    'te_blur_gradact_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
+    'te_upfirdn2d_direct_cover': (C.c_int64, [_L]),
+    'te_chan_scale_cover': (C.c_int64, [_L, _L, _I]),
+    'te_bias_act_f32_cover': (C.c_int64, [_L, _L, _I, _P]),
+    'te_bias_act_any_cover': (C.c_int64, [_L]),
+    'te_conv_finalize_cover': (C.c_int64, [_L]),
+    'te_small_gemm_splitk_finish_cover': (C.c_int64, [_I, _I]),
+    'te_conv_pack_plan': (C.c_int, [_I, _I, _I, _I, _P, _P]),
+    'te_wgrad_reduce_plan': (C.c_int, [_I, _I, _I, _I, _I, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

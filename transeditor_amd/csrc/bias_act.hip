@@ -196,6 +196,13 @@ __global__ __launch_bounds__(256) void bias_act_bwd_2d_kernel(float* __restrict_
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// capped grid of the elementwise kernels and the fp32 path choice (shared by the launches and the te_bias_act_*_cover queries);
+// `items` are 16-byte vectors on the fp32 vector path, elements elsewhere
+inline int bias_act_grid(int64_t items) { return (int)std::min<int64_t>(te::cdiv(items, 256), te::kNumCU * 8); }
+inline bool bias_act_vec(int64_t size_x, bool has_b, int64_t step_b, bool al16) {
+    return (size_x % 4 == 0) && (!has_b || step_b % 4 == 0) && al16 && (size_x / 4 < (int64_t)0xFFFFFFFF);
+}
+
 // The reference dispatches the op over half / float / double (AT_DISPATCH_FLOATING_TYPES_AND_HALF,
 // fused_bias_act_kernel.cu:79) and converts its float alpha / scale arguments to scalar_t.  The model runs in fp32 (the
 // streaming kernels above); the other two types take this element-per-lane kernel: arithmetic in T's own precision for
@@ -233,7 +240,7 @@ int bias_act_any(T* out, const T* x, const T* b, const T* ref, int act, int grad
     TE_REQUIRE(size_x >= 0, TE_ERR_SHAPE, "%s: size_x < 0", what);
     TE_REQUIRE(!b || (step_b > 0 && size_b > 0), TE_ERR_SHAPE, "%s: bias given but step_b/size_b <= 0", what);
     if (size_x == 0) return 0;
-    const int grid = (int)std::min<int64_t>(te::cdiv(size_x, 256), te::kNumCU * 8);
+    const int grid = bias_act_grid(size_x);
     bias_act_any_kernel<T><<<grid, 256, 0, (hipStream_t)stream_>>>(out, x, b, ref, act * 10 + grad, alpha, scale, size_x,
                                                                    b ? step_b : 1, b ? size_b : 1);
     return te::launch_status(what);
@@ -261,20 +268,32 @@ extern "C" int te_bias_act_f32(float* out, const float* x, const float* b, const
     if (size_x == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     const int mode = act * 10 + grad;
-    const bool vec = (size_x % 4 == 0) && (!b || step_b % 4 == 0) && aligned16(out) && aligned16(x) &&
-                     (!ref || aligned16(ref)) && (size_x / 4 < (int64_t)0xFFFFFFFF);
+    const bool vec = bias_act_vec(size_x, b != nullptr, step_b, aligned16(out) && aligned16(x) && (!ref || aligned16(ref)));
     if (vec) {
         const uint32_t n4 = (uint32_t)(size_x / 4);
-        const int grid = (int)std::min<int64_t>(te::cdiv(n4, 256), te::kNumCU * 8);
+        const int grid = bias_act_grid(n4);
         bias_act_vec4_kernel<<<grid, 256, 0, stream>>>((float4*)out, (const float4*)x, b, (const float4*)ref, mode, alpha,
                                                        scale, n4, b ? (uint32_t)(step_b / 4) : 1u,
                                                        b ? (uint32_t)size_b : 1u);
     } else {
-        const int grid = (int)std::min<int64_t>(te::cdiv(size_x, 256), te::kNumCU * 8);
+        const int grid = bias_act_grid(size_x);
         bias_act_scalar_kernel<<<grid, 256, 0, stream>>>(out, x, b, ref, mode, alpha, scale, size_x, b ? step_b : 1,
                                                          b ? size_b : 1);
     }
     return te::launch_status("te_bias_act_f32");
+}
+
+// elements that one trip of the full grid covers (host only).  te_bias_act_f32_cover: *vec = 1 where the 16-byte path runs; step_b
+// = 0 without a bias; aligned16: every tensor is 16-byte aligned.  te_bias_act_any_cover: the f16 / f64 entry points.
+extern "C" int64_t te_bias_act_f32_cover(int64_t size_x, int64_t step_b, int aligned16_, int* vec_out) {
+    if (size_x <= 0 || step_b < 0) return TE_ERR_SHAPE;
+    const bool vec = bias_act_vec(size_x, step_b > 0, step_b, aligned16_ != 0);
+    if (vec_out) *vec_out = vec ? 1 : 0;
+    return (int64_t)bias_act_grid(vec ? size_x / 4 : size_x) * 256 * (vec ? 4 : 1);
+}
+
+extern "C" int64_t te_bias_act_any_cover(int64_t size_x) {
+    return size_x > 0 ? (int64_t)bias_act_grid(size_x) * 256 : TE_ERR_SHAPE;
 }
 
 static bool bwd_rows_path(int64_t outer, int64_t C, int64_t inner) {

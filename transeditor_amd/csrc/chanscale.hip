@@ -99,7 +99,25 @@ __global__ __launch_bounds__(256) void chan_dot_kernel(float* __restrict__ out, 
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// which kernel te_chan_scale_f32 takes and its capped grid (shared by the launch and te_chan_scale_cover); `items` are 16-byte
+// vectors on the two vector paths, elements on the scalar one
+enum ScalePath { SCALE_VEC4, SCALE_FLAT4, SCALE_SCALAR };
+inline ScalePath chan_scale_path(int64_t n, int64_t hw, bool al16) {
+    if (hw % 4 == 0 && al16 && hw / 4 < (int64_t)0xFFFFFFFF) return SCALE_VEC4;
+    if (hw >= 4 && n >= 1024 && al16) return SCALE_FLAT4;
+    return SCALE_SCALAR;
+}
+inline int chan_scale_grid(int64_t items) { return (int)std::min<int64_t>(te::cdiv(items, 256), te::kNumCU * 16); }
+
 }  // namespace
+
+// elements that one trip of te_chan_scale_f32's full grid covers (host only; aligned16: both tensors are 16-byte aligned)
+extern "C" int64_t te_chan_scale_cover(int64_t rows, int64_t hw, int aligned16_) {
+    if (rows <= 0 || hw <= 0) return TE_ERR_SHAPE;
+    const int64_t n = rows * hw;
+    const bool scalar = chan_scale_path(n, hw, aligned16_ != 0) == SCALE_SCALAR;
+    return (int64_t)chan_scale_grid(scalar ? n : n / 4) * 256 * (scalar ? 1 : 4);
+}
 
 extern "C" int te_chan_scale_f32(float* out, const float* x, const float* s, int64_t rows, int64_t hw, te_stream_t stream_) {
     TE_REQUIRE(out && x && s, TE_ERR_NULL, "te_chan_scale_f32: NULL pointer");
@@ -107,15 +125,16 @@ extern "C" int te_chan_scale_f32(float* out, const float* x, const float* s, int
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream_;
     const int64_t n = rows * hw;
-    if (hw % 4 == 0 && aligned16(out) && aligned16(x) && hw / 4 < (int64_t)0xFFFFFFFF) {
-        const int grid = (int)std::min<int64_t>(te::cdiv(n / 4, 256), te::kNumCU * 16);
+    const ScalePath path = chan_scale_path(n, hw, aligned16(out) && aligned16(x));
+    if (path == SCALE_VEC4) {
+        const int grid = chan_scale_grid(n / 4);
         chan_scale_vec4_kernel<<<grid, 256, 0, st>>>((float4*)out, (const float4*)x, s, n / 4, (uint32_t)(hw / 4));
-    } else if (hw >= 4 && n >= 1024 && aligned16(out) && aligned16(x)) {
-        const int grid = (int)std::min<int64_t>(te::cdiv(n / 4, 256), te::kNumCU * 16);
+    } else if (path == SCALE_FLAT4) {
+        const int grid = chan_scale_grid(n / 4);
         chan_scale_flat4_kernel<<<grid, 256, 0, st>>>((float4*)out, (const float4*)x, s, n / 4, hw);
         if (n % 4) chan_scale_kernel<<<1, 64, 0, st>>>(out, x, s, n, hw, n - n % 4);
     } else {
-        const int grid = (int)std::min<int64_t>(te::cdiv(n, 256), te::kNumCU * 16);
+        const int grid = chan_scale_grid(n);
         chan_scale_kernel<<<grid, 256, 0, st>>>(out, x, s, n, hw, 0);
     }
     return te::launch_status("te_chan_scale_f32");

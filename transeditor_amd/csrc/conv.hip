@@ -1030,6 +1030,21 @@ extern "C" int64_t te_conv_packed_numel(int kind_pack, int Co, int Ci, int ksize
     return (int64_t)(pack_is_wino6(kind_pack) ? 18 : (pack_is_wino(kind_pack) ? 12 : d.ntap)) * d.Kp * d.Mp;
 }
 
+// 32 x 32 tiles of a packing job and the capped grid.x of a launch whose biggest job has `biggest` tiles: a block walks the tiles
+// blockIdx.x, blockIdx.x + gridDim.x, ... (shared by pack_launch and te_conv_pack_plan)
+static int64_t pack_job_tiles(const PackDims& d) { return te::cdiv(d.Kp, PT) * te::cdiv(d.Mp, PT); }
+static unsigned pack_grid_x(int64_t biggest) { return (unsigned)std::min<int64_t>(biggest, 256); }
+
+// blocks along x of a single-job packing launch and the job's tile count (host only)
+extern "C" int te_conv_pack_plan(int kind_pack, int Co, int Ci, int ksize, int* blocks, int* tiles) {
+    if (!blocks || !tiles) return TE_ERR_NULL;
+    if (Co <= 0 || Ci <= 0 || (ksize != 1 && ksize != 3) || kind_pack < 0 || kind_pack > 12) return TE_ERR_SHAPE;
+    const int64_t t = pack_job_tiles(pack_dims(kind_pack, Co, Ci, ksize));
+    *tiles = (int)t;
+    *blocks = (int)pack_grid_x(t);
+    return 0;
+}
+
 static int pack_launch(const char* what, int n, float* const* wp, const float* const* w, const float* wscale, const int* kind_pack,
                        const int* Co, const int* Ci, const int* ksize, hipStream_t s);
 
@@ -1081,10 +1096,10 @@ static int pack_launch(const char* what, int n, float* const* wp, const float* c
                        "%s: the Winograd layouts need 3x3 taps and channel counts that are multiples of 8 (job %d)", what, e);
             const PackDims d = pack_dims(kind_pack[e], Co[e], Ci[e], ksize[e]);
             P.j[i] = PackJob{wp[e], w[e], wscale[e], kind_pack[e], Ci[e], d.ntap, d.K, d.M, d.Kp, d.Mp};
-            biggest = std::max<int64_t>(biggest, te::cdiv(d.Kp, PT) * te::cdiv(d.Mp, PT));
+            biggest = std::max<int64_t>(biggest, pack_job_tiles(d));
         }
         // one block per 32 x 32 tile of the biggest job (512 x 512: 256 blocks); small jobs walk their few tiles and exit
-        dim3 grid((unsigned)std::min<int64_t>(biggest, 256), (unsigned)cnt);
+        dim3 grid(pack_grid_x(biggest), (unsigned)cnt);
         pack_weights_multi_kernel<<<grid, 256, 0, s>>>(P);
     }
     return te::launch_status(what);
@@ -1132,6 +1147,14 @@ static ConvPlan conv_plan(int kind, int B, int K, int M, int H, int W) {
 }
 
 extern "C" int64_t te_conv_t2s6_ws_floats(int B, int K, int H) { return (B > 0 && K > 0 && H > 0) ? (int64_t)B * K * H : TE_ERR_SHAPE; }
+
+// capped grid of conv_finalize_kernel (shared by the launch and te_conv_finalize_cover)
+static int conv_finalize_grid(int64_t total) { return (int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 8); }
+
+// outputs that one trip of the split-K epilogue's full grid covers (host only)
+extern "C" int64_t te_conv_finalize_cover(int64_t outputs) {
+    return outputs > 0 ? (int64_t)conv_finalize_grid(outputs) * 256 : TE_ERR_SHAPE;
+}
 
 extern "C" int te_conv_splitk_count(int kind, int B, int K, int M, int H, int W) {
     if (B <= 0 || K <= 0 || M <= 0 || H <= 0 || W <= 0 || kind < 0 || kind > 8) return TE_ERR_SHAPE;
@@ -1211,8 +1234,8 @@ extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const flo
     if (a.ksplit > 1 && (a.ws || osc || bias || act)) {
         const int plane = a.Ho * a.Wo;
         const int64_t total = (int64_t)B * M * plane;
-        conv_finalize_kernel<<<(int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 8), 256, 0, s>>>(out, a.ws, a.ksplit, osc, bias, res,
-                                                                                                     mask_ref, mask_gain, act, M, plane, total);
+        conv_finalize_kernel<<<conv_finalize_grid(total), 256, 0, s>>>(out, a.ws, a.ksplit, osc, bias, res, mask_ref, mask_gain, act, M,
+                                                                        plane, total);
     }
     return te::launch_status("te_conv_f32");
 }

@@ -210,6 +210,14 @@ extern "C" int te_small_gemm_batched_f32(float* c, const float* a, const float* 
     return te::launch_status("te_small_gemm_batched_f32");
 }
 
+// capped grid of splitk_finish_kernel (shared by the launch and te_small_gemm_splitk_finish_cover)
+static int splitk_finish_grid(int64_t total) { return (int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 4); }
+
+// outputs that one trip of the finishing kernel's full grid covers (host only)
+extern "C" int64_t te_small_gemm_splitk_finish_cover(int I, int J) {
+    return (I > 0 && J > 0) ? (int64_t)splitk_finish_grid((int64_t)I * J) * 256 : TE_ERR_SHAPE;
+}
+
 /* wide reductions (the discriminator's 8192 -> 512 linear, model_spatial_query.py:831-834): K is cut into S chunks that run
  * as the z dimension of the same kernel (S x tiles blocks instead of `tiles`), partial tiles go to the caller's workspace
  * ws[S][I][J], a second tiny kernel sums them in fixed order and applies the epilogue.  Deterministic, no atomics. */
@@ -229,7 +237,6 @@ extern "C" int te_small_gemm_splitk_f32(float* c, float* pre, float* ws, int S, 
     hipStream_t s = (hipStream_t)stream_;
     launch_small_gemm(p, S, s);
     const int64_t total = (int64_t)I * J;
-    splitk_finish_kernel<<<(int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 4), 256, 0, s>>>(c, pre, ws, bias, residual, S, I, J,
-                                                                                                     alpha, beta, act);
+    splitk_finish_kernel<<<splitk_finish_grid(total), 256, 0, s>>>(c, pre, ws, bias, residual, S, I, J, alpha, beta, act);
     return te::launch_status("te_small_gemm_splitk_f32");
 }

@@ -246,11 +246,19 @@ inline int64_t fir_planes_z(int64_t major, int64_t tiles) {
     return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(major, 32768), te::cdiv(6144, tiles)));
 }
 
+// grid of a fir_tile_kernel launch; fills q.tiles_x / tiles_y / zgroups (shared by the launches and the te_*_plan queries)
+inline unsigned tile_grid(FirParams& q) {
+    const int64_t tiles = te::cdiv(q.out_w, TOW) * te::cdiv(q.out_h, TOH);
+    return xcd_grid(q, (int)te::cdiv(q.out_w, TOW), (int)te::cdiv(q.out_h, TOH), fir_planes_z(q.major, tiles));
+}
+
+// grid of the direct kernels: one output per thread up to the cap, the threads stride over the rest
+inline int fir_direct_grid(int64_t total) { return (int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 16); }
+
 template <int UP, int DOWN, int KH, int KW>
 void launch_tile(float* out, const float* x, const float* k, const float* b, const FirParams& p, hipStream_t s) {
-    const int64_t tiles = te::cdiv(p.out_w, TOW) * te::cdiv(p.out_h, TOH);
     FirParams q = p;
-    dim3 grid(xcd_grid(q, (int)te::cdiv(p.out_w, TOW), (int)te::cdiv(p.out_h, TOH), fir_planes_z(p.major, tiles)), 1u, 1u);
+    dim3 grid(tile_grid(q), 1u, 1u);
     fir_tile_kernel<UP, DOWN, KH, KW><<<grid, 256, 0, s>>>(out, x, k, b, q);
 }
 
@@ -500,15 +508,20 @@ __global__ __launch_bounds__(256) void blur44_kernel(float* __restrict__ out, co
 
 inline int blur44_tiles(int n, int t) { return (n > t && n % t == 1) ? n / t : (int)te::cdiv(n, t); }     // the +1 rule
 
+// grid of a blur44_kernel launch; fills q.ext_x / ext_y / tiles_x / tiles_y / zgroups (shared by the launch and the te_*_plan queries)
+inline unsigned blur44_grid(FirParams& q) {
+    const int tx_n = blur44_tiles(q.out_w, BOW), ty_n = blur44_tiles(q.out_h, BOH);
+    q.ext_x = tx_n * BOW < q.out_w;
+    q.ext_y = ty_n * BOH < q.out_h;
+    const int64_t tiles = (int64_t)tx_n * ty_n;
+    return xcd_grid(q, tx_n, ty_n, fir_planes_z(q.major, 2 * tiles));
+}
+
 template <int AG>
 void launch_blur44(float* out, const float* x, const float* k, const float* b, const FirParams& p, hipStream_t s, const float* ref,
                    float* partial) {
     FirParams q = p;
-    const int tx_n = blur44_tiles(p.out_w, BOW), ty_n = blur44_tiles(p.out_h, BOH);
-    q.ext_x = tx_n * BOW < p.out_w;
-    q.ext_y = ty_n * BOH < p.out_h;
-    const int64_t tiles = (int64_t)tx_n * ty_n;
-    dim3 grid(xcd_grid(q, tx_n, ty_n, fir_planes_z(p.major, 2 * tiles)), 1u, 1u);
+    dim3 grid(blur44_grid(q), 1u, 1u);
     const int d = (-p.pad_x0) & 3;
     if (q.ext_x || q.ext_y) {
         switch (d) {
@@ -525,6 +538,45 @@ void launch_blur44(float* out, const float* x, const float* k, const float* b, c
             default: blur44_kernel<AG, 3, false><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
         }
     }
+}
+
+// which kernel a te_upfirdn2d_f32 problem takes (shared by the launch and te_upfirdn2d_plan)
+enum FirRoute { FIR_DIRECT, FIR_BLUR44, FIR_TILE_UP2, FIR_TILE_DOWN2 };
+inline FirRoute fir_route(const FirParams& p) {
+    const bool sq = (p.up_x == p.up_y) && (p.down_x == p.down_y) && p.minor == 1;
+    if (sq && p.kh == 4 && p.kw == 4 && p.up_x == 1 && p.down_x == 1 && p.in_w >= 4 && (int64_t)p.in_h * p.in_w * 4 < 0x7FFFFFFF) return FIR_BLUR44;
+    if (sq && p.kh == 4 && p.kw == 4 && p.up_x == 2 && p.down_x == 1) return FIR_TILE_UP2;
+    if (sq && p.kh == 4 && p.kw == 4 && p.up_x == 1 && p.down_x == 2) return FIR_TILE_DOWN2;
+    return FIR_DIRECT;
+}
+
+// geometry of a general upfirdn2d problem / of the two fused blur backward passes (up = down = 1)
+inline FirParams fir_geometry(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                              int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
+    FirParams p{};
+    p.in_h = in_h; p.in_w = in_w;
+    p.out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
+    p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
+    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
+    p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.minor = minor; p.major = major;
+    return p;
+}
+inline FirParams blur_bwd_geometry(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
+    FirParams p{};
+    p.in_h = in_h; p.in_w = in_w;
+    p.out_h = in_h + pad_y0 + pad_y1 - kh + 1;
+    p.out_w = in_w + pad_x0 + pad_x1 - kw + 1;
+    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
+    p.up_x = p.up_y = p.down_x = p.down_y = 1; p.minor = 1; p.major = major;
+    return p;
+}
+// te_blur_actgrad_f32 takes the blur kernel unless a row is narrower than one 16-byte group
+inline bool actgrad_blur44(const FirParams& p) { return p.in_w >= 4; }
+
+inline int plan_out(const FirParams& q, bool walks, int* zgroups, int* tiles) {
+    *zgroups = walks ? q.zgroups : 0;
+    *tiles = walks ? q.tiles_x * q.tiles_y : 0;
+    return 0;
 }
 
 }  // namespace
@@ -544,22 +596,16 @@ extern "C" int te_blur_actgrad_f32(float* gx, float* partial, const float* g, co
     TE_REQUIRE(kh == 4 && kw == 4, TE_ERR_UNSUPPORTED, "te_blur_actgrad_f32: 4x4 taps only");
     TE_REQUIRE(pad_x0 >= 0 && pad_x1 >= 0 && pad_y0 >= 0 && pad_y1 >= 0, TE_ERR_UNSUPPORTED,
                "te_blur_actgrad_f32: pads must be >= 0 (every input element has to be staged by some tile)");
-    FirParams p{};
-    p.in_h = in_h; p.in_w = in_w;
-    p.out_h = in_h + pad_y0 + pad_y1 - kh + 1;
-    p.out_w = in_w + pad_x0 + pad_x1 - kw + 1;
+    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
     TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "te_blur_actgrad_f32: empty output");
-    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
-    p.up_x = p.up_y = p.down_x = p.down_y = 1; p.minor = 1; p.major = major;
     p.size_b = 1; p.act = 0; p.alpha = alpha; p.scale = scale;
     if (major == 0) return 0;
     TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "te_blur_actgrad_f32: too many planes");
     TE_REQUIRE((int64_t)in_h * in_w * 4 < 0x7FFFFFFF, TE_ERR_UNSUPPORTED, "te_blur_actgrad_f32: plane too large");
-    if (in_w >= 4) {
+    if (actgrad_blur44(p)) {
         launch_blur44<1>(gx, g, k, nullptr, p, (hipStream_t)stream_, ref, partial);
     } else {
-        const int64_t tiles = te::cdiv(p.out_w, TOW) * te::cdiv(p.out_h, TOH);
-        dim3 grid(xcd_grid(p, (int)te::cdiv(p.out_w, TOW), (int)te::cdiv(p.out_h, TOH), fir_planes_z(major, tiles)), 1u, 1u);
+        dim3 grid(tile_grid(p), 1u, 1u);
         fir_tile_kernel<1, 1, 4, 4, true><<<grid, 256, 0, (hipStream_t)stream_>>>(gx, g, k, nullptr, p, ref, partial);
     }
     return te::launch_status("te_blur_actgrad_f32");
@@ -571,13 +617,8 @@ extern "C" int te_blur_gradact_f32(float* gx, float* partial, const float* g, co
     TE_REQUIRE(gx && partial && g && ref && k, TE_ERR_NULL, "te_blur_gradact_f32: NULL pointer");
     TE_REQUIRE(major >= 0 && in_h > 0 && in_w >= 4, TE_ERR_SHAPE, "te_blur_gradact_f32: bad dims (in_w >= 4)");
     TE_REQUIRE(kh == 4 && kw == 4, TE_ERR_UNSUPPORTED, "te_blur_gradact_f32: 4x4 taps only");
-    FirParams p{};
-    p.in_h = in_h; p.in_w = in_w;
-    p.out_h = in_h + pad_y0 + pad_y1 - kh + 1;
-    p.out_w = in_w + pad_x0 + pad_x1 - kw + 1;
+    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
     TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "te_blur_gradact_f32: empty output");
-    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
-    p.up_x = p.up_y = p.down_x = p.down_y = 1; p.minor = 1; p.major = major;
     p.size_b = 1; p.act = 0; p.alpha = alpha; p.scale = scale;
     if (major == 0) return 0;
     TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "te_blur_gradact_f32: too many planes");
@@ -631,7 +672,7 @@ int upfirdn2d_any(T* out, const T* x, const T* k, int64_t major, int in_h, int i
     p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.minor = minor; p.major = major;
     if (major == 0) return 0;
     const int64_t total = major * p.out_h * p.out_w * minor;
-    const int grid = (int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 16);
+    const int grid = fir_direct_grid(total);
     fir_direct_any_kernel<T, A><<<grid, 256, 0, (hipStream_t)stream_>>>(out, x, k, p);
     return te::launch_status(what);
 }
@@ -662,25 +703,64 @@ extern "C" int te_upfirdn2d_f32(float* out, const float* x, const float* k, int6
     TE_REQUIRE(act == 0 || act == 3, TE_ERR_UNSUPPORTED, "te_upfirdn2d_f32: act must be 0 or 3");
     TE_REQUIRE(!(b || act) || minor == 1, TE_ERR_UNSUPPORTED, "te_upfirdn2d_f32: fused epilogue needs minor == 1");
     TE_REQUIRE(!b || size_b > 0, TE_ERR_SHAPE, "te_upfirdn2d_f32: bias given but size_b <= 0");
-    FirParams p{};
-    p.in_h = in_h; p.in_w = in_w;
-    p.out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
-    p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
+    FirParams p = fir_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
     TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "te_upfirdn2d_f32: empty output (%d x %d)", p.out_h, p.out_w);
-    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
-    p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.minor = minor; p.major = major;
     p.size_b = (int)size_b; p.act = act; p.alpha = alpha; p.scale = (b || act) ? scale : 1.f;
     if (major == 0) return 0;
     hipStream_t s = (hipStream_t)stream_;
-    const bool sq = (up_x == up_y) && (down_x == down_y) && minor == 1;
-    if (sq && kh == 4 && kw == 4 && up_x == 1 && down_x == 1 && in_w >= 4 && (int64_t)in_h * in_w * 4 < 0x7FFFFFFF)
-        launch_blur44<0>(out, x, k, b, p, s, nullptr, nullptr);
-    else if (sq && kh == 4 && kw == 4 && up_x == 2 && down_x == 1) launch_tile<2, 1, 4, 4>(out, x, k, b, p, s);
-    else if (sq && kh == 4 && kw == 4 && up_x == 1 && down_x == 2) launch_tile<1, 2, 4, 4>(out, x, k, b, p, s);
-    else {
-        const int64_t total = major * p.out_h * p.out_w * minor;
-        const int grid = (int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 16);
-        fir_direct_kernel<<<grid, 256, 0, s>>>(out, x, k, b, p);
+    switch (fir_route(p)) {
+        case FIR_BLUR44: launch_blur44<0>(out, x, k, b, p, s, nullptr, nullptr); break;
+        case FIR_TILE_UP2: launch_tile<2, 1, 4, 4>(out, x, k, b, p, s); break;
+        case FIR_TILE_DOWN2: launch_tile<1, 2, 4, 4>(out, x, k, b, p, s); break;
+        default: {
+            const int64_t total = major * p.out_h * p.out_w * minor;
+            fir_direct_kernel<<<fir_direct_grid(total), 256, 0, s>>>(out, x, k, b, p);
+        }
     }
     return te::launch_status("te_upfirdn2d_f32");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Launch plans (host only, nothing is launched): what the entry points above would launch for these arguments.  *zgroups = plane
+// groups of the plane-walking kernels (a block filters the planes pg, pg + zgroups, ... < major), *tiles = tiles per plane; both 0
+// where the direct kernel runs.  te_upfirdn2d_direct_cover: outputs that one trip of the direct kernels' full grid covers (a thread
+// of a launch with more outputs strides over the rest; the f16 / f64 entry points launch the same grid).
+extern "C" int te_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                                 int pad_x0, int pad_x1, int pad_y0, int pad_y1, int* zgroups, int* tiles) {
+    if (!zgroups || !tiles) return TE_ERR_NULL;
+    if (major <= 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
+        return TE_ERR_SHAPE;
+    FirParams p = fir_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
+    switch (fir_route(p)) {
+        case FIR_BLUR44: blur44_grid(p); return plan_out(p, true, zgroups, tiles);
+        case FIR_TILE_UP2:
+        case FIR_TILE_DOWN2: tile_grid(p); return plan_out(p, true, zgroups, tiles);
+        default: return plan_out(p, false, zgroups, tiles);
+    }
+}
+
+extern "C" int te_blur_actgrad_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                                    int* zgroups, int* tiles) {
+    if (!zgroups || !tiles) return TE_ERR_NULL;
+    if (major <= 0 || in_h <= 0 || in_w <= 0 || kh != 4 || kw != 4 || pad_x0 < 0 || pad_x1 < 0 || pad_y0 < 0 || pad_y1 < 0) return TE_ERR_SHAPE;
+    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
+    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
+    if (actgrad_blur44(p)) blur44_grid(p);
+    else tile_grid(p);
+    return plan_out(p, true, zgroups, tiles);
+}
+
+extern "C" int te_blur_gradact_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                                    int* zgroups, int* tiles) {
+    if (!zgroups || !tiles) return TE_ERR_NULL;
+    if (major <= 0 || in_h <= 0 || in_w < 4 || kh != 4 || kw != 4) return TE_ERR_SHAPE;
+    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
+    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
+    blur44_grid(p);
+    return plan_out(p, true, zgroups, tiles);
+}
+
+extern "C" int64_t te_upfirdn2d_direct_cover(int64_t outputs) {
+    return outputs > 0 ? (int64_t)fir_direct_grid(outputs) * 256 : TE_ERR_SHAPE;
 }

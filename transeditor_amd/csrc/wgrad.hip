@@ -859,12 +859,15 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(SumJobs jobs) {
     }
 }
 
+// capped grid.x of sum_parts_kernel for a launch whose longest job has mx elements (shared by the launch and te_wgrad_reduce_plan)
+inline unsigned sum_parts_grid(int64_t mx) { return (unsigned)std::min<int64_t>(te::cdiv(mx, 256), 4 * te::kNumCU); }
+
 inline void launch_sum_parts(const SumJob* jobs, int n, hipStream_t s) {
     if (!n) return;
     SumJobs t{};
     int64_t mx = 0;
     for (int i = 0; i < n; ++i) { t.j[i] = jobs[i]; mx = std::max(mx, jobs[i].n); }
-    sum_parts_kernel<<<dim3((unsigned)std::min<int64_t>(te::cdiv(mx, 256), 4 * te::kNumCU), (unsigned)n), 256, 0, s>>>(t);
+    sum_parts_kernel<<<dim3(sum_parts_grid(mx), (unsigned)n), 256, 0, s>>>(t);
 }
 
 // chunk counts of the reducer paths (shared by te_wgrad_reduce_ws_floats and the launch)
@@ -1001,6 +1004,25 @@ extern "C" int64_t te_wgrad_reduce_ws_floats(int B, int S, int Co, int Ci, int t
         if (want_isc && nzf > 1) f += (int64_t)nzf * B * Ci;
     }
     return std::max(n, std::max(m, f));
+}
+
+// Second pass of the dW output of te_wgrad_reduce_f32 with 16-byte aligned tensors and only dW wanted (host only): *parts = partial
+// tensors that sum_parts_kernel adds up (1: the first pass writes dW itself and no second pass runs), *cover = elements that one
+// trip of its full grid covers.
+extern "C" int te_wgrad_reduce_plan(int B, int S, int Co, int Ci, int taps, int* parts, int64_t* cover) {
+    if (B <= 0 || S <= 0 || Co <= 0 || Ci <= 0 || (taps != 1 && taps != 9) || !parts || !cover) return TE_ERR_SHAPE;
+    const int64_t E = (int64_t)Co * Ci * taps;
+    if (reduce_fused_ok(Co, Ci, taps)) {
+        int nzs, nzb;
+        reduce_fused_split(B, S, Co, Ci, nzs, nzb);
+        *parts = nzs * nzb;
+    } else if (taps == 1 && Co <= 4) {
+        *parts = reduce_few_nz(B, S, Ci) * B;
+    } else {
+        *parts = reduce_w_nchunk(B, S, E, E % 4 == 0);
+    }
+    *cover = (int64_t)sum_parts_grid(E) * 256;
+    return 0;
 }
 
 extern "C" int te_wgrad_reduce_f32(float* gw, float* gisc, float* gosc, float* ws, const float* slabs, const float* w, float wscale,
