@@ -755,6 +755,35 @@ int te_conv2d_f32(float* out, const float* x, const float* w, const float* bias,
 int te_pool3_f32(float* out, const float* x, int B, int C, int H, int W, int mode, int Ctot, int c0, te_stream_t stream);
 int te_resize_bilinear_f32(float* out, const float* x, int64_t planes, int H, int W, int OH, int OW, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M5  the two ends of the DEX age / gender scorer of attribute editing (our_interfaceGAN/ffhq_utils/dex/models.py:27-69: a VGG16 whose
+ * last layer has 101 or 2 classes; ffhq_utils/dex/api.py:42-65; called from edit_all_noinversion_ffhq.py:113-131).  conv1_2 ...
+ * conv5_3 and the max-pools are L1's, the two hidden fc layers are M2's te_fc_stream_f32; here the input and the output end.
+ * Forward only (the scorer runs under no_grad in eval mode: Dropout is the identity).
+ *
+ * te_dex_stem_fwd_f32 (edit_all_noinversion_ffhq.py:113-116, api.py:47-65, models.py:11-12; replaces the channel flip, the
+ * clamp / add / div / mul / round chain, the centre crop and Conv2d(3, 64, 3, padding=1) + ReLU): img [N,3,H,W] RGB, nominally in
+ * [-1, 1]; w [64,3,3,3], b [64]; out [N,64,crop,crop].  With y0 = (H - crop) / 2, x0 = (W - crop) / 2 and
+ *     v(t) = rint(((clamp(t, -1, 1) + 1) * 0.5) * 255)        each step rounded to fp32, ties to even: torch's result bit for bit
+ *     out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * v(img[n, 2 - c, y0 + y + ky - 1, x0 + x + kx - 1]))
+ * where a tap with y + ky - 1 or x + kx - 1 outside [0, crop) is ZERO: the padding is that of the crop, image pixels outside the
+ * window are never read.  A NaN pixel stays a NaN (torch's clamp) and a NaN propagates through the ReLU.  TE_ERR_SHAPE, nothing
+ * launched, for crop < 1, crop > H or W, an odd H - crop or W - crop, or N >= 65536.  Deviation from the reference: api.py:50-52 slices
+ * offset:-offset, which is empty at H == 224 and one pixel too large for an odd difference; an odd difference is refused here.
+ *
+ * te_cls_score_f32 (models.py:55-56 and api.py:42-44, :56-58, :64; replaces cls = nn.Linear, F.softmax(dim=1), the arange(1, 102)
+ * weighting with its sum, and the [:, 0] slice): a [I,K], w [C,K] (torch Linear layout), bias [C]:
+ *     p[i,:] = softmax(a[i,:] @ w.T + bias)     in fp32, the row maximum subtracted
+ *     score[i] = sum_c (c + 1) * p[i,c]  (mode 0; the reference's weights start at 1)      score[i] = p[i,0]  (mode 1)
+ * prob [I,C] receives p, or is NULL.  Shaped for latency: one workgroup per row, its waves split the classes, the lanes stride K with
+ * 16-byte loads; all reductions are fixed-shape trees, no atomics; a row's result is bitwise independent of I.  1 <= C <= 1024,
+ * K >= 4, K % 4 == 0, 16-byte aligned a and w, I >= 1, anything else is TE_ERR_SHAPE; another mode is TE_ERR_UNSUPPORTED; nothing is
+ * launched on a refusal.
+ */
+int te_dex_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, int N, int H, int W, int crop, te_stream_t stream);
+int te_cls_score_f32(float* score, float* prob, const float* a, const float* w, const float* bias, int64_t I, int C, int K, int mode,
+                     te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

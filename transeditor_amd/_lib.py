@@ -125,6 +125,8 @@ _SIGNATURES = {
     'te_conv2d_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 13 + [_P]),
     'te_pool3_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'te_resize_bilinear_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
+    'te_dex_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'te_cls_score_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     # loop-trip queries (host only)
     'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
     'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
@@ -1159,6 +1161,33 @@ def resize_bilinear(x, OH, OW):
     return out
 
 
+# --------------------------------------------------------------------------------------------- M5 DEX age / gender scorer
+CLS_EXPECTATION, CLS_FIRST = 0, 1
+
+
+def dex_stem_fwd(img, w, b, crop):
+    """RGB [-1, 1] -> BGR byte levels -> centre crop -> conv1_1 -> bias -> ReLU: img [N,3,H,W] -> [N,64,crop,crop].  The ABI refuses a
+    crop that does not fit or is not centred (an odd H - crop or W - crop); nothing is launched then."""
+    img = img.contiguous()
+    N, _, H, W = img.shape
+    out = torch.empty(N, 64, max(crop, 0), max(crop, 0), device=img.device, dtype=img.dtype)
+    _check(lib().te_dex_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, crop, _stream()), 'te_dex_stem_fwd_f32')
+    return out
+
+
+def cls_score(a, w, bias, mode, want_prob=False):
+    """p = softmax(a @ w.T + bias) over the classes: a [I,K], w [C,K] (torch Linear layout), bias [C] -> score [I] = sum_c (c + 1) p_c
+    (CLS_EXPECTATION) or p_0 (CLS_FIRST); want_prob: -> (score, p [I,C]).  The ABI refuses C > 1024, K % 4 != 0 and misaligned
+    operands; nothing is launched then."""
+    if a.ndim != 2 or w.ndim != 2 or bias.ndim != 1 or a.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0]:
+        raise RuntimeError(f'te_hip: cls_score: inconsistent shapes a {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
+    (I, K), Cn = a.shape, w.shape[0]
+    score = torch.empty(I, device=a.device, dtype=a.dtype)
+    prob = torch.empty(I, Cn, device=a.device, dtype=a.dtype) if want_prob else None
+    _check(lib().te_cls_score_f32(_ptr(score), _ptr(prob), _ptr(a), _ptr(w), _ptr(bias), I, Cn, K, mode, _stream()), 'te_cls_score_f32')
+    return (score, prob) if want_prob else score
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1173,7 +1202,7 @@ def _install_roctx():
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
-             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear']
+             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score']
     g = globals()
 
     def wrap(fn, name):

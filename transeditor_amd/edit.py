@@ -14,8 +14,9 @@ Differences from the reference, all deliberate:
   - no shrinking in the SMO solve (libsvm's heuristic that drops bounded variables from the working set; it changes the path, not the
     optimum), and ties in the working-set selection go to the lowest index, so a solve is bit-reproducible;
   - the train / validation split is drawn from a seeded torch generator (`seed`), not from np.random's global state;
-  - the DEX age / gender classifier is not part of this module: `score_fn` is any callable images [B,3,S,S] -> [B], and it is handed
-    the generator's image as it is (the reference converts to BGR in [0, 255] for DEX first);
+  - `score_fn` is any callable images [B,3,S,S] -> [B], and it is handed the generator's image as it is.  The DEX age / gender
+    classifier is transeditor_amd.dex.DEXScorer, whose stem does the reference's conversion to BGR in [0, 255] and the centre crop
+    itself; transeditor_amd.dex.fit_boundaries goes from a generator and a scorer to the z+ and p+ boundaries;
   - at most 8192 training rows (the one-workgroup solver's limit; the reference's default run needs 4200);
   - make_image does not clamp its argument in place.
 With invalid_value=None nothing synchronises with the host before the report and the boundary are read; filtering invalid scores
