@@ -1,8 +1,9 @@
 """our_interfaceGAN/ffhq_utils/dex/__init__.py of the reference: `eval(attribute_name)`, `estimate_age(img)` and `estimate_gender(img)` on
 transeditor_amd.dex.DEXScorer.  The editing scripts (edit_all_noinversion_ffhq.py:113-121) hand over the image already flipped to BGR
 and scaled to [0, 255], so the scorer only crops (preprocessed=True).  The weights are $TE_DEX_DIR/age_sd.pth and
-$TE_DEX_DIR/gender_sd.pth, the reference's own files.  Only the two DEX attributes exist here (no CelebA or pose classifier); the centre
-crop takes any size with an even margin, a 224 px image included (api.py:50-52 returns an empty crop for it)."""
+$TE_DEX_DIR/gender_sd.pth, the reference's own files.  Only the two DEX attributes exist here (the CelebA-HQ attribute classifiers are
+dropin/celebahq_utils/dex.py; there is no pose classifier); the centre crop takes any size with an even margin, a 224 px image included
+(api.py:50-52 returns an empty crop for it)."""
 import os
 
 from transeditor_amd.dex import DEXScorer

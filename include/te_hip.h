@@ -784,6 +784,52 @@ int te_dex_stem_fwd_f32(float* out, const float* img, const float* w, const floa
 int te_cls_score_f32(float* score, float* prob, const float* a, const float* w, const float* bias, int64_t I, int C, int K, int mode,
                      te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M6  the CelebA-HQ attribute classifier of attribute editing (our_interfaceGAN/celebahq_utils/dex/networks/classifiers/
+ * attribute_classifier.py:152-215: D with fixed_size=True, use_mbstd=False, a progressive-GAN discriminator with one logit per
+ * attribute; attribute_utils.py:8-60; called from edit_all_noinversion_celebahq.py:175-182).  Its 3x3 convolutions are F1's with bias
+ * and act 4 (conv0, the 4x4 convolution) or act 0 (conv1), dense0 is M2's te_fc_stream_f32; here the input end, the downscale between
+ * the blocks and the output end.  Forward only (the classifier runs under no_grad in eval mode), NCHW fp32, no atomics.  The constant
+ * scales of the equalised learning rate (WScaleLayer, attribute_classifier.py:11-33) are folded into the weights by the caller.
+ *
+ * te_attr_stem_fwd_f32 (edit_all_noinversion_celebahq.py:175-177, attribute_utils.py:8-19, attribute_classifier.py:62-71, :201;
+ * replaces the channel flip, the clamp / add / div / mul / round chain, the view + mean(dim=[3, 5]) box filter and fromrgb_lod0 =
+ * Conv2d(3, C0, 1) * scale + bias + LeakyReLU(0.2)): img [N,3,S,S], w [C0,3] (scaled), b [C0], out [N,C0,R,R], f = S / R.
+ *     preprocessed = 0: img is RGB, nominally in [-1, 1]:  v[n,c] = rint(((clamp(img[n, 2 - c], -1, 1) + 1) * 0.5) * 255), each step
+ *                       rounded to fp32, ties to even: torch's result bit for bit (the chain of te_dex_stem_fwd_f32)
+ *     preprocessed = 1: img is what the editing scripts hand over, BGR byte levels:  v[n,c] = img[n,c]
+ *     m_c[y,x] = (sum over the f x f block at (f y, f x) of v[n,c], row-major in fp32, starting from 0) / (f * f)       (= v at f == 1)
+ *     out[n,o,y,x] = lrelu_0.2(b[o] + sum_c w[o,c] * m_c[y,x])
+ * The mean is taken of the byte levels, as the reference takes it, not of the raw image.  A NaN pixel stays a NaN (torch's clamp)
+ * and reaches the one output pixel whose block holds it.  One thread per output pixel, the weights in LDS.  TE_ERR_SHAPE, nothing
+ * launched, unless S is a positive multiple of R (S <= 32768), 1 <= C0 <= 1024 and 1 <= N < 65536; another value of preprocessed is
+ * TE_ERR_UNSUPPORTED.
+ *
+ * te_avgpool2_act_f32 (attribute_classifier.py:74-80, :100-104; replaces nn.AvgPool2d(2, 2) and the LeakyReLU(0.2) after it):
+ * x [planes,H,W] -> out [planes,H/2,W/2],
+ *     out[p,y,x] = act((((x[p,2y,2x] + x[p,2y,2x+1]) + x[p,2y+1,2x]) + x[p,2y+1,2x+1]) * 0.25),    act(v) = v > 0 ? v : slope * v
+ * so a NaN tap gives a NaN in its own output only and slope = 1 is the plain pool.  planes >= 1, H and W even and >= 2, at most 2^40
+ * input elements, else TE_ERR_SHAPE.  Memory bound: where W % 4 == 0 (and x is 16-byte, out 8-byte aligned) a thread reads two
+ * 16-byte row pieces and writes two outputs; elsewhere a thread reads four scalars and writes one.  The grid is NOT capped: one
+ * thread per work item with 64-bit offsets, no thread loops.
+ *
+ * te_attr_score_f32 (attribute_classifier.py:147-148 and attribute_utils.py:28-32; replaces the LeakyReLU after dense0, dense1 =
+ * Linear(K, 1) * scale + bias, torch.cat([logit, -logit], 1), Softmax(dim=1) and the [:, 1] slice): a [I,K] = dense0's output BEFORE
+ * its activation, w [K] (scaled), bias [1]:
+ *     logit[i] = bias[0] + sum_k w[k] * act(a[i,k])                         act as above
+ *     score[i] = softmax([l, -l])[1] = 1 / (1 + exp(2 l))                   DECREASING in l, as the reference's is
+ * evaluated as e / (1 + e), e = exp(-2 l), for l >= 0 and as 1 / (1 + exp(2 l)) for l < 0, so nothing overflows: never Inf, NaN only
+ * from a NaN row; a score below FLT_MIN (l > 43.66) is returned as 0, so l = 50 gives exactly 0 and l = -50 exactly 1.  logit or
+ * score may be NULL, not both.  Shaped for latency: one wave per row, its lanes stride K with 16-byte loads, the sum is a fixed-shape
+ * butterfly; a row's result is bitwise independent of I.  I >= 1, K >= 4, K % 4 == 0, 16-byte aligned a and w, anything else is
+ * TE_ERR_SHAPE; nothing is launched on a refusal.
+ */
+int te_attr_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, int N, int S, int R, int C0, int preprocessed,
+                         te_stream_t stream);
+int te_avgpool2_act_f32(float* out, const float* x, int64_t planes, int H, int W, float slope, te_stream_t stream);
+int te_attr_score_f32(float* logit, float* score, const float* a, const float* w, const float* bias, int64_t I, int K, float slope,
+                      te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

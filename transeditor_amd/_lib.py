@@ -127,6 +127,9 @@ _SIGNATURES = {
     'te_resize_bilinear_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
     'te_dex_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'te_cls_score_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'te_attr_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'te_avgpool2_act_f32': (C.c_int, [_P, _P, _L, _I, _I, _F, _P]),
+    'te_attr_score_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P]),
     # loop-trip queries (host only)
     'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
     'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
@@ -1188,6 +1191,45 @@ def cls_score(a, w, bias, mode, want_prob=False):
     return (score, prob) if want_prob else score
 
 
+# --------------------------------------------------------------------------------------------- M6 CelebA-HQ attribute classifier
+def attr_stem_fwd(img, w, b, R, preprocessed=False):
+    """RGB [-1, 1] -> BGR byte levels (preprocessed: img already is) -> f x f box mean, f = S / R -> 1x1 convolution -> bias ->
+    leaky ReLU 0.2: img [N,3,S,S], w [C0,3] (scaled), b [C0] -> [N,C0,R,R].  The ABI refuses an S that is no multiple of R and
+    C0 > 1024; nothing is launched then."""
+    if img.ndim != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3] or w.ndim != 2 or w.shape[1] != 3 or b.shape != (w.shape[0],):
+        raise RuntimeError(f'te_hip: attr_stem_fwd: inconsistent shapes img {tuple(img.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}')
+    img = img.contiguous()
+    N, S, C0 = img.shape[0], img.shape[2], w.shape[0]
+    out = torch.empty(N, C0, max(R, 0), max(R, 0), device=img.device, dtype=img.dtype)
+    _check(lib().te_attr_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, S, R, C0, 1 if preprocessed else 0, _stream()),
+           'te_attr_stem_fwd_f32')
+    return out
+
+
+def avgpool2_act(x, slope=1.0):
+    """2 x 2 average pool, then v > 0 ? v : slope * v (slope 1: the plain pool): x [N,C,H,W] -> [N,C,H/2,W/2]"""
+    if x.ndim != 4:
+        raise RuntimeError(f'te_hip: avgpool2_act expects [N,C,H,W], got {tuple(x.shape)}')
+    x = x.contiguous()
+    N, Cn, H, W = x.shape
+    out = torch.empty(N, Cn, H // 2, W // 2, device=x.device, dtype=x.dtype)
+    _check(lib().te_avgpool2_act_f32(_ptr(out), _ptr(x), N * Cn, H, W, slope, _stream()), 'te_avgpool2_act_f32')
+    return out
+
+
+def attr_score(a, w, bias, slope=0.2, want_logit=True, want_score=True):
+    """logit = bias + act(a) @ w, score = 1 / (1 + exp(2 logit)): a [I,K] (dense0's output before its activation), w [K] (scaled),
+    bias [1] -> (logit [I] or None, score [I] or None).  The ABI refuses K % 4 != 0 and misaligned operands; nothing is launched
+    then."""
+    if a.ndim != 2 or w.ndim != 1 or a.shape[1] != w.shape[0] or bias.shape != (1,):
+        raise RuntimeError(f'te_hip: attr_score: inconsistent shapes a {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
+    I, K = a.shape
+    logit = torch.empty(I, device=a.device, dtype=a.dtype) if want_logit else None
+    score = torch.empty(I, device=a.device, dtype=a.dtype) if want_score else None
+    _check(lib().te_attr_score_f32(_ptr(logit), _ptr(score), _ptr(a), _ptr(w), _ptr(bias), I, K, slope, _stream()), 'te_attr_score_f32')
+    return logit, score
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1202,7 +1244,8 @@ def _install_roctx():
              'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
-             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score']
+             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score',
+             'attr_stem_fwd', 'avgpool2_act', 'attr_score']
     g = globals()
 
     def wrap(fn, name):

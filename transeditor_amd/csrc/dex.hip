@@ -11,16 +11,11 @@
 // lanes of a wave stride K with 16-byte loads.  Every reduction is a fixed-shape tree (no atomics) over the row's own data, so a row's
 // result is bitwise independent of the batch it is in.
 #include "te_common.h"
+#include "byte_level.h"
 
 namespace {
 
-// clamp(-1, 1).add(1).div(2).mul(255).round() of torch, step by step in fp32 (division by 2 and multiplication by 0.5 are the same
-// exact operation; round is to nearest, ties to even).  The comparisons leave a NaN as it is, as torch's clamp does.
-__device__ __forceinline__ float to_byte_level(float x) {
-#pragma clang fp contract(off)
-    const float c = x < -1.f ? -1.f : (x > 1.f ? 1.f : x);
-    return rintf(__fmul_rn(__fmul_rn(__fadd_rn(c, 1.f), 0.5f), 255.f));
-}
+using te::to_byte_level;                           // clamp / +1 / /2 / *255 / round in torch's bits (byte_level.h)
 
 // out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * v[n, 2 - c, y0 + y + ky - 1, x0 + x + kx - 1]), v = to_byte_level(img), for
 // (y, x) in the crop x crop window at (y0, x0); a tap outside the WINDOW is zero (the reference crops first, then nn.Conv2d pads).
