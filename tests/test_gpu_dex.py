@@ -53,6 +53,17 @@ def test_stem_against_fp64(N, H, W, crop):
     assert float((y.double().cpu() - ref)[:, :, 0].abs().max()) < 1e-5 * float(ref.abs().max())      # first row (padding side)
 
 
+@pytest.mark.parametrize('N,H,W,crop', [(2, 40, 40, 32), (1, 50, 50, 36)])       # the second: a ragged last block
+def test_stem_is_the_vgg_stem_on_the_preprocessed_crop(N, H, W, crop):
+    """te_dex_stem_fwd_f32 and te_vgg_stem_fwd_f32 are one kernel body with two input rules: the same 27-term chain on the same
+    integers (the byte-level chain is torch's own bits by construction), so the outputs are bitwise equal."""
+    from transeditor_amd import _lib
+    w, b = _stem_weights(N + crop)
+    x = _stem_input(N, H, W, crop, 3 * H + W)
+    y = _lib.dex_stem_fwd(x.to(DEV), w.to(DEV), b.to(DEV), crop)
+    assert torch.equal(y, _lib.vgg_stem_fwd(R.preprocess(x, crop).to(DEV), w.to(DEV), b.to(DEV)))
+
+
 def test_stem_pads_the_crop_not_the_image():
     """the window holds -1 (level 0) everywhere and the image around it +5 (clamped: level 255): every output is relu(bias) exactly,
     also next to the window's edge.  A tap that read the image outside the window would add 255 * w."""

@@ -13,29 +13,12 @@ Run under `rocprofv3 --kernel-trace --stats -- python tools/inception_time.py --
 """
 import argparse
 import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import torch
+import torch.nn.functional as F
 
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-
-def timed(fn, reps):
-    fn()                                                       # first call: code-object load, allocator growth, kernel selection
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e))
-    return sorted(ts)[len(ts) // 2], ts
+from net_timing import event_log, rate, timed, write_json
 
 
 def conv_kind(w, stride):
@@ -50,36 +33,16 @@ def conv_kind(w, stride):
 def shares(net, x):
     """one forward pass with HIP events around every library call -> {kind: (ms, calls, GFLOP)}"""
     from transeditor_amd import _lib
-    log = []
 
-    def wrap(fn, kind_of, flop_of):
-        def run(*a, **k):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            out = fn(*a, **k)
-            e.record()
-            log.append((kind_of(*a, **k), s, e, flop_of(out, *a, **k)))
-            return out
-        return run
-    saved = {n: getattr(_lib, n) for n in ('conv2d', 'pool3', 'resize_bilinear', 'adaptive_avgpool')}
-
-    def conv_flop(out, x_, w, *a, c0=0, **k):
+    def conv(out, x_, w, b, stride=1, *a, **k):
         Co, Ci, kh, kw = w.shape
-        return 2.0 * x_.shape[0] * out.shape[2] * out.shape[3] * Co * Ci * kh * kw
-    try:
-        _lib.conv2d = wrap(saved['conv2d'], lambda x_, w, b, stride=1, *a, **k: conv_kind(w, stride), conv_flop)
-        _lib.pool3 = wrap(saved['pool3'], lambda *a, **k: 'pool 3x3', lambda *a, **k: 0.0)
-        _lib.resize_bilinear = wrap(saved['resize_bilinear'], lambda *a, **k: 'resize', lambda *a, **k: 0.0)
-        _lib.adaptive_avgpool = wrap(saved['adaptive_avgpool'], lambda *a, **k: 'global average', lambda *a, **k: 0.0)
-        net(x)
-        torch.cuda.synchronize()
-    finally:
-        for n, fn in saved.items():
-            setattr(_lib, n, fn)
+        return conv_kind(w, stride), 2.0 * x_.shape[0] * out.shape[2] * out.shape[3] * Co * Ci * kh * kw
+    log = event_log(lambda: net(x), [(_lib, 'conv2d', conv), (_lib, 'pool3', ('pool 3x3', 0.0)), (_lib, 'resize_bilinear', ('resize', 0.0)),
+                                     (_lib, 'adaptive_avgpool', ('global average', 0.0))])
     out = {}
-    for kind, s, e, flop in log:
+    for (kind, flop), t in log:
         ms, calls, gf = out.get(kind, (0.0, 0, 0.0))
-        out[kind] = (ms + s.elapsed_time(e), calls + 1, gf + flop / 1e9)
+        out[kind] = (ms + t, calls + 1, gf + flop / 1e9)
     return out
 
 
@@ -120,7 +83,7 @@ def main():
     x = torch.rand(a.batch, 3, a.size, a.size, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1)) * 2 - 1
     res = {'command': ' '.join(['python tools/inception_time.py'] + sys.argv[1:]), 'batch': a.batch, 'size': a.size}
     med, ts = timed(lambda: net(x), a.reps)
-    res['library'] = {'ms_median': round(med, 2), 'ms_all': [round(t, 2) for t in ts], 'images_per_s': round(a.batch / (med * 1e-3), 1)}
+    res['library'] = rate(med, ts, a.batch, 2)
     sh = shares(net, x)
     total = sum(v[0] for v in sh.values())
     res['shares'] = {k: {'ms': round(ms, 3), 'calls': n, 'share': round(ms / total, 4), 'gflop': round(gf, 1),
@@ -132,16 +95,12 @@ def main():
     if not a.no_torch:
         ref_run = torch_network(net)
         medt, tst = timed(lambda: ref_run(x), a.reps)
-        res['torch'] = {'ms_median': round(medt, 2), 'ms_all': [round(t, 2) for t in tst], 'images_per_s': round(a.batch / (medt * 1e-3), 1)}
+        res['torch'] = rate(medt, tst, a.batch, 2)
         lib, ref = net(x).double(), ref_run(x).double()
         res['rel_l2_library_against_torch'] = float((lib - ref).norm() / ref.norm())
         res['library_time_over_torch_time'] = round(med / medt, 2)
     print(json.dumps(res), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            json.dump(res, f, indent=1)
-            f.write('\n')
+    write_json(res, a.out)
 
 
 if __name__ == '__main__':

@@ -1,11 +1,13 @@
 """Compare the gfx950 machine code of the library's kernels between two source trees (a refactor's "same code" check; no GPU needed).
 
     python tools/isa_compare.py PARENT_TREE BRANCH_TREE [-o profiles/NAME.txt] [--keep DIR] [-D NAME[=VALUE] ...]
+                                [--renamed 'FILE: OLD=FILE: NEW' ...]
 
 Both trees are compiled with build.py's flags plus --save-temps (and every -D given, e.g. a profiler build of both); for every kernel of
 every source in build.py's SOURCES the table gives registers, scratch, LDS, occupancy, instruction counts by class (parent | branch) and
-whether the instruction streams are identical after dropping comments, directives and the function number inside local labels.  Exit
-status 1 if any kernel differs.
+whether the instruction streams are identical after dropping comments, directives and the function number inside local labels.  A kernel
+that the branch renamed is compared under its new name with --renamed (both names as the table prints them).  Exit status 1 if any
+kernel differs.
 """
 import argparse
 import os
@@ -73,6 +75,7 @@ def main():
     ap.add_argument('branch')
     ap.add_argument('-o', '--output')
     ap.add_argument('--keep', help='directory for the compiler outputs (default: a temporary one)')
+    ap.add_argument('--renamed', action='append', default=[], metavar='OLD=NEW', help='a parent kernel and its name in the branch')
     ap.add_argument('-D', dest='defines', action='append', default=[], metavar='NAME[=VALUE]', help='extra define for both trees')
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
@@ -82,6 +85,10 @@ def main():
             compile_tree(tree, os.path.join(base, tag), a.defines)
             sides.append(kernels(os.path.join(base, tag)))
     par, br = sides
+    for pair in a.renamed:
+        old, new = pair.split('=')
+        par[f'{new} (parent: {old})'] = par.pop(old)
+        br[f'{new} (parent: {old})'] = br.pop(new)
     lines = ['machine code of the library\'s kernels, parent | branch (build.py flags' + ''.join(' -D' + d for d in a.defines) + ' + --save-temps, gfx950)', '']
     ndiff = 0
     for name in sorted(set(par) | set(br)):

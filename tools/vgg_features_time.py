@@ -13,28 +13,17 @@ summarises the trace): the events include launch gaps, the trace does not.  GPU 
 """
 import argparse
 import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import torch
 
-import torch  # noqa: E402
+import net_timing
 
 
 def timed(fn, reps):
-    fn()                                                       # first call: code-object load, allocator growth, weight packing
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e) * 1e3)
-    return sorted(ts)[len(ts) // 2], ts
+    """net_timing.timed in microseconds"""
+    med, ts = net_timing.timed(fn, reps)
+    return med * 1e3, [t * 1e3 for t in ts]
 
 
 def fc6(a):
@@ -88,11 +77,7 @@ def main():
     res = {'command': ' '.join(['python tools/vgg_features_time.py'] + [x for x in sys.argv[1:]])}
     res.update(fc6(a) if a.what == 'fc6' else net(a))
     print(json.dumps(res), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            json.dump(res, f, indent=1)
-            f.write('\n')
+    net_timing.write_json(res, a.out)
 
 
 if __name__ == '__main__':

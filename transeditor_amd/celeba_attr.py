@@ -6,7 +6,7 @@ edit_all_noinversion_celebahq.py:136, :175-182 and editing_evaluate.py call them
     s = scorer(images)                                                  # [B,3,S,S] RGB in [-1, 1] -> [B]: softmax([l, -l])[:, 1]
     l = scorer.logits(images)                                           # [B]: the logit
     scorers = load_scorers('pth_celeba', ['Smiling', 'Male'])           # {name: scorer}, for edit_eval.score_sweeps
-    res = dex.fit_boundaries(G, scorer, n_sample=10000, batch=16)       # an instance is a score_fn of transeditor_amd.edit
+    res = edit.fit_boundaries(G, scorer, n_sample=10000, batch=16)      # an instance is a score_fn of transeditor_amd.edit
 
     python -m transeditor_amd.celeba_attr --ckpt G.pt --weights net_best.pth [--name Smiling] --num_sample 10000
                                           --write_z_boundary zb.npy --write_p_boundary pb.npy [--write_scores s.npy] [--no_soft]
@@ -27,38 +27,28 @@ scorer, which takes the generator's image as it is; preprocessed=True takes what
 larger than R is box-averaged down (attribute_utils.downsample, for any R), a smaller one is refused.
 There is no speed bar for this path; see profiles/README.md, 'CelebA-HQ attribute scorer'.
 """
-import argparse
-import json
 import math
 import os
 import re
 import sys
 
-import numpy as np
 import torch
 
 from . import _lib
-from .dex import fit_boundaries
-from .lpips import VGGTrunk, _load
+from .edit import scorer_main, scorer_parser
+from .frozen_net import FrozenConvs, check_images, no_gpu, resolve, weight_bias
 from .op import modconv
 
 SLOPE = 0.2
-_NO_GPU = 'CelebAAttributeScorer needs a GPU (the network runs on the gfx950 kernels only; there is no CPU path)'
+_NO_GPU = no_gpu('CelebAAttributeScorer')
 _LAYOUT = 'not an attribute classifier state dict: fromrgb_lod0.conv.*, {r}x{r}.conv{0,1}.*, 4x4.conv.*, 4x4.dense{0,1}.*'
 _BLOCK = re.compile(r'^(\d+)x\1\.conv0\.conv\.weight$')
 
 
 def _pair(sd, prefix, kind, path, shape):
     """(weight, bias) of one layer; `shape` is the expected weight shape with None where the state dict decides"""
-    kw, kb = f'{prefix}.{kind}.weight', f'{prefix}.wscale.b'
-    if kw not in sd or kb not in sd:
-        raise ValueError(f'CelebAAttributeScorer: {path} has no {kw} / {kb} ({_LAYOUT})')
-    w, b = sd[kw], sd[kb]
-    ok = w.ndim == len(shape) and all(s is None or s == d for s, d in zip(shape, w.shape))
-    if not ok or b.ndim != 1 or b.shape[0] != w.shape[0]:
-        want = '(' + ', '.join('*' if s is None else str(s) for s in shape) + ')'
-        raise ValueError(f'CelebAAttributeScorer: {kw} is {tuple(w.shape)} / bias {tuple(b.shape)}, expected {want} / (Co,)')
-    return w.detach().float().contiguous(), b.detach().float().contiguous()
+    return weight_bias(sd, f'{prefix}.{kind}.weight', f'{prefix}.wscale.b', shape, 'CelebAAttributeScorer', path, _LAYOUT,
+                       want='(' + ', '.join('*' if s is None else str(s) for s in shape) + ') / (Co,)')
 
 
 def _scaled(w, gain2):
@@ -103,35 +93,19 @@ def parse_state_dict(sd, path='state_dict'):
                 dense1=(_scaled(w1, 1.0).view(-1).contiguous(), b1))
 
 
-class CelebAAttributeScorer(VGGTrunk, torch.nn.Module):
-    """buffers: stem_w / stem_b, w{i} / b{i} of convolution i (VGGTrunk's names: its pack cache is used), dense0_w / dense0_b,
+class CelebAAttributeScorer(FrozenConvs, torch.nn.Module):
+    """buffers: stem_w / stem_b, w{i} / b{i} of convolution i (FrozenConvs's names), dense0_w / dense0_b,
     dense1_w / dense1_b; all weights scaled"""
 
     def __init__(self, path=None, state_dict=None, name=None):
         super().__init__()
-        if state_dict is None:
-            state_dict = _load(path, f'attribute classifier{f" {name!r}" if name else ""}', who='CelebAAttributeScorer')
-        else:
-            if path is not None:
-                raise ValueError('CelebAAttributeScorer: give path or state_dict, not both')
-            if not isinstance(state_dict, dict):
-                raise ValueError(f'CelebAAttributeScorer: state_dict must be a dict, got {type(state_dict).__name__}')
-            path = 'state_dict'
+        state_dict, path = resolve(path, state_dict, 'CelebAAttributeScorer', f'attribute classifier{f" {name!r}" if name else ""}')
         net = parse_state_dict(state_dict, path)
         self.name, self.resolution, self.channels = name, net['resolution'], net['channels']
         self.register_buffer('stem_w', net['stem'][0])
         self.register_buffer('stem_b', net['stem'][1])
-        for i, (w, b) in enumerate(net['convs']):
-            self.register_buffer(f'w{i}', w)
-            self.register_buffer(f'b{i}', b)
-        for key in ('dense0', 'dense1'):
-            self.register_buffer(f'{key}_w', net[key][0])
-            self.register_buffer(f'{key}_b', net[key][1])
         self.n_convs = len(net['convs'])
-        self._packs = {}
-        self.eval()
-        if torch.cuda.is_available():
-            self.to('cuda')
+        self._freeze(net['convs'], [(f'{key}_{t}', v) for key in ('dense0', 'dense1') for t, v in zip('wb', net[key])])
 
     def train(self, mode=True):
         if mode:
@@ -147,19 +121,10 @@ class CelebAAttributeScorer(VGGTrunk, torch.nn.Module):
                 H //= 2
         return out
 
-    def _conv(self, i, x, act):
-        w = self._w(i)
-        B, _, H, W = x.shape
-        pk, ck = modconv.fwd_kinds('3x3', B, w, H, W)
-        return _lib.conv(x, self._packed(i, pk), ck, w.shape[0], H, W, bias=getattr(self, f'b{i}'), act=act)
-
     def _dense0(self, images, preprocessed):
         """[B,3,S,S] -> dense0's output before its activation [B,J]; an activation is dropped once the next layer has read it"""
-        if images.ndim != 4 or images.shape[1] != 3:
-            raise ValueError(f'CelebAAttributeScorer: expected [B,3,S,S] images, got {tuple(images.shape)}')
+        check_images(images, 'CelebAAttributeScorer', '[B,3,S,S]', square=True)
         S, R = images.shape[2], self.resolution
-        if images.shape[3] != S:
-            raise ValueError(f'CelebAAttributeScorer: the images must be square, got {images.shape[2]}x{images.shape[3]}')
         if S < R or S % R:
             raise ValueError(f'CelebAAttributeScorer: the image size must be a multiple of the resolution {R}, got {S}')
         if not images.is_cuda:
@@ -193,58 +158,20 @@ def load_scorers(directory, names):
 
 # ------------------------------------------------------------------------------------------------------------------------ CLI
 def build_parser():
-    parser = argparse.ArgumentParser(description='score sampled images with a CelebA-HQ attribute classifier and fit the z+ and p+ editing '
-                                                 'boundaries (edit_all_noinversion_celebahq.py:136-240)')
-    parser.add_argument('--ckpt', required=True, help='a generator checkpoint file')
-    parser.add_argument('--weights', required=True, help="the classifier's net_best.pth in the reference's layout")
+    parser = scorer_parser('score sampled images with a CelebA-HQ attribute classifier and fit the z+ and p+ editing boundaries '
+                           '(edit_all_noinversion_celebahq.py:136-240)', "the classifier's net_best.pth in the reference's layout")
     parser.add_argument('--name', default=None, help='the attribute (reported only), e.g. Smiling')
-    parser.add_argument('--num_sample', type=int, default=10000)
-    parser.add_argument('--write_z_boundary', required=True, help='output .npy file of the z+ boundary [1,D]')
-    parser.add_argument('--write_p_boundary', required=True, help='output .npy file of the p+ boundary [1,D]')
-    parser.add_argument('--write_scores', help='output .npy file of the scores [N,1]')
     parser.add_argument('--no_soft', action='store_true', help='score with the logit instead of softmax([l, -l])[:, 1]')
-    parser.add_argument('--ratio', type=float, default=0.02, help='chosen_num_or_ratio')
-    parser.add_argument('--split_ratio', type=float, default=0.7)
-    parser.add_argument('--seed', type=int, default=None, help='seed of the sampled codes and of the train / validation splits')
-    parser.add_argument('--size', type=int, default=256)
-    parser.add_argument('--batch', type=int, default=16)
-    parser.add_argument('--truncation', type=float, default=0.7)
-    parser.add_argument('--para_num', type=int, default=16)
-    parser.add_argument('--channel_multiplier', type=int, default=2)
-    parser.add_argument('--num_trans', type=int, default=8)
     return parser
 
 
 def main(argv=None):
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    if args.size < 8 or args.size & (args.size - 1):
-        parser.error(f'--size must be a power of two >= 8, got {args.size}')
-    if args.num_sample < 1 or args.batch < 1:
-        parser.error('--num_sample and --batch must be positive')
-    if not torch.cuda.is_available():
-        raise RuntimeError(_NO_GPU)
-    from .inference import GeneratorSampler
-    from .model_spatial_query import Generator
-    from .train_step import load_checkpoint_into
-    scorer = CelebAAttributeScorer(args.weights, name=args.name)
-    score_fn = (lambda images: scorer(images, no_soft=True)) if args.no_soft else scorer
-    g = Generator(args.size, 512, 512, 2 * (int(math.log(args.size, 2)) - 1), channel_multiplier=args.channel_multiplier,
-                  n_trans=args.num_trans, pixel_norm_op_dim=1).to('cuda')
-    load_checkpoint_into(args.ckpt, g, device='cuda', g_ema_only_ok=True)
-    out = fit_boundaries(GeneratorSampler(g), score_fn, n_sample=args.num_sample, batch=args.batch, ratio=args.ratio,
-                         split_ratio=args.split_ratio, truncation=args.truncation, seed=args.seed, para_num=args.para_num)
-    np.save(args.write_z_boundary, out['z_boundary'])
-    np.save(args.write_p_boundary, out['p_boundary'])
-    scores = out['scores'].cpu().numpy()
-    if args.write_scores:
-        np.save(args.write_scores, scores)
-    res = {'name': args.name, 'ckpt': args.ckpt, 'weights': args.weights, 'n': args.num_sample, 'resolution': scorer.resolution,
-           'channels': list(scorer.channels), 'no_soft': bool(args.no_soft), 'score_mean': float(scores.mean()),
-           'score_min': float(scores.min()), 'score_max': float(scores.max()), 'z': out['z_report'], 'p': out['p_report'],
-           'wrote': [args.write_z_boundary, args.write_p_boundary] + ([args.write_scores] if args.write_scores else [])}
-    print(json.dumps(res), flush=True)
-    return res
+    def make_scorer(args):
+        scorer = CelebAAttributeScorer(args.weights, name=args.name)
+        score_fn = (lambda images: scorer(images, no_soft=True)) if args.no_soft else scorer
+        return score_fn, {'name': args.name}, {'resolution': scorer.resolution, 'channels': list(scorer.channels),
+                                               'no_soft': bool(args.no_soft)}
+    return scorer_main(build_parser(), argv, _NO_GPU, make_scorer)
 
 
 if __name__ == '__main__':

@@ -194,8 +194,6 @@ __global__ __launch_bounds__(256) void bias_act_bwd_2d_kernel(float* __restrict_
     if (gb) gb[c] = acc;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // capped grid of the elementwise kernels and the fp32 path choice (shared by the launches and the te_bias_act_*_cover queries);
 // `items` are 16-byte vectors on the fp32 vector path, elements elsewhere
 inline int bias_act_grid(int64_t items) { return (int)std::min<int64_t>(te::cdiv(items, 256), te::kNumCU * 8); }
@@ -268,7 +266,7 @@ extern "C" int te_bias_act_f32(float* out, const float* x, const float* b, const
     if (size_x == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     const int mode = act * 10 + grad;
-    const bool vec = bias_act_vec(size_x, b != nullptr, step_b, aligned16(out) && aligned16(x) && (!ref || aligned16(ref)));
+    const bool vec = bias_act_vec(size_x, b != nullptr, step_b, te::aligned16(out) && te::aligned16(x) && (!ref || te::aligned16(ref)));
     if (vec) {
         const uint32_t n4 = (uint32_t)(size_x / 4);
         const int grid = bias_act_grid(n4);
@@ -313,7 +311,7 @@ extern "C" int te_bias_act_bwd_f32(float* gi, float* gb, float* ws, const float*
     hipStream_t stream = (hipStream_t)stream_;
     if (inner == 1) {
         bias_act_bwd_2d_kernel<<<(int)te::cdiv(C, 256), 256, 0, stream>>>(gi, gb, g, ref, alpha, scale, outer, C);
-    } else if (bwd_rows_path(outer, C, inner) && aligned16(gi) && aligned16(g) && aligned16(ref) && (!gb || ws)) {
+    } else if (bwd_rows_path(outer, C, inner) && te::aligned16(gi) && te::aligned16(g) && te::aligned16(ref) && (!gb || ws)) {
         const uint32_t inner4 = (uint32_t)(inner / 4);
         dim3 grid((unsigned)te::cdiv(inner4, 256 * kBwdVecPerThread), (unsigned)C, (unsigned)outer);
         bias_act_bwd_rows_kernel<<<grid, 256, 0, stream>>>((float4*)gi, gb ? ws : nullptr, (const float4*)g, (const float4*)ref, alpha,
@@ -336,7 +334,7 @@ extern "C" int te_bias_act_bwd_rgb_f32(float* gi, float* gb, float* ws, const fl
     TE_REQUIRE(!gb || ws, TE_ERR_NULL, "te_bias_act_bwd_rgb_f32: the bias gradient needs the workspace (te_bias_act_bwd_ws_floats)");
     TE_REQUIRE(te_bias_act_bwd_rgb_supported(outer, C, inner), TE_ERR_UNSUPPORTED,
                "te_bias_act_bwd_rgb_f32: needs inner %% 4 == 0 and inner >= 1024 (use te_rgb_dgrad_f32 + te_bias_act_bwd_f32)");
-    TE_REQUIRE(aligned16(gi) && (!g || aligned16(g)) && aligned16(ref) && aligned16(grgb), TE_ERR_UNSUPPORTED,
+    TE_REQUIRE(te::aligned16(gi) && (!g || te::aligned16(g)) && te::aligned16(ref) && te::aligned16(grgb), TE_ERR_UNSUPPORTED,
                "te_bias_act_bwd_rgb_f32: 16-byte aligned tensors required");
     const uint32_t inner4 = (uint32_t)(inner / 4);
     dim3 grid((unsigned)te::cdiv(inner4, 256 * kBwdVecPerThread), (unsigned)C, (unsigned)outer);

@@ -9,7 +9,7 @@
 //     te_attr_score_f32    : the activation of dense0, dense1 (attribute_classifier.py:147-148) and softmax([l, -l])[:, 1]
 //                            (attribute_utils.py:28-32)
 //
-// The stem is dex_stem_kernel's shape: one thread per output pixel, the weights in LDS, the three channel means in registers, the
+// The stem is vgg_stem_kernel's shape (vgg_stem.h): one thread per output pixel, the weights in LDS, the three channel means in registers, the
 // stores of one channel coalesced over the pixels.  The pool is memory bound: one thread per two output pixels with two 16-byte
 // loads where the rows allow it, one thread per output pixel elsewhere; the grid is NOT capped and no thread loops.  The score head is
 // shaped for latency: one wave per row, its lanes stride K with 16-byte loads, the sum is a fixed-shape butterfly (no atomics), so a
@@ -17,12 +17,13 @@
 #include <float.h>
 #include "te_common.h"
 #include "byte_level.h"
+#include "wave_dot.h"
 
 namespace {
 
 constexpr int kStemMaxC0 = 1024;                   // the stem's LDS holds w [C0,3] and b [C0]: 16 KB at the most
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using te::f32x4;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 // v > 0 ? v : slope * v: a NaN fails the comparison and stays a NaN
@@ -100,31 +101,12 @@ __global__ __launch_bounds__(256) void avgpool2_act_kernel(float* __restrict__ o
     out[t] = pool4(x0[0], x0[1], x0[W], x0[W + 1], slope);
 }
 
-// all 64 lanes end with the same value: a butterfly whose shape does not depend on the data
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Row i = blockIdx.x, one wave: lane l takes k = 4 l, 4 l + 256, ... of a[i,:] and w as 16-byte loads into four fma chains (one per
-// vector component); the lanes' sums meet in a butterfly.
+// Row i = blockIdx.x, one wave: te::wave_dot (wave_dot.h) of leaky(a[i,:]) and w.
 __global__ __launch_bounds__(64) void attr_score_kernel(float* __restrict__ logit, float* __restrict__ score, const float* __restrict__ a,
                                                         const float* __restrict__ w, const float* __restrict__ bias, int K, float slope) {
     const int lane = threadIdx.x;
     const int64_t i = blockIdx.x;
-    const float* ai = a + i * K;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-    for (int k = 4 * lane; k < K; k += 256) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(ai + k);
-        const f32x4 y = *reinterpret_cast<const f32x4*>(w + k);
-        acc.x = fmaf(y.x, leaky(x.x, slope), acc.x);
-        acc.y = fmaf(y.y, leaky(x.y, slope), acc.y);
-        acc.z = fmaf(y.z, leaky(x.z, slope), acc.z);
-        acc.w = fmaf(y.w, leaky(x.w, slope), acc.w);
-    }
-    const float l = wave_sum((acc.x + acc.y) + (acc.z + acc.w)) + bias[0];
+    const float l = te::wave_dot<2>(a + i * K, w, K, lane, [slope](float v) { return leaky(v, slope); }) + bias[0];
     if (lane != 0) return;
     if (logit) logit[i] = l;
     if (score) {
@@ -140,8 +122,6 @@ __global__ __launch_bounds__(64) void attr_score_kernel(float* __restrict__ logi
         score[i] = s;
     }
 }
-
-inline bool aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
 }  // namespace
 
@@ -169,7 +149,7 @@ extern "C" int te_avgpool2_act_f32(float* out, const float* x, int64_t planes, i
     const int64_t outputs = planes * (H / 2) * (W / 2);
     TE_REQUIRE(planes <= ((int64_t)1 << 40) / ((int64_t)H * W) && te::cdiv(outputs, 256) <= 0x7fffffff, TE_ERR_SHAPE,
                "te_avgpool2_act_f32: %lld planes of %d x %d are more than one launch covers", (long long)planes, H, W);
-    if (W % 4 == 0 && aligned(x, 16) && aligned(out, 8)) {
+    if (W % 4 == 0 && te::aligned16(x) && ((uintptr_t)out & 7) == 0) {
         const int64_t items = outputs / 2;
         avgpool2_act_vec_kernel<<<(unsigned)te::cdiv(items, 256), 256, 0, (hipStream_t)stream>>>(out, x, items, W, slope);
     } else {
@@ -183,7 +163,7 @@ extern "C" int te_attr_score_f32(float* logit, float* score, const float* a, con
     TE_REQUIRE((logit || score) && a && w && bias, TE_ERR_NULL, "te_attr_score_f32: NULL pointer (one of logit and score may be NULL)");
     TE_REQUIRE(I >= 1 && I <= 0x7fffffff, TE_ERR_SHAPE, "te_attr_score_f32: 1 <= I < 2^31 (got %lld)", (long long)I);
     TE_REQUIRE(K >= 4 && K % 4 == 0, TE_ERR_SHAPE, "te_attr_score_f32: K must be a positive multiple of 4 (got %d)", K);
-    TE_REQUIRE(aligned(a, 16) && aligned(w, 16), TE_ERR_SHAPE, "te_attr_score_f32: a and w must be 16-byte aligned");
+    TE_REQUIRE(te::aligned16(a) && te::aligned16(w), TE_ERR_SHAPE, "te_attr_score_f32: a and w must be 16-byte aligned");
     attr_score_kernel<<<(unsigned)I, 64, 0, (hipStream_t)stream>>>(logit, score, a, w, bias, K, slope);
     return te::launch_status("te_attr_score_f32");
 }

@@ -97,8 +97,6 @@ __global__ __launch_bounds__(256) void chan_dot_kernel(float* __restrict__ out, 
     if (tid == 0) out[r] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // which kernel te_chan_scale_f32 takes and its capped grid (shared by the launch and te_chan_scale_cover); `items` are 16-byte
 // vectors on the two vector paths, elements on the scalar one
 enum ScalePath { SCALE_VEC4, SCALE_FLAT4, SCALE_SCALAR };
@@ -125,7 +123,7 @@ extern "C" int te_chan_scale_f32(float* out, const float* x, const float* s, int
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream_;
     const int64_t n = rows * hw;
-    const ScalePath path = chan_scale_path(n, hw, aligned16(out) && aligned16(x));
+    const ScalePath path = chan_scale_path(n, hw, te::aligned16(out) && te::aligned16(x));
     if (path == SCALE_VEC4) {
         const int grid = chan_scale_grid(n / 4);
         chan_scale_vec4_kernel<<<grid, 256, 0, st>>>((float4*)out, (const float4*)x, s, n / 4, (uint32_t)(hw / 4));
@@ -144,7 +142,7 @@ extern "C" int te_chan_dot_f32(float* out, const float* a, const float* b, int64
     TE_REQUIRE(out && a && b, TE_ERR_NULL, "te_chan_dot_f32: NULL pointer");
     TE_REQUIRE(rows >= 0 && hw > 0 && rows < (int64_t)0x7FFFFFFF, TE_ERR_SHAPE, "te_chan_dot_f32: bad dims");
     if (rows == 0) return 0;
-    const int vec = (hw % 4 == 0 && aligned16(a) && aligned16(b)) ? 1 : 0;
+    const int vec = (hw % 4 == 0 && te::aligned16(a) && te::aligned16(b)) ? 1 : 0;
     const int64_t blocks = hw <= 64 ? te::cdiv(rows, 4) : rows;
     chan_dot_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream_>>>(out, a, b, rows, hw, vec);
     return te::launch_status("te_chan_dot_f32");

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const ConvArgs a) {
             const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
             if (m < a.Co) {
                 float v = acc[i][e] + a.bias[m];
-                if (a.act == 1) v = v > 0.f ? v : (v != v ? v : 0.f);    // torch's relu: a NaN propagates
+                if (a.act == 1) v = te::relu_nan(v);
                 dst[(int64_t)m * HoWo] = v;
             }
         }
@@ -261,8 +261,6 @@ __global__ __launch_bounds__(256) void resize_kernel(float* __restrict__ out, co
     out[plane * OH * OW + i] = ly0 * (lx0 * ra[xa] + lx1 * ra[xb]) + ly1 * (lx0 * rb[xa] + lx1 * rb[xb]);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int BN>
 void launch_conv(const ConvArgs& a, bool al, hipStream_t st) {
     const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
@@ -297,7 +295,7 @@ extern "C" int te_conv2d_f32(float* out, const float* x, const float* w, const f
     a.Ho = Ho; a.Wo = Wo; a.Ctot = Ctot; a.c0 = c0; a.act = act; a.K = Ci * kh * kw;
     TE_REQUIRE(te::cdiv(a.P, 64) <= 0x7fffffff && te::cdiv(Co, BM) <= 65535, TE_ERR_SHAPE,
                "te_conv2d_f32: too many outputs (%lld pixels, %d channels)", (long long)a.P, Co);
-    const bool al = a.K % 4 == 0 && aligned16(w);
+    const bool al = a.K % 4 == 0 && te::aligned16(w);
     hipStream_t st = (hipStream_t)stream;
     if (te::cdiv(a.P, 128) * te::cdiv(Co, BM) >= kWideGridMin) launch_conv<128>(a, al, st);
     else launch_conv<64>(a, al, st);

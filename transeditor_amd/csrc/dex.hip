@@ -6,73 +6,30 @@
 //     te_cls_score_f32    : cls -> softmax (models.py:55-56) -> the expected age sum_c (c + 1) p_c (api.py:42-44, :56-58) or the
 //                           first class's probability (api.py:64)
 //
-// The stem is stem_fwd_kernel of csrc/lpips.hip with another input rule: one thread per output pixel, the weights in LDS, the 27
-// inputs in registers.  The head is shaped for latency, not throughput: one workgroup per row, its 16 waves split the classes, the
+// The stem is vgg_stem_kernel (vgg_stem.h) with the rule StemByteBgr on the crop's window: one thread per output pixel, the weights
+// in LDS, the 27 inputs in registers.  The head is shaped for latency, not throughput: one workgroup per row, its 16 waves split the classes, the
 // lanes of a wave stride K with 16-byte loads.  Every reduction is a fixed-shape tree (no atomics) over the row's own data, so a row's
 // result is bitwise independent of the batch it is in.
 #include "te_common.h"
 #include "byte_level.h"
+#include "vgg_stem.h"
+#include "wave_dot.h"
 
 namespace {
 
-using te::to_byte_level;                           // clamp / +1 / /2 / *255 / round in torch's bits (byte_level.h)
-
-// out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * v[n, 2 - c, y0 + y + ky - 1, x0 + x + kx - 1]), v = to_byte_level(img), for
-// (y, x) in the crop x crop window at (y0, x0); a tap outside the WINDOW is zero (the reference crops first, then nn.Conv2d pads).
-__global__ __launch_bounds__(256) void dex_stem_kernel(float* __restrict__ out, const float* __restrict__ img, const float* __restrict__ w,
-                                                       const float* __restrict__ b, int H, int W, int crop, int y0, int x0) {
-    __shared__ float ws[64 * 27];
-    __shared__ float bs[64];
-    for (int i = threadIdx.x; i < 64 * 27; i += 256) ws[i] = w[i];
-    if (threadIdx.x < 64) bs[threadIdx.x] = b[threadIdx.x];
-    __syncthreads();
-    const int n = blockIdx.y;
-    const int64_t HW = (int64_t)H * W;
-    const int CC = crop * crop;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= CC) return;
-    const int yy = p / crop, xx = p % crop;
-    float in[27];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* xc = img + ((int64_t)n * 3 + (2 - c)) * HW;             // BGR: the convolution's channel c is the image's 2 - c
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int iy = yy + ky - 1, ix = xx + kx - 1;
-                const bool ok = iy >= 0 && iy < crop && ix >= 0 && ix < crop;
-                in[c * 9 + ky * 3 + kx] = ok ? to_byte_level(xc[(int64_t)(y0 + iy) * W + (x0 + ix)]) : 0.f;
-            }
-        }
-    }
-    float* o = out + (int64_t)n * 64 * CC + p;
-    for (int m = 0; m < 64; ++m) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc = fmaf(ws[m * 27 + k], in[k], acc);
-        acc += bs[m];
-        o[(int64_t)m * CC] = acc > 0.f ? acc : (acc != acc ? acc : 0.f);      // torch's relu: a NaN propagates
-    }
-}
+// the stem's input rule: v = to_byte_level(img[n, 2 - c]), clamp / +1 / /2 / *255 / round in torch's bits (byte_level.h); the reference
+// crops first, then nn.Conv2d pads
+struct StemByteBgr {
+    static constexpr bool kWindow = true;
+    static __device__ __forceinline__ int channel(int c) { return 2 - c; }
+    static __device__ __forceinline__ float value(float v, int) { return te::to_byte_level(v); }
+};
 
 constexpr int kHeadThreads = 1024;                 // 16 waves; also the most classes (one thread per class in the softmax)
 constexpr int kHeadWaves = kHeadThreads / 64;
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// all 64 lanes end with the same value: a butterfly whose shape does not depend on the data
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
+using te::wave_max;
+using te::wave_sum;
 
 // the 16 wave values in wave order, by every thread alike.  `part` is free again when the call returns.
 template <bool MAX>
@@ -89,7 +46,7 @@ __device__ __forceinline__ float block_reduce(float v, float* part) {
 }
 
 // Row i = blockIdx.x.  Pass 1: wave `wid` owns the classes wid, wid + 16, ...; lane l takes k = 4 l, 4 l + 256, ... of a[i,:] and
-// w[c,:] as 16-byte loads into four fma chains (one per vector component), the lanes' sums meet in a butterfly, the logit goes to LDS.
+// w[c,:] (te::wave_dot, wave_dot.h), the logit goes to LDS.
 // Pass 2: thread c owns class c: the row maximum, exp(logit - max), their sum, p = e / sum, the score's weighted sum.
 __global__ __launch_bounds__(kHeadThreads) void cls_score_kernel(float* __restrict__ score, float* __restrict__ prob,
                                                                  const float* __restrict__ a, const float* __restrict__ w,
@@ -100,18 +57,7 @@ __global__ __launch_bounds__(kHeadThreads) void cls_score_kernel(float* __restri
     const int64_t i = blockIdx.x;
     const float* ai = a + i * K;
     for (int c = wid; c < C; c += kHeadWaves) {
-        const float* wc = w + (int64_t)c * K;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int k = 4 * lane; k < K; k += 256) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(ai + k);
-            const f32x4 y = *reinterpret_cast<const f32x4*>(wc + k);
-            acc.x = fmaf(x.x, y.x, acc.x);
-            acc.y = fmaf(x.y, y.y, acc.y);
-            acc.z = fmaf(x.z, y.z, acc.z);
-            acc.w = fmaf(x.w, y.w, acc.w);
-        }
-        const float s = wave_sum((acc.x + acc.y) + (acc.z + acc.w));
+        const float s = te::wave_dot<4>(ai, w + (int64_t)c * K, K, lane, [](float v) { return v; });
         if (lane == 0) logit[c] = s + bias[c];
     }
     __syncthreads();
@@ -131,8 +77,6 @@ __global__ __launch_bounds__(kHeadThreads) void cls_score_kernel(float* __restri
     }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int te_dex_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, int N, int H, int W, int crop,
@@ -143,9 +87,7 @@ extern "C" int te_dex_stem_fwd_f32(float* out, const float* img, const float* w,
                "te_dex_stem_fwd_f32: the crop (%d) must be positive and fit the %d x %d image", crop, H, W);
     TE_REQUIRE((H - crop) % 2 == 0 && (W - crop) % 2 == 0, TE_ERR_SHAPE,
                "te_dex_stem_fwd_f32: a centre crop of %d needs H - crop and W - crop even (got %d x %d)", crop, H, W);
-    const int CC = crop * crop;
-    dex_stem_kernel<<<dim3((unsigned)te::cdiv(CC, 256), N), 256, 0, (hipStream_t)stream>>>(out, img, w, b, H, W, crop, (H - crop) / 2,
-                                                                                          (W - crop) / 2);
+    te::launch_vgg_stem<StemByteBgr>(out, img, w, b, N, H, W, crop, crop, (H - crop) / 2, (W - crop) / 2, stream);
     return te::launch_status("te_dex_stem_fwd_f32");
 }
 
@@ -155,7 +97,7 @@ extern "C" int te_cls_score_f32(float* score, float* prob, const float* a, const
     TE_REQUIRE(I >= 1 && I <= 0x7fffffff, TE_ERR_SHAPE, "te_cls_score_f32: 1 <= I < 2^31 (got %lld)", (long long)I);
     TE_REQUIRE(C >= 1 && C <= kHeadThreads, TE_ERR_SHAPE, "te_cls_score_f32: 1 <= C <= %d (got %d)", kHeadThreads, C);
     TE_REQUIRE(K >= 4 && K % 4 == 0, TE_ERR_SHAPE, "te_cls_score_f32: K must be a positive multiple of 4 (got %d)", K);
-    TE_REQUIRE(aligned16(a) && aligned16(w), TE_ERR_SHAPE, "te_cls_score_f32: a and w must be 16-byte aligned");
+    TE_REQUIRE(te::aligned16(a) && te::aligned16(w), TE_ERR_SHAPE, "te_cls_score_f32: a and w must be 16-byte aligned");
     TE_REQUIRE(mode == 0 || mode == 1, TE_ERR_UNSUPPORTED, "te_cls_score_f32: mode must be 0 (expectation) or 1 (p_0), got %d", mode);
     cls_score_kernel<<<(unsigned)I, kHeadThreads, 0, (hipStream_t)stream>>>(score, prob, a, w, bias, C, K, mode);
     return te::launch_status("te_cls_score_f32");

@@ -205,7 +205,6 @@ inline int split(int64_t N, int D) {
     if (S > NS) S = NS;
     return (int)S;
 }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -222,7 +221,7 @@ extern "C" int te_fid_moments_f64(double* S, double* s, void* ws, const float* x
     const int SP = split(N, D), TD = tiles(D);
     TE_REQUIRE(SP == 1 || ws, TE_ERR_NULL, "te_fid_moments_f64: a workspace of te_fid_moments_ws_bytes(N, D) bytes is required");
     hipStream_t st = (hipStream_t)stream;
-    const bool al = D % 4 == 0 && aligned16(x);
+    const bool al = D % 4 == 0 && te::aligned16(x);
     const dim3 grid(TD, TD, SP);
     const int acc = accumulate ? 1 : 0;
     if (SP == 1) {

@@ -95,7 +95,5 @@ __device__ __forceinline__ void gemm_tile(f32x16 (&acc)[2][2], float* As, float*
 // row of accumulator register e inside a 32 x 32 tile (the column is lane & 31)
 __device__ __forceinline__ int acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace nt
 }  // namespace te

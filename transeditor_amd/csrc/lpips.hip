@@ -1,7 +1,9 @@
 // LPIPS-VGG perceptual distance (utils/lpips/networks_basic.py:21-87, pretrained_networks.py:98-136): the kernels whose shapes the
 // convolution family does not cover.  conv1_2 ... conv5_3 run on the plain 3x3 convolution (op/modconv.py planner); here:
 //
-//     stem   : ScalingLayer -> conv1_1 (3 -> 64, pad 1) -> bias -> ReLU, and its data gradient (64 -> 3, relu1_1 mask, 1/scale)
+//     stem   : ScalingLayer -> conv1_1 (3 -> 64, pad 1) -> bias -> ReLU (vgg_stem_kernel of vgg_stem.h with the rule StemScaled; with
+//              StemIdentity it is torchvision's vgg16.features[0:2], te_vgg_stem_fwd_f32) and its data gradient (64 -> 3, relu1_1
+//              mask, 1/scale)
 //     pool   : 2x2 / stride 2 max-pool forward and backward (torch's rule: first maximum in row-major order, NaN propagates)
 //     head   : normalize_tensor, squared difference, lin weights, spatial mean (per-block partials + a fixed-order sum) and the
 //              gradient with respect to the pred features
@@ -11,6 +13,7 @@
 //
 // One thread per output pixel everywhere except the paired head; every reduction is a fixed-order loop or a fixed-shape tree (no atomics).
 #include "te_common.h"
+#include "vgg_stem.h"
 
 namespace {
 
@@ -19,46 +22,19 @@ __constant__ float kShift[3] = {-.030f, -.088f, -.188f};
 __constant__ float kScale[3] = {.458f, .448f, .450f};
 constexpr float kEps = 1e-10f;   // normalize_tensor eps (utils/lpips/__init__.py:43-45)
 
-// out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * s(x)[n,c,y+ky-1,x+kx-1]); s(x) is zero outside the image (the scaling
-// happens BEFORE nn.Conv2d's zero padding).  w: [64,3,3,3] in LDS, 27 scaled inputs per thread in registers.
-// SCALED = false: s is the identity (torchvision's vgg16.features[0] on the raw input: te_vgg_stem_fwd_f32).
-template <bool SCALED>
-__global__ __launch_bounds__(256) void stem_fwd_kernel(float* __restrict__ out, const float* __restrict__ x,
-                                                       const float* __restrict__ w, const float* __restrict__ b, int H, int W) {
-    __shared__ float ws[64 * 27];
-    __shared__ float bs[64];
-    for (int i = threadIdx.x; i < 64 * 27; i += 256) ws[i] = w[i];
-    if (threadIdx.x < 64) bs[threadIdx.x] = b[threadIdx.x];
-    __syncthreads();
-    const int n = blockIdx.y;
-    const int64_t HW = (int64_t)H * W;
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
-    const int yy = (int)(p / W), xx = (int)(p % W);
-    float in[27];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* xc = x + ((int64_t)n * 3 + c) * HW;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int iy = yy + ky - 1, ix = xx + kx - 1;
-                const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-                const float v = ok ? xc[(int64_t)iy * W + ix] : 0.f;
-                in[c * 9 + ky * 3 + kx] = SCALED ? (ok ? (v - kShift[c]) / kScale[c] : 0.f) : v;
-            }
-        }
-    }
-    float* o = out + (int64_t)n * 64 * HW + p;
-    for (int m = 0; m < 64; ++m) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc = fmaf(ws[m * 27 + k], in[k], acc);
-        acc += bs[m];
-        o[(int64_t)m * HW] = acc > 0.f ? acc : (acc != acc ? acc : 0.f);
-    }
-}
+// the stem's input rules (vgg_stem.h).  StemIdentity: torchvision's vgg16.features[0] on the raw input.  StemScaled: the scaling
+// happens BEFORE nn.Conv2d's zero padding
+struct StemIdentity {
+    static constexpr bool kWindow = false;
+    static __device__ __forceinline__ int channel(int c) { return c; }
+    static __device__ __forceinline__ float value(float v, int) { return v; }
+};
+
+struct StemScaled {
+    static constexpr bool kWindow = false;
+    static __device__ __forceinline__ int channel(int c) { return c; }
+    static __device__ __forceinline__ float value(float v, int c) { return (v - kShift[c]) / kScale[c]; }
+};
 
 // gx[n,c,y,x] = (1/scale[c]) * sum_{o,ky,kx} w[o,c,ky,kx] * g[n,o,y+1-ky,x+1-kx] * (y1[n,o,...] > 0)
 __global__ __launch_bounds__(256) void stem_dgrad_kernel(float* __restrict__ gx, const float* __restrict__ g,
@@ -359,16 +335,14 @@ __global__ __launch_bounds__(64) void dist_kernel(float* __restrict__ d, DistArg
 extern "C" int te_lpips_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, te_stream_t stream) {
     TE_REQUIRE(out && x && w && b, TE_ERR_NULL, "te_lpips_stem_fwd_f32: NULL pointer");
     TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_lpips_stem_fwd_f32: bad dims");
-    const int64_t HW = (int64_t)H * W;
-    stem_fwd_kernel<true><<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, w, b, H, W);
+    te::launch_vgg_stem<StemScaled>(out, x, w, b, N, H, W, H, W, 0, 0, stream);
     return te::launch_status("te_lpips_stem_fwd_f32");
 }
 
 extern "C" int te_vgg_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, te_stream_t stream) {
     TE_REQUIRE(out && x && w && b, TE_ERR_NULL, "te_vgg_stem_fwd_f32: NULL pointer");
     TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_vgg_stem_fwd_f32: bad dims");
-    const int64_t HW = (int64_t)H * W;
-    stem_fwd_kernel<false><<<dim3((unsigned)te::cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(out, x, w, b, H, W);
+    te::launch_vgg_stem<StemIdentity>(out, x, w, b, N, H, W, H, W, 0, 0, stream);
     return te::launch_status("te_vgg_stem_fwd_f32");
 }
 

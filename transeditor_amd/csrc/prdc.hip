@@ -247,7 +247,7 @@ inline int64_t counts_bytes(int N, int M) { return up256((int64_t)split(N) * M *
 template <int KP>
 int launch_knn(float* r2, const float* x, const float* nx, int N, int D, int k, float* part, hipStream_t st) {
     const int S = split(N), grid = tiles(N) * S;
-    if (D % 4 == 0 && aligned16(x))
+    if (D % 4 == 0 && te::aligned16(x))
         prdc_knn_kernel<KP, true><<<grid, NT, 0, st>>>(part, x, nx, N, D, S);
     else
         prdc_knn_kernel<KP, false><<<grid, NT, 0, st>>>(part, x, nx, N, D, S);
@@ -298,7 +298,7 @@ extern "C" int te_prdc_counts_f32(int32_t* col_count, int32_t* row_any, float* r
     int* cc = (int*)w;
     float* pmin = (float*)(w + up256((int64_t)S * M * 4));
     int* pany = (int*)(w + up256((int64_t)S * M * 4) + up256((int64_t)CB * N * 4));
-    if (D % 4 == 0 && aligned16(x) && aligned16(y))
+    if (D % 4 == 0 && te::aligned16(x) && te::aligned16(y))
         prdc_counts_kernel<true><<<grid, NT, 0, st>>>(cc, pmin, pany, x, nx, rr2, y, ny, rf2, N, M, D, S);
     else
         prdc_counts_kernel<false><<<grid, NT, 0, st>>>(cc, pmin, pany, x, nx, rr2, y, ny, rf2, N, M, D, S);

@@ -363,7 +363,7 @@ extern "C" int te_gram_f32(float* K, const float* x, int n, int D, te_stream_t s
     TE_REQUIRE(K && x, TE_ERR_NULL, "te_gram_f32: NULL pointer");
     TE_REQUIRE(n >= 1 && n <= kMaxGramRows && D >= 1, TE_ERR_SHAPE, "te_gram_f32: 1 <= n <= %d, D >= 1 (got %d, %d)", kMaxGramRows, n, D);
     const int T = (n + BT - 1) / BT;
-    if (D % 4 == 0 && aligned16(x))
+    if (D % 4 == 0 && te::aligned16(x))
         gram_kernel<true><<<dim3(T, T), NT, 0, (hipStream_t)stream>>>(K, x, n, D);
     else
         gram_kernel<false><<<dim3(T, T), NT, 0, (hipStream_t)stream>>>(K, x, n, D);

@@ -1,4 +1,4 @@
-// Shared host-side helpers for libte_hip.so (gfx950 only; no CUDA / multi-arch paths).
+// Shared helpers for libte_hip.so: host-side, and the few device one-liners that several files use (gfx950 only; no CUDA / multi-arch paths).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +20,11 @@ inline int launch_status(const char* what) {
 }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// torch's relu: a NaN fails both comparisons and propagates
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE property: do it once per (kernel, device), safely from
 // any host thread (the autograd engine's backward threads call the ABI concurrently; setting it twice is harmless).

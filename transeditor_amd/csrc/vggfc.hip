@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void fc_reduce_kernel(float* __restrict__ c, c
     float v = ws[o];
     for (int s = 1; s < S; ++s) v += ws[(int64_t)s * IJ + o];
     v += bias[o % J];
-    if (act == 1) v = v > 0.f ? v : (v != v ? v : 0.f);      // torch's relu: a NaN propagates
+    if (act == 1) v = te::relu_nan(v);
     c[o] = v;
 }
 
@@ -163,8 +163,6 @@ __global__ __launch_bounds__(256) void adaptive_avgpool_kernel(float* __restrict
         }
     out[o] = s / (float)((y1 - y0) * (x1 - x0));
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline bool fc_dims_ok(int J, int K) { return J >= 1 && K >= 4 && K % 4 == 0; }
 
 }  // namespace
@@ -185,7 +183,7 @@ extern "C" int te_fc_stream_f32(float* c, float* ws, const float* a, const float
     TE_REQUIRE(I >= 1 && I <= kMaxRows && J >= 1, TE_ERR_SHAPE, "te_fc_stream_f32: 1 <= I <= %lld, J >= 1 (got %lld, %d)",
                (long long)kMaxRows, (long long)I, J);
     TE_REQUIRE(K >= 4 && K % 4 == 0, TE_ERR_SHAPE, "te_fc_stream_f32: K must be a positive multiple of 4 (got %d)", K);
-    TE_REQUIRE(aligned16(a) && aligned16(w), TE_ERR_SHAPE, "te_fc_stream_f32: a and w must be 16-byte aligned");
+    TE_REQUIRE(te::aligned16(a) && te::aligned16(w), TE_ERR_SHAPE, "te_fc_stream_f32: a and w must be 16-byte aligned");
     TE_REQUIRE(act == 0 || act == 1, TE_ERR_UNSUPPORTED, "te_fc_stream_f32: act must be 0 (none) or 1 (ReLU), got %d", act);
     hipStream_t st = (hipStream_t)stream;
     const Plan p = plan(J, K);

@@ -26,21 +26,20 @@ Differences from the reference, both deliberate:
     hands its own functions (BGR in [0, 255]) and only crops.
 There is no speed bar for this path; measured, the convolution trunk is nearly all of its cost (profiles/README.md, 'DEX scorer').
 """
-import argparse
-import json
 import math
 import sys
 import warnings
 
-import numpy as np
 import torch
 
 from . import _lib
-from .lpips import POOL_AFTER, VGG_CHANNELS, VGGTrunk, _load
+from .edit import fit_boundaries, scorer_main, scorer_parser  # noqa: F401  (fit_boundaries: importable from here)
+from .frozen_net import VGGTrunk, check_images, no_gpu, resolve, weight_bias
+from .lpips import VGG_CHANNELS
 
 BLOCK_CONVS = (2, 2, 3, 3, 3)                                         # models.py:30-36: vgg_block(..., more) per block
 ATTRIBUTES = {'age': (_lib.CLS_EXPECTATION, 101), 'gender': (_lib.CLS_FIRST, 2)}     # attribute -> (score mode, the real file's classes)
-_NO_GPU = 'DEXScorer needs a GPU (the network runs on the gfx950 kernels only; there is no CPU path)'
+_NO_GPU = no_gpu('DEXScorer')
 
 
 def dex_conv_keys():
@@ -48,15 +47,9 @@ def dex_conv_keys():
     return [f'conv.{blk}.conv{j}' for blk, n in enumerate(BLOCK_CONVS) for j in range(1, n + 1)]
 
 
-def _pair(sd, key, path, shape=None):
-    kw, kb = f'{key}.weight', f'{key}.bias'
-    if kw not in sd or kb not in sd:
-        raise ValueError(f'DEXScorer: {path} has no {kw} / {kb} (not a DEX state dict: conv.N.convM.*, fc1.0.*, fc2.0.*, cls.*)')
-    w, b = sd[kw], sd[kb]
-    if shape is not None and tuple(w.shape) != shape or b.ndim != 1 or b.shape[0] != w.shape[0]:
-        want = f'{shape} / {(shape[0],)}' if shape is not None else '[J,K] / [J]'
-        raise ValueError(f'DEXScorer: {kw} is {tuple(w.shape)} / bias {tuple(b.shape)}, expected {want}')
-    return w.detach().float().contiguous(), b.detach().float().contiguous()
+def _pair(sd, key, path, shape=(None, None)):
+    return weight_bias(sd, f'{key}.weight', f'{key}.bias', shape, 'DEXScorer', path,
+                       'not a DEX state dict: conv.N.convM.*, fc1.0.*, fc2.0.*, cls.*', want=None if shape[0] else '[J,K] / [J]')
 
 
 def parse_state_dict(sd, path='state_dict'):
@@ -89,52 +82,31 @@ class DEXScorer(VGGTrunk, torch.nn.Module):
         super().__init__()
         if attribute not in ATTRIBUTES:
             raise ValueError(f"DEXScorer: attribute must be 'age' or 'gender', got {attribute!r}")
-        if state_dict is None:
-            state_dict = _load(path, f'DEX {attribute}', who='DEXScorer')
-        else:
-            if path is not None:
-                raise ValueError('DEXScorer: give path or state_dict, not both')
-            if not isinstance(state_dict, dict):
-                raise ValueError(f'DEXScorer: state_dict must be a dict, got {type(state_dict).__name__}')
-            path = 'state_dict'
+        state_dict, path = resolve(path, state_dict, 'DEXScorer', f'DEX {attribute}')
         net = parse_state_dict(state_dict, path)
         self.attribute, (self.mode, real) = attribute, ATTRIBUTES[attribute]
         self.pool, self.crop, self.hidden, self.classes = net['pool'], net['crop'], net['hidden'], net['classes']
         if self.classes != real:
             warnings.warn(f"DEXScorer: attribute '{attribute}' with {self.classes} classes (the reference's {attribute} file has {real})",
                           RuntimeWarning, stacklevel=2)
-        for i, (w, b) in enumerate(net['convs']):
-            self.register_buffer(f'w{i}', w)
-            self.register_buffer(f'b{i}', b)
-        for name in ('fc1', 'fc2', 'cls'):
-            self.register_buffer(f'{name}_w', net[name][0])
-            self.register_buffer(f'{name}_b', net[name][1])
-        self._packs = {}
-        self.eval()
-        if torch.cuda.is_available():
-            self.to('cuda')
+        self._freeze(net['convs'], [(f'{name}_{t}', v) for name in ('fc1', 'fc2', 'cls') for t, v in zip('wb', net[name])])
 
     def _features(self, images, preprocessed):
         """[B,3,S,S] -> fc2's output [B,hidden[1]]; an activation is dropped once the next layer has read it"""
-        if images.ndim != 4 or images.shape[1] != 3:
-            raise ValueError(f'DEXScorer: expected [B,3,S,S] images, got {tuple(images.shape)}')
+        check_images(images, 'DEXScorer', '[B,3,S,S]', square=True)
         S = images.shape[2]
-        if images.shape[3] != S:
-            raise ValueError(f'DEXScorer: the images must be square, got {images.shape[2]}x{images.shape[3]}')
         if S < self.crop or (S - self.crop) % 2:
             raise ValueError(f'DEXScorer: the {self.crop} px centre crop needs S >= {self.crop} with S - {self.crop} even, got {S}')
         if not images.is_cuda:
             raise RuntimeError(_NO_GPU)
         x = images.detach().float()
-        if preprocessed:
-            o = (S - self.crop) // 2
-            a = _lib.vgg_stem_fwd(x[:, :, o:o + self.crop, o:o + self.crop].contiguous(), self._w(0), self.b0)
-        else:
-            a = _lib.dex_stem_fwd(x, self._w(0), self.b0, self.crop)
-        for i in range(1, 13):
-            if (i - 1) in POOL_AFTER:
-                a = _lib.maxpool2_fwd(a)
-            a = self._conv_fwd(i, a)
+        o = (S - self.crop) // 2
+
+        def stem():
+            if preprocessed:
+                return _lib.vgg_stem_fwd(x[:, :, o:o + self.crop, o:o + self.crop].contiguous(), self._w(0), self.b0)
+            return _lib.dex_stem_fwd(x, self._w(0), self.b0, self.crop)
+        a = self._walk(stem)
         a = _lib.maxpool2_fwd(a).view(a.shape[0], -1)                          # pool5 + x.view(in_size, -1)
         a = _lib.fc_stream(a, self.fc1_w, self.fc1_b, act=1)                   # fc1 (Dropout: identity)
         return _lib.fc_stream(a, self.fc2_w, self.fc2_b, act=1)                # fc2
@@ -150,72 +122,20 @@ class DEXScorer(VGGTrunk, torch.nn.Module):
         return _lib.cls_score(self._features(images, preprocessed), self.cls_w, self.cls_b, self.mode, want_prob=True)[1]
 
 
-def fit_boundaries(generator, scorer, *, n_sample, batch, ratio=0.02, split_ratio=0.7, truncation=0.7, seed=None, latent=512,
-                   para_num=16, invalid_value=None):
-    """edit_all_noinversion_ffhq.py:103-166: sample n_sample codes, score their images with `scorer` and fit one boundary in z+ and one
-    in p+ to the extreme scores (edit.sample_codes, then edit.train_boundary twice; `seed` seeds the sampling and both splits).
-    -> dict(z_boundary, p_boundary: [1, tokens * latent] float32 numpy, unit norm; z_report, p_report: train_boundary's reports;
-            scores: [n_sample, 1] on the device)"""
-    from . import edit
-    z_codes, p_codes, scores = edit.sample_codes(generator, scorer, n_sample=n_sample, batch=batch, truncation=truncation, seed=seed,
-                                                 latent=latent, para_num=para_num)
-    z_boundary, z_report = edit.train_boundary(z_codes, scores, ratio, split_ratio, invalid_value, seed)
-    p_boundary, p_report = edit.train_boundary(p_codes, scores, ratio, split_ratio, invalid_value, seed)
-    return dict(z_boundary=z_boundary, p_boundary=p_boundary, z_report=z_report, p_report=p_report, scores=scores)
-
-
 # ------------------------------------------------------------------------------------------------------------------------ CLI
 def build_parser():
-    parser = argparse.ArgumentParser(description='score sampled images with the DEX age / gender classifier and fit the z+ and p+ editing '
-                                                 'boundaries (edit_all_noinversion_ffhq.py:103-166)')
-    parser.add_argument('--ckpt', required=True, help='a generator checkpoint file')
-    parser.add_argument('--weights', required=True, help="the DEX state dict in the reference's layout (age_sd.pth / gender_sd.pth)")
+    parser = scorer_parser('score sampled images with the DEX age / gender classifier and fit the z+ and p+ editing boundaries '
+                           '(edit_all_noinversion_ffhq.py:103-166)',
+                           "the DEX state dict in the reference's layout (age_sd.pth / gender_sd.pth)")
     parser.add_argument('--attribute', choices=sorted(ATTRIBUTES), default='age')
-    parser.add_argument('--num_sample', type=int, default=10000)
-    parser.add_argument('--write_z_boundary', required=True, help='output .npy file of the z+ boundary [1,D]')
-    parser.add_argument('--write_p_boundary', required=True, help='output .npy file of the p+ boundary [1,D]')
-    parser.add_argument('--write_scores', help='output .npy file of the scores [N,1]')
-    parser.add_argument('--ratio', type=float, default=0.02, help='chosen_num_or_ratio')
-    parser.add_argument('--split_ratio', type=float, default=0.7)
-    parser.add_argument('--seed', type=int, default=None, help='seed of the sampled codes and of the train / validation splits')
-    parser.add_argument('--size', type=int, default=256)
-    parser.add_argument('--batch', type=int, default=16)
-    parser.add_argument('--truncation', type=float, default=0.7)
-    parser.add_argument('--para_num', type=int, default=16)
-    parser.add_argument('--channel_multiplier', type=int, default=2)
-    parser.add_argument('--num_trans', type=int, default=8)
     return parser
 
 
 def main(argv=None):
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    if args.size < 8 or args.size & (args.size - 1):
-        parser.error(f'--size must be a power of two >= 8, got {args.size}')
-    if args.num_sample < 1 or args.batch < 1:
-        parser.error('--num_sample and --batch must be positive')
-    if not torch.cuda.is_available():
-        raise RuntimeError(_NO_GPU)
-    from .inference import GeneratorSampler
-    from .model_spatial_query import Generator
-    from .train_step import load_checkpoint_into
-    scorer = DEXScorer(args.weights, attribute=args.attribute)
-    g = Generator(args.size, 512, 512, 2 * (int(math.log(args.size, 2)) - 1), channel_multiplier=args.channel_multiplier,
-                  n_trans=args.num_trans, pixel_norm_op_dim=1).to('cuda')
-    load_checkpoint_into(args.ckpt, g, device='cuda', g_ema_only_ok=True)
-    out = fit_boundaries(GeneratorSampler(g), scorer, n_sample=args.num_sample, batch=args.batch, ratio=args.ratio,
-                         split_ratio=args.split_ratio, truncation=args.truncation, seed=args.seed, para_num=args.para_num)
-    np.save(args.write_z_boundary, out['z_boundary'])
-    np.save(args.write_p_boundary, out['p_boundary'])
-    scores = out['scores'].cpu().numpy()
-    if args.write_scores:
-        np.save(args.write_scores, scores)
-    res = {'attribute': args.attribute, 'ckpt': args.ckpt, 'weights': args.weights, 'n': args.num_sample, 'classes': scorer.classes,
-           'crop': scorer.crop, 'score_mean': float(scores.mean()), 'score_min': float(scores.min()), 'score_max': float(scores.max()),
-           'z': out['z_report'], 'p': out['p_report'], 'wrote': [args.write_z_boundary, args.write_p_boundary] +
-           ([args.write_scores] if args.write_scores else [])}
-    print(json.dumps(res), flush=True)
-    return res
+    def make_scorer(args):
+        scorer = DEXScorer(args.weights, attribute=args.attribute)
+        return scorer, {'attribute': args.attribute}, {'classes': scorer.classes, 'crop': scorer.crop}
+    return scorer_main(build_parser(), argv, _NO_GPU, make_scorer)
 
 
 if __name__ == '__main__':

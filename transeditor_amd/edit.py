@@ -16,7 +16,7 @@ Differences from the reference, all deliberate:
   - the train / validation split is drawn from a seeded torch generator (`seed`), not from np.random's global state;
   - `score_fn` is any callable images [B,3,S,S] -> [B], and it is handed the generator's image as it is.  The DEX age / gender
     classifier is transeditor_amd.dex.DEXScorer, whose stem does the reference's conversion to BGR in [0, 255] and the centre crop
-    itself; transeditor_amd.dex.fit_boundaries goes from a generator and a scorer to the z+ and p+ boundaries;
+    itself; fit_boundaries (also transeditor_amd.dex.fit_boundaries) goes from a generator and a scorer to the z+ and p+ boundaries;
   - at most 8192 training rows (the one-workgroup solver's limit; the reference's default run needs 4200);
   - make_image does not clamp its argument in place.
 With invalid_value=None nothing synchronises with the host before the report and the boundary are read; filtering invalid scores
@@ -207,6 +207,19 @@ def sample_codes(generator, score_fn, *, n_sample, batch, truncation=0.7, seed=N
     return torch.cat(zs).contiguous(), torch.cat(ps).contiguous(), torch.cat(scores).contiguous()
 
 
+def fit_boundaries(generator, scorer, *, n_sample, batch, ratio=0.02, split_ratio=0.7, truncation=0.7, seed=None, latent=512,
+                   para_num=16, invalid_value=None):
+    """edit_all_noinversion_ffhq.py:103-166: sample n_sample codes, score their images with `scorer` and fit one boundary in z+ and one
+    in p+ to the extreme scores (sample_codes, then train_boundary twice; `seed` seeds the sampling and both splits).
+    -> dict(z_boundary, p_boundary: [1, tokens * latent] float32 numpy, unit norm; z_report, p_report: train_boundary's reports;
+            scores: [n_sample, 1] on the device)"""
+    z_codes, p_codes, scores = sample_codes(generator, scorer, n_sample=n_sample, batch=batch, truncation=truncation, seed=seed,
+                                            latent=latent, para_num=para_num)
+    z_boundary, z_report = train_boundary(z_codes, scores, ratio, split_ratio, invalid_value, seed)
+    p_boundary, p_report = train_boundary(p_codes, scores, ratio, split_ratio, invalid_value, seed)
+    return dict(z_boundary=z_boundary, p_boundary=p_boundary, z_report=z_report, p_report=p_report, scores=scores)
+
+
 def _ends(distance):
     return (-distance, distance) if isinstance(distance, (int, float)) else tuple(distance)
 
@@ -306,6 +319,65 @@ def build_parser():
     return parser
 
 
+def _generator(args):
+    """the sampler of the checkpoint args.ckpt"""
+    import math
+    from .inference import GeneratorSampler
+    from .model_spatial_query import Generator
+    from .train_step import load_checkpoint_into
+    g = Generator(args.size, 512, 512, 2 * (int(math.log(args.size, 2)) - 1), channel_multiplier=args.channel_multiplier,
+                  n_trans=args.num_trans, pixel_norm_op_dim=1).to('cuda')
+    load_checkpoint_into(args.ckpt, g, device='cuda', g_ema_only_ok=True)
+    return GeneratorSampler(g)
+
+
+def scorer_parser(description, weights_help):
+    """the command line of `python -m transeditor_amd.dex` / `.celeba_attr` (generator + scorer -> z+ and p+ boundaries) without the
+    scorer's own options"""
+    parser = argparse.ArgumentParser(description=description)
+    parser.add_argument('--ckpt', required=True, help='a generator checkpoint file')
+    parser.add_argument('--weights', required=True, help=weights_help)
+    parser.add_argument('--num_sample', type=int, default=10000)
+    parser.add_argument('--write_z_boundary', required=True, help='output .npy file of the z+ boundary [1,D]')
+    parser.add_argument('--write_p_boundary', required=True, help='output .npy file of the p+ boundary [1,D]')
+    parser.add_argument('--write_scores', help='output .npy file of the scores [N,1]')
+    parser.add_argument('--ratio', type=float, default=0.02, help='chosen_num_or_ratio')
+    parser.add_argument('--split_ratio', type=float, default=0.7)
+    parser.add_argument('--seed', type=int, default=None, help='seed of the sampled codes and of the train / validation splits')
+    parser.add_argument('--size', type=int, default=256)
+    parser.add_argument('--batch', type=int, default=16)
+    parser.add_argument('--truncation', type=float, default=0.7)
+    parser.add_argument('--para_num', type=int, default=16)
+    parser.add_argument('--channel_multiplier', type=int, default=2)
+    parser.add_argument('--num_trans', type=int, default=8)
+    return parser
+
+
+def scorer_main(parser, argv, no_gpu, make_scorer):
+    """parse, build the scorer and the generator, fit, save the arrays, print the JSON line.  make_scorer(args) -> (score_fn, the
+    report's leading fields, its fields about the scorer); `no_gpu` is the scorer's message without a GPU."""
+    args = parser.parse_args(argv)
+    if args.size < 8 or args.size & (args.size - 1):
+        parser.error(f'--size must be a power of two >= 8, got {args.size}')
+    if args.num_sample < 1 or args.batch < 1:
+        parser.error('--num_sample and --batch must be positive')
+    if not torch.cuda.is_available():
+        raise RuntimeError(no_gpu)
+    score_fn, lead, own = make_scorer(args)
+    out = fit_boundaries(_generator(args), score_fn, n_sample=args.num_sample, batch=args.batch, ratio=args.ratio,
+                         split_ratio=args.split_ratio, truncation=args.truncation, seed=args.seed, para_num=args.para_num)
+    np.save(args.write_z_boundary, out['z_boundary'])
+    np.save(args.write_p_boundary, out['p_boundary'])
+    scores = out['scores'].cpu().numpy()
+    if args.write_scores:
+        np.save(args.write_scores, scores)
+    res = {**lead, 'ckpt': args.ckpt, 'weights': args.weights, 'n': args.num_sample, **own, 'score_mean': float(scores.mean()),
+           'score_min': float(scores.min()), 'score_max': float(scores.max()), 'z': out['z_report'], 'p': out['p_report'],
+           'wrote': [args.write_z_boundary, args.write_p_boundary] + ([args.write_scores] if args.write_scores else [])}
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -318,15 +390,8 @@ def main(argv=None):
         res = {'mode': 'boundary', 'codes': args.codes, 'n': int(codes.shape[0]), 'dim': int(codes.shape[1]), 'wrote': args.write_boundary}
         res.update(report)
     else:
-        import math
-        from .inference import GeneratorSampler
-        from .model_spatial_query import Generator
-        from .train_step import load_checkpoint_into
         from .utils.sample import prepare_noise_new, prepare_param
-        g = Generator(args.size, 512, 512, 2 * (int(math.log(args.size, 2)) - 1), channel_multiplier=args.channel_multiplier,
-                      n_trans=args.num_trans, pixel_norm_op_dim=1).to('cuda')
-        load_checkpoint_into(args.ckpt, g, device='cuda', g_ema_only_ok=True)
-        sampler = GeneratorSampler(g)
+        sampler = _generator(args)
         ns = types.SimpleNamespace(latent=512, para_num=args.para_num)
         with torch.random.fork_rng(devices=['cuda'], enabled=args.seed is not None):
             if args.seed is not None:

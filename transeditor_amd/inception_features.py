@@ -25,12 +25,14 @@ import os
 import torch
 
 from . import _lib
+from .frozen_net import check_images, no_gpu, resolve, weight_bias
 
 WEIGHTS_FILE = 'pt_inception-2015-12-05-6726825d.pth'
 BN_EPS = 0.001
 FEATURE_DIM = 2048
 MIN_SIZE = 75                    # the smallest input that still reaches Mixed_7a's stride-2 layers with 3 x 3 pixels
-_NO_GPU = 'InceptionV3Features needs a GPU (the network runs on the gfx950 kernels only; there is no CPU path)'
+_NO_GPU = no_gpu('InceptionV3Features')
+_HINT = "not an Inception-v3 state dict with torchvision's keys"
 
 
 def default_inception_path():
@@ -102,48 +104,19 @@ def fold_bn(w, gamma, beta, mean, var, eps=BN_EPS):
 def inception_convs(sd, path):
     """{layer: (w' [Co,Ci,kh,kw], b' [Co])} for all of LAYERS from a state dict with torchvision's keys; `path` names it in messages.
     Every shape is checked; keys that are not in LAYERS (fc.*, num_batches_tracked, AuxLogits) are ignored."""
-    out = {}
-    for name, ci, co, k, _, _ in LAYERS:
-        kw = f'{name}.conv.weight'
-        if kw not in sd:
-            raise ValueError(f'InceptionV3Features: {path} has no {kw} (not an Inception-v3 state dict with torchvision\'s keys)')
-        w = sd[kw]
-        if tuple(w.shape) != (co, ci, *k):
-            raise ValueError(f'InceptionV3Features: {kw} is {tuple(w.shape)}, expected {(co, ci, *k)}')
-        bn = []
-        for b in _BN_KEYS:
-            kb = f'{name}.bn.{b}'
-            if kb not in sd:
-                raise ValueError(f'InceptionV3Features: {path} has no {kb} (not an Inception-v3 state dict with torchvision\'s keys)')
-            if tuple(sd[kb].shape) != (co,):
-                raise ValueError(f'InceptionV3Features: {kb} is {tuple(sd[kb].shape)}, expected {(co,)}')
-            bn.append(sd[kb])
-        out[name] = fold_bn(w, *bn)
-    return out
-
-
-def _load(path):
-    if path is None or not os.path.isfile(path):
-        raise FileNotFoundError(f'InceptionV3Features: Inception-v3 weight file not found: {path} (the pytorch-fid file {WEIGHTS_FILE}; '
-                                f'it is never downloaded from here)')
-    sd = torch.load(path, map_location='cpu')
-    if not isinstance(sd, dict):
-        raise ValueError(f'InceptionV3Features: {path} does not hold a state dict')
-    return sd
+    def get(key, shape):
+        return weight_bias(sd, key, None, shape, 'InceptionV3Features', path, _HINT)
+    return {name: fold_bn(get(f'{name}.conv.weight', (co, ci, *k)), *(get(f'{name}.bn.{b}', (co,)) for b in _BN_KEYS))
+            for name, ci, co, k, _, _ in LAYERS}
 
 
 class InceptionV3Features(torch.nn.Module):
     def __init__(self, weights_path=None, state_dict=None, resize_input=True):
         super().__init__()
-        if state_dict is None:
-            path = weights_path if weights_path is not None else default_inception_path()
-            state_dict = _load(path)
-        else:
-            if weights_path is not None:
-                raise ValueError('InceptionV3Features: give weights_path or state_dict, not both')
-            if not isinstance(state_dict, dict):
-                raise ValueError(f'InceptionV3Features: state_dict must be a dict, got {type(state_dict).__name__}')
-            path = 'state_dict'
+        if state_dict is None and weights_path is None:
+            weights_path = default_inception_path()
+        state_dict, path = resolve(weights_path, state_dict, 'InceptionV3Features', 'Inception-v3 weight', arg='weights_path', named=False,
+                                   note=f' (the pytorch-fid file {WEIGHTS_FILE}; it is never downloaded from here)')
         self.resize_input = bool(resize_input)
         self._spec = {}
         for i, (name, _, _, _, stride, pad) in enumerate(LAYERS):
@@ -222,8 +195,7 @@ class InceptionV3Features(torch.nn.Module):
     def forward(self, images):
         """[B,3,H,W] in [-1, 1] -> [B,2048] fp32 on the device.  resize_input=True: any H, W, resized to 299 x 299; False: any
         H, W >= 75.  An activation is dropped once its readers have run (no reference to it is left)."""
-        if images.ndim != 4 or images.shape[1] != 3:
-            raise ValueError(f'InceptionV3Features: expected [B,3,H,W] images, got {tuple(images.shape)}')
+        check_images(images, 'InceptionV3Features')
         if not self.resize_input and (images.shape[2] < MIN_SIZE or images.shape[3] < MIN_SIZE):
             raise ValueError(f'InceptionV3Features: without resize_input H and W must be at least {MIN_SIZE}, got '
                              f'{images.shape[2]}x{images.shape[3]}')

@@ -21,12 +21,12 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
+from .frozen_net import POOL_AFTER, VGGTrunk, check_images, load, weight_bias  # noqa: F401  (POOL_AFTER, VGGTrunk: importable from here)
 from .op import modconv
 
 VGG_CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)      # conv layers of torchvision vgg16.features[0:30]
 VGG_CHANNELS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
 TAPS = (1, 3, 6, 9, 12)          # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (pretrained_networks.py:98-136, five slices)
-POOL_AFTER = (1, 3, 6, 9)        # 2x2 max-pool between the slices (features[4, 9, 16, 23])
 LIN_CHANNELS = (64, 128, 256, 512, 512)
 
 
@@ -35,47 +35,26 @@ def default_vgg_path():
     return os.path.join(torch.hub.get_dir(), 'checkpoints', 'vgg16-397923af.pth')
 
 
-def _load(path, what, who='LPIPS'):
-    if path is None or not os.path.isfile(path):
-        raise FileNotFoundError(f'{who}: {what} file not found: {path}')
-    sd = torch.load(path, map_location='cpu')
-    if not isinstance(sd, dict):
-        raise ValueError(f'{who}: {what} file {path} does not hold a state dict')
-    return sd
-
-
 def vgg16_convs(sd, path, who='LPIPS'):
     """[(weight [Co,Ci,3,3], bias [Co])] * 13 from a torchvision vgg16 state dict (other keys ignored); `path` names it in messages"""
     out, ci = [], 3
     for idx, co in zip(VGG_CONV_INDEX, VGG_CHANNELS):
-        kw, kb = f'features.{idx}.weight', f'features.{idx}.bias'
-        if kw not in sd or kb not in sd:
-            raise ValueError(f'{who}: {path} has no {kw} / {kb} (not a torchvision vgg16 state dict)')
-        w, b = sd[kw], sd[kb]
-        if tuple(w.shape) != (co, ci, 3, 3) or tuple(b.shape) != (co,):
-            raise ValueError(f'{who}: {kw} is {tuple(w.shape)} / bias {tuple(b.shape)}, expected {(co, ci, 3, 3)} / {(co,)}')
-        out.append((w.detach().float().contiguous(), b.detach().float().contiguous()))
+        out.append(weight_bias(sd, f'features.{idx}.weight', f'features.{idx}.bias', (co, ci, 3, 3), who, path,
+                               'not a torchvision vgg16 state dict'))
         ci = co
     return out
 
 
 def load_vgg16(path):
     """vgg16_convs of the state dict in the file `path`"""
-    return vgg16_convs(_load(path, 'vgg16'), path)
+    return vgg16_convs(load(path, 'vgg16', 'LPIPS'), path)
 
 
 def load_lin(path):
     """[w [C]] * 5 from the LPIPS v0.1 head file (lin{l}.model.1.weight [1,C,1,1])"""
-    sd = _load(path, 'LPIPS lin')
-    out = []
-    for l, c in enumerate(LIN_CHANNELS):
-        k = f'lin{l}.model.1.weight'
-        if k not in sd:
-            raise ValueError(f'LPIPS: {path} has no {k} (not an LPIPS v0.1 vgg head file)')
-        if tuple(sd[k].shape) != (1, c, 1, 1):
-            raise ValueError(f'LPIPS: {k} is {tuple(sd[k].shape)}, expected {(1, c, 1, 1)}')
-        out.append(sd[k].detach().float().reshape(c).contiguous())
-    return out
+    sd = load(path, 'LPIPS lin', 'LPIPS')
+    return [weight_bias(sd, f'lin{l}.model.1.weight', None, (1, c, 1, 1), 'LPIPS', path, 'not an LPIPS v0.1 vgg head file')
+            .detach().float().reshape(c).contiguous() for l, c in enumerate(LIN_CHANNELS)]
 
 
 class TargetFeatures:
@@ -83,13 +62,6 @@ class TargetFeatures:
 
     def __init__(self, feats, shape):
         self.feats, self.shape = feats, shape
-
-
-def _relu_(y):
-    """in-place ReLU as te_bias_act_f32 (act 3 = leaky ReLU, alpha 0, scale 1)"""
-    _lib._check(_lib.lib().te_bias_act_f32(_lib._ptr(y), _lib._ptr(y), None, None, 3, 0, 0.0, 1.0, y.numel(), 1, 1, _lib._stream()),
-                'te_bias_act_f32')
-    return y
 
 
 class _Distance(Function):
@@ -120,29 +92,6 @@ class _Distance(Function):
         return _lib.lpips_stem_dgrad(g, acts[0], net._w(0)), None, None
 
 
-class VGGTrunk:
-    """conv1_2 ... conv5_3 of a frozen vgg16 on the project's 3x3 convolution: shared by PerceptualLoss and
-    vgg_features.VGG16Features.  The module keeps conv i's weight / bias as the buffers w{i} / b{i} and a dict `_packs`."""
-
-    def _w(self, i):
-        return getattr(self, f'w{i}')
-
-    def _packed(self, i, pack_kind):
-        """packed layout of conv i (the trunk is frozen: kept as long as the buffer's version and address are unchanged)"""
-        w = self._w(i)
-        key = (i, pack_kind)
-        ent = self._packs.get(key)
-        if ent is None or ent[0] != (w._version, w.data_ptr()):
-            ent = self._packs[key] = ((w._version, w.data_ptr()), _lib.conv_pack(w, pack_kind))
-        return ent[1]
-
-    def _conv_fwd(self, i, x):
-        w = self._w(i)
-        B, _, H, W = x.shape
-        pk, ck = modconv.fwd_kinds('3x3', B, w, H, W)
-        return _relu_(_lib.conv(x, self._packed(i, pk), ck, w.shape[0], H, W, bias=getattr(self, f'b{i}')))
-
-
 class PerceptualLoss(VGGTrunk, torch.nn.Module):
     def __init__(self, model='net-lin', net='vgg', colorspace='rgb', spatial=False, use_gpu=True, gpu_ids=[0], vgg_path=None,
                  lin_path=None):
@@ -158,14 +107,7 @@ class PerceptualLoss(VGGTrunk, torch.nn.Module):
         self.model, self.net, self.colorspace, self.spatial = model, net, colorspace, spatial   # (colorspace: unused by net-lin)
         vgg = load_vgg16(vgg_path if vgg_path is not None else default_vgg_path())
         lin = load_lin(lin_path)
-        for i, (w, b) in enumerate(vgg):
-            self.register_buffer(f'w{i}', w)
-            self.register_buffer(f'b{i}', b)
-        for l, w in enumerate(lin):
-            self.register_buffer(f'lin{l}', w)
-        self._packs = {}
-        if use_gpu and torch.cuda.is_available():
-            self.to(f'cuda:{gpu_ids[0]}')
+        self._freeze(vgg, [(f'lin{l}', w) for l, w in enumerate(lin)], device=f'cuda:{gpu_ids[0]}' if use_gpu else None, evaluate=False)
 
     def _lin(self, l):
         return getattr(self, f'lin{l}')
@@ -176,18 +118,17 @@ class PerceptualLoss(VGGTrunk, torch.nn.Module):
         pk, ck = modconv.bwd_kinds('3x3', B, w, H, W)
         return _lib.conv(g, self._packed(i, pk), ck, w.shape[1], H, W)
 
-    def _trunk(self, x):
-        """the 13 ReLU outputs of vgg16.features[0:30] for x in [-1, 1]"""
-        if x.ndim != 4 or x.shape[1] != 3:
-            raise ValueError(f'PerceptualLoss: expected [N,3,H,W] images, got {tuple(x.shape)}')
+    def _stem(self, x, who='PerceptualLoss', dims='[N,3,H,W]', pairs=False):
+        """relu1_1 of x in [-1, 1], after the input checks"""
+        check_images(x, who, dims, pairs=pairs)
         if x.shape[2] % 16 or x.shape[3] % 16:
             raise ValueError(f'PerceptualLoss: H and W must be multiples of 16, got {x.shape[2]}x{x.shape[3]}')
-        acts = [_lib.lpips_stem_fwd(x, self._w(0), self.b0)]
-        for i in range(1, 13):
-            a = acts[-1]
-            if (i - 1) in POOL_AFTER:
-                a = _lib.maxpool2_fwd(a)
-            acts.append(self._conv_fwd(i, a))
+        return _lib.lpips_stem_fwd(x, self._w(0), self.b0)
+
+    def _trunk(self, x):
+        """the 13 ReLU outputs of vgg16.features[0:30] for x in [-1, 1]"""
+        acts = []
+        self._walk(lambda: self._stem(x), lambda i, a: acts.append(a))
         return acts
 
     @torch.no_grad()
@@ -205,21 +146,15 @@ class PerceptualLoss(VGGTrunk, torch.nn.Module):
         Forward only.  The trunk runs once over the interleaved batch; an activation is dropped once its tap's head and the next
         layer have read it; the heads normalise both sides themselves (te_lpips_pair_head_fwd_f32), so no normalised features are
         stored."""
-        if images.ndim != 4 or images.shape[1] != 3 or images.shape[0] % 2:
-            raise ValueError(f'PerceptualLoss.pair_distance: expected [2N,3,H,W] images, got {tuple(images.shape)}')
-        if images.shape[2] % 16 or images.shape[3] % 16:
-            raise ValueError(f'PerceptualLoss: H and W must be multiples of 16, got {images.shape[2]}x{images.shape[3]}')
         if normalize:
             images = 2 * images - 1
-        a = _lib.lpips_stem_fwd(images.detach(), self._w(0), self.b0)
         partials, hws = [], []
-        for i in range(1, 13):
-            if (i - 1) in POOL_AFTER:
-                a = _lib.maxpool2_fwd(a)
-            a = self._conv_fwd(i, a)
+
+        def head(i, a):
             if i in TAPS:
                 partials.append(_lib.lpips_pair_head_fwd(a, self._lin(TAPS.index(i))))
                 hws.append(a.shape[2] * a.shape[3])
+        self._walk(lambda: self._stem(images.detach(), 'PerceptualLoss.pair_distance', '[2N,3,H,W]', pairs=True), head)
         return _lib.lpips_dist(partials, hws)
 
     def forward(self, pred, target, normalize=False):

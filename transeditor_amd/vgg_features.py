@@ -20,65 +20,37 @@ kernels exist so that the extractor exists, not to make the metric faster.  Meas
 import torch
 
 from . import _lib
-from .lpips import POOL_AFTER, VGGTrunk, _load, default_vgg_path, vgg16_convs
+from .frozen_net import VGGTrunk, check_images, no_gpu, resolve, weight_bias
+from .lpips import default_vgg_path, vgg16_convs
 
 FC_SHAPES = ((0, 4096, 512 * 7 * 7), (3, 4096, 4096))        # (index in vgg16.classifier, out features, in features): fc6, fc7
 
 
 def vgg16_classifier(sd, path):
     """[(weight [J,K], bias [J])] for fc6 and fc7 from a torchvision vgg16 state dict (classifier.6.* ignored)"""
-    out = []
-    for idx, j, k in FC_SHAPES:
-        kw, kb = f'classifier.{idx}.weight', f'classifier.{idx}.bias'
-        if kw not in sd or kb not in sd:
-            raise ValueError(f'VGG16Features: {path} has no {kw} / {kb} (not a full torchvision vgg16 state dict)')
-        w, b = sd[kw], sd[kb]
-        if tuple(w.shape) != (j, k) or tuple(b.shape) != (j,):
-            raise ValueError(f'VGG16Features: {kw} is {tuple(w.shape)} / bias {tuple(b.shape)}, expected {(j, k)} / {(j,)}')
-        out.append((w.detach().float().contiguous(), b.detach().float().contiguous()))
-    return out
+    return [weight_bias(sd, f'classifier.{idx}.weight', f'classifier.{idx}.bias', (j, k), 'VGG16Features', path,
+                        'not a full torchvision vgg16 state dict') for idx, j, k in FC_SHAPES]
 
 
 class VGG16Features(VGGTrunk, torch.nn.Module):
     def __init__(self, vgg_path=None, state_dict=None):
         super().__init__()
-        if state_dict is None:
-            path = vgg_path if vgg_path is not None else default_vgg_path()
-            state_dict = _load(path, 'vgg16', who='VGG16Features')
-        else:
-            if vgg_path is not None:
-                raise ValueError('VGG16Features: give vgg_path or state_dict, not both')
-            if not isinstance(state_dict, dict):
-                raise ValueError(f'VGG16Features: state_dict must be a dict, got {type(state_dict).__name__}')
-            path = 'state_dict'
-        convs = vgg16_convs(state_dict, path, who='VGG16Features')
-        fcs = vgg16_classifier(state_dict, path)
-        for i, (w, b) in enumerate(convs):
-            self.register_buffer(f'w{i}', w)
-            self.register_buffer(f'b{i}', b)
-        for n, (w, b) in zip((6, 7), fcs):
-            self.register_buffer(f'fc{n}_w', w)
-            self.register_buffer(f'fc{n}_b', b)
-        self._packs = {}
-        self.eval()
-        if torch.cuda.is_available():
-            self.to('cuda')
+        if state_dict is None and vgg_path is None:
+            vgg_path = default_vgg_path()
+        state_dict, path = resolve(vgg_path, state_dict, 'VGG16Features', 'vgg16', arg='vgg_path')
+        convs, fcs = vgg16_convs(state_dict, path, who='VGG16Features'), vgg16_classifier(state_dict, path)
+        self._freeze(convs, [(f'fc{n}_{t}', v) for n, wb in zip((6, 7), fcs) for t, v in zip('wb', wb)])
 
     @torch.no_grad()
     def forward(self, images):
         """[B,3,H,W] in [-1, 1] -> [B,4096] fp32 on the device; H and W multiples of 32.  An activation is dropped once the next layer
         has read it."""
-        if images.ndim != 4 or images.shape[1] != 3:
-            raise ValueError(f'VGG16Features: expected [B,3,H,W] images, got {tuple(images.shape)}')
+        check_images(images, 'VGG16Features')
         if images.shape[2] % 32 or images.shape[3] % 32 or images.shape[2] < 32 or images.shape[3] < 32:
             raise ValueError(f'VGG16Features: H and W must be multiples of 32, got {images.shape[2]}x{images.shape[3]}')
         if not images.is_cuda:
-            raise RuntimeError('VGG16Features needs a GPU (the network runs on the gfx950 kernels only; there is no CPU path)')
-        a = _lib.vgg_stem_fwd(images.detach().float(), self._w(0), self.b0)
-        for i in range(1, 13):
-            if (i - 1) in POOL_AFTER:
-                a = _lib.maxpool2_fwd(a)
-            a = self._conv_fwd(i, a)
+            raise RuntimeError(no_gpu('VGG16Features'))
+        a = self._walk(lambda: _lib.vgg_stem_fwd(images.detach().float(), self._w(0), self.b0))
         a = _lib.maxpool2_fwd(a)                                               # features[30]
         a = _lib.adaptive_avgpool(a, 7, 7).view(a.shape[0], -1)                # avgpool + flatten
         a = _lib.fc_stream(a, self.fc6_w, self.fc6_b, act=1)                   # classifier[0:3] (Dropout: identity)
