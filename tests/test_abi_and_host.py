@@ -186,7 +186,8 @@ def test_modconv_host_argument_logic():
         M.modconv(x, w, isc=torch.ones(1, 8), osc=torch.ones(1, 8), demod_eps=1e-8)
     with pytest.raises(RuntimeError, match='demod_eps'):
         M.modconv(x, w, demod_eps=1e-8)                                       # demodulation without a style scale
-    assert M._bwd_pack_kind('up') == M._bwd_pack_kind('down') != M._bwd_pack_kind('3x3')
+    dgrad_pack = lambda op: M._PACK[M._ROUTES[M._ADJOINT[op]][0]][True]      # (layout the fp32 data gradient of `op` reads)
+    assert dgrad_pack('up') == dgrad_pack('down') != dgrad_pack('3x3')
     with M.second_order(), M.no_weight_grads():
         assert M._STATE == {'second_order': True, 'skip_w': True}
     assert M._STATE == {'second_order': False, 'skip_w': False}
@@ -365,6 +366,69 @@ def test_packed_weight_cache_refresh_logic(monkeypatch):
         assert calls['single'] == 5
         mc.packed(p2[1], 0, 1.0)                                  # the dropped entry is repacked at its next use
         assert calls['single'] == 6 and len(cache) == 4
+
+
+def test_forward_plans_and_packs_once(monkeypatch, libpath):
+    """host logic of op/modconv.packed_route / _fwd_raw with the launches replaced by recording fakes, on two shapes that take a split
+    kernel on both sides (tests/conv_routes.py: '3x3_w6_both', 'down_s2s6_t2s6'): (a) a forward that will meet a data gradient packs
+    both layouts in ONE launch and keeps (data-gradient layout, its kind), which _dgrad_raw(wp=...) launches even after the switches
+    moved; (b) a no-grad forward on a parameter inside an open packed_weights_cache packs the data-gradient layout ahead; (c) any other
+    forward packs the forward layout alone; (d) every launch runs the kind the selector names"""
+    import conv_routes as cr
+    from transeditor_amd import _lib
+    from transeditor_amd.op import modconv as mc
+    log = []
+
+    def conv_pack(w, kind, wscale=1.0):
+        log.append(('pack', kind))
+        return torch.full((1,), float(kind))
+
+    def conv_pack2(w, ka, kb, wscale=1.0):
+        log.append(('pack2', ka, kb))
+        return torch.full((1,), float(ka)), torch.full((1,), float(kb))
+
+    def conv(x, wp, kind, M, H, W, *a, **k):
+        log.append(('conv', kind, int(wp[0])))
+        return torch.empty(_lib.conv_out_shape(kind, x.shape[0], M, H, W))
+    monkeypatch.setattr(_lib, 'conv_pack', conv_pack)
+    monkeypatch.setattr(_lib, 'conv_pack2', conv_pack2)
+    monkeypatch.setattr(_lib, 'conv', conv)
+    for op, (B, K, M, H, W) in (('3x3', (1, 64, 64, 8, 32)), ('down', (1, 64, 64, 8, 16))):
+        w = torch.nn.Parameter(torch.empty(M, K, 3, 3))
+        x = torch.empty(B, K, H, W) if op == '3x3' else torch.empty(B, K, 2 * H + 1, 2 * W + 1)
+        (pf, cf), (pb, cb) = mc.fwd_kinds(op, B, w, H, W), mc.bwd_kinds(op, B, w, H, W)
+        assert (cr.PACK_NAMES[pf], cr.CONV_NAMES[cf]) == cr.BY_NAME['3x3_w6_both' if op == '3x3' else 'down_s2s6_t2s6'].fwd
+        assert cf != cb or pf != pb
+        # (a), through the helper and through _fwd_raw
+        del log[:]
+        wp, ck, (wpb, ckb) = mc.packed_route(op, B, w, H, W, 0.5, True)
+        assert log == [('pack2', pf, pb)] and (int(wp[0]), ck, int(wpb[0]), ckb) == (pf, cf, pb, cb)
+        del log[:]
+        y, kept = mc._fwd_raw(x, w, op, wscale=0.5, with_bwd_pack=True)
+        assert log == [('pack2', pf, pb), ('conv', cf, pf)] and (int(kept[0][0]), kept[1]) == (pb, cb)          # (d)
+        del log[:]
+        with cr.switches(split_bf16=False):                      # the kind decided at forward time is the one launched
+            assert mc.bwd_kinds(op, B, w, H, W) != (pb, cb)
+            mc._dgrad_raw(y, w, op, wscale=0.5, wp=kept)
+        assert log == [('conv', cb, pb)]
+        del log[:]
+        mc._dgrad_raw(y, w, op, wscale=0.5)                       # (without a kept pair: planned and packed now)
+        assert log == [('pack', pb), ('conv', cb, pb)]
+        # (b)
+        del log[:]
+        cache = {}
+        with mc.packed_weights_cache(cache), torch.no_grad():
+            mc._fwd_raw(x, w, op, wscale=0.5)
+        assert log == [('pack2', pf, pb), ('conv', cf, pf)] and sorted(k[2] for k in cache) == sorted((pf, pb))
+        # (c): no cache open; a cache open but a forward that records; the helper asked for one layout
+        del log[:]
+        with torch.no_grad():
+            mc._fwd_raw(x, w, op, wscale=0.5)
+        with mc.packed_weights_cache({}):
+            mc._fwd_raw(x, w, op, wscale=0.5)
+        assert log == [('pack', pf), ('conv', cf, pf)] * 2
+        del log[:]
+        assert mc.packed_route(op, B, w, H, W, 0.5, False)[1:] == (cf, None) and log == [('pack', pf)]
 
 
 def test_convolution_form_selection_is_a_pure_function_of_the_shape(libpath):

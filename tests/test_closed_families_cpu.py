@@ -114,7 +114,7 @@ from transeditor_amd.op import chanscale, modconv
 
 
 def _conv_ref(x, w, kind):
-    """the four kinds as stock framework convolutions (op/modconv.py::_KIND; 'up' = transposed stride 2 -> 2H+1, 'down' = stride 2)"""
+    """the four kinds as stock framework convolutions (the fp32 kinds of op/modconv.py::_ROUTES; 'up' = transposed stride 2 -> 2H+1, 'down' = stride 2)"""
     if kind == '3x3':
         return F.conv2d(x, w, padding=1)
     if kind == '1x1':

@@ -279,12 +279,9 @@ def _modconv_frozen(x, w, isc, osc, bias, act, kind, wscale, demod_eps):
     ent = _frozen_entry(w, kind, wscale, demod_eps is not None, pk)
     if demod_eps is not None:
         osc = _lib.demod_from_wsq(ent['wsq'], isc, demod_eps)
-    if kind == '1x1' and osc is None and not act and _lib.rgb_supported(w.shape[0], w.shape[1], x.shape[2] * x.shape[3]):
+    if _rgb_ok(kind, w.shape[0], w.shape[1], x, osc, act):
         return _lib.rgb_fwd(x, w.reshape(w.shape[0], w.shape[1]), isc, bias, wscale)
     return _lib.conv(x, ent['wp'], ck, w.shape[0], H, W, isc, osc, bias, _act_code(act))
-
-
-_KIND = {'3x3': _lib.CONV_3X3, '1x1': _lib.CONV_1X1, 'up': _lib.CONV_T2, 'down': _lib.CONV_S2}
 
 
 _SQRT2 = 2 ** 0.5
@@ -316,83 +313,92 @@ def _lowres_hw(kind, is_output, t):
     return H, W
 
 
-def _bwd_pack_kind(kind):
-    return _lib.PACK_SWAP if kind in ('up', 'down') else _lib.PACK_DGRAD
-
-
-# 3x3 / stride 1 launches that the 1-D Winograd F(2,3) kernel covers (csrc/wino.hip: >= 32x32 images, K % 8 == 0, M % 128 == 0 - the
-# launches that carry the FLOPs of both networks) use it: same result to fp32 round-off, 2/3 of the MFMAs.  A forward that packs the
-# data-gradient layout ahead also keeps the convolution kind it was packed for, and the backward launches that kind: the module flags
-# below may change in between without a layout reaching a kernel that reads another.
-USE_WINOGRAD = True      # False: the direct kernel everywhere (A/B measurements)
-# the Winograd form on the bf16 matrix pipe (TE_CONV_3X3W6: three-piece split, fp32-equivalent results) where it applies;
-# TE_SPLIT_BF16=0 (or False here): fp32 matrix instructions everywhere (A/B measurements)
+# Which kernel a convolution runs on, and which packed weight layout that kernel reads: decided by conv_route below from these tables
+# and nowhere else.  The module switches are for A/B measurements; they are named in _ROUTES and read when a route is asked for, so an
+# assignment at run time (tests, tools, the benchmark) takes effect at the next launch.
+USE_WINOGRAD = True      # False: the direct 3x3 kernel everywhere
+# TE_SPLIT_BF16=0 (or False here; written through set_split_bf16): fp32 matrix instructions everywhere.  The three below keep one family
+# of launches on them while the others keep the split-bf16 form (TE_SPLIT_S2 / _T2 / _1X1 = 0)
 USE_SPLIT_BF16 = os.environ.get('TE_SPLIT_BF16', '1') != '0'
+USE_SPLIT_S2 = os.environ.get('TE_SPLIT_S2', '1') != '0'
+USE_SPLIT_T2 = os.environ.get('TE_SPLIT_T2', '1') != '0'
+USE_SPLIT_1X1 = os.environ.get('TE_SPLIT_1X1', '1') != '0'
+
+# op -> (the fp32 kind, which covers every shape; the kinds preferred to it, best first: (switches that must all be on, the library's
+# host predicate (B, K = input channels, M = output channels, H, W = low-resolution size), kind)).  'plain1x1' is the 1x1 product
+# without scales, bias or activation, at most a residual: the skip branch of the discriminator's ResBlocks (op/resblock.py).
+_ROUTES = {
+    # 1-D Winograd F(2,3) (csrc/wino.hip: 2/3 of the MFMAs, same result to fp32 round-off), on the bf16 matrix pipe where the
+    # three-piece split form covers the shape (csrc/wino6.hip: fp32-equivalent results)
+    '3x3': (_lib.CONV_3X3, ((('USE_WINOGRAD', 'USE_SPLIT_BF16'), _lib.wino6_ok, _lib.CONV_3X3W6),
+                            (('USE_WINOGRAD',), _lib.wino_ok, _lib.CONV_3X3W))),
+    'down': (_lib.CONV_S2, ((('USE_SPLIT_BF16', 'USE_SPLIT_S2'), _lib.s2s6_ok, _lib.CONV_S2S6),)),          # csrc/s2s6.hip
+    'up': (_lib.CONV_T2, ((('USE_SPLIT_BF16', 'USE_SPLIT_T2'), _lib.t2s6_ok, _lib.CONV_T2S6),)),            # csrc/t2s6.hip
+    '1x1': (_lib.CONV_1X1, ()),
+    'plain1x1': (_lib.CONV_1X1, ((('USE_SPLIT_BF16', 'USE_SPLIT_1X1'), _lib.p1s6_ok, _lib.CONV_1X1S6),)),   # csrc/p1s6.hip
+}
+# the data gradient of an op is the forward of its adjoint from Co to Ci channels: strided <-> transposed, the others their own
+_ADJOINT = {'3x3': '3x3', 'down': 'up', 'up': 'down', '1x1': '1x1', 'plain1x1': 'plain1x1'}
+# kind launched -> weight layout it reads (as a forward, as a data gradient)
+_PACK = {
+    _lib.CONV_3X3: (_lib.PACK_FWD, _lib.PACK_DGRAD), _lib.CONV_1X1: (_lib.PACK_FWD, _lib.PACK_DGRAD),
+    _lib.CONV_T2: (_lib.PACK_FWD, _lib.PACK_SWAP), _lib.CONV_S2: (_lib.PACK_FWD, _lib.PACK_SWAP),
+    _lib.CONV_3X3W: (_lib.PACK_WFWD, _lib.PACK_WDGRAD), _lib.CONV_3X3W6: (_lib.PACK_W6FWD, _lib.PACK_W6DGRAD),
+    _lib.CONV_S2S6: (_lib.PACK_S6FWD, _lib.PACK_S6SWAP), _lib.CONV_T2S6: (_lib.PACK_T6FWD, _lib.PACK_T6SWAP),
+    _lib.CONV_1X1S6: (_lib.PACK_P6FWD, _lib.PACK_P6DGRAD),
+}
+
+
+def conv_route(op, B, K, M, H, W, dgrad=False):
+    """(weight pack kind, convolution kind code) of the launch that computes `op` from K to M channels, or with dgrad its data gradient
+    (back from M to K channels); H, W = low-resolution size.  The first alternative whose switches are on and whose predicate holds."""
+    if dgrad:
+        op, K, M = _ADJOINT[op], M, K
+    ck, preferred = _ROUTES[op]
+    switch = globals().__getitem__
+    for names, covers, kind in preferred:
+        if all(map(switch, names)) and covers(B, K, M, H, W):
+            ck = kind
+            break
+    return _PACK[ck][bool(dgrad)], ck
 
 
 def fwd_kinds(kind, B, w, H, W):
     """(weight pack kind, convolution kind code) of the forward launch; H, W = low-resolution size"""
-    if kind == '3x3' and USE_WINOGRAD:
-        if USE_SPLIT_BF16 and _lib.wino6_ok(B, w.shape[1], w.shape[0], H, W):
-            return _lib.PACK_W6FWD, _lib.CONV_3X3W6
-        if _lib.wino_ok(B, w.shape[1], w.shape[0], H, W):
-            return _lib.PACK_WFWD, _lib.CONV_3X3W
-    if kind == 'down' and USE_SPLIT_BF16 and USE_SPLIT_S2 and _lib.s2s6_ok(B, w.shape[1], w.shape[0], H, W):
-        return _lib.PACK_S6FWD, _lib.CONV_S2S6          # the stride-2 convolution on the bf16 matrix pipe (csrc/s2s6.hip)
-    if kind == 'up' and USE_SPLIT_BF16 and USE_SPLIT_T2 and _lib.t2s6_ok(B, w.shape[1], w.shape[0], H, W):
-        return _lib.PACK_T6FWD, _lib.CONV_T2S6          # the transposed stride-2 convolution likewise (csrc/t2s6.hip)
-    return _lib.PACK_FWD, _KIND[kind]
-
-
-# TE_SPLIT_1X1=0: the 1x1 launches stay on the fp32 matrix instructions (A/B)
-USE_SPLIT_1X1 = os.environ.get('TE_SPLIT_1X1', '1') != '0'
-
-
-def plain_1x1_kinds(B, w, H, W, dgrad=False):
-    """(pack kind, convolution kind) of a PLAIN 1x1 product - no scales, bias or activation, at most a residual: the skip branch of the
-    discriminator's ResBlocks (op/resblock.py) - forward (Ci -> Co) or data gradient (Co -> Ci): the split-bf16 kernel of csrc/p1s6.hip
-    (round 6) where it applies, the fp32 kernel elsewhere"""
-    K, M = (w.shape[0], w.shape[1]) if dgrad else (w.shape[1], w.shape[0])
-    if USE_SPLIT_BF16 and USE_SPLIT_1X1 and _lib.p1s6_ok(B, K, M, H, W):
-        return (_lib.PACK_P6DGRAD if dgrad else _lib.PACK_P6FWD), _lib.CONV_1X1S6
-    return (_lib.PACK_DGRAD if dgrad else _lib.PACK_FWD), _lib.CONV_1X1
-
-
-# TE_SPLIT_S2=0: the stride-2 launches stay on the fp32 matrix instructions while the 3x3 stride-1 ones keep the split form (A/B)
-USE_SPLIT_S2 = os.environ.get('TE_SPLIT_S2', '1') != '0'
-USE_SPLIT_T2 = os.environ.get('TE_SPLIT_T2', '1') != '0'
+    return conv_route(kind, B, w.shape[1], w.shape[0], H, W)
 
 
 def bwd_kinds(kind, B, w, H, W):
     """the same for the data gradient (a convolution from Co to Ci channels)"""
-    if kind == '3x3' and USE_WINOGRAD:
-        if USE_SPLIT_BF16 and _lib.wino6_ok(B, w.shape[0], w.shape[1], H, W):
-            return _lib.PACK_W6DGRAD, _lib.CONV_3X3W6
-        if _lib.wino_ok(B, w.shape[0], w.shape[1], H, W):
-            return _lib.PACK_WDGRAD, _lib.CONV_3X3W
-    if kind == 'up' and USE_SPLIT_BF16 and USE_SPLIT_S2 and _lib.s2s6_ok(B, w.shape[0], w.shape[1], H, W):
-        return _lib.PACK_S6SWAP, _lib.CONV_S2S6         # adjoint of the transposed kind = the strided one, from Co to Ci channels
-    if kind == 'down' and USE_SPLIT_BF16 and USE_SPLIT_T2 and _lib.t2s6_ok(B, w.shape[0], w.shape[1], H, W):
-        return _lib.PACK_T6SWAP, _lib.CONV_T2S6         # adjoint of the strided kind = the transposed one, from Co to Ci channels
-    ck = {'up': _lib.CONV_S2, 'down': _lib.CONV_T2}.get(kind)          # adjoint of the transposed / strided kind
-    return _bwd_pack_kind(kind), (ck if ck is not None else _KIND[kind])
+    return conv_route(kind, B, w.shape[1], w.shape[0], H, W, dgrad=True)
+
+
+def plain_1x1_kinds(B, w, H, W, dgrad=False):
+    """the same for a plain 1x1 product, forward (Ci -> Co) or data gradient (Co -> Ci)"""
+    return conv_route('plain1x1', B, w.shape[1], w.shape[0], H, W, dgrad)
+
+
+def packed_route(op, B, w, H, W, wscale, both):
+    """Plan the forward of `op` with weights w and pack for it -> (packed layout, convolution kind, None).  both: a data gradient
+    will be asked for - plan it now as well and pack the two layouts in one launch; the third value is then (its packed layout, its
+    convolution kind), which _dgrad_raw(wp=...) launches later whatever the switches say by then."""
+    K, M = w.shape[1], w.shape[0]
+    pk, ck = conv_route(op, B, K, M, H, W)
+    if not both:
+        return packed(w, pk, wscale), ck, None
+    pkb, ckb = conv_route(op, B, K, M, H, W, dgrad=True)
+    wp, wpb = packed2(w, pk, pkb, wscale)
+    return wp, ck, (wpb, ckb)
 
 
 def _fwd_raw(x, w, kind, isc=None, osc=None, bias=None, act=0, wscale=1.0, with_bwd_pack=False):
-    """with_bwd_pack: also return (the data-gradient packing of w, the convolution kind it is packed for) - one launch packs both
-    layouts; _dgrad_raw(wp=...) launches that kind."""
+    """with_bwd_pack: also return (the data-gradient packing of w, the convolution kind it is packed for) for _dgrad_raw(wp=...)."""
     H, W = _lowres_hw(kind, False, x)
-    pk, ck = fwd_kinds(kind, x.shape[0], w, H, W)
-    if with_bwd_pack:
-        pkb, ckb = bwd_kinds(kind, x.shape[0], w, H, W)
-        wp, wpb = packed2(w, pk, pkb, wscale)
-        return _lib.conv(x, wp, ck, w.shape[0], H, W, isc, osc, bias, act), (wpb, ckb)
-    if _STATE.pack_cache is not None and torch.is_grad_enabled() is False:
-        # (a no-grad forward inside a training loop: the same weights meet a backward later in the iteration)
-        wp, _ = packed2(w, pk, bwd_kinds(kind, x.shape[0], w, H, W)[0], wscale)
-    else:
-        wp = packed(w, pk, wscale)
-    return _lib.conv(x, wp, ck, w.shape[0], H, W, isc, osc, bias, act)
+    # (a no-grad forward inside a training loop: the same weights meet a backward later in the iteration, so pack for it ahead)
+    ahead = _STATE.pack_cache is not None and torch.is_grad_enabled() is False
+    wp, ck, bwd = packed_route(kind, x.shape[0], w, H, W, wscale, with_bwd_pack or ahead)
+    y = _lib.conv(x, wp, ck, w.shape[0], H, W, isc, osc, bias, act)
+    return (y, bwd) if with_bwd_pack else y
 
 
 def _dgrad_raw(g, w, kind, isc=None, osc=None, wscale=1.0, wp=None):
@@ -415,7 +421,7 @@ def _wgrad_raw(g, x, kind, group=False):
         H, W = g.shape[2], g.shape[3]
         return _lib.wgrad_slabs(x, g, _lib.CONV_T2, H, W, group)
     H, W = x.shape[2], x.shape[3]
-    return _lib.wgrad_slabs(g, x, _KIND[kind], H, W, group)
+    return _lib.wgrad_slabs(g, x, _ROUTES[kind][0], H, W, group)
 
 
 def _slab_sum(slabs, kind):
@@ -552,9 +558,10 @@ class _Floor(Function):
         return g
 
 
-def _rgb_ok(w, d, x_like, kind):
-    return (kind == '1x1' and d is None and w.shape[0] == 3
-            and _lib.rgb_supported(3, w.shape[1], x_like.shape[2] * x_like.shape[3]))
+def _rgb_ok(kind, Co, Ci, x_like, osc, act=False):
+    """ToRGB - a modulated 1x1 to 3 channels (te_rgb_supported asks for them) without demodulation or activation - is HBM-bound: the
+    dedicated streaming kernels (csrc/rgb.hip) run it"""
+    return kind == '1x1' and osc is None and not act and _lib.rgb_supported(Co, Ci, x_like.shape[2] * x_like.shape[3])
 
 
 def _chan_dot(a, b):
@@ -568,7 +575,7 @@ class _MCFwd(Function):
         ctx.kind, ctx.wscale = kind, wscale
         ctx.graph = current_graph()
         keep_cache(ctx)
-        if _rgb_ok(w, d, x, kind):          # ToRGB: HBM-bound streaming kernel
+        if _rgb_ok(kind, w.shape[0], w.shape[1], x, d):
             y = _lib.rgb_fwd(x, w.reshape(3, w.shape[1]), s.contiguous(), None, wscale)
         else:
             y = _fwd_raw(x, w, kind, s.contiguous(), None if d is None else d.contiguous(), None, 0, wscale)
@@ -593,7 +600,7 @@ class _MCDgrad(Function):
     def forward(ctx, gy, w, s, d, kind, wscale):       # s (.) dgrad(d (.) gy, wscale w), shaped like the convolution's input
         ctx.kind, ctx.wscale = kind, wscale
         keep_cache(ctx)
-        if _rgb_ok(w, d, gy, kind):
+        if _rgb_ok(kind, w.shape[0], w.shape[1], gy, d):
             gx = _lib.rgb_dgrad(gy, w.reshape(3, w.shape[1]), s.contiguous(), w.shape[1], wscale)
         else:
             gx = _dgrad_raw(gy, w, kind, isc=None if d is None else d.contiguous(), osc=s.contiguous(), wscale=wscale)
@@ -620,7 +627,7 @@ class _MCWgrad(Function):
         ctx.save_for_backward(gy, x, s, d)
         Co, Ci = gy.shape[1], x.shape[1]
         gyc, xc = gy.contiguous(), x.contiguous()
-        if kind == '1x1' and d is None and Co == 3 and _lib.rgb_supported(3, Ci, x.shape[2] * x.shape[3]):
+        if _rgb_ok(kind, Co, Ci, x, d):
             slabs = _lib.rgb_wgrad_slabs(gyc, xc)
         else:
             slabs = _wgrad_raw(gyc, xc, kind)
@@ -682,9 +689,7 @@ class _ModConvFused(Function):
             w3 = w.reshape(w.shape[0], w.shape[1], -1)
             osc, wsq = _lib.demod_fwd(w3, isc, wscale, demod_eps)
             ctx.demod = (demod_eps, wsq)
-        # ToRGB (1x1 to 3 channels, no demodulation / activation) is HBM-bound: dedicated streaming kernels
-        ctx.rgb = (kind == '1x1' and osc is None and not act
-                   and _lib.rgb_supported(w.shape[0], w.shape[1], x.shape[2] * x.shape[3]))
+        ctx.rgb = _rgb_ok(kind, w.shape[0], w.shape[1], x, osc, act)
         if ctx.rgb:
             out = _lib.rgb_fwd(x, w.reshape(w.shape[0], w.shape[1]), isc, bias, wscale)
             ctx.save_for_backward(x, w, isc, osc, bias, None)

@@ -25,8 +25,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from .modconv import (_composite, _dgrad_raw, _wgrad_plain, bwd_kinds, cache_of, fwd_kinds, keep_cache, packed, packed2,
-                      plain_1x1_kinds)
+from .modconv import _act_code, _composite, _dgrad_raw, _wgrad_plain, cache_of, keep_cache, packed_route
 from .upfirdn2d import _geometry, flipped_taps, upfirdn2d
 
 _SQRT2 = math.sqrt(2.0)
@@ -62,44 +61,22 @@ class _ResBlock(Function):
         front = need_x or need[1] or need[2]                  # anything upstream of the blur wants a gradient
         H, W = x.shape[2], x.shape[3]
         # conv1 (+ its data-gradient packing when dx will be asked for).  Each data gradient's convolution kind is decided here, once,
-        # and kept with its packed weights: the backward launches it without asking the planners again (op/modconv.py)
-        pk1, ck1 = fwd_kinds('3x3', x.shape[0], w1, H, W)       # (the Winograd form where it applies: op/modconv.py)
-        if need_x:
-            pk1b, ck1b = bwd_kinds('3x3', x.shape[0], w1, H, W)
-            wp1, wp1b = packed2(w1, pk1, pk1b, s1)
-            bwd1 = (wp1b, ck1b)
-        else:
-            wp1, bwd1 = packed(w1, pk1, s1), None
+        # and kept with its packed weights (bwd1, bwd2, bwds): the backward launches it without asking for a route again (op/modconv.py)
+        wp1, ck1, bwd1 = packed_route('3x3', x.shape[0], w1, H, W, s1, need_x)
         y1 = _lib.conv(x, wp1, ck1, w1.shape[0], H, W, None, None, b1, 3)
         pm = (pad_main[0], pad_main[1], pad_main[0], pad_main[1])
         yb = _lib.upfirdn2d_raw(y1, k_main, (1, 1), (1, 1), pm)
         if yb.shape[2] % 2 == 0 or yb.shape[3] % 2 == 0:
             raise RuntimeError(f'resblock: blurred size {tuple(yb.shape[2:])} is not (2h+1)x(2w+1)')
         h, w_ = (yb.shape[2] - 1) // 2, (yb.shape[3] - 1) // 2
-        pk2, ck2 = fwd_kinds('down', x.shape[0], w2, h, w_)     # (the split-bf16 form of the strided convolution where it applies)
-        if front:
-            pk2b, ck2b = bwd_kinds('down', x.shape[0], w2, h, w_)
-            wp2, wp2b = packed2(w2, pk2, pk2b, s2)
-            bwd2 = (wp2b, ck2b)
-        else:
-            wp2, bwd2 = packed(w2, pk2, s2), None
-        act2 = 3 if abs(_SQRT2 * gain - _SQRT2) < 1e-6 else 4
-        if act2 == 4 and abs(_SQRT2 * gain - 1.0) > 1e-6:
-            raise RuntimeError(f'resblock: leaky-ReLU gain {_SQRT2 * gain} is not one the kernels fuse (sqrt(2) or 1)')
-        y2 = _lib.conv(yb, wp2, ck2, w2.shape[0], h, w_, None, None, b2, act2)
+        wp2, ck2, bwd2 = packed_route('down', x.shape[0], w2, h, w_, s2, front)
+        y2 = _lib.conv(yb, wp2, ck2, w2.shape[0], h, w_, None, None, b2, _act_code(_SQRT2 * gain))
         ps = (pad_skip[0], pad_skip[1], pad_skip[0], pad_skip[1])
         xs = _lib.upfirdn2d_raw(x, k_skip, (1, 1), (2, 2), ps)
         if xs.shape[2:] != y2.shape[2:]:
             raise RuntimeError(f'resblock: branch sizes differ {tuple(xs.shape[2:])} vs {tuple(y2.shape[2:])}')
-        # the skip branch's 1x1 product (+ the main branch as its residual) and, in backward, its data gradient: the split-bf16 kernel
-        # of csrc/p1s6.hip where it applies (round 6)
-        pks, cks = plain_1x1_kinds(x.shape[0], ws, xs.shape[2], xs.shape[3])
-        if need_x:
-            pksb, cksb = plain_1x1_kinds(x.shape[0], ws, xs.shape[2], xs.shape[3], dgrad=True)
-            wps, wpsb = packed2(ws, pks, pksb, ss * gain)
-            bwds = (wpsb, cksb)
-        else:
-            wps, bwds = packed(ws, pks, ss * gain), None
+        # the skip branch's plain 1x1 product (+ the main branch as its residual) and, in backward, its data gradient
+        wps, cks, bwds = packed_route('plain1x1', x.shape[0], ws, xs.shape[2], xs.shape[3], ss * gain, need_x)
         out = _lib.conv(xs, wps, cks, ws.shape[0], xs.shape[2], xs.shape[3], None, None, None, 0, res=y2)
         ctx.save_for_backward(x, w1, b1, w2, b2, ws, k_main, k_skip, y1, yb, y2, xs, img, w0, b0)
         ctx.packs = (bwd1, bwd2, bwds)
