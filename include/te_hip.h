@@ -830,6 +830,52 @@ int te_avgpool2_act_f32(float* out, const float* x, int64_t planes, int H, int W
 int te_attr_score_f32(float* logit, float* score, const float* a, const float* w, const float* bias, int64_t I, int K, float slope,
                       te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M7  the ResNet-18 pose classifier of attribute editing (our_interfaceGAN/ffhq_utils/dex/models.py:73-89: ClassifyModel = torchvision's
+ * resnet18 without its fc, Linear(512, 2) and a softmax; ffhq_utils/dex/api.py:61-65 estimate_gender, which runs it after eval('pose'),
+ * api.py:34-39; called from edit_all_noinversion_ffhq.py:113-131).  Every other convolution of the network (the first of each block,
+ * the 3x3 and 1x1 stride-2 ones) is M4's te_conv2d_f32, the global average is M2's te_adaptive_avgpool_f32 with OH = OW = 1, and
+ * extra_layer + softmax + [:, 0] is M5's te_cls_score_f32 mode 1; here the residual epilogue, the input end and the padded max pool.
+ * Forward only (the classifier runs under no_grad in eval mode), NCHW fp32, no atomics, no workspace.  Every BatchNorm2d (eps 1e-5,
+ * eval) is folded into its convolution's weight and bias by the caller.  Both convolutions below run te_conv2d_f32's main loop
+ * (csrc/conv2d_body.h) with the same k permutation, so their accumulators are te_conv2d_f32's bit for bit.
+ *
+ * te_conv2d_res_f32 (torchvision BasicBlock.forward as models.py:74-75 builds it: conv2 + bn2, `out += identity`, ReLU; replaces the
+ * second convolution of each of the eight blocks with its batch norm, the addition and the activation):
+ *     out[b,m,oy,ox] = act((acc + bias[m]) + res[b,m,oy,ox])        acc = sum_{c,ky,kx} w[m,c,ky,kx] * x[b, c, oy*s + ky - py, ox*s + kx - px]
+ * with two separately rounded fp32 additions in this order; act 0 none, 1 ReLU (a NaN propagates: a NaN in res reaches its own
+ * element only).  x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co]; out and res are contiguous [B,Co,Ho,Wo] (no channel slice); res may be
+ * neither out nor overlap it.  For every input the result is bitwise relu(te_conv2d_f32(act = 0) + res), and an image's outputs
+ * do not depend on the batch it is in.  Refusals are te_conv2d_f32's (s other than 1 or 2, act other than 0 or 1, a kernel above
+ * 7 x 7: TE_ERR_UNSUPPORTED; padding >= the kernel, Ho or Wo < 1, a non-positive size, sizes past 31 bits: TE_ERR_SHAPE) plus a NULL
+ * res (TE_ERR_NULL); nothing is launched on a refusal.
+ *
+ * te_pose_stem_fwd_f32 (edit_all_noinversion_ffhq.py:113-116, api.py:62 CenterCrop(224), resnet18's conv1 + bn1 + relu as models.py:75
+ * keeps them; replaces the channel flip, the clamp / add / div / mul / round chain, the centre crop and Conv2d(3, Co, 7, stride=2,
+ * padding=3, bias=False) + BatchNorm2d + ReLU): img [N,3,H,W]; w [Co,3,7,7] and b [Co] with the batch norm folded in; out [N,Co,Hc,Wc],
+ * Hc = Wc = (crop - 1) / 2 + 1.  With y0 = (H - crop) / 2, x0 = (W - crop) / 2:
+ *     preprocessed = 0: img is RGB, nominally in [-1, 1]:  v[n,c] = rint(((clamp(img[n, 2 - c], -1, 1) + 1) * 0.5) * 255), each step
+ *                       rounded to fp32, ties to even: torch's result bit for bit (the chain of te_dex_stem_fwd_f32)
+ *     preprocessed = 1: img is what the editing scripts hand over, BGR byte levels:  v[n,c] = img[n,c]
+ *     out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * v[n, c, y0 + 2y + ky - 3, x0 + 2x + kx - 3])
+ * where a tap with 2y + ky - 3 or 2x + kx - 3 outside [0, crop) is ZERO: the padding is that of the crop, image pixels outside the
+ * window are never read (as in te_dex_stem_fwd_f32).  A NaN pixel stays a NaN and reaches exactly the outputs whose 7 x 7 window
+ * holds it.  An implicit GEMM with K = 147 whose gather does the preprocessing on the way into LDS; the result is bitwise
+ * te_conv2d_f32(v of the crop, s = 2, padding 3, act 1).  TE_ERR_SHAPE, nothing launched, for crop < 1, crop > H or W, an odd H - crop
+ * or W - crop (DEX's rule), N < 1 or N >= 65536, Co < 1; another value of preprocessed is TE_ERR_UNSUPPORTED.
+ *
+ * te_maxpool3s2p1_f32 (resnet18's maxpool as models.py:75 keeps it; replaces nn.MaxPool2d(3, 2, 1)): x [planes,H,W] ->
+ * out [planes,Ho,Wo], Ho = (H - 1) / 2 + 1, Wo likewise; the window of output (y, x) is rows 2y - 1 ... 2y + 1 and columns
+ * 2x - 1 ... 2x + 1 inside the plane.  The padding never wins (a plane of -inf stays -inf); a greater value or a NaN replaces, the
+ * rule of te_maxpool2_fwd_f32, so a NaN tap gives a NaN in the outputs that see it.  planes, H, W >= 1 with H * W below 2^31 and at
+ * most 2^40 input elements, else TE_ERR_SHAPE; nothing is launched on a refusal.  One thread per output element.
+ */
+int te_conv2d_res_f32(float* out, const float* x, const float* w, const float* bias, const float* res, int B, int Ci, int Co, int H, int W,
+                      int kh, int kw, int s, int py, int px, int act, te_stream_t stream);
+int te_pose_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, int N, int H, int W, int crop, int Co,
+                         int preprocessed, te_stream_t stream);
+int te_maxpool3s2p1_f32(float* out, const float* x, int64_t planes, int H, int W, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

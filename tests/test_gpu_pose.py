@@ -1,0 +1,456 @@
+"""The pose scorer (transeditor_amd.pose, csrc/resnet.hip on the main loop of csrc/conv2d_body.h) against te_conv2d_f32, fp64 torch and the
+plain-torch restatement (tests/pose_restated.py): the residual convolution, the stem with the preprocessing and the centre crop in its
+gather, the padded max pool, the whole network on small geometries and on the true one (224 of 256 px, widths 64 ... 512, against what
+the reference's own ClassifyModel returns: tests/golden/pose_ref.npz), and the plumbing around it (fit_boundaries, score_sweeps, the
+input checks)."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import pose_restated as R
+from conftest import load_golden, rel_l2
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+EPS = 2.0 ** -24
+SENTINEL = -777.25
+SPLITS = 1                       # the main loop does not split K
+
+
+# ---------------------------------------------------------------------------------------------------------- 1. the residual convolution
+# (B, Ci, Co, H, W, kh, kw, s, py, px)
+RES_CASES = [(3, 8, 72, 7, 7, 3, 3, 1, 1, 1),           # a ragged channel block (72 = 64 + 8), 147 pixels: a tile that spans images
+             (2, 3, 64, 9, 11, 3, 3, 1, 1, 1),          # K = 27: the unaligned weight path
+             (2, 16, 40, 8, 8, 1, 1, 2, 0, 0),          # the downsample geometry
+             (1, 4, 64, 256, 256, 3, 3, 1, 1, 1)]       # 512 workgroups of 128 pixels: the wide tile (kWideGridMin)
+
+
+def _res_case(case):
+    """x, w ~ N(0, 1); biases of scale 4 sqrt(K), as test_gpu_inception_features._conv_case draws them (few pre-activations lie near
+    0); res ~ N(0, 1)"""
+    B, Ci, Co, H, W, kh, kw, s, py, px = case
+    g = torch.Generator().manual_seed(sum(p * v for p, v in zip((3, 5, 7, 11, 13, 17, 19, 23, 29, 31), case)))
+    x, w = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, kh, kw, generator=g)
+    b = torch.randn(Co, generator=g) * 4 * (Ci * kh * kw) ** 0.5
+    Ho, Wo = (H + 2 * py - kh) // s + 1, (W + 2 * px - kw) // s + 1
+    return x, w, b, torch.randn(B, Co, Ho, Wo, generator=g)
+
+
+@pytest.fixture(scope='module')
+def res_refs():
+    """per case: the inputs, the fp64 pre-activation conv + bias + res, the elementwise bound and what torch's own fp32 convolution gives
+    on the CPU.  Computed once, shared and never modified."""
+    out = {}
+    for case in RES_CASES:
+        B, Ci, Co, H, W, kh, kw, s, py, px = case
+        x, w, b, res = _res_case(case)
+        K = Ci * kh * kw
+        pre = F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=(py, px)) + res.double()
+        bound = (K + SPLITS + 3) * EPS * (F.conv2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=s, padding=(py, px))
+                                          + res.double().abs())
+        cpu32 = F.conv2d(x, w, b, stride=s, padding=(py, px)) + res
+        out[case] = dict(x=x, w=w, b=b, res=res, pre=pre, bound=bound, cpu32=cpu32, K=K)
+    return out
+
+
+@pytest.mark.parametrize('act', [0, 1])
+@pytest.mark.parametrize('case', RES_CASES, ids=lambda c: 'x'.join(map(str, c)))
+def test_conv2d_res(res_refs, case, act):
+    """Bitwise act(te_conv2d_f32(act = 0) + res), torch doing the addition and the ReLU.  Against fp64 the elementwise bound of
+    test_gpu_inception_features.py::test_conv2d_against_fp64 with one more rounding and the residual's magnitude:
+    |out - out64| <= (K + S + 3) 2^-24 (|w| * |x| + |bias| + |res|); under ReLU the elements whose fp64 pre-activation is within the bound
+    of 0 are left out, at most 1 % of them (torch's own fp32 convolution on the CPU meets the same bound on the same elements, and the
+    share left out is far below the cap)."""
+    from transeditor_amd import _lib
+    B, Ci, Co, H, W, kh, kw, s, py, px = case
+    d = res_refs[case]
+    x, w, b, res = (d[k].to(DEV) for k in ('x', 'w', 'b', 'res'))
+    out = _lib.conv2d_res(x, w, b, res, s, (py, px), act=act)
+    assert out.shape == d['pre'].shape and out.dtype == torch.float32 and out.is_contiguous()
+    plain = _lib.conv2d(x, w, b, s, (py, px), act=0) + res
+    assert torch.equal(out, torch.relu(plain) if act else plain)
+    pre, bound = d['pre'], d['bound']
+    keep = torch.ones_like(pre, dtype=torch.bool) if not act else pre.abs() > bound
+    share = 1.0 - float(keep.double().mean())
+    want = torch.relu(pre) if act else pre
+    err = (out.double().cpu() - want).abs()
+    err_cpu = ((torch.relu(d['cpu32']) if act else d['cpu32']).double() - want).abs()
+    print(f'conv2d_res {case} act={act}: K={d["K"]}, max err / bound {float((err / bound)[keep].max()):.3f} (torch fp32 on the CPU '
+          f'{float((err_cpu / bound)[keep].max()):.3f}), left out {share:.5f}')
+    assert share <= 0.01
+    assert share <= 0.001 and bool((err_cpu <= bound)[keep].all())             # the yardstick itself: far below the cap, inside the bound
+    assert bool((err <= bound)[keep].all())
+
+
+def test_conv2d_res_nan_and_batch(res_refs):
+    from transeditor_amd import _lib
+    case = RES_CASES[0]
+    d = res_refs[case]
+    x, w, b, res = (d[k].to(DEV) for k in ('x', 'w', 'b', 'res'))
+    full = _lib.conv2d_res(x, w, b, res, 1, (1, 1), act=1)
+    # the first image of a batch equals a batch of one (its 49 pixels share a tile with the second image's)
+    assert torch.equal(full[:1], _lib.conv2d_res(x[:1].contiguous(), w, b, res[:1].contiguous(), 1, (1, 1), act=1))
+    assert torch.equal(full, _lib.conv2d_res(x, w, b, res, 1, (1, 1), act=1))                 # two runs
+    # a NaN in res reaches its own element only, with and without the ReLU
+    bad = res.clone()
+    bad[1, 70, 3, 4] = float('nan')
+    for act in (0, 1):
+        got = _lib.conv2d_res(x, w, b, bad, 1, (1, 1), act=act)
+        clean = _lib.conv2d_res(x, w, b, res, 1, (1, 1), act=act)
+        hit = torch.zeros_like(got, dtype=torch.bool)
+        hit[1, 70, 3, 4] = True
+        assert torch.equal(got.isnan(), hit) and torch.equal(got[~hit], clean[~hit])
+
+
+def test_conv2d_res_refusals():
+    from transeditor_amd import _lib
+    L = _lib.lib()
+    x, w, b = torch.zeros(2, 3, 9, 9, device=DEV), torch.zeros(4, 3 * 8 * 8, device=DEV), torch.zeros(4, device=DEV)
+    res = torch.zeros(2, 4, 9, 9, device=DEV)
+    out = torch.full((2, 4, 9, 9), SENTINEL, device=DEV)
+    st = _lib._stream()
+
+    def call(o=out, xx=x, ww=w, bb=b, rr=res, B=2, Ci=3, Co=4, H=9, W=9, kh=3, kw=3, s=1, py=1, px=1, act=0):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return L.te_conv2d_res_f32(ptr(o), ptr(xx), ptr(ww), ptr(bb), ptr(rr), B, Ci, Co, H, W, kh, kw, s, py, px, act, st)
+    assert call(s=3) == -3 and call(s=0) == -3
+    assert call(kh=8, py=0) == -3 and call(kw=0) == -3
+    assert call(py=3) == -2 and call(px=3) == -2 and call(py=-1) == -2
+    assert call(H=2, kh=3, py=0) == -2 and call(W=1, kw=5, px=1) == -2                        # Ho < 1, Wo < 1
+    assert call(o=None) == -1 and call(xx=None) == -1 and call(ww=None) == -1 and call(bb=None) == -1
+    assert call(rr=None) == -1 and b'NULL' in L.te_last_error_string()                         # the residual is not optional
+    assert call(B=0) == -2 and call(Ci=0) == -2 and call(Co=0) == -2 and call(act=2) == -3
+    with pytest.raises(RuntimeError, match='stride must be 1 or 2'):
+        _lib.conv2d_res(x, w[:, :27].reshape(4, 3, 3, 3).contiguous(), b, res[:, :, :3, :3].contiguous(), 3, (1, 1))
+    with pytest.raises(RuntimeError, match='residual must be'):
+        _lib.conv2d_res(x, w[:, :27].reshape(4, 3, 3, 3).contiguous(), b, res[:, :3].contiguous(), 1, (1, 1))
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())                                                     # nothing was launched
+    assert call() == 0                                                                       # ... and the same call with valid arguments runs
+    torch.cuda.synchronize()
+    assert bool((out == 0).all())
+
+
+# ---------------------------------------------------------------------------------------------------------- 2. the stem
+# (N, H, W, crop, Co)
+STEM_CASES = [(2, 40, 40, 32, 64), (1, 50, 50, 36, 24), (3, 31, 31, 31, 16), (1, 44, 40, 30, 64)]
+#              equal offsets        ragged channels,     an odd crop, no      H != W: unequal offsets
+#                                   a ragged last tile   margin
+
+
+def _stem_weights(Co, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(Co, 3, 7, 7, generator=g) * (2.0 / 147) ** 0.5 / 128, torch.randn(Co, generator=g) * 0.05
+
+
+def _stem_input(N, H, W, crop, seed):
+    """1.5 * randn (a good half of the pixels are clamped) and, in rows 1 ... of image 0's window, the 255 values (k + 0.5) / 255 * 2 - 1
+    in all three channels: each maps to k + 0.5 up to rounding, next to a tie of the final round() (test_gpu_dex._stem_input)"""
+    x = 1.5 * torch.randn(N, 3, H, W, generator=torch.Generator().manual_seed(seed))
+    ties = ((torch.arange(255, dtype=torch.float32) + 0.5) / 255 * 2 - 1)
+    y0, x0 = (H - crop) // 2, (W - crop) // 2
+    k = torch.arange(255)
+    x[0, :, y0 + 1 + k // crop, x0 + k % crop] = ties
+    return x
+
+
+def _levels(x):
+    """the preprocessing of the whole image: what the editing scripts hand over"""
+    return torch.stack([x[:, 2], x[:, 1], x[:, 0]], 1).clamp(-1, 1).add(1).div(2).mul(255).round()
+
+
+@pytest.mark.parametrize('N,H,W,crop,Co', STEM_CASES)
+def test_stem_is_conv2d_on_the_preprocessed_crop(N, H, W, crop, Co):
+    """te_pose_stem_fwd_f32 and te_conv2d_f32 are one main loop with two gathers: the same 147-term chain on the same integers (the
+    byte-level chain is torch's own bits by construction), so the outputs are bitwise equal - from the RGB image, from the BGR levels,
+    and whatever lies outside the window."""
+    from transeditor_amd import _lib
+    w, b = (t.to(DEV) for t in _stem_weights(Co, N + crop))
+    x = _stem_input(N, H, W, crop, 3 * H + W)
+    v = R.preprocess(x, crop)
+    assert float((v == 0).float().mean()) > 0.1 and float((v == 255).float().mean()) > 0.1        # the clamp is live on both sides
+    want = _lib.conv2d(v.contiguous().to(DEV), w, b, 2, (3, 3), act=1)
+    Hc = (crop - 1) // 2 + 1
+    y = _lib.pose_stem_fwd(x.to(DEV), w, b, crop)
+    assert y.shape == (N, Co, Hc, Hc) and y.dtype == torch.float32 and y.is_contiguous()
+    assert torch.equal(y, want)
+    assert float((y > 0).float().mean()) > 0.2                                                 # (not a comparison of zeros)
+    assert torch.equal(_lib.pose_stem_fwd(_levels(x).to(DEV), w, b, crop, preprocessed=True), want)
+    # 1e30 around the window (level 255 after the clamp; 1e30 as a level) changes nothing: the padding is that of the crop
+    y0, x0 = (H - crop) // 2, (W - crop) // 2
+    far = torch.full_like(x, 1e30)
+    far[:, :, y0:y0 + crop, x0:x0 + crop] = x[:, :, y0:y0 + crop, x0:x0 + crop]
+    assert torch.equal(_lib.pose_stem_fwd(far.to(DEV), w, b, crop), want)
+    lv = torch.full_like(x, 1e30)
+    lv[:, :, y0:y0 + crop, x0:x0 + crop] = v
+    assert torch.equal(_lib.pose_stem_fwd(lv.to(DEV), w, b, crop, preprocessed=True), want)
+
+
+def test_stem_against_fp64():
+    """rel_l2 < 1e-6 against conv + ReLU of the preprocessed crop in fp64, the bar of test_gpu_dex.py::test_stem_against_fp64 (integer
+    inputs, a 147-term fp32 chain)"""
+    from transeditor_amd import _lib
+    N, H, W, crop, Co = STEM_CASES[0]
+    w, b = _stem_weights(Co, 7)
+    x = _stem_input(N, H, W, crop, 11)
+    y = _lib.pose_stem_fwd(x.to(DEV), w.to(DEV), b.to(DEV), crop)
+    ref = F.relu(F.conv2d(R.preprocess(x, crop).double(), w.double(), b.double(), stride=2, padding=3))
+    e = rel_l2(y, ref)
+    print(f'pose stem N={N} {H}x{W} crop {crop}: rel_l2 {e:.3e}')
+    assert e < 1e-6
+
+
+@pytest.mark.parametrize('preprocessed', [False, True])
+def test_stem_nan_pixel_reaches_its_windows(preprocessed):
+    from transeditor_amd import _lib
+    N, H, W, crop, Co = 1, 44, 40, 30, 64
+    w, b = (t.to(DEV) for t in _stem_weights(Co, 2))
+    x = _stem_input(N, H, W, crop, 5)
+    if preprocessed:
+        x = _levels(x)
+    clean = _lib.pose_stem_fwd(x.to(DEV), w, b, crop, preprocessed).cpu()
+    py, px = 10, 21                                                            # window position, image channel 1
+    x[0, 1, 7 + py, 5 + px] = float('nan')
+    y = _lib.pose_stem_fwd(x.to(DEV), w, b, crop, preprocessed).cpu()
+    oy, ox = torch.arange(15).view(-1, 1), torch.arange(15).view(1, -1)
+    hit = ((2 * oy - 3 <= py) & (py <= 2 * oy + 3) & (2 * ox - 3 <= px) & (px <= 2 * ox + 3)).expand(1, Co, 15, 15)
+    assert int(hit[0, 0].sum()) == 4 * 3                                       # rows 4 ... 6 (an even position: 3 windows), columns 9 ... 12
+    assert torch.equal(y.isnan(), hit)                                         # all channels: no weight is exactly 0
+    assert torch.equal(y[~hit], clean[~hit])
+
+
+def test_stem_refusals():
+    from transeditor_amd import _lib
+    L = _lib.lib()
+    w, b = (t.to(DEV) for t in _stem_weights(8, 3))
+    x = torch.zeros(1, 3, 40, 40, device=DEV)
+    out = torch.full((1, 8, 20, 20), SENTINEL, device=DEV)
+    st = _lib._stream()
+
+    def call(N, H, W, crop, Co=8, pre=0):
+        return L.te_pose_stem_fwd_f32(out.data_ptr(), x.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, crop, Co, pre, st)
+    for N, H, W, crop in [(1, 40, 40, 0), (1, 40, 40, -2), (1, 40, 40, 42), (1, 30, 40, 32), (1, 40, 30, 32), (1, 40, 40, 33), (1, 41, 40, 32),
+                          (1, 40, 41, 32), (65536, 40, 40, 32), (0, 40, 40, 32)]:
+        assert call(N, H, W, crop) == -2, (N, H, W, crop)
+    assert call(1, 40, 40, 32, Co=0) == -2 and call(1, 40, 40, 32, Co=-3) == -2
+    assert call(1, 40, 40, 32, pre=2) == -3 and call(1, 40, 40, 32, pre=-1) == -3
+    assert L.te_pose_stem_fwd_f32(out.data_ptr(), None, w.data_ptr(), b.data_ptr(), 1, 40, 40, 32, 8, 0, st) == -1
+    with pytest.raises(RuntimeError, match='even'):
+        _lib.pose_stem_fwd(x, w, b, 33)
+    torch.cuda.synchronize()
+    assert float((out - SENTINEL).abs().max()) == 0.0                          # nothing was launched
+
+
+# ---------------------------------------------------------------------------------------------------------- 3. the max pool
+POOL_PLANES = [(6, 16, 16), (5, 15, 17), (3, 1, 1), (2, 2, 3)]
+
+
+@pytest.mark.parametrize('planes,H,W', POOL_PLANES)
+def test_maxpool3s2p1(planes, H, W):
+    from transeditor_amd import _lib
+    x = torch.randn(1, planes, H, W, generator=torch.Generator().manual_seed(planes + 10 * H + W))
+    want = F.max_pool2d(x, 3, 2, 1)
+    got = _lib.maxpool3s2p1(x.to(DEV))
+    assert got.shape == (1, planes, (H - 1) // 2 + 1, (W - 1) // 2 + 1) and got.dtype == torch.float32
+    assert torch.equal(got.cpu(), want)
+    # the padding never wins: a plane of -inf stays -inf
+    xi = x.clone()
+    xi[0, planes - 1] = float('-inf')
+    gi = _lib.maxpool3s2p1(xi.to(DEV)).cpu()
+    assert bool((gi[0, planes - 1] == float('-inf')).all()) and torch.equal(gi, F.max_pool2d(xi, 3, 2, 1))
+    # a NaN tap gives a NaN in the outputs that see it, and in no other
+    xn = x.clone()
+    xn[0, 0, H // 2, W // 2] = float('nan')
+    gn, wn = _lib.maxpool3s2p1(xn.to(DEV)).cpu(), F.max_pool2d(xn, 3, 2, 1)
+    assert bool(wn.isnan().any()) and torch.equal(gn.isnan(), wn.isnan()) and torch.equal(gn[~wn.isnan()], wn[~wn.isnan()])
+
+
+def test_maxpool3s2p1_refusals():
+    from transeditor_amd import _lib
+    L = _lib.lib()
+    x = torch.zeros(2, 8, 8, device=DEV)
+    out = torch.full((2, 4, 4), SENTINEL, device=DEV)
+    st = _lib._stream()
+    assert L.te_maxpool3s2p1_f32(out.data_ptr(), None, 2, 8, 8, st) == -1 and L.te_maxpool3s2p1_f32(None, x.data_ptr(), 2, 8, 8, st) == -1
+    for planes, H, W in [(0, 8, 8), (-1, 8, 8), (2, 0, 8), (2, 8, 0), (2, 65536, 65536)]:
+        assert L.te_maxpool3s2p1_f32(out.data_ptr(), x.data_ptr(), planes, H, W, st) == -2, (planes, H, W)
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())                                       # nothing was launched
+
+
+# ---------------------------------------------------------------------------------------------------------- 4. end to end, small
+E2E_CASES = [(80, 64, (16, 32, 64, 128), 5), (70, 62, (24, 40, 72, 136), 3)]    # (S, crop, widths, B)
+
+
+def _nondegenerate(p64, bar):
+    """conditions on the fp64 restatement (not on the library): nothing saturates and the rows are told apart far above the bar"""
+    s64 = p64[:, 0]
+    assert 0.05 < float(s64.min()) and float(s64.max()) < 0.95
+    gaps = (s64.view(-1, 1) - s64.view(1, -1)).abs() + torch.eye(s64.shape[0], dtype=torch.float64) * 1e30
+    assert float(gaps.min()) > 100 * float(R.score_bar(bar, p64, 'gender').max())
+
+
+@pytest.fixture(scope='module')
+def e2e():
+    """per case: the scorer, the images, the library's probabilities and scores, the fp64 restatement and the yardstick = rel_l2 of the
+    SAME restatement run by torch in fp32 against fp64.  Computed once, shared and never modified."""
+    from transeditor_amd.pose import PoseScorer
+    out = {}
+    for S, crop, widths, B in E2E_CASES:
+        x = R.images(101, B, S)
+        sd = R.state_dict(1, widths=widths, images=x, crop=crop)
+        scorer = PoseScorer(state_dict=sd, crop=crop)
+        p64 = R.probabilities(x, sd, torch.float64, crop)
+        out[(S, crop, widths, B)] = dict(scorer=scorer, x=x.to(DEV), prob=scorer.probabilities(x.to(DEV)), score=scorer(x.to(DEV)), p64=p64,
+                                         yard=rel_l2(R.probabilities(x, sd, torch.float32, crop), p64))
+    return out
+
+
+@pytest.mark.parametrize('S,crop,widths,B', E2E_CASES)
+def test_scorer_end_to_end(e2e, S, crop, widths, B):
+    """Bar: 4 x the error of the fp32 torch restatement (batch norms unfolded) on the same inputs, on the rel_l2 of the probabilities, as
+    test_gpu_dex.py::test_scorer_end_to_end.  Measured on the MI355X (library / fp32 torch): see profiles/README.md, 'Pose scorer'."""
+    d = e2e[(S, crop, widths, B)]
+    scorer = d['scorer']
+    assert (scorer.crop, scorer.widths, scorer.classes) == (crop, widths, 2)
+    assert d['prob'].shape == (B, 2) and d['score'].shape == (B,) and d['score'].dtype == torch.float32 and d['score'].is_cuda
+    bar = 4 * d['yard']
+    _nondegenerate(d['p64'], bar)
+    e = rel_l2(d['prob'], d['p64'])
+    es, sb = (d['score'].double().cpu() - d['p64'][:, 0]).abs(), R.score_bar(bar, d['p64'], 'gender')
+    print(f'PoseScorer S={S} crop {crop} widths {widths} B={B}: library {e:.3e}, fp32 torch {d["yard"]:.3e} (rel_l2 of the probabilities '
+          f'against fp64), ratio {e / d["yard"]:.2f}; score max err / bar {float((es / sb).max()):.3f}')
+    assert e <= bar
+    assert bool((es <= sb).all())
+    assert torch.equal(d['score'], d['prob'][:, 0])
+    # the first row of the batch against a batch of one: the same bits
+    assert torch.equal(scorer(d['x'][:1]), d['score'][:1]) and torch.equal(scorer.probabilities(d['x'][:1]), d['prob'][:1])
+
+
+@pytest.mark.parametrize('S,crop,widths,B', E2E_CASES)
+def test_preprocessed_path_meets_the_bar(e2e, S, crop, widths, B):
+    """what the drop-in hands over (BGR levels, uncropped) against fp64, on the same bar"""
+    d = e2e[(S, crop, widths, B)]
+    p = d['scorer'].probabilities(_levels(d['x'].cpu()).to(DEV), preprocessed=True)
+    e = rel_l2(p, d['p64'])
+    print(f'PoseScorer preprocessed S={S} crop {crop}: library {e:.3e}, ratio {e / d["yard"]:.2f}')
+    assert e <= 4 * d['yard']
+
+
+# ---------------------------------------------------------------------------------------------------------- 5. the true geometry
+@pytest.fixture(scope='module')
+def true_geometry():
+    """the 224-of-256 px network with widths 64 ... 512: every weight but extra_layer is drawn from the seed; the calibrated extra_layer
+    is the golden file's (tools/pose_golden.py computed it in fp64)"""
+    from transeditor_amd.pose import PoseScorer
+    z, G = load_golden('pose_ref'), R.GOLDEN
+    sd = R.state_dict(G['seed'])
+    sd['extra_layer.weight'], sd['extra_layer.bias'] = z['extra_w'], z['extra_b']
+    scorer = PoseScorer(state_dict=sd)
+    x = R.images(G['image_seed'], G['B'], G['S']).to(DEV)
+    return dict(prob=scorer.probabilities(x).cpu(), score=scorer(x).cpu(), geometry=(scorer.crop, scorer.widths, scorer.classes),
+                shapes={k: tuple(t.shape) for k, t in sd.items()})
+
+
+def test_true_geometry_against_the_reference(true_geometry):
+    """tests/golden/pose_ref.npz (tools/pose_golden.py): the probabilities the reference's own ClassifyModel returns in fp32 on the CPU
+    for these weights and images, and the fp64 restatement's.  The yardstick is the reference's rel_l2 against fp64; the library is held
+    to 4 x it against fp64, hence to 5 x it against the reference.  The keys PoseScorer reads are the reference class's."""
+    from transeditor_amd.pose import pose_conv_keys
+    z, G, d = load_golden('pose_ref'), R.GOLDEN, true_geometry
+    assert [int(z[k]) for k in ('seed', 'image_seed', 'B', 'S', 'crop')] == [G[k] for k in ('seed', 'image_seed', 'B', 'S', 'crop')]
+    assert d['geometry'] == (224, (64, 128, 256, 512), 2)
+    ref_shapes = {str(k): tuple(int(v) for v in str(s).split(',') if v) for k, s in zip(z['keys'], z['shapes'])}
+    assert ref_shapes == d['shapes']                                           # the synthetic state dict IS the reference class's layout
+    read = {f'{c}.weight' for c, *_ in pose_conv_keys()} | {f'{b}.{t}' for _, b, *_ in pose_conv_keys() for t in R.BN_KEYS} \
+        | {'extra_layer.weight', 'extra_layer.bias'}
+    assert read == {k for k in ref_shapes if not k.endswith('num_batches_tracked')}
+    p_ref, p64 = z['prob'], z['prob64']
+    yard = rel_l2(p_ref, p64)
+    bar = 4 * yard
+    _nondegenerate(p64.double(), bar)
+    e, e_ref = rel_l2(d['prob'], p64), rel_l2(d['prob'], p_ref)
+    es, sb = (d['score'].double() - p64[:, 0].double()).abs(), R.score_bar(bar, p64, 'gender')
+    print(f'PoseScorer, 224 px crop of 256, widths 64 ... 512: library {e:.3e}, the reference {yard:.3e} (rel_l2 of the probabilities '
+          f'against fp64), ratio {e / yard:.2f}; library against the reference {e_ref:.3e}; score max err / bar {float((es / sb).max()):.3f}')
+    assert e <= bar and e_ref <= 5 * yard
+    assert bool((es <= sb).all())
+    assert bool(((d['score'].double() - p_ref[:, 0].double()).abs() <= 2 * sb).all())          # each within the bar of fp64 (POSE_REPORT.txt)
+
+
+# ---------------------------------------------------------------------------------------------------------- 6. plumbing
+@pytest.fixture(scope='module')
+def generator():
+    from transeditor_amd import synth
+    from transeditor_amd.model_spatial_query import Generator
+    G = Generator(64, 512, 512, 2 * (int(np.log2(64)) - 1), n_trans=8, pixel_norm_op_dim=1)
+    sd = G.state_dict()
+    synth.fill_state_dict(sd, 5)
+    G.load_state_dict(sd)
+    return G.to(DEV)
+
+
+@pytest.fixture(scope='module')
+def small_scorer(generator):
+    """a 32 px crop, widths 16 ... 128, extra_layer calibrated on 16 images of the generator and 8 of the random test images together,
+    so that neither kind saturates the softmax"""
+    from transeditor_amd.edit import sample_codes
+    from transeditor_amd.pose import PoseScorer
+    seen = []
+
+    def capture(images):
+        seen.append(images.detach().cpu())
+        return images.mean((1, 2, 3))
+    sample_codes(generator, capture, n_sample=16, batch=16, truncation=0.7, seed=4, latent=512, para_num=16)
+    x = torch.cat([seen[0], R.images(12, 8, 64)])
+    return PoseScorer(state_dict=R.state_dict(9, widths=(16, 32, 64, 128), images=x, crop=32), crop=32)
+
+
+def test_fit_boundaries(generator, small_scorer):
+    from transeditor_amd.pose import fit_boundaries
+    kw = dict(n_sample=40, batch=16, ratio=0.25, seed=4)                                      # batches of 16, 16 and 8; 7 + 7 training rows
+    res = fit_boundaries(generator, small_scorer, **kw)
+    assert set(res) == {'z_boundary', 'p_boundary', 'z_report', 'p_report', 'scores'}
+    assert res['scores'].shape == (40, 1) and res['scores'].is_cuda and bool(torch.isfinite(res['scores']).all())
+    assert float(res['scores'].std()) > 0 and 0.0 < float(res['scores'].min()) and float(res['scores'].max()) < 1.0
+    for k in ('z_boundary', 'p_boundary'):
+        b = res[k]
+        assert b.ndim == 2 and b.shape[0] == 1 and b.shape[1] % 512 == 0 and b.dtype == np.float32
+        assert abs(float(np.linalg.norm(b.astype(np.float64))) - 1.0) < 1e-6
+    for k in ('z_report', 'p_report'):
+        assert res[k]['n_train'] == 14 and res[k]['n_val'] == 6 and res[k]['chosen_num'] == 10
+    again = fit_boundaries(generator, small_scorer, **kw)
+    assert torch.equal(again['scores'], res['scores'])
+    assert np.array_equal(again['z_boundary'], res['z_boundary']) and np.array_equal(again['p_boundary'], res['p_boundary'])
+    assert again['z_report'] == res['z_report'] and again['p_report'] == res['p_report']
+
+
+def test_score_sweeps_on_the_device(small_scorer):
+    from transeditor_amd.edit_eval import score_sweeps
+    g = torch.Generator().manual_seed(12)
+    origin = (0.6 * torch.randn(2, 3, 64, 64, generator=g)).to(DEV)
+    sweeps = {k: (0.6 * torch.randn(2, 7, 3, 64, 64, generator=g)).to(DEV) for k in ('p', 'z', 'pz')}
+    res = score_sweeps({'pose': small_scorer}, origin, sweeps, batch=4)                       # 14 images in batches of 4, 4, 4 and 2
+    want = small_scorer(origin).cpu().numpy()
+    for space in ('p', 'z', 'pz'):
+        got = res['pose'][space]
+        assert got.shape == (2, 8) and got.dtype == np.float32
+        assert np.array_equal(got[:, 3], want)                                                # the origin, in the middle
+        each = small_scorer(sweeps[space].flatten(0, 1)).view(2, 7).cpu().numpy()
+        assert np.array_equal(np.delete(got, 3, axis=1), each)                                # another batch split: still the same bits
+        assert 0.0 < float(got.min()) and float(got.max()) < 1.0 and float(got.std()) > 0
+
+
+def test_scorer_input_checks(small_scorer):
+    with pytest.raises(ValueError, match='square'):
+        small_scorer(torch.zeros(1, 3, 64, 48, device=DEV))
+    with pytest.raises(ValueError, match='S >= 32'):
+        small_scorer(torch.zeros(1, 3, 30, 30, device=DEV))
+    with pytest.raises(ValueError, match='even'):
+        small_scorer(torch.zeros(1, 3, 63, 63, device=DEV))
+    with pytest.raises(ValueError, match=r'\[B,3,S,S\]'):
+        small_scorer(torch.zeros(1, 1, 64, 64, device=DEV))
+    with pytest.raises(RuntimeError, match='needs a GPU'):
+        small_scorer(torch.zeros(1, 3, 64, 64))
+    assert small_scorer(torch.zeros(2, 3, 32, 32, device=DEV)).shape == (2,)                  # S == crop: offset 0

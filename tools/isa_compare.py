@@ -32,6 +32,8 @@ def compile_tree(tree, out, defines=()):
     procs = []
     for f in FILES:
         src = os.path.join(os.path.abspath(tree), 'transeditor_amd', 'csrc', f + '.hip')
+        if not os.path.exists(src):                            # a source the other tree added: its kernels are listed as 'only in'
+            continue
         cmd = [_hipcc(), *FLAGS, *EXTRA_FLAGS.get(f + '.hip', []), *('-D' + d for d in defines), '--save-temps', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', f + '.o']
         procs.append((f, subprocess.Popen(cmd, cwd=out, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     for f, p in procs:
@@ -44,7 +46,10 @@ def kernels(out):
     """{demangled-ish kernel name: (resources, instruction list)} of every kernel in the device assembly of a compiled tree."""
     found = {}
     for f in FILES:
-        text = open(os.path.join(out, f + '-hip-amdgcn-amd-amdhsa-gfx950.s')).read()
+        path = os.path.join(out, f + '-hip-amdgcn-amd-amdhsa-gfx950.s')
+        if not os.path.exists(path):
+            continue
+        text = open(path).read()
         for m in re.finditer(r'^(_Z\w+):.*?^\.Lfunc_end\d+:(.*?^; Occupancy: \d+)', text, re.S | re.M):
             name = subprocess.check_output(['c++filt', m.group(1)]).decode().strip()
             name = re.sub(r'\(anonymous namespace\)::|\(.*\)$|^void ', '', name)

@@ -130,6 +130,9 @@ _SIGNATURES = {
     'te_attr_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'te_avgpool2_act_f32': (C.c_int, [_P, _P, _L, _I, _I, _F, _P]),
     'te_attr_score_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P]),
+    'te_conv2d_res_f32': (C.c_int, [_P, _P, _P, _P, _P] + [_I] * 11 + [_P]),
+    'te_pose_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'te_maxpool3s2p1_f32': (C.c_int, [_P, _P, _L, _I, _I, _P]),
     # loop-trip queries (host only)
     'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
     'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
@@ -1230,6 +1233,49 @@ def attr_score(a, w, bias, slope=0.2, want_logit=True, want_score=True):
     return logit, score
 
 
+# --------------------------------------------------------------------------------------------- M7 ResNet-18 pose classifier
+def conv2d_res(x, w, bias, res, stride=1, pad=(0, 0), act=1):
+    """act((conv2d(x, w, stride, pad) + bias) + res), the end of a ResNet BasicBlock: x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co],
+    res [B,Co,Ho,Wo] -> a new [B,Co,Ho,Wo] tensor, bitwise relu(conv2d(act=0) + res).  The ABI refuses what te_conv2d_f32 refuses;
+    nothing is launched then."""
+    if x.ndim != 4 or w.ndim != 4 or bias.ndim != 1 or x.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0]:
+        raise RuntimeError(f'te_hip: conv2d_res: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
+    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    if tuple(res.shape) != (B, Co, Ho, Wo):
+        raise RuntimeError(f'te_hip: conv2d_res: the residual must be [{B},{Co},{Ho},{Wo}], got {tuple(res.shape)}')
+    out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
+    _check(lib().te_conv2d_res_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(res), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], act,
+                                   _stream()), 'te_conv2d_res_f32')
+    return out
+
+
+def pose_stem_fwd(img, w, b, crop, preprocessed=False):
+    """RGB [-1, 1] -> BGR byte levels (preprocessed: img already is) -> centre crop -> 7x7 stride-2 pad-3 convolution -> bias -> ReLU:
+    img [N,3,H,W], w [Co,3,7,7], b [Co] -> [N,Co,Hc,Hc], Hc = (crop - 1) // 2 + 1.  The ABI refuses a crop that does not fit or is not
+    centred (an odd H - crop or W - crop); nothing is launched then."""
+    if img.ndim != 4 or img.shape[1] != 3 or w.ndim != 4 or tuple(w.shape[1:]) != (3, 7, 7) or b.shape != (w.shape[0],):
+        raise RuntimeError(f'te_hip: pose_stem_fwd: inconsistent shapes img {tuple(img.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}')
+    img = img.contiguous()
+    (N, _, H, W), Co = img.shape, w.shape[0]
+    Hc = (max(crop, 1) - 1) // 2 + 1
+    out = torch.empty(N, Co, Hc, Hc, device=img.device, dtype=img.dtype)
+    _check(lib().te_pose_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, crop, Co, 1 if preprocessed else 0, _stream()),
+           'te_pose_stem_fwd_f32')
+    return out
+
+
+def maxpool3s2p1(x):
+    """nn.MaxPool2d(3, 2, 1): x [N,C,H,W] -> [N,C,(H - 1) // 2 + 1,(W - 1) // 2 + 1]; the padding never wins, a NaN propagates"""
+    if x.ndim != 4:
+        raise RuntimeError(f'te_hip: maxpool3s2p1 expects [N,C,H,W], got {tuple(x.shape)}')
+    x = x.contiguous()
+    N, Cn, H, W = x.shape
+    out = torch.empty(N, Cn, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, dtype=x.dtype)
+    _check(lib().te_maxpool3s2p1_f32(_ptr(out), _ptr(x), N * Cn, H, W, _stream()), 'te_maxpool3s2p1_f32')
+    return out
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1245,7 +1291,7 @@ def _install_roctx():
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
              'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score',
-             'attr_stem_fwd', 'avgpool2_act', 'attr_score']
+             'attr_stem_fwd', 'avgpool2_act', 'attr_score', 'conv2d_res', 'pose_stem_fwd', 'maxpool3s2p1']
     g = globals()
 
     def wrap(fn, name):

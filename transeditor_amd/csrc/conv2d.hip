@@ -19,6 +19,8 @@
 // Taps outside the image, pixels >= P, channels >= Co and k >= K are zeros.  No im2col tensor, no workspace, no split of K, no atomics.
 // An output element is one chain over k ascending in the permutation of gemm_nt_f32.h (lane half h feeds k = 8q + 4h + u of every step
 // to MFMA (q, u)), which depends on nothing but K: an image's outputs are bitwise the same whatever batch and whatever tile it is in.
+// The kernel itself is the template conv2d_kernel<BN, AL, Gather, Epilogue> of conv2d_body.h, which resnet.hip instantiates with other
+// gathers and epilogues; te_conv2d_f32 is <GatherPlain, EpiBiasAct>.
 #include "te_common.h"
 
 #ifdef CONV2D_PROF   // experimental builds: per-wave cycle counts of the three phases of the K loop, read back with te_debug_conv2d_prof
@@ -26,176 +28,13 @@
 #endif
 #include "te_prof.h"
 
-namespace {
-
-constexpr int BM = 64;           // output channels per workgroup
-constexpr int BK = 32;
-constexpr int LD = 36;           // LDS row pitch in floats (csrc/gemm_nt_f32.h)
-constexpr int NT = 256;
-constexpr int kMaxKernel = 7;
-constexpr int kWideGridMin = 512;    // BN = 128 only where it still gives two workgroups per CU
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 PROF_BUFFER(conv2d, 1024 * 4 * 4)
 
-struct ConvArgs {
-    float* out;
-    const float* x;
-    const float* w;
-    const float* bias;
-    int64_t P;                   // B * Ho * Wo
-    int Ci, Co, H, W, kh, kw, s, py, px, Ho, Wo, Ctot, c0, act, K;
-};
+#include "conv2d_body.h"         // the kernel template (shared with resnet.hip); its profiling lines write the buffer above
 
-// 64 rows x 32 k of the weight [Co, K] -> two 4-float groups per thread; rows >= Co and k >= K are zeros
-template <bool AL>
-__device__ __forceinline__ void load_weights(f32x4 (&r)[2], const float* __restrict__ w, int m0, int Co, int K, int k0) {
-    const int t = threadIdx.x;
-    const int k = k0 + (t & 7) * 4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = m0 + (t >> 3) + 32 * i;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row < Co) {
-            const float* p = w + (int64_t)row * K + k;
-            if (AL) {
-                if (k < K) v = *reinterpret_cast<const f32x4*>(p);       // K % 4 == 0: the four are inside the row or all past it
-            } else {
-                if (k < K) v.x = p[0];
-                if (k + 1 < K) v.y = p[1];
-                if (k + 2 < K) v.z = p[2];
-                if (k + 3 < K) v.w = p[3];
-            }
-        }
-        r[i] = v;
-    }
-}
+namespace {
 
-// the thread's pixel, decoded once
-struct Pixel {
-    const float* img;            // x + b * Ci * H * W
-    int iy0, ix0;                // the input row / column of tap (0, 0); may be negative
-    bool live;
-};
-
-// NPT consecutive k (from k0, wave-uniform) of the thread's pixel: x[b, c, iy0 + ky, ix0 + kx] or 0
-template <int NPT>
-__device__ __forceinline__ void gather(float (&r)[NPT], const Pixel& px, const ConvArgs& a, int k0) {
-    const int khw = a.kh * a.kw;
-    int c = k0 / khw;
-    const int rem = k0 - c * khw;
-    int ky = rem / a.kw, kx = rem - ky * a.kw;
-    const int HW = a.H * a.W;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int iy = px.iy0 + ky, ix = px.ix0 + kx;
-        const bool in = px.live && c < a.Ci && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        r[j] = in ? px.img[c * HW + iy * a.W + ix] : 0.f;
-        if (++kx == a.kw) {
-            kx = 0;
-            if (++ky == a.kh) { ky = 0; ++c; }
-        }
-    }
-}
-
-template <int BN, bool AL>
-__global__ __launch_bounds__(NT) void conv2d_kernel(const ConvArgs a) {
-    constexpr int NACC = BN / 64;                // 32 x 32 tiles per wave along the pixels
-    constexpr int NPT = BN * BK / NT;            // patch elements per thread and step: 8 or 16 consecutive k
-    constexpr int KG = BK / NPT;                 // k runs per step; a wave has one
-    __shared__ __attribute__((aligned(16))) float Ws[BM * LD];
-    __shared__ __attribute__((aligned(16))) float Xs[BN * LD];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm = wid >> 1, wn = wid & 1, c = lane & 31, h = lane >> 5;
-    const int m0 = blockIdx.y * BM;
-    const int64_t p0 = (int64_t)blockIdx.x * BN;
-    const int HoWo = a.Ho * a.Wo;
-
-    // gather role: pixel n of the tile, k run kg (threadIdx.x / BN is the same for a whole wave: BN is a multiple of 64)
-    const int n = threadIdx.x % BN;
-    const int kg = __builtin_amdgcn_readfirstlane(threadIdx.x / BN);
-    static_assert(KG * BN == NT, "one k run per group of BN threads");
-    Pixel px;
-    {
-        const int64_t p = p0 + n;
-        px.live = p < a.P;
-        const int64_t b = px.live ? p / HoWo : 0;
-        const int r = px.live ? (int)(p - b * HoWo) : 0;
-        const int oy = r / a.Wo, ox = r - oy * a.Wo;
-        px.img = a.x + b * a.Ci * a.H * a.W;
-        px.iy0 = oy * a.s - a.py;
-        px.ix0 = ox * a.s - a.px;
-    }
-
-    f32x16 acc[NACC];
-#pragma unroll
-    for (int i = 0; i < NACC; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-    f32x4 rw[2];
-    float rx[NPT];
-    load_weights<AL>(rw, a.w, m0, a.Co, a.K, 0);
-    gather<NPT>(rx, px, a, kg * NPT);
-    const float* wp = Ws + (wm * 32 + c) * LD + 4 * h;
-    const float* xp = Xs + (wn * (BN / 2) + c) * LD + 4 * h;
-    PROF_ONLY(unsigned long long pc[3] = {0, 0, 0}; unsigned long long tlast = __builtin_readcyclecounter();)
-    for (int kk = 0; kk < a.K; kk += BK) {
-        __syncthreads();                                     // the previous step's LDS reads are done
-        {
-            const int t = threadIdx.x;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(Ws + ((t >> 3) + 32 * i) * LD + (t & 7) * 4) = rw[i];
-#pragma unroll
-            for (int j = 0; j < NPT; j += 4) {
-                const f32x4 v = {rx[j], rx[j + 1], rx[j + 2], rx[j + 3]};
-                *reinterpret_cast<f32x4*>(Xs + n * LD + kg * NPT + j) = v;
-            }
-        }
-        __syncthreads();
-        PROF_LAP(pc[0]);
-        if (kk + BK < a.K) {                                 // in flight behind the MFMAs below
-            load_weights<AL>(rw, a.w, m0, a.Co, a.K, kk + BK);
-            gather<NPT>(rx, px, a, kk + BK + kg * NPT);
-        }
-        PROF_LAP(pc[1]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(wp + 8 * q);
-#pragma unroll
-            for (int i = 0; i < NACC; ++i) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(xp + i * 32 * LD + 8 * q);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.x, v.x, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.y, v.y, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.z, v.z, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.w, v.w, acc[i], 0, 0, 0);
-            }
-        }
-        PROF_LAP(pc[2]);
-    }
-    PROF_ONLY(if (lane == 0 && blockIdx.y == 0 && blockIdx.x < 1024) {
-        for (int i = 0; i < 3; ++i) te_conv2d_prof_buf[(blockIdx.x * 4 + wid) * 4 + i] = pc[i];
-    })
-    // accumulator register e of lane (c, h): channel (e & 3) + 8 (e >> 2) + 4 h of the wave's 32, pixel c of tile i
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) {
-        const int64_t p = p0 + wn * (BN / 2) + i * 32 + c;
-        if (p >= a.P) continue;
-        const int64_t b = p / HoWo;
-        const int r = (int)(p - b * HoWo);
-        float* dst = a.out + (b * a.Ctot + a.c0) * HoWo + r;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (m < a.Co) {
-                float v = acc[i][e] + a.bias[m];
-                if (a.act == 1) v = te::relu_nan(v);
-                dst[(int64_t)m * HoWo] = v;
-            }
-        }
-    }
-}
+using namespace te::conv2d;
 
 // mode 0: max, stride 2, no padding (floor); 1: max, stride 1, pad 1 (padding never wins); 2: average, stride 1, pad 1, over the taps
 // inside the image.  One thread per output element, lanes along ox.  Max: a greater value or a NaN replaces (te_maxpool2_fwd_f32).
@@ -264,8 +103,8 @@ __global__ __launch_bounds__(256) void resize_kernel(float* __restrict__ out, co
 template <int BN>
 void launch_conv(const ConvArgs& a, bool al, hipStream_t st) {
     const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (al) conv2d_kernel<BN, true><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false><<<grid, NT, 0, st>>>(a);
+    if (al) conv2d_kernel<BN, true, GatherPlain, EpiBiasAct><<<grid, NT, 0, st>>>(a);
+    else conv2d_kernel<BN, false, GatherPlain, EpiBiasAct><<<grid, NT, 0, st>>>(a);
 }
 
 }  // namespace
@@ -273,31 +112,12 @@ void launch_conv(const ConvArgs& a, bool al, hipStream_t st) {
 extern "C" int te_conv2d_f32(float* out, const float* x, const float* w, const float* bias, int B, int Ci, int Co, int H, int W, int kh,
                              int kw, int s, int py, int px, int Ctot, int c0, int act, te_stream_t stream) {
     TE_REQUIRE(out && x && w && bias, TE_ERR_NULL, "te_conv2d_f32: NULL pointer");
-    TE_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, TE_ERR_SHAPE,
-               "te_conv2d_f32: B, Ci, Co, H, W must be positive (got %d, %d, %d, %d, %d)", B, Ci, Co, H, W);
-    TE_REQUIRE(kh >= 1 && kh <= kMaxKernel && kw >= 1 && kw <= kMaxKernel, TE_ERR_UNSUPPORTED,
-               "te_conv2d_f32: 1 <= kh, kw <= %d (got %d x %d)", kMaxKernel, kh, kw);
-    TE_REQUIRE(s == 1 || s == 2, TE_ERR_UNSUPPORTED, "te_conv2d_f32: the stride must be 1 or 2 (got %d)", s);
-    TE_REQUIRE(py >= 0 && py < kh && px >= 0 && px < kw, TE_ERR_SHAPE,
-               "te_conv2d_f32: 0 <= py < kh and 0 <= px < kw (got padding %d, %d for a %d x %d kernel)", py, px, kh, kw);
-    TE_REQUIRE(act == 0 || act == 1, TE_ERR_UNSUPPORTED, "te_conv2d_f32: act must be 0 (none) or 1 (ReLU), got %d", act);
-    TE_REQUIRE(H + 2 * py >= kh && W + 2 * px >= kw, TE_ERR_SHAPE,
-               "te_conv2d_f32: a %d x %d kernel with padding %d, %d does not fit a %d x %d image (Ho, Wo >= 1)", kh, kw, py, px, H, W);
-    TE_REQUIRE(c0 >= 0 && Ctot >= 1 && (int64_t)c0 + Co <= Ctot, TE_ERR_SHAPE,
-               "te_conv2d_f32: the slice [%d, %d + %d) is outside the %d output channels", c0, c0, Co, Ctot);
-    const int Ho = (H + 2 * py - kh) / s + 1, Wo = (W + 2 * px - kw) / s + 1;
-    TE_REQUIRE((int64_t)Ci * H * W <= 0x7fffffff && (int64_t)Ci * kh * kw <= 0x7fffffff - BK && (int64_t)Ho * Wo <= 0x7fffffff, TE_ERR_SHAPE,
-               "te_conv2d_f32: one image (Ci * H * W), Ci * kh * kw and Ho * Wo must fit 31 bits");
     ConvArgs a;
     a.out = out; a.x = x; a.w = w; a.bias = bias;
-    a.P = (int64_t)B * Ho * Wo;
-    a.Ci = Ci; a.Co = Co; a.H = H; a.W = W; a.kh = kh; a.kw = kw; a.s = s; a.py = py; a.px = px;
-    a.Ho = Ho; a.Wo = Wo; a.Ctot = Ctot; a.c0 = c0; a.act = act; a.K = Ci * kh * kw;
-    TE_REQUIRE(te::cdiv(a.P, 64) <= 0x7fffffff && te::cdiv(Co, BM) <= 65535, TE_ERR_SHAPE,
-               "te_conv2d_f32: too many outputs (%lld pixels, %d channels)", (long long)a.P, Co);
+    if (const int rc = fill_args(a, "te_conv2d_f32", B, Ci, Co, H, W, kh, kw, s, py, px, Ctot, c0, act)) return rc;
     const bool al = a.K % 4 == 0 && te::aligned16(w);
     hipStream_t st = (hipStream_t)stream;
-    if (te::cdiv(a.P, 128) * te::cdiv(Co, BM) >= kWideGridMin) launch_conv<128>(a, al, st);
+    if (wide_grid(a.P, Co)) launch_conv<128>(a, al, st);
     else launch_conv<64>(a, al, st);
     return te::launch_status("te_conv2d_f32");
 }

@@ -93,12 +93,13 @@ LAYERS = tuple(
 _BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
 
 
-def fold_bn(w, gamma, beta, mean, var, eps=BN_EPS):
-    """conv (no bias) followed by an eval-mode batch norm -> (w', b') fp32: fp64 arithmetic on the host, one rounding"""
+def fold_bn(w, gamma, beta, mean, var, eps=BN_EPS, dtype=torch.float32):
+    """conv (no bias) followed by an eval-mode batch norm -> (w', b') fp32: fp64 arithmetic on the host, one rounding (dtype=
+    torch.float64: the values before it)"""
     g = gamma.detach().double().cpu() / torch.sqrt(var.detach().double().cpu() + eps)
     wf = w.detach().double().cpu() * g.view(-1, 1, 1, 1)
     bf = beta.detach().double().cpu() - mean.detach().double().cpu() * g
-    return wf.float().contiguous(), bf.float().contiguous()
+    return wf.to(dtype).contiguous(), bf.to(dtype).contiguous()
 
 
 def inception_convs(sd, path):
