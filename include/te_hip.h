@@ -876,6 +876,50 @@ int te_pose_stem_fwd_f32(float* out, const float* img, const float* w, const flo
                          int preprocessed, te_stream_t stream);
 int te_maxpool3s2p1_f32(float* out, const float* x, int64_t planes, int H, int W, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M8  the AlexNet LPIPS of the diversity score (metrics/lpips.py:49-82 LPIPS.forward, called for all 780 pairs of a group of 40 images by
+ * metrics/evaluate_query.py:82-91 calculate_lpips_given_images from :94-133 evaluate_lpips).  conv2 ... conv5 of torchvision's
+ * alexnet().features are M4's te_conv2d_f32 with act 1, its max pools te_pool3_f32 mode 0; here the stem, the normalisation and the
+ * head (csrc/lpips_alex.hip).  The reference runs the network on both images of every pair again (1 560 passes per group); here it
+ * runs once over the group and the pairs are a property of the head.  Forward only, NCHW fp32, no atomics, fixed-order reductions:
+ * results are bit-reproducible from run to run.
+ *
+ * te_alex_stem_fwd_f32 (lpips.py:73 (x - mu) / sigma and features[0:2] = Conv2d(3, 64, 11, stride=4, padding=2) + ReLU): x [N,3,H,W]
+ * generator images, w [Co,3,11,11], b [Co]; out [N,Co,Ho,Wo], Ho = (H - 7) / 4 + 1, Wo likewise.
+ *     s(x)[n,c] = (x[n,c] - mu[c]) / sigma[c]      mu (-0.03, -0.088, -0.188), sigma (0.458, 0.448, 0.450), each step rounded to fp32
+ *     out[n,o,y,x] = relu(b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * s(x)[n, c, 4y + ky - 2, 4x + kx - 2])
+ * where a tap outside the image is ZERO: the padding is that of the scaled image, as in te_lpips_stem_fwd_f32.  An implicit GEMM with
+ * K = 363 on te_conv2d_f32's main loop (csrc/conv2d_body.h) whose gather scales a tap on the way into LDS: the loop sees the fp32
+ * values torch's (x - mu) / sigma would store, in te_conv2d_f32's order of k, so an image's outputs do not depend on its batch or its
+ * tile.  A NaN pixel reaches exactly the outputs whose 11 x 11 window holds it.  The 11 x 11 kernel and the stride of 4 are this
+ * entry point's own limits: te_conv2d_f32 keeps refusing them.  TE_ERR_NULL for a NULL pointer; TE_ERR_SHAPE for N < 1, N >= 65536,
+ * H, W or Co < 1, H + 4 < 11 or W + 4 < 11, 3 * H * W past 31 bits; nothing is launched on a refusal.
+ *
+ * te_lpips_unit_f32 (lpips.py:16-17 normalize): out[n,c,p] = f[n,c,p] * rsqrt(sum_c f[n,c,p]^2 + 1e-10), f and out [N,C,HW]; out may
+ * be f.  The eps sits INSIDE the root: this is the one place where this LPIPS differs from L1's te_lpips_normalize_f32, which is
+ * f / (sqrt(sum) + 1e-10).  A pixel's sum of squares is taken in fp64 (channel slices added in slice order, as
+ * te_lpips_pair_head_fwd_f32 does) and rsqrt rounded to fp32 once; a pixel that is zero on every channel gives exactly 0.
+ *
+ * The all-pairs head, for NORMALISED taps fh [N,C,HW] (te_lpips_unit_f32's output) and a head w [C] of either sign:
+ *     te_lpips_allpairs_ws_floats(N, C, HW) : the floats of one layer's workspace (negative: a refused size)
+ *     te_lpips_allpairs_fwd_f32             : the workspace's partials (one per pair, block of 256 pixels and slice of 32 channels) of
+ *                                             sum_p sum_c w[c] (fh[i,c,p] - fh[j,c,p])^2 for all i <= j
+ *     te_lpips_allpairs_dist_f32            : D[i,j] = sum_{l < L} (sum_b partial_l[(i,j), b]) / hw[l], D [N,N], the partials (pixel
+ *                                             blocks, a block's channel slices inside it) and the layers in ascending order
+ *                                             (lpips.py:77-81 `lpips_value +=`); partial / c / hw are HOST arrays of L <= 8 entries
+ * The difference is formed before the square (never a^2 + b^2 - 2ab), w[c] * d is rounded, then one fma per term; a pair's sum is a
+ * chain over a slice's channels per pixel, a fixed tree over the 256 pixels of a block, then the partials in order.  Hence: the
+ * diagonal is exactly 0; D[i,j] == D[j,i] bit for bit; D[i,j] depends on images i and j, C and HW alone, not on N or on the other
+ * images of the group; a NaN in image i reaches row i and column i only.  A workgroup takes 256 pixels, 32 channels and a tile of
+ * 8 x 8 images, so a tap is read about N / 8 + 1 times, not N - 1.  1 <= N < 65536 (N = 1 gives [[0]]), C, HW >= 1,
+ * HW <= 65535 * 256, C <= 65535 * 32, C * HW below 2^31, else TE_ERR_SHAPE; nothing is launched on a refusal.
+ */
+int te_alex_stem_fwd_f32(float* out, const float* x, const float* w, const float* b, int N, int H, int W, int Co, te_stream_t stream);
+int te_lpips_unit_f32(float* out, const float* f, int N, int C, int64_t HW, te_stream_t stream);
+int64_t te_lpips_allpairs_ws_floats(int N, int C, int64_t HW);
+int te_lpips_allpairs_fwd_f32(float* partial, const float* fh, const float* w, int N, int C, int64_t HW, te_stream_t stream);
+int te_lpips_allpairs_dist_f32(float* D, const float* const* partial, const int* c, const int64_t* hw, int L, int N, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

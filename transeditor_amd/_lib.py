@@ -133,6 +133,11 @@ _SIGNATURES = {
     'te_conv2d_res_f32': (C.c_int, [_P, _P, _P, _P, _P] + [_I] * 11 + [_P]),
     'te_pose_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'te_maxpool3s2p1_f32': (C.c_int, [_P, _P, _L, _I, _I, _P]),
+    'te_alex_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'te_lpips_unit_f32': (C.c_int, [_P, _P, _I, _I, _L, _P]),
+    'te_lpips_allpairs_ws_floats': (C.c_int64, [_I, _I, _L]),
+    'te_lpips_allpairs_fwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _L, _P]),
+    'te_lpips_allpairs_dist_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
     # loop-trip queries (host only)
     'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
     'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
@@ -1276,6 +1281,58 @@ def maxpool3s2p1(x):
     return out
 
 
+# --------------------------------------------------------------------------------------------- M8 AlexNet LPIPS (diversity score)
+def alex_stem_fwd(img, w, b):
+    """(x - mu) / sigma -> 11x11 stride-4 pad-2 convolution -> bias -> ReLU: img [N,3,H,W], w [Co,3,11,11], b [Co] ->
+    [N,Co,(H - 7) // 4 + 1,(W - 7) // 4 + 1].  The ABI refuses an image below 7 px; nothing is launched then."""
+    if img.ndim != 4 or img.shape[1] != 3 or w.ndim != 4 or tuple(w.shape[1:]) != (3, 11, 11) or b.shape != (w.shape[0],):
+        raise RuntimeError(f'te_hip: alex_stem_fwd: inconsistent shapes img {tuple(img.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}')
+    img = img.contiguous()
+    (N, _, H, W), Co = img.shape, w.shape[0]
+    Ho, Wo = conv2d_out_hw(H, W, 11, 11, 4, (2, 2))
+    out = torch.empty(N, Co, max(Ho, 0), max(Wo, 0), device=img.device, dtype=img.dtype)
+    _check(lib().te_alex_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, Co, _stream()), 'te_alex_stem_fwd_f32')
+    return out
+
+
+def lpips_unit(f, out=None):
+    """f * rsqrt(sum_c f^2 + 1e-10) of f [N,C,H,W] (or [N,C,HW]); out=f normalises in place"""
+    if f.ndim not in (3, 4):
+        raise RuntimeError(f'te_hip: lpips_unit expects [N,C,H,W] or [N,C,HW], got {tuple(f.shape)}')
+    if out is None:
+        out = torch.empty_like(f)
+    _check(lib().te_lpips_unit_f32(_ptr(out), _ptr(f), f.shape[0], f.shape[1], f[0, 0].numel(), _stream()), 'te_lpips_unit_f32')
+    return out
+
+
+def lpips_allpairs_fwd(fh, w):
+    """one layer's per-block partials of the all-pairs head for normalised taps fh [N,C,H,W] (or [N,C,HW]) and the head w [C]: a flat
+    workspace of te_lpips_allpairs_ws_floats(N, C, HW) floats that lpips_allpairs_dist reads"""
+    if fh.ndim not in (3, 4) or w.ndim != 1 or w.shape[0] != fh.shape[1]:
+        raise RuntimeError(f'te_hip: lpips_allpairs_fwd: inconsistent shapes fh {tuple(fh.shape)}, w {tuple(w.shape)}')
+    N, Cn, HW = fh.shape[0], fh.shape[1], fh[0, 0].numel()
+    n = lib().te_lpips_allpairs_ws_floats(N, Cn, HW)
+    if n < 0:
+        raise RuntimeError(f'te_hip: lpips_allpairs_fwd: a group of {N} taps of {HW} pixels is outside the limits (1 <= N < 65536)')
+    partial = torch.empty(n, device=fh.device, dtype=fh.dtype)
+    _check(lib().te_lpips_allpairs_fwd_f32(_ptr(partial), _ptr(fh), _ptr(w), N, Cn, HW, _stream()), 'te_lpips_allpairs_fwd_f32')
+    return partial
+
+
+def lpips_allpairs_dist(partials, shapes, N):
+    """D [N,N] = sum over the layers (in order) of the pairs' spatial means; shapes: each layer's (C, HW), as its partials were made"""
+    L = len(partials)
+    D = torch.empty(N, N, device=partials[0].device, dtype=torch.float32)
+    ptrs = (C.c_void_p * L)(*[_ptr(p) for p in partials])
+    cs = (C.c_int * L)(*[s[0] for s in shapes])
+    hw = (C.c_int64 * L)(*[s[1] for s in shapes])
+    for p, (Cn, HW) in zip(partials, shapes):
+        if p.numel() != lib().te_lpips_allpairs_ws_floats(N, Cn, HW):
+            raise RuntimeError(f'te_hip: lpips_allpairs_dist: {p.numel()} partials are not those of a group of {N} taps [{Cn},{HW}]')
+    _check(lib().te_lpips_allpairs_dist_f32(_ptr(D), ptrs, cs, hw, L, N, _stream()), 'te_lpips_allpairs_dist_f32')
+    return D
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1291,7 +1348,8 @@ def _install_roctx():
              'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
              'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score',
-             'attr_stem_fwd', 'avgpool2_act', 'attr_score', 'conv2d_res', 'pose_stem_fwd', 'maxpool3s2p1']
+             'attr_stem_fwd', 'avgpool2_act', 'attr_score', 'conv2d_res', 'pose_stem_fwd', 'maxpool3s2p1',
+             'alex_stem_fwd', 'lpips_unit', 'lpips_allpairs_fwd', 'lpips_allpairs_dist']
     g = globals()
 
     def wrap(fn, name):

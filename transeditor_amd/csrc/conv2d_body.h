@@ -1,5 +1,5 @@
 // The implicit-GEMM kernel of the general fp32 convolution as a template, shared by te_conv2d_f32 (conv2d.hip) and the ResNet entry points
-// (resnet.hip: te_conv2d_res_f32, te_pose_stem_fwd_f32), written once.  Two compile-time policies make the variants:
+// (resnet.hip: te_conv2d_res_f32, te_pose_stem_fwd_f32) and the AlexNet stem (lpips_alex.hip: te_alex_stem_fwd_f32), written once.  Two compile-time policies make the variants:
 //     the gather   : where a tap of the patch comes from (GatherPlain: x[b, c, iy, ix] of a dense [B,Ci,H,W] tensor), and
 //     the epilogue : what happens to acc + bias before the store (EpiBiasAct: the activation).
 // Everything else - the tile shapes, the LDS layout, the order of k inside an output's one fp32 fma chain (the permutation of
@@ -206,14 +206,16 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
 // BN = 128 where that still fills the chip, else 64 (the result does not depend on the choice)
 inline bool wide_grid(int64_t P, int Co) { return te::cdiv(P, 128) * te::cdiv(Co, BM) >= kWideGridMin; }
 
-// the checks and the fill of ConvArgs that every entry point on this loop shares; `who` names the entry point in the messages
+// the checks and the fill of ConvArgs that every entry point on this loop shares; `who` names the entry point in the messages.
+// The loop itself takes any kernel size and stride; `max_kernel` and `stride4` are the entry point's own limits (the AlexNet stem of
+// lpips_alex.hip is 11 x 11 with stride 4, every other entry point keeps 7 x 7 and strides 1 and 2).
 inline int fill_args(ConvArgs& a, const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int Ctot, int c0,
-                     int act) {
+                     int act, int max_kernel = kMaxKernel, bool stride4 = false) {
     TE_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, TE_ERR_SHAPE, "%s: B, Ci, Co, H, W must be positive (got %d, %d, %d, %d, %d)", who,
                B, Ci, Co, H, W);
-    TE_REQUIRE(kh >= 1 && kh <= kMaxKernel && kw >= 1 && kw <= kMaxKernel, TE_ERR_UNSUPPORTED, "%s: 1 <= kh, kw <= %d (got %d x %d)", who,
-               kMaxKernel, kh, kw);
-    TE_REQUIRE(s == 1 || s == 2, TE_ERR_UNSUPPORTED, "%s: the stride must be 1 or 2 (got %d)", who, s);
+    TE_REQUIRE(kh >= 1 && kh <= max_kernel && kw >= 1 && kw <= max_kernel, TE_ERR_UNSUPPORTED, "%s: 1 <= kh, kw <= %d (got %d x %d)", who,
+               max_kernel, kh, kw);
+    TE_REQUIRE(s == 1 || s == 2 || (stride4 && s == 4), TE_ERR_UNSUPPORTED, "%s: the stride must be 1 or 2 (got %d)", who, s);
     TE_REQUIRE(py >= 0 && py < kh && px >= 0 && px < kw, TE_ERR_SHAPE,
                "%s: 0 <= py < kh and 0 <= px < kw (got padding %d, %d for a %d x %d kernel)", who, py, px, kh, kw);
     TE_REQUIRE(act == 0 || act == 1, TE_ERR_UNSUPPORTED, "%s: act must be 0 (none) or 1 (ReLU), got %d", who, act);

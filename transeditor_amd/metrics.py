@@ -1,7 +1,9 @@
-"""Perceptual path length (PPL) of a checkpoint in the z, p and joint latent spaces: the reference's metrics/evaluate_query.py:135-249
-on this project's frozen-generator sampler (transeditor_amd.inference) and LPIPS-VGG (transeditor_amd.lpips).
+"""Perceptual path length (PPL) of a checkpoint in the z, p and joint latent spaces, and its LPIPS diversity score: the reference's
+metrics/evaluate_query.py:135-249 and :82-133 on this project's frozen-generator sampler (transeditor_amd.inference), LPIPS-VGG
+(transeditor_amd.lpips) and AlexNet LPIPS (transeditor_amd.lpips_alex).
 
     python -m transeditor_amd.metrics --ckpt 790000.pt --ppl --vgg16 vgg16-397923af.pth --lpips_lin vgg.pth
+    python -m transeditor_amd.metrics --ckpt 790000.pt --lpips --alexnet alexnet-owt-7be5be79.pth --lpips_alex_lin lpips_weights.ckpt
 
 Each sample is the LPIPS distance of two images whose latents are `eps` apart on the path between two random codes, divided by
 eps^2.  Hot path: the generator (one captured graph per batch shape), te_crop_resize_bilinear_f32 for the crop / resize to the LPIPS
@@ -13,8 +15,18 @@ Differences from the reference, all deliberate:
   - the distances stay on the device until the run ends (no host synchronisation inside the loop);
   - the reference hard-codes 10000 samples in batches of 64 inside evaluate_ppl (:142-143) whatever the command line says; here they
     are arguments with those defaults (--ppl_n_sample, --batch);
-  - FID and the AlexNet LPIPS diversity score are not built (they need networks and weights this library does not have):
-    --fid / --lpips exit with a message.  PRDC is built on given features: transeditor_amd.prdc.
+  - FID is not run from here (--fid exits with a message): transeditor_amd.fid.  PRDC is built on given features: transeditor_amd.prdc.
+
+The diversity score (evaluate_diversity, --lpips): per iteration three groups of 40 images are drawn and each is scored as the mean of
+the AlexNet LPIPS over its 780 pairs; a figure is the mean over the iterations.  The groups, in the reference's draw order (param
+before latent, :108-124):
+    all     p and z vary                 ('spatial' + 'query')
+    same_p  one p for the group, z varies ('spatial_same' + 'query')
+    same_z  one z for the group, p varies ('spatial' + 'query_same')
+The figures are named by what the group SHARES.  Inside the reference's evaluate_lpips the p-shared group is collected as `fix_z` and
+the z-shared one as `fix_p`, the function returns (all, fix_z, fix_p) and its caller (:350) unpacks that as (all, fix_p, fix_z): the two
+swaps cancel, so of the three numbers the reference prints after "lpips:" the first is `all`, the second `same_p`, the third `same_z`.
+Hot path: the generator, AlexLPIPS.group_mean (the network once over the group, then the all-pairs head te_lpips_allpairs_fwd_f32).
 """
 import argparse
 import json
@@ -30,6 +42,8 @@ from .inference import GeneratorSampler
 from .utils.sample import prepare_noise_new, prepare_param
 
 SPACES = ('all', 'z', 'p')
+# the diversity score's groups in draw order: (figure, prepare_param method, prepare_noise_new method)  (evaluate_query.py:108-124)
+DIVERSITY_GROUPS = (('all', 'spatial', 'query'), ('same_p', 'spatial_same', 'query'), ('same_z', 'spatial', 'query_same'))
 
 
 def normalize(x):                                                               # :27-28
@@ -170,10 +184,38 @@ def evaluate_ppl(generator, percept, *, space='all', eval_plus=False, use_slerp=
     return filter_mean(distances), distances
 
 
+@torch.no_grad()
+def evaluate_diversity(generator, lpips, *, n_iter=1000, group=40, truncation=1.0, seed=None, latent=512, para_num=16):
+    """The reference's evaluate_lpips (:94-133) -> {'all', 'same_p', 'same_z': floats, 'per_iteration': {figure: float32 numpy array
+    [n_iter]}}.  `lpips`: an AlexLPIPS (anything with group_mean(images) -> 0-d tensor).  Figures are named by what the group shares;
+    against the reference's print see the module docstring.  Draw order as the reference's: param before latent, the three groups in
+    the order of DIVERSITY_GROUPS.  `seed` as in evaluate_ppl.  The values stay on the device until the run ends."""
+    if n_iter < 1 or group < 2:
+        raise ValueError(f'evaluate_diversity: n_iter >= 1 and group >= 2, got {n_iter}, {group}')
+    g = _as_sampler(generator)
+    device = next(g.g.parameters()).device
+    args = types.SimpleNamespace(latent=latent, para_num=para_num)
+    values = {name: [] for name, _, _ in DIVERSITY_GROUPS}
+    with torch.random.fork_rng(devices=[device] if device.type == 'cuda' else [], enabled=seed is not None):
+        if seed is not None:
+            torch.manual_seed(seed)
+        for _ in range(n_iter):
+            for name, p_method, z_method in DIVERSITY_GROUPS:
+                sample_param = prepare_param(group, args, device, method=p_method) * truncation
+                latent_z = prepare_noise_new(group, args, device, method=z_method) * truncation
+                img, _, _ = g(latent_z, sample_param)
+                values[name].append(lpips.group_mean(img))
+    stacked = {name: torch.stack(v).float() for name, v in values.items()}
+    out = {name: float(v.mean()) for name, v in stacked.items()}                # (:130-132: the fp32 mean of the stacked values)
+    out['per_iteration'] = {name: v.to('cpu').numpy() for name, v in stacked.items()}
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------------ CLI
-def build_parser():
+def build_parser(diversity=False):
     """the reference's flags with their names and defaults (:256-288; --inception is not required here: nothing reads it), plus
-    --vgg16, --lpips_lin, --ppl_n_sample and --seed"""
+    --vgg16, --lpips_lin, --ppl_n_sample and --seed; diversity=True (what main() parses with) adds the diversity score's --alexnet,
+    --lpips_alex_lin, --lpips_iters and --lpips_group"""
     parser = argparse.ArgumentParser(description='evaluate a checkpoint (metrics/evaluate_query.py): perceptual path length')
     parser.add_argument('--truncation', type=float, default=1)
     parser.add_argument('--truncation_mean', type=int, default=4096)
@@ -200,7 +242,12 @@ def build_parser():
     parser.add_argument('--vgg16', type=str, default=None, help='torchvision vgg16 state dict (default: the torch hub cache path)')
     parser.add_argument('--lpips_lin', type=str, default=None, help='LPIPS v0.1 vgg head weights (weights/v0.1/vgg.pth)')
     parser.add_argument('--ppl_n_sample', type=int, default=10000, help='paths per PPL figure (the reference hard-codes 10000)')
-    parser.add_argument('--seed', type=int, default=None, help='draw the codes of every PPL figure from this seed')
+    parser.add_argument('--seed', type=int, default=None, help='draw the codes of every figure from this seed')
+    if diversity:
+        parser.add_argument('--alexnet', type=str, default=None, help='torchvision alexnet state dict (default: the torch hub cache path)')
+        parser.add_argument('--lpips_alex_lin', type=str, default=None, help="the AlexNet LPIPS head file (the reference's metrics/lpips_weights.ckpt)")
+        parser.add_argument('--lpips_iters', type=int, default=1000, help='iterations of the diversity score (the reference hard-codes 1000)')
+        parser.add_argument('--lpips_group', type=int, default=40, help='images per group (the reference hard-codes 40: 780 pairs)')
     return parser
 
 
@@ -225,17 +272,17 @@ def checkpoints(ckpt, start_num):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(diversity=True).parse_args(argv)
     if args.fid:
         raise SystemExit('transeditor_amd.metrics: --fid is not built: it needs the patched Inception-v3 network, its weights and the '
                          'dataset statistics file (--inception), none of which this library has')
-    if args.lpips:
-        raise SystemExit("transeditor_amd.metrics: --lpips is not built: the diversity score uses the reference's AlexNet LPIPS "
-                         '(metrics/lpips.py), a different network and normalisation from the LPIPS-VGG this library has')
+    if args.lpips and args.lpips_alex_lin is None:
+        raise SystemExit("transeditor_amd.metrics: --lpips_alex_lin (the AlexNet LPIPS head file, the reference's metrics/lpips_weights.ckpt) "
+                         'is required; nothing is downloaded')
     configs = ppl_configurations(args)
-    if not configs:
-        raise SystemExit('transeditor_amd.metrics: nothing to do (give --ppl or --ppl_all)')
-    if args.lpips_lin is None:
+    if not configs and not args.lpips:
+        raise SystemExit('transeditor_amd.metrics: nothing to do (give --ppl, --ppl_all or --lpips)')
+    if configs and args.lpips_lin is None:
         raise SystemExit('transeditor_amd.metrics: --lpips_lin (the LPIPS v0.1 vgg head file) is required; nothing is downloaded')
     if not torch.cuda.is_available():
         raise RuntimeError('transeditor_amd.metrics needs a GPU (the generator and LPIPS run on the gfx950 kernels only)')
@@ -246,7 +293,11 @@ def main(argv=None):
     args.latent = 512
     args.token = 2 * (int(math.log(args.size, 2)) - 1)
     args.use_spatial_mapping = True                                             # :294 (whatever --no_spatial_map says)
-    percept = PerceptualLoss(model='net-lin', net='vgg', use_gpu=True, vgg_path=args.vgg16, lin_path=args.lpips_lin)
+    percept = PerceptualLoss(model='net-lin', net='vgg', use_gpu=True, vgg_path=args.vgg16, lin_path=args.lpips_lin) if configs else None
+    alex = None
+    if args.lpips:
+        from .lpips_alex import AlexLPIPS
+        alex = AlexLPIPS(args.alexnet, args.lpips_alex_lin)
     results = []
     for model_path in checkpoints(args.ckpt, args.start_num):
         g = Generator(args.size, args.latent, args.latent, args.token, channel_multiplier=args.channel_multiplier,
@@ -255,6 +306,13 @@ def main(argv=None):
                       no_trans=args.no_trans).to(device)
         load_checkpoint_into(model_path, g, device=device, g_ema_only_ok=True)
         sampler = GeneratorSampler(g)
+        if alex is not None:                                                    # :348-351
+            div = evaluate_diversity(sampler, alex, n_iter=args.lpips_iters, group=args.lpips_group, truncation=1.0, seed=args.seed,
+                                     latent=args.latent, para_num=args.para_num)
+            res = {'metric': 'lpips_diversity', 'ckpt': model_path, 'n_iter': args.lpips_iters, 'group': args.lpips_group,
+                   'all': div['all'], 'same_p': div['same_p'], 'same_z': div['same_z']}
+            print(json.dumps(res), flush=True)
+            results.append(res)
         for space, eval_plus, use_slerp, crop in configs:
             ppl, _ = evaluate_ppl(sampler, percept, space=space, eval_plus=eval_plus, use_slerp=use_slerp, crop=crop,
                                   n_sample=args.ppl_n_sample, batch=args.batch, seed=args.seed, latent=args.latent,
