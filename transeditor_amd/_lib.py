@@ -214,6 +214,14 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _aligned16(t):
+    """t, or a fresh (16-byte aligned) copy of it when its data is not: a contiguous view at an offset into its storage keeps
+    that offset through .contiguous()"""
+    if t is None or t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 # --------------------------------------------------------------------------------------------- K1
 _OTHER = {torch.float16: 'f16', torch.float64: 'f64'}       # K1 / K2 also exist in the reference's other two dispatch types
 
@@ -283,9 +291,11 @@ def bias_act_bwd_rgb_supported(shape):
 
 
 def bias_act_bwd_rgb(g, ref, grgb, wrgb, srgb, wscale, alpha, scale, want_bias=True):
-    """activation gradient with a ToRGB data gradient folded in (see te_hip.h); g may be None.  -> (gi, gb | None)"""
-    ref, grgb = ref.contiguous(), grgb.contiguous()
-    g = g.contiguous() if g is not None else None
+    """activation gradient with a ToRGB data gradient folded in (see te_hip.h); g may be None.  -> (gi, gb | None)
+    The kernel reads g, ref and grgb with 16-byte accesses and the ABI refuses misaligned ones: an operand whose data is not
+    16-byte aligned (an upstream gradient that is a view at an offset into its storage) is handed over as an aligned copy."""
+    ref, grgb = _aligned16(ref.contiguous()), _aligned16(grgb.contiguous())
+    g = _aligned16(g.contiguous()) if g is not None else None
     gi = torch.empty_like(ref)
     Cn = ref.shape[1]
     inner = 1
@@ -454,14 +464,6 @@ def conv_out_shape(kind, B, M, H, W):
     return (B, M, H, W)
 
 
-def _aligned16(t):
-    """t, or a fresh (16-byte aligned) copy of it when its data is not: a contiguous view at an offset into its storage keeps
-    that offset through .contiguous()"""
-    if t is None or t.data_ptr() % 16 == 0:
-        return t
-    return t.clone(memory_format=torch.contiguous_format)
-
-
 def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, mask_ref=None, mask_gain=1.0):
     """H, W = LOW-resolution size (see te_hip.h).  x [B,K,Hin,Win].  res: residual added after the activation; mask_ref:
     leaky-ReLU gradient mask (saved output of the layer this data gradient lands on) applied last.  The kinds that read
@@ -566,7 +568,8 @@ def rgb_supported(M, K, HW):
 
 
 def rgb_fwd(x, w, isc, bias, wscale=1.0):
-    x = x.contiguous()
+    """ToRGB forward [B,K,H,W] -> [B,3,H,W].  The kernel reads x with 16-byte accesses: a misaligned x goes in as an aligned copy."""
+    x = _aligned16(x.contiguous())
     B, K, H, W = x.shape
     out = torch.empty(B, 3, H, W, device=x.device, dtype=x.dtype)
     _check(lib().te_rgb_fwd_f32(_ptr(out), _ptr(x), _ptr(w.contiguous()), _ptr(isc), _ptr(bias), wscale, B, K, H * W, _stream()),
@@ -575,7 +578,9 @@ def rgb_fwd(x, w, isc, bias, wscale=1.0):
 
 
 def rgb_dgrad(g, w, isc, K, wscale=1.0):
-    g = g.contiguous()
+    """ToRGB data gradient [B,3,H,W] -> [B,K,H,W].  The kernel reads g with 16-byte accesses: a misaligned g goes in as an aligned
+    copy."""
+    g = _aligned16(g.contiguous())
     B, _, H, W = g.shape
     gx = torch.empty(B, K, H, W, device=g.device, dtype=g.dtype)
     _check(lib().te_rgb_dgrad_f32(_ptr(gx), _ptr(g), _ptr(w.contiguous()), _ptr(isc), wscale, B, K, H * W, _stream()),
@@ -594,8 +599,9 @@ def rgb_wgrad_sum_slabs(g3, x):
 
 
 def rgb_expand(x3, w3k, bias, act, wscale=1.0):
-    """from-RGB stem: x3 [B,3,H,W], w3k [3,K] -> act(wscale * sum_o w3k[o,k] x3[b,o] + bias[k])  [B,K,H,W]"""
-    x3 = x3.contiguous()
+    """from-RGB stem: x3 [B,3,H,W], w3k [3,K] -> act(wscale * sum_o w3k[o,k] x3[b,o] + bias[k])  [B,K,H,W].  The kernel reads x3
+    with 16-byte accesses: a misaligned x3 goes in as an aligned copy."""
+    x3 = _aligned16(x3.contiguous())
     B, _, H, W = x3.shape
     K = w3k.shape[1]
     out = torch.empty(B, K, H, W, device=x3.device, dtype=x3.dtype)
@@ -605,6 +611,8 @@ def rgb_expand(x3, w3k, bias, act, wscale=1.0):
 
 
 def rgb_wgrad_slabs(g, x):
+    """correlation slabs [B,S,3,K,1] of the ToRGB weight gradient.  Operands go in as they come: the kernel itself stages a
+    misaligned x through its scalar path (the same LDS tile, bit-identical slabs) and reads g element by element."""
     g, x = g.contiguous(), x.contiguous()
     B, K, H, W = x.shape
     S = lib().te_rgb_wgrad_slab_count(B, K, H * W)
