@@ -920,6 +920,76 @@ int64_t te_lpips_allpairs_ws_floats(int N, int C, int64_t HW);
 int te_lpips_allpairs_fwd_f32(float* partial, const float* fh, const float* w, int N, int C, int64_t HW, te_stream_t stream);
 int te_lpips_allpairs_dist_f32(float* D, const float* const* partial, const int* c, const int64_t* hw, int L, int N, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M9  the ArcFace IR-SE50 identity network of edit evaluation (pSp/models/encoders/model_irse.py:10-49 Backbone with
+ * pSp/models/encoders/helpers.py:16-120, applied by pSp/criteria/id_loss.py:8-21 behind the crop [35:223, 32:220] and
+ * AdaptiveAvgPool2d((112, 112)); pSp/scripts/calc_id_loss_parallel.py:58-67 takes the paired dot products).  The second convolution of
+ * a unit (3x3, stride 1 or 2, its batch norm folded in) and the 1x1 stride-s shortcut convolution are M4's te_conv2d_f32 with act 0,
+ * the squeeze is M2's te_adaptive_avgpool_f32 with OH = OW = 1, and output_layer (BatchNorm2d, Dropout in eval mode, Flatten, Linear,
+ * BatchNorm1d, folded exactly by the caller) is M2's te_fc_stream_f32 with act 0; here what is left (csrc/irse.hip).  Forward only
+ * (IDLoss.forward as a loss and every backward pass are not provided), NCHW fp32, no atomics, no workspace, bit-reproducible; an
+ * image's result is bitwise independent of the batch it is in.  Nothing is launched on a refusal.
+ *
+ * te_conv2d_prelu_f32 (helpers.py:86-90, :108-112: BatchNorm2d(in_channel), Conv2d(in_channel, depth, 3, 1, 1, bias=False), PReLU(depth);
+ * replaces the batch norm in FRONT of the zero-padded convolution, the convolution and the activation):
+ *     v[b,c,iy,ix] = fma(in_scale[c], x[b,c,iy,ix], in_shift[c])   for a tap INSIDE the image (one fma: a single rounding),
+ *                    exactly 0 for a tap of the padding          (in_scale == in_shift == NULL: v = x)
+ *     t = acc + bias[m],  acc = sum_{c,ky,kx} w[m,c,ky,kx] * v[b, c, oy*s + ky - py, ox*s + kx - px];   out = t > 0 ? t : slope[m] * t
+ * The shift cannot be folded into the bias: the padded taps do not carry it, so border outputs would differ.  x [B,Ci,H,W],
+ * w [Co,Ci,kh,kw], bias, slope [Co], in_scale, in_shift [Ci]; out a contiguous [B,Co,Ho,Wo] (no channel slice, no `act`).  This is
+ * te_conv2d_f32's main loop (csrc/conv2d_body.h) with another gather and another epilogue, the k permutation untouched: without the
+ * affine the accumulators are te_conv2d_f32's bit for bit and the result is bitwise prelu(te_conv2d_f32(act = 0)); the product
+ * slope[m] * t is one rounding.  A NaN propagates (it fails t > 0, and slope * NaN is a NaN): a NaN pixel reaches exactly the outputs
+ * whose window holds it.  Kernel sizes, strides, padding rules and size limits are te_conv2d_f32's (s other than 1 or 2, a kernel above
+ * 7 x 7: TE_ERR_UNSUPPORTED; padding >= the kernel, Ho or Wo < 1, a non-positive size, sizes past 31 bits: TE_ERR_SHAPE); a NULL out, x,
+ * w, bias or slope, or exactly one of in_scale and in_shift: TE_ERR_NULL.
+ *
+ * te_id_stem_fwd_f32 (id_loss.py:18-19 and model_irse.py:21-23 input_layer; replaces the crop, AdaptiveAvgPool2d((Pn, Pn)) and
+ * Conv2d(3, Co, 3, 1, 1, bias=False) + BatchNorm2d + PReLU, the batch norm folded into w and b by the caller): img [N,3,H,W],
+ * w [Co,3,3,3], b, slope [Co]; out [N,Co,Pn,Pn].  With Lh = y1 - y0, Lw = x1 - x0:
+ *     p[n,c,i,j] = (sum of img[n, c, y0 + floor(i Lh / Pn) : y0 + ceil((i + 1) Lh / Pn), x0 + floor(j Lw / Pn) : x0 + ceil((j + 1) Lw / Pn)],
+ *                   row-major in fp32) / the count                                     torch's rule per axis, as te_adaptive_avgpool_f32
+ *     t = b[o] + sum_{c,ky,kx} w[o,c,ky,kx] * p[n, c, y + ky - 1, x + kx - 1]   (0 outside the Pn x Pn plane);   out = t > 0 ? t : slope[o] * t
+ * An implicit GEMM with K = 27 whose gather averages a tap's window on the way into LDS; image pixels outside the window are never
+ * read.  The result is bitwise te_conv2d_prelu_f32(te_adaptive_avgpool_f32(the contiguous crop), NULL, NULL, ...).  TE_ERR_SHAPE for an
+ * empty window (y1 <= y0 or x1 <= x0), a window outside the image, Pn < 1, Pn or a window side above 32768, N < 1 or N >= 65536,
+ * Co < 1, 3 * H * W past 31 bits; TE_ERR_NULL for a NULL pointer.
+ *
+ * te_se_excite_f32 (helpers.py:57-72 SEModule without its final product; replaces fc1, ReLU, fc2 and the sigmoid on the pooled vector):
+ *     gate[b,c] = sigmoid(sum_r w2[c,r] * relu(sum_k w1[r,k] * pooled[b,k]))
+ * pooled [B,C] (te_adaptive_avgpool_f32 with OH = OW = 1), w1 [R,C], w2 [C,R], neither with a bias (helpers.py:61-63); gate [B,C].
+ * Shaped for latency: one workgroup of four waves per image; a hidden unit is one wave's dot product (lane l takes k = l, l + 64, ...
+ * as one fma chain, the lanes meet in a fixed butterfly), a gate one thread's fma chain over r in ascending order.  The sigmoid is
+ * 1 / (1 + exp(-z)) for z >= 0 and e / (1 + e), e = exp(z), for z < 0, so nothing overflows: a logit of +-100 gives a finite gate in
+ * [0, 1].  A NaN in pooled[b] makes the gates of image b NaN and no other (relu keeps a NaN); a row is bitwise independent of B.
+ * B, C >= 1, 1 <= R <= 1024 (the hidden units live in LDS) and C * R below 2^31, else TE_ERR_SHAPE.
+ *
+ * te_se_scale_add_f32 (helpers.py:73 `module_input * x` and :92-95, :117-120 `res + shortcut`, with MaxPool2d(1, stride) at :80, :102):
+ *     out[b,c,y,x] = res[b,c,y,x] * gate[b,c] + sc[b, c, s*y, s*x]
+ * res, out [B,C,Ho,Wo], gate [B,C] or NULL (mode 'ir': out = res + sc), sc [B,C,Hs,Ws].  s = 1: the shortcut is the 1x1 convolution +
+ * batch norm output; s = 2: it is the unit's input seen through MaxPool2d(1, 2).  The product and the sum are two separately rounded
+ * fp32 operations (no fma).  Refused (TE_ERR_SHAPE) unless Ho == (Hs - 1) / s + 1 and Wo == (Ws - 1) / s + 1, all sizes positive, a plane
+ * below 2^31 and the shortcut at most 2^40 elements; s other than 1 or 2 is TE_ERR_UNSUPPORTED.  Memory bound: where s == 1, Wo % 4 == 0
+ * and out, res, sc are 16-byte aligned a thread moves 16 bytes of each; elsewhere one element.  One thread per work item with 64-bit
+ * offsets, no thread loops (as te_avgpool2_act_f32).
+ *
+ * te_rows_unit_f32 (helpers.py:16-19 l2_norm): out[i,:] = a[i,:] / norm_i, norm_i = (float)sqrt(sum_d (double)a[i,d]^2): the squares
+ * are exact in fp64, their sum is taken in fp64 (a chain per lane, a fixed butterfly over the 64 lanes), the root rounded to fp32
+ * once, then one fp32 division per element.  A zero row gives NaN (0 / 0), as the reference's does.  out may be a.
+ * te_rows_dot_f32 (id_loss.py:34-36, calc_id_loss_parallel.py:67): out[i] = sum_d a[i,d] * b[i,d], one wave per row: the products are
+ * exact in fp64, summed in fp64 in the same fixed shape and rounded to fp32 once.  Both: a, b, out rows of D contiguous floats,
+ * 1 <= I < 2^31, D >= 1, else TE_ERR_SHAPE; a row's result is bitwise independent of I.
+ */
+int te_conv2d_prelu_f32(float* out, const float* x, const float* w, const float* bias, const float* slope, const float* in_scale,
+                        const float* in_shift, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, te_stream_t stream);
+int te_id_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, const float* slope, int N, int H, int W, int y0, int y1,
+                       int x0, int x1, int Pn, int Co, te_stream_t stream);
+int te_se_excite_f32(float* gate, const float* pooled, const float* w1, const float* w2, int B, int C, int R, te_stream_t stream);
+int te_se_scale_add_f32(float* out, const float* res, const float* gate, const float* sc, int B, int C, int Ho, int Wo, int Hs, int Ws, int s,
+                        te_stream_t stream);
+int te_rows_unit_f32(float* out, const float* a, int64_t I, int D, te_stream_t stream);
+int te_rows_dot_f32(float* out, const float* a, const float* b, int64_t I, int D, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,12 @@ _SIGNATURES = {
     'te_lpips_allpairs_ws_floats': (C.c_int64, [_I, _I, _L]),
     'te_lpips_allpairs_fwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _L, _P]),
     'te_lpips_allpairs_dist_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    'te_conv2d_prelu_f32': (C.c_int, [_P] * 7 + [_I] * 10 + [_P]),
+    'te_id_stem_fwd_f32': (C.c_int, [_P] * 5 + [_I] * 9 + [_P]),
+    'te_se_excite_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    'te_se_scale_add_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 7 + [_P]),
+    'te_rows_unit_f32': (C.c_int, [_P, _P, _L, _I, _P]),
+    'te_rows_dot_f32': (C.c_int, [_P, _P, _P, _L, _I, _P]),
     # loop-trip queries (host only)
     'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
     'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
@@ -1341,6 +1347,81 @@ def lpips_allpairs_dist(partials, shapes, N):
     return D
 
 
+# --------------------------------------------------------------------------------------------- M9 ArcFace IR-SE50 identity network
+def conv2d_prelu(x, w, bias, slope, in_scale=None, in_shift=None, stride=1, pad=(0, 0)):
+    """prelu(conv2d(v, w, stride, pad) + bias, slope) with v = in_scale[c] * x + in_shift[c] inside the image and 0 in the padding (both
+    None: v = x): x [B,Ci,H,W], w [Co,Ci,kh,kw], bias, slope [Co], in_scale, in_shift [Ci] -> a new [B,Co,Ho,Wo] tensor.  The ABI
+    refuses what te_conv2d_f32 refuses and an affine given by half; nothing is launched then."""
+    if x.ndim != 4 or w.ndim != 4 or x.shape[1] != w.shape[1] or bias.shape != (w.shape[0],) or slope.shape != (w.shape[0],) \
+            or any(t is not None and t.shape != (x.shape[1],) for t in (in_scale, in_shift)):
+        raise RuntimeError(f'te_hip: conv2d_prelu: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, '
+                           f'slope {tuple(slope.shape)}, affine {[None if t is None else tuple(t.shape) for t in (in_scale, in_shift)]}')
+    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
+    _check(lib().te_conv2d_prelu_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), B, Ci, Co, H, W,
+                                     kh, kw, stride, pad[0], pad[1], _stream()), 'te_conv2d_prelu_f32')
+    return out
+
+
+def id_stem_fwd(img, w, b, slope, box, pool):
+    """the window box = (y0, y1, x0, x1) of img [N,3,H,W] -> adaptive average to pool x pool -> 3x3 pad-1 convolution -> bias -> PReLU:
+    w [Co,3,3,3], b, slope [Co] -> [N,Co,pool,pool].  The ABI refuses an empty window and one outside the image; nothing is launched
+    then."""
+    if img.ndim != 4 or img.shape[1] != 3 or w.ndim != 4 or tuple(w.shape[1:]) != (3, 3, 3) or b.shape != (w.shape[0],) \
+            or slope.shape != (w.shape[0],):
+        raise RuntimeError(f'te_hip: id_stem_fwd: inconsistent shapes img {tuple(img.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}, '
+                           f'slope {tuple(slope.shape)}')
+    img = img.contiguous()
+    (N, _, H, W), Co = img.shape, w.shape[0]
+    y0, y1, x0, x1 = box
+    out = torch.empty(N, Co, max(pool, 0), max(pool, 0), device=img.device, dtype=img.dtype)
+    _check(lib().te_id_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), _ptr(slope), N, H, W, y0, y1, x0, x1, pool, Co, _stream()),
+           'te_id_stem_fwd_f32')
+    return out
+
+
+def se_excite(pooled, w1, w2):
+    """sigmoid(relu(pooled @ w1.T) @ w2.T): pooled [B,C], w1 [R,C], w2 [C,R] -> the gates [B,C]"""
+    if pooled.ndim != 2 or w1.ndim != 2 or w2.ndim != 2 or w1.shape[1] != pooled.shape[1] or tuple(w2.shape) != (w1.shape[1], w1.shape[0]):
+        raise RuntimeError(f'te_hip: se_excite: inconsistent shapes pooled {tuple(pooled.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}')
+    (B, Cn), R = pooled.shape, w1.shape[0]
+    gate = torch.empty(B, Cn, device=pooled.device, dtype=pooled.dtype)
+    _check(lib().te_se_excite_f32(_ptr(gate), _ptr(pooled), _ptr(w1), _ptr(w2), B, Cn, R, _stream()), 'te_se_excite_f32')
+    return gate
+
+
+def se_scale_add(res, gate, sc, stride=1):
+    """res * gate[:, :, None, None] + sc[:, :, ::stride, ::stride] (gate None: res + sc[...]): res [B,C,Ho,Wo], gate [B,C],
+    sc [B,C,Hs,Ws] -> a new [B,C,Ho,Wo] tensor.  The ABI refuses a shortcut whose size does not match; nothing is launched then."""
+    if res.ndim != 4 or sc.ndim != 4 or tuple(sc.shape[:2]) != tuple(res.shape[:2]) or gate is not None and tuple(gate.shape) != tuple(res.shape[:2]):
+        raise RuntimeError(f'te_hip: se_scale_add: inconsistent shapes res {tuple(res.shape)}, gate '
+                           f'{None if gate is None else tuple(gate.shape)}, sc {tuple(sc.shape)}')
+    (B, Cn, Ho, Wo), (Hs, Ws) = res.shape, sc.shape[2:]
+    out = torch.empty_like(res)
+    _check(lib().te_se_scale_add_f32(_ptr(out), _ptr(res), _ptr(gate), _ptr(sc), B, Cn, Ho, Wo, Hs, Ws, stride, _stream()),
+           'te_se_scale_add_f32')
+    return out
+
+
+def rows_unit(a):
+    """a / ||a||_2 per row of a [I,D] (the norm's square summed in fp64); a zero row gives NaN"""
+    if a.ndim != 2:
+        raise RuntimeError(f'te_hip: rows_unit expects [I,D], got {tuple(a.shape)}')
+    out = torch.empty_like(a)
+    _check(lib().te_rows_unit_f32(_ptr(out), _ptr(a), a.shape[0], a.shape[1], _stream()), 'te_rows_unit_f32')
+    return out
+
+
+def rows_dot(a, b):
+    """sum_d a[i,d] * b[i,d] of a, b [I,D] -> [I]"""
+    if a.ndim != 2 or tuple(a.shape) != tuple(b.shape):
+        raise RuntimeError(f'te_hip: rows_dot expects two [I,D] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}')
+    out = torch.empty(a.shape[0], device=a.device, dtype=a.dtype)
+    _check(lib().te_rows_dot_f32(_ptr(out), _ptr(a), _ptr(b), a.shape[0], a.shape[1], _stream()), 'te_rows_dot_f32')
+    return out
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
@@ -1357,7 +1438,8 @@ def _install_roctx():
              'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
              'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score',
              'attr_stem_fwd', 'avgpool2_act', 'attr_score', 'conv2d_res', 'pose_stem_fwd', 'maxpool3s2p1',
-             'alex_stem_fwd', 'lpips_unit', 'lpips_allpairs_fwd', 'lpips_allpairs_dist']
+             'alex_stem_fwd', 'lpips_unit', 'lpips_allpairs_fwd', 'lpips_allpairs_dist',
+             'conv2d_prelu', 'id_stem_fwd', 'se_excite', 'se_scale_add', 'rows_unit', 'rows_dot']
     g = globals()
 
     def wrap(fn, name):

@@ -1,0 +1,255 @@
+"""The ArcFace identity network of edit evaluation on the gfx950 kernels (the reference's pSp/models/encoders/model_irse.py:10-49 Backbone
+with helpers.py:16-120, as pSp/criteria/id_loss.py:8-21 applies it: Backbone(112, 50, mode='ir_se') behind the crop [35:223, 32:220] and
+AdaptiveAvgPool2d((112, 112))): is an edited image still the same person?
+
+    net = ArcFaceID('model_ir_se50.pth')                            # the reference's own weight file
+    e = net(images)                                                 # [B,3,S,S] in [-1, 1] -> [B,512] unit rows on the device
+    s = net.similarity(net(a), net(b))                              # [B]: the paired dot products (calc_id_loss_parallel.py:67)
+    f = edit_eval.feature_sweeps(net, origin, sweeps, batch=16)     # an instance is an `embed` of transeditor_amd.edit_eval
+
+    python -m transeditor_amd.arcface --weights model_ir_se50.pth --a A.pt --b B.pt [--batch 16]
+
+Weights come from a local file with the reference Backbone's keys (input_layer.{0,1,2}, body.N.res_layer.{0,1,2,3,4},
+body.N.res_layer.5.fc{1,2}, body.N.shortcut_layer.{0,1}, output_layer.{0,3,4}; num_batches_tracked is ignored); nothing is downloaded.
+The geometry is read from the shapes: the units are body.0, body.1, ... as long as the keys go on, a unit's (in, depth) are its first
+convolution's, it has a squeeze-and-excitation where it has res_layer.5 (mode 'ir' has none) and a convolution shortcut where it has
+shortcut_layer.0.  A stride is not stored in a state dict; the reference's rule is taken (helpers.py:26-27 get_block: the first unit of
+a stage has stride 2, and a stage starts at body.0 and wherever in != depth), which gives get_blocks(50) for the real file; `units`
+names another list of (in, depth, stride), which must be the one the keys describe.  An output_layer.4 without weight and bias is taken
+as affine-less (IR_SE_50() builds it so, IDLoss with affine=True).
+
+Layers: te_id_stem_fwd_f32 (the crop, the adaptive average and input_layer in one pass), then per unit te_conv2d_prelu_f32 (the
+leading BatchNorm2d as an affine GATHER in front of the zero-padded convolution: its shift cannot be a bias, the padded taps do not
+carry it; then PReLU), te_conv2d_f32 (the second convolution, stride 1 or 2, its batch norm folded in), te_adaptive_avgpool_f32 to 1 x 1
+and te_se_excite_f32 (the gates), the shortcut (the unit's input read with the stride, or te_conv2d_f32 1x1 with its batch norm folded)
+and te_se_scale_add_f32 (res * gate + shortcut).  output_layer is folded exactly on the host in fp64 (BatchNorm2d into the columns of
+the Linear - there is no padding there -, BatchNorm1d into its rows and bias; Dropout is the identity in eval mode) and runs as
+te_fc_stream_f32; te_rows_unit_f32 normalises.  Every convolution is the exact-fp32 implicit GEMM of csrc/conv2d_body.h.  An image's
+embedding is bitwise the same whatever batch it is in.  Eval only: there is no backward pass, so IDLoss.forward as a training loss is
+not provided.  Measured deviations and times: profiles/README.md, 'Identity embedding'.
+"""
+import argparse
+import json
+import sys
+
+import torch
+
+from . import _lib
+from .frozen_net import check_images, no_gpu, resolve, weight_bias
+from .inception_features import fold_bn
+
+BN_EPS = 1e-5
+BOX = (35, 223, 32, 220)                                              # id_loss.py:18: rows 35:223, columns 32:220
+POOL = 112                                                            # id_loss.py:14
+_NO_GPU = no_gpu('ArcFaceID')
+_HINT = 'not a Backbone state dict: input_layer.*, body.N.res_layer.*, output_layer.*'
+_BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
+
+
+def default_units():
+    """helpers.py:30-37 get_blocks(50): [(in, depth, stride)] * 24"""
+    out = []
+    for cin, depth, n in ((64, 64, 3), (64, 128, 4), (128, 256, 14), (256, 512, 3)):
+        out += [(cin, depth, 2)] + [(depth, depth, 1)] * (n - 1)
+    return out
+
+
+def _out_side(h, units):
+    for _, _, s in units:
+        h = (h - 1) // s + 1
+    return h
+
+
+def parse_state_dict(sd, path='state_dict', units=None, pool=POOL, dtype=torch.float32):
+    """-> dict(stem (w', b', slope), units [dict(cin, depth, stride, scale, shift, w1, slope, w2, b2, fc1, fc2, sc)], fc (w'', b''), keys):
+    the batch norms folded as the module docstring says, `keys` the set of keys that were read; ValueError naming the key that is missing,
+    has the wrong shape or does not fit the unit list.  dtype=torch.float64: the folded values before their one rounding"""
+    read = set()
+
+    def get(key, shape):
+        read.add(key)
+        return weight_bias(sd, key, None, shape, 'ArcFaceID', path, _HINT)
+
+    def bn(key, c):
+        return [get(f'{key}.{t}', (c,)) for t in _BN_KEYS]
+
+    def affine(key, c):
+        """an eval-mode batch norm as (scale, shift) in fp64"""
+        g, b, m, v = (t.detach().double().cpu() for t in bn(key, c))
+        scale = g / torch.sqrt(v + BN_EPS)
+        return scale, b - m * scale
+    w0 = get('input_layer.0.weight', (None, 3, 3, 3))
+    c0 = w0.shape[0]
+    stem = (*fold_bn(w0, *bn('input_layer.1', c0), eps=BN_EPS, dtype=dtype), get('input_layer.2.weight', (c0,)).detach().to(dtype).contiguous())
+    if units is not None:
+        units = [tuple(int(v) for v in u) for u in units]
+        if not units or any(len(u) != 3 or u[0] < 1 or u[1] < 1 or u[2] not in (1, 2) for u in units):
+            raise ValueError(f'ArcFaceID: units must be a list of (in, depth, stride) with stride 1 or 2, got {units!r}')
+    parsed, ci, n = [], c0, 0
+    while f'body.{n}.res_layer.1.weight' in sd or (units is not None and n < len(units)):
+        p = f'body.{n}'
+        w1 = get(f'{p}.res_layer.1.weight', (None, None, 3, 3))
+        depth, cin = w1.shape[:2]
+        if cin != ci:
+            raise ValueError(f'ArcFaceID: {p}.res_layer.1.weight is {tuple(w1.shape)}: the unit takes {cin} channels, the layer before it gives {ci}')
+        stride = 2 if n == 0 or cin != depth else 1
+        if units is not None:
+            if n >= len(units):
+                raise ValueError(f'ArcFaceID: {path} has {p}.res_layer.1.weight, past the {len(units)} units that were named')
+            if units[n][:2] != (cin, depth):
+                raise ValueError(f'ArcFaceID: {p}.res_layer.1.weight is {tuple(w1.shape)}, which is not unit {n} of the list, {units[n]}')
+            stride = units[n][2]
+        scale, shift = affine(f'{p}.res_layer.0', cin)
+        u = dict(cin=cin, depth=depth, stride=stride, scale=scale.to(dtype).contiguous(), shift=shift.to(dtype).contiguous(),
+                 w1=w1.detach().to(dtype).contiguous(), slope=get(f'{p}.res_layer.2.weight', (depth,)).detach().to(dtype).contiguous())
+        u['w2'], u['b2'] = fold_bn(get(f'{p}.res_layer.3.weight', (depth, depth, 3, 3)), *bn(f'{p}.res_layer.4', depth), eps=BN_EPS, dtype=dtype)
+        u['fc1'] = u['fc2'] = u['sc'] = None
+        if f'{p}.res_layer.5.fc1.weight' in sd or f'{p}.res_layer.5.fc2.weight' in sd:
+            fc1 = get(f'{p}.res_layer.5.fc1.weight', (None, depth, 1, 1))
+            fc2 = get(f'{p}.res_layer.5.fc2.weight', (depth, fc1.shape[0], 1, 1))
+            u['fc1'], u['fc2'] = (t.detach().to(dtype).reshape(t.shape[:2]).contiguous() for t in (fc1, fc2))
+        if cin != depth or f'{p}.shortcut_layer.0.weight' in sd:
+            u['sc'] = fold_bn(get(f'{p}.shortcut_layer.0.weight', (depth, cin, 1, 1)), *bn(f'{p}.shortcut_layer.1', depth), eps=BN_EPS, dtype=dtype)
+        parsed.append(u)
+        ci, n = depth, n + 1
+    if not parsed:
+        raise ValueError(f'ArcFaceID: {path} has no body.0.res_layer.1.weight ({_HINT})')
+    # output_layer: BatchNorm2d(ci) -> Flatten -> Linear(ci * h * h, D) -> BatchNorm1d(D), folded in fp64 and rounded once
+    h = _out_side(pool, [(u['cin'], u['depth'], u['stride']) for u in parsed])
+    read.add('output_layer.3.bias')
+    wl, bl = weight_bias(sd, 'output_layer.3.weight', 'output_layer.3.bias', (None, ci * h * h), 'ArcFaceID', path, _HINT,
+                         want=f'[D, {ci} * {h} * {h}]: {len(parsed)} units take a {pool} px plane to {h} px')
+    read.add('output_layer.3.weight')
+    D = wl.shape[0]
+    if (ci * h * h) % 4:
+        raise ValueError(f'ArcFaceID: output_layer.3.weight is {tuple(wl.shape)}: the flattened features must be a multiple of 4')
+    s2, t2 = affine('output_layer.0', ci)
+    wl, bl = wl.double(), bl.double()
+    bl = bl + wl @ t2.repeat_interleave(h * h)
+    wl = wl * s2.repeat_interleave(h * h).view(1, -1)
+    has = [f'output_layer.4.{t}' in sd for t in ('weight', 'bias')]
+    if has[0] != has[1]:
+        raise ValueError(f'ArcFaceID: {path} has only one of output_layer.4.weight / output_layer.4.bias')
+    mean, var = (get(f'output_layer.4.{t}', (D,)).detach().double().cpu() for t in ('running_mean', 'running_var'))
+    g1 = 1.0 / torch.sqrt(var + BN_EPS)
+    b1 = torch.zeros(D, dtype=torch.float64)
+    if has[0]:
+        g1 = g1 * get('output_layer.4.weight', (D,)).detach().double().cpu()
+        b1 = get('output_layer.4.bias', (D,)).detach().double().cpu()
+    fc = ((wl * g1.view(-1, 1)).to(dtype).contiguous(), ((bl - mean) * g1 + b1).to(dtype).contiguous())
+    return dict(stem=stem, units=parsed, fc=fc, keys=read, affine=has[0], side=h)
+
+
+class ArcFaceID(torch.nn.Module):
+    def __init__(self, path=None, state_dict=None, box=BOX, pool=POOL, units=None):
+        super().__init__()
+        if not isinstance(pool, int) or not 1 <= pool <= 32768:
+            raise ValueError(f'ArcFaceID: pool must be an integer in [1, 32768], got {pool!r}')
+        box = tuple(box)
+        if len(box) != 4 or not all(isinstance(v, int) for v in box) or not (0 <= box[0] < box[1] and 0 <= box[2] < box[3]):
+            raise ValueError(f'ArcFaceID: box must be (y0, y1, x0, x1) with 0 <= y0 < y1 and 0 <= x0 < x1, got {box!r}')
+        state_dict, path = resolve(path, state_dict, 'ArcFaceID', 'ArcFace IR-SE weight')
+        net = parse_state_dict(state_dict, path, units, pool)
+        self.box, self.pool, self.keys, self.affine = box, pool, frozenset(net['keys']), net['affine']
+        self.units = tuple((u['cin'], u['depth'], u['stride']) for u in net['units'])
+        self.se = tuple(u['fc1'] is not None for u in net['units'])
+        self.dim = net['fc'][0].shape[0]
+        for name, t in zip(('stem_w', 'stem_b', 'stem_slope', 'fc_w', 'fc_b'), (*net['stem'], *net['fc'])):
+            self.register_buffer(name, t)
+        for i, u in enumerate(net['units']):
+            for k in ('scale', 'shift', 'w1', 'slope', 'w2', 'b2', 'fc1', 'fc2'):
+                if u[k] is not None:
+                    self.register_buffer(f'u{i}_{k}', u[k])
+            self.register_buffer(f'u{i}_zero', torch.zeros(u['depth']))             # the first convolution has no bias
+            if u['sc'] is not None:
+                self.register_buffer(f'u{i}_sc_w', u['sc'][0])
+                self.register_buffer(f'u{i}_sc_b', u['sc'][1])
+        self.eval()
+        if torch.cuda.is_available():
+            self.to('cuda')
+
+    def _unit(self, i, x):
+        """bottleneck_IR(_SE).forward.  An activation is dropped once its last reader has run: the first convolution's output when the
+        second has read it, the unit's input (or its convolved shortcut) and the residual branch after the final addition."""
+        def g(k):
+            return getattr(self, f'u{i}_{k}', None)
+        stride = self.units[i][2]
+        t = _lib.conv2d_prelu(x, g('w1'), g('zero'), g('slope'), g('scale'), g('shift'), 1, (1, 1))
+        r = _lib.conv2d(t, g('w2'), g('b2'), stride, (1, 1), act=0)
+        del t
+        gate = None
+        if self.se[i]:
+            gate = _lib.se_excite(_lib.adaptive_avgpool(r, 1, 1).view(r.shape[0], -1), g('fc1'), g('fc2'))
+        if g('sc_w') is not None:
+            x, stride = _lib.conv2d(x, g('sc_w'), g('sc_b'), stride, (0, 0), act=0), 1
+        return _lib.se_scale_add(r, gate, x, stride)
+
+    @torch.no_grad()
+    def embed(self, images):
+        """[B,3,S,S] in [-1, 1] -> [B,D] fp32 unit rows on the device"""
+        check_images(images, 'ArcFaceID', '[B,3,S,S]', square=True)
+        S = images.shape[2]
+        if self.box[1] > S or self.box[3] > S:
+            raise ValueError(f'ArcFaceID: the box {self.box} does not lie inside a {S} px image')
+        if not images.is_cuda:
+            raise RuntimeError(_NO_GPU)
+        a = _lib.id_stem_fwd(images.detach().float(), self.stem_w, self.stem_b, self.stem_slope, self.box, self.pool)
+        for i in range(len(self.units)):
+            a = self._unit(i, a)
+        return _lib.rows_unit(_lib.fc_stream(a.view(a.shape[0], -1), self.fc_w, self.fc_b, act=0))
+
+    forward = embed
+
+    @torch.no_grad()
+    def similarity(self, a, b):
+        """the paired dot products of two sets of embeddings [B,D] -> [B] (id_loss.py:34-36, calc_id_loss_parallel.py:67)"""
+        if a.ndim != 2 or tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f'ArcFaceID: similarity expects two [B,D] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}')
+        if not (a.is_cuda and b.is_cuda):
+            raise RuntimeError(_NO_GPU)
+        return _lib.rows_dot(a.detach().float().contiguous(), b.detach().float().contiguous())
+
+
+# ------------------------------------------------------------------------------------------------------------------------ CLI
+def build_parser():
+    parser = argparse.ArgumentParser(description='identity similarity of two sets of images with the ArcFace IR-SE50 network '
+                                                 '(pSp/criteria/id_loss.py:8-21, pSp/scripts/calc_id_loss_parallel.py:58-67, :100-103)')
+    parser.add_argument('--weights', required=True, help="the Backbone state dict in the reference's layout (model_ir_se50.pth)")
+    parser.add_argument('--a', required=True, help='a torch file holding [N,3,S,S] images in [-1, 1]')
+    parser.add_argument('--b', required=True, help='a second file of the same shape: image i of --a is paired with image i of --b')
+    parser.add_argument('--batch', type=int, default=16)
+    parser.add_argument('--box', type=int, nargs=4, default=list(BOX), metavar=('Y0', 'Y1', 'X0', 'X1'), help='the crop in front of the pool')
+    parser.add_argument('--pool', type=int, default=POOL, help='side of the plane the network sees')
+    return parser
+
+
+def result_line(scores):
+    """calc_id_loss_parallel.py:100-103 (np.mean, np.std: the population deviation)"""
+    s = torch.as_tensor(scores, dtype=torch.float64)
+    return 'New Average score is {:.2f}+-{:.2f}'.format(float(s.mean()), float(s.std(unbiased=False)))
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.batch < 1:
+        raise SystemExit('--batch must be positive')
+    if not torch.cuda.is_available():
+        raise RuntimeError(_NO_GPU)
+    net = ArcFaceID(args.weights, box=tuple(args.box), pool=args.pool)
+    a, b = (torch.load(p, map_location='cpu') for p in (args.a, args.b))
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.shape != b.shape:
+        raise SystemExit('--a and --b must hold two image tensors of one shape')
+    sims = []
+    for at in range(0, a.shape[0], args.batch):
+        ea, eb = (net(t[at:at + args.batch].to('cuda')) for t in (a, b))
+        sims.append(net.similarity(ea, eb).double().cpu())
+    sims = torch.cat(sims)
+    print(result_line(sims))
+    print(json.dumps({'metric': 'arcface_id_similarity', 'n': int(sims.numel()), 'mean': float(sims.mean()),
+                      'std': float(sims.std(unbiased=False)), 'units': len(net.units), 'dim': net.dim, 'box': list(net.box),
+                      'pool': net.pool}))
+    return sims
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])
