@@ -38,6 +38,117 @@ def test_binding_table_matches_header(libpath):
     assert _lib.lib().te_version() == 3
 
 
+def _declared_prototypes():
+    """{name: parameter list text} by a regex of this file's own (not the product's parser), on the header without comments"""
+    header = open(os.path.join(ROOT, 'include', 'te_hip.h')).read()
+    header = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', header, flags=re.S))
+    return dict(re.findall(r'\b(te_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', header))
+
+
+def test_bindings_pinned_by_hand():
+    """the prototypes lib() binds are READ from include/te_hip.h; a dozen of them written out here by hand, one for every type of the
+    vocabulary and for the awkward shapes (no arguments, char* results, runs of doubles, out-parameters, pointer arrays, 24 arguments)"""
+    from transeditor_amd import _abi
+    P, I, L, F, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
+    table = _abi.parse(open(os.path.join(ROOT, 'include', 'te_hip.h')).read())
+    want = {
+        'te_version': (I, []),
+        'te_last_error_string': (ctypes.c_char_p, []),
+        'te_arch': (ctypes.c_char_p, []),
+        'te_bias_act_bwd_ws_floats': (L, [L, L, L]),
+        'te_mt_adam_f32': (I, [P, P, I, I, I, D, D, D, D, I, P]),
+        'te_svm_smo_f64': (I, [P, P, P, P, P, I, D, D, L, P]),
+        'te_upfirdn2d_f32': (I, [P, P, P, L, I, I, I, I, I, I, I, I, I, I, I, I, I, P, L, I, F, F, P]),
+        'te_small_gemm_batched_f32': (I, [P, P, P, P, I, L, L, L, L, P, P, I, I, I, L, L, L, L, L, L, F, F, I, P]),
+        'te_wgrad_group_plan': (I, [I, I, I, I, I, I, P, P]),
+        'te_lpips_allpairs_dist_f32': (I, [P, P, P, P, I, I, P]),
+        'te_conv2d_prelu_f32': (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+        'te_fid_moments_f64': (I, [P, P, P, P, L, I, I, P]),
+    }
+    assert len(want['te_upfirdn2d_f32'][1]) == 23 and len(want['te_small_gemm_batched_f32'][1]) == 24
+    for name, (res, args) in want.items():
+        got_res, got_args = table[name]
+        assert got_res is res, name
+        assert len(got_args) == len(args) and all(a is b for a, b in zip(got_args, args)), (name, got_args)
+
+
+def test_every_binding_has_the_declared_number_of_arguments(libpath):
+    from transeditor_amd import _lib
+    declared = _declared_prototypes()
+    assert tuple(declared) == _lib.EXPORTS and len(declared) >= 134          # header order
+    L = _lib.lib()
+    for name, params in declared.items():
+        n = 0 if params.strip() == 'void' else params.count(',') + 1       # (no nested parentheses: every comma is top-level)
+        assert len(getattr(L, name).argtypes) == n, name
+
+
+def test_header_parser_on_synthetic_headers():
+    from transeditor_amd import _abi
+    P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    text = """
+    #ifndef X
+    #define TE_ABI_VERSION 7
+    /* int te_in_block_comment(int a);
+       te_bias_act_bwd_ws_floats(outer, C, inner) floats */
+    // int te_in_line_comment(int a);
+    typedef void* te_stream_t;
+    enum { TE_A = 0, TE_B = 1 };
+    int64_t
+    te_four_lines(const float* const* p,     /* a comment between parameters */
+                  int64_t const n, float w[3],
+                  te_stream_t stream);
+    const char* te_name(void);
+    double te_unnamed(int, const double*, float, int64_t);
+    int te_empty();
+    #endif
+    """
+    table = _abi.parse(text)
+    assert list(table) == ['te_four_lines', 'te_name', 'te_unnamed', 'te_empty']
+    assert table['te_four_lines'] == (L, [P, L, P, P])
+    assert table['te_name'] == (ctypes.c_char_p, [])
+    assert table['te_unnamed'] == (ctypes.c_double, [I, P, F, L])
+    assert table['te_empty'] == (I, [])
+    assert _abi.abi_version(text) == 7
+    for bad in ('int te_bad(size_t n);', 'int te_bad(int a, struct foo x);', 'int te_bad(unsigned int n);', 'void te_bad(int n);',
+                'float* te_bad(int n);', 'int te_bad(int (*cb)(int));'):
+        with pytest.raises(RuntimeError, match='te_bad'):
+            _abi.parse(bad)
+    with pytest.raises(RuntimeError, match='TE_ABI_VERSION'):
+        _abi.abi_version('int te_version(void);')
+
+
+def test_missing_header_and_stale_library_are_refused(libpath, monkeypatch, tmp_path):
+    """lib() refuses to bind without the header, and a library whose te_version() is not the header's TE_ABI_VERSION"""
+    from transeditor_amd import _lib
+    header = open(os.path.join(ROOT, 'include', 'te_hip.h')).read()
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, 'include', 'te_hip.h'))
+    monkeypatch.setattr(_lib, '_lib', None)
+    monkeypatch.setattr(_lib, '_protos', None)
+    monkeypatch.setattr(_lib, 'HEADER_PATH', str(tmp_path / 'te_hip.h'))
+    with pytest.raises(RuntimeError, match='te_hip.h is missing'):
+        _lib.lib()
+    assert '#define TE_ABI_VERSION 3' in header
+    monkeypatch.setattr(_lib, '_header_text', lambda: header.replace('#define TE_ABI_VERSION 3', '#define TE_ABI_VERSION 4'))
+    with pytest.raises(RuntimeError, match='ABI version 3 but include/te_hip.h declares 4'):
+        _lib.lib()
+    assert _lib._lib is None
+    monkeypatch.undo()
+    assert _lib.lib().te_version() == 3
+
+
+def test_launch_sites_name_their_entry_point_once():
+    """every launch goes through _launch(name, ...): no `_check(lib().te_x(..., _stream()), 'te_x')` with its second copy of the name
+    is left; what still calls _check is _launch itself and the host-only plan query"""
+    src = open(os.path.join(ROOT, 'transeditor_amd', '_lib.py')).read()
+    calls = [m.start() for m in re.finditer(r'\b_check\(', src)]
+    stmts = [src[i:src.index('\n\n', i)] for i in calls]
+    assert not [s for s in stmts if '_check(lib().' in s and '_stream()' in s]
+    assert len([s for s in stmts if not s.startswith('_check(rc, what)')]) == 2
+    assert src.count("_launch('te_") >= 75
+    for f in ('frozen_net.py',):
+        assert '_check(' not in open(os.path.join(ROOT, 'transeditor_amd', f)).read()
+
+
 def test_argument_validation_returns_error_codes(libpath):
     """No compute without a GPU: only the host-side validation paths are exercised."""
     from transeditor_amd import _lib
@@ -237,17 +348,41 @@ def test_tools_and_entry_points_compile():
         compile(open(f).read(), f, 'exec')
 
 
+_RANGED_BEFORE = [          # the hand-kept list _install_roctx had: the floor of what carries a range
+    'bias_act', 'bias_act_bwd', 'upfirdn2d_raw', 'blur_actgrad', 'blur_gradact', 'conv_pack', 'conv_pack2', 'conv_pack_multi', 'conv',
+    'wgrad_slabs', 'wgrad_reduce', 'rgb_fwd', 'rgb_dgrad', 'rgb_expand', 'rgb_wgrad_slabs', 'small_gemm', 'small_gemm_splitk',
+    'small_gemm_batched', 'minibatch_stddev_fwd', 'minibatch_stddev_bwd', 'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd',
+    'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd', 'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot',
+    'lpips_stem_fwd', 'lpips_stem_dgrad', 'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist',
+    'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd', 'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm',
+    'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream', 'fid_moments', 'fid_finalize', 'gram', 'svm_smo',
+    'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score', 'attr_stem_fwd', 'avgpool2_act', 'attr_score',
+    'conv2d_res', 'pose_stem_fwd', 'maxpool3s2p1', 'alex_stem_fwd', 'lpips_unit', 'lpips_allpairs_fwd', 'lpips_allpairs_dist',
+    'conv2d_prelu', 'id_stem_fwd', 'se_excite', 'se_scale_add', 'rows_unit', 'rows_dot']
+
+
 def test_roctx_ranges_behind_env_switch():
-    """TE_ROCTX=1 wraps every tensor-level entry of _lib in a roctx range (operator names in rocprofv3 marker traces)"""
+    """TE_ROCTX=1 wraps every tensor-level entry of _lib in a roctx range (operator names in rocprofv3 marker traces): the wrappers
+    are the ones marked @_op where they are defined, which is every wrapper that launches"""
     import subprocess
     import sys
     code = ("from transeditor_amd import _lib; assert _lib.ROCTX and _lib.conv.__wrapped__.__name__ == 'conv' "
-            "and _lib.upfirdn2d_raw.__wrapped__.__name__ == 'upfirdn2d_raw'; print('ok')")
+            "and _lib.upfirdn2d_raw.__wrapped__.__name__ == 'upfirdn2d_raw'; "
+            "assert all(hasattr(f, '__wrapped__') and getattr(_lib, f.__name__) is f for f in _lib._OPS); "
+            "print('ranged', ' '.join(f.__name__ for f in _lib._OPS))")
     env = dict(os.environ, TE_ROCTX='1', PYTHONPATH=ROOT)
     out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and 'ok' in out.stdout, out.stderr
+    assert out.returncode == 0 and 'ranged' in out.stdout, out.stderr
+    ranged = out.stdout.split('ranged', 1)[1].split()
+    assert len(_RANGED_BEFORE) == 78 and set(ranged) >= set(_RANGED_BEFORE)
+    assert 'bias_act_bwd_rgb' in ranged and 'rgb_wgrad_sum_slabs' in ranged and len(set(ranged)) == len(ranged)
     from transeditor_amd import _lib
     assert not _lib.ROCTX and not hasattr(_lib.conv, '__wrapped__')
+    assert [f.__name__ for f in _lib._OPS] == ranged
+    assert not [f.__name__ for f in _lib._OPS if hasattr(f, '__wrapped__') or getattr(_lib, f.__name__) is not f]
+    # the host-only predicates and hooks carry no range
+    assert not {'wino_ok', 'wino6_form', 'wgrad_split', 'rgb_supported', 'bias_act_bwd_rgb_supported', 'fid_moments_ws_bytes',
+                'fc_stream_splits', 'wgrad6_form', 'layer_norm_supported'} & set(ranged)
 
 
 def test_fused_adam_loads_reference_style_optimizer_state():

@@ -640,6 +640,59 @@ def test_upfirdn2d_other_dtypes(dtype, tol, up, down, pad, taps):
     assert rel_err(gx.double(), gx_ref) < tol
 
 
+# ------------------------------------------------------------------------------------------------ wrappers against the raw ABI
+@pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.float64])
+def test_wrappers_equal_direct_abi_calls(dtype):
+    """_lib.bias_act, _lib.upfirdn2d_raw and (fp32) _lib.conv give, bit for bit, what their entry points give when called directly on
+    the CDLL with the arguments built here by hand: pins the launch helper and the one-body dtype dispatch to the C ABI itself"""
+    from transeditor_amd import _lib
+    L, st, sfx = _lib.lib(), _lib._stream(), {torch.float32: 'f32', torch.float16: 'f16', torch.float64: 'f64'}[dtype]
+    nan = lambda *shape: torch.full(shape, float('nan'), device=DEV, dtype=dtype)
+    # K1 on [2,5,3]: forward with a bias, then the gradient mode with the forward's output as reference
+    x, b = synth.normal((2, 5, 3), 'abi.k1.x').to(DEV, dtype), synth.normal((5,), 'abi.k1.b').to(DEV, dtype)
+    fn, out = getattr(L, 'te_bias_act_' + sfx), nan(2, 5, 3)
+    assert fn(out.data_ptr(), x.data_ptr(), b.data_ptr(), None, 3, 0, 0.2, 2 ** 0.5, 30, 3, 5, st) == 0
+    y = _lib.bias_act(x, b, None, 3, 0, 0.2, 2 ** 0.5)
+    assert y.dtype == dtype and torch.equal(y, out) and not torch.isnan(out).any()
+    gi = nan(2, 5, 3)
+    assert fn(gi.data_ptr(), x.data_ptr(), None, out.data_ptr(), 3, 1, 0.2, 2 ** 0.5, 30, 3, 1, st) == 0
+    assert torch.equal(_lib.bias_act(x, None, out, 3, 1, 0.2, 2 ** 0.5), gi) and not torch.isnan(gi).any()
+    # K2 on [2,3,9,11], up 2 with pad (2, 1): [2,3,18,22]; the fp32 entry takes the fused bias + leaky ReLU epilogue as well
+    x = synth.normal((2, 3, 9, 11), 'abi.k2.x').to(DEV, dtype)
+    k = O.fir_kernel((1, 3, 3, 1), 4.0).to(DEV, dtype)
+    geometry = (6, 9, 11, 1, 4, 4, 2, 2, 1, 1, 2, 1, 2, 1)
+    out = nan(2, 3, 18, 22)
+    if dtype == torch.float32:
+        bias = synth.normal((3,), 'abi.k2.b').to(DEV)
+        assert L.te_upfirdn2d_f32(out.data_ptr(), x.data_ptr(), k.data_ptr(), *geometry, bias.data_ptr(), 3, 3, 0.2, 2 ** 0.5, st) == 0
+        y = _lib.upfirdn2d_raw(x, k, (2, 2), (1, 1), (2, 1, 2, 1), bias=bias, act=3, alpha=0.2, scale=2 ** 0.5)
+        assert torch.equal(y, out) and not torch.isnan(out).any()
+        out = nan(2, 3, 18, 22)
+        assert L.te_upfirdn2d_f32(out.data_ptr(), x.data_ptr(), k.data_ptr(), *geometry, None, 1, 0, 0.2, 1.0, st) == 0
+    else:
+        assert getattr(L, 'te_upfirdn2d_' + sfx)(out.data_ptr(), x.data_ptr(), k.data_ptr(), *geometry, st) == 0
+        with pytest.raises(RuntimeError, match='fp32 only'):
+            _lib.upfirdn2d_raw(x, k, (2, 2), (1, 1), (2, 1, 2, 1), act=3)
+    y = _lib.upfirdn2d_raw(x, k, (2, 2), (1, 1), (2, 1, 2, 1))
+    assert y.dtype == dtype and torch.equal(y, out) and not torch.isnan(out).any()
+    if dtype != torch.float32:
+        return
+    # F1 on CONV_SHAPES[0], 3x3 with bias and leaky ReLU
+    B, K, M, H, W = CONV_SHAPES[0]
+    x = synth.normal((B, K, H, W), 'abi.cv.x').to(DEV)
+    w = (synth.normal((M, K, 3, 3), 'abi.cv.w') / math.sqrt(9 * K)).to(DEV)
+    bias = synth.normal((M,), 'abi.cv.b').to(DEV)
+    wp = _lib.conv_pack(w, _lib.PACK_FWD)
+    S = L.te_conv_splitk_count(_lib.CONV_3X3, B, K, M, H, W)
+    assert S >= 1
+    out = nan(B, M, H, W)
+    ws = torch.empty(S, B, M, H, W, device=DEV) if S > 1 else None
+    assert L.te_conv_res_f32(out.data_ptr(), ws.data_ptr() if S > 1 else None, x.data_ptr(), wp.data_ptr(), None, None, bias.data_ptr(),
+                             None, None, 1.0, 3, _lib.CONV_3X3, B, K, M, H, W, st) == 0
+    y = _lib.conv(x, wp, _lib.CONV_3X3, M, H, W, bias=bias, act=3)
+    assert torch.equal(y, out) and not torch.isnan(out).any()
+
+
 # ------------------------------------------------------------------------------------------------ channel scale / dot pair
 @pytest.mark.parametrize('shape', [(2, 5, 7, 9), (3, 16, 8, 8), (2, 4, 64, 64), (1, 3, 1, 1), (2, 130, 33, 20), (1, 5, 33, 33),
                                    (2, 6, 65, 65), (1, 2, 129, 257)])

@@ -3,161 +3,48 @@
 The product path has NO fallback: if the shared object is missing, was built for another
 architecture, or a tensor is not a contiguous fp32 CUDA(HIP) tensor, these wrappers raise.
 PyTorch is used here only for device memory and the current HIP stream.
+
+Every entry point is declared once, in include/te_hip.h: lib() reads the ctypes prototypes from the header (_abi.parse), so
+there is no table to keep in step.  A new entry point needs its prototype in the header and one wrapper here that hands its
+arguments to _launch('te_name', ...), decorated with @_op (which gives it its roctx range under TE_ROCTX=1).
 """
 import ctypes as C
 import os
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libte_hip.so')
-_lib = None
+HEADER_PATH = os.path.join(_HERE, '..', 'include', 'te_hip.h')
+_lib = _protos = None
 
 CONV_3X3, CONV_T2, CONV_S2, CONV_1X1, CONV_3X3W, CONV_3X3W6, CONV_S2S6, CONV_T2S6, CONV_1X1S6 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 (PACK_FWD, PACK_DGRAD, PACK_SWAP, PACK_WFWD, PACK_WDGRAD, PACK_W6FWD, PACK_W6DGRAD, PACK_S6FWD, PACK_S6SWAP, PACK_T6FWD,
  PACK_T6SWAP, PACK_P6FWD, PACK_P6DGRAD) = range(13)
 
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
-_SIGNATURES = {
-    'te_version': (C.c_int, []),
-    'te_last_error_string': (C.c_char_p, []),
-    'te_arch': (C.c_char_p, []),
-    'te_bias_act_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _F, _F, _L, _L, _L, _P]),
-    'te_bias_act_f16': (C.c_int, [_P, _P, _P, _P, _I, _I, _F, _F, _L, _L, _L, _P]),
-    'te_bias_act_f64': (C.c_int, [_P, _P, _P, _P, _I, _I, _F, _F, _L, _L, _L, _P]),
-    'te_bias_act_bwd_ws_floats': (C.c_int64, [_L, _L, _L]),
-    'te_bias_act_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _F, _F, _L, _L, _L, _P]),
-    'te_bias_act_bwd_rgb_supported': (C.c_int, [_L, _L, _L]),
-    'te_bias_act_bwd_rgb_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _L, _L, _L, _P]),
-    'te_upfirdn2d_f32': (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
-                                   _P, _L, _I, _F, _F, _P]),
-    'te_upfirdn2d_f16': (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_upfirdn2d_f64': (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_conv_packed_numel': (C.c_int64, [_I, _I, _I, _I]),
-    'te_conv_pack_weights_f32': (C.c_int, [_P, _P, _F, _I, _I, _I, _I, _P]),
-    'te_conv_pack_weights2_f32': (C.c_int, [_P, _I, _P, _I, _P, _F, _I, _I, _I, _P]),
-    'te_conv_pack_weights_multi_f32': (C.c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'te_conv_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_conv_splitk_count': (C.c_int, [_I, _I, _I, _I, _I, _I]),
-    'te_conv_wino_supported': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_conv_wino6_supported': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_conv_wino6_form': (C.c_int, [_I]),
-    'te_conv_wino6_tiles_per_block': (C.c_int, [_I]),
-    'te_conv_s2s6_form': (C.c_int, [_I]),
-    'te_conv_t2s6_form': (C.c_int, [_I]),
-    'te_conv_t2s6_ws_floats': (C.c_int64, [_I, _I, _I]),
-    'te_conv_s2s6_supported': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_conv_t2s6_supported': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_conv_p1s6_supported': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_conv_ws_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_conv_res_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_wgrad_slab_count': (C.c_int, [_I, _I, _I, _I, _I, _I]),
-    'te_wgrad_pair_form': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_wgrad_split_supported': (C.c_int, [_I, _I, _I, _I, _I]),
-    'te_wgrad_split_bf16': (C.c_int, [_I]),
-    'te_wgrad_t2_wide': (C.c_int, [_I]),
-    'te_wgrad6_form': (C.c_int, [_I, _I, _I, _I, _I, _I, _I]),
-    'te_wgrad_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_wgrad_group_plan': (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P]),
-    'te_wgrad_group_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_wgrad_reduce_ws_floats': (C.c_int64, [_I, _I, _I, _I, _I, _I, _I, _I]),
-    'te_wgrad_reduce_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
-    'te_rgb_supported': (C.c_int, [_I, _I, _I]),
-    'te_rgb_fwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P]),
-    'te_rgb_dgrad_f32': (C.c_int, [_P, _P, _P, _P, _F, _I, _I, _I, _P]),
-    'te_rgb_wgrad_sum_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    'te_rgb_expand_f32': (C.c_int, [_P, _P, _P, _P, _I, _F, _I, _I, _I, _P]),
-    'te_rgb_wgrad_slab_count': (C.c_int, [_I, _I, _I]),
-    'te_rgb_wgrad_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    'te_blur_actgrad_tiles': (C.c_int, [_I] * 8),
-    'te_blur_actgrad_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
-    'te_blur_gradact_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
-    'te_small_gemm_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _L, _L, _L, _L, _F, _F, _I, _P]),
-    'te_small_gemm_batched_f32': (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _L, _L, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _L,
-                                             _F, _F, _I, _P]),
-    'te_layer_norm_supported': (C.c_int, [_L, _I]),
-    'te_layer_norm_fwd_f32': (C.c_int, [_P, _P, _P, _L, _I, _F, _P]),
-    'te_layer_norm_bwd_f32': (C.c_int, [_P, _P, _P, _P, _L, _I, _P]),
-    'te_pixel_norm_supported': (C.c_int, [_L, _I, _I]),
-    'te_pixel_norm_fwd_f32': (C.c_int, [_P, _P, _P, _L, _I, _I, _F, _P]),
-    'te_pixel_norm_bwd_f32': (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
-    'te_demod_fwd_f32': (C.c_int, [_P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
-    'te_demod_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
-    'te_attn_fwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
-    'te_attn_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
-    'te_small_gemm_splitk_f32': (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _F, _I, _P]),
-    'te_minibatch_stddev_fwd_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _F, _P]),
-    'te_minibatch_stddev_bwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    'te_mt_adam_f32': (C.c_int, [_P, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),
-    'te_mt_ema_f32': (C.c_int, [_P, _P, _I, _I, _I, C.c_double, _P]),
-    'te_chan_scale_f32': (C.c_int, [_P, _P, _P, _L, _L, _P]),
-    'te_chan_dot_f32': (C.c_int, [_P, _P, _P, _L, _L, _P]),
-    'te_lpips_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    'te_lpips_stem_dgrad_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    'te_maxpool2_fwd_f32': (C.c_int, [_P, _P, _L, _I, _I, _P]),
-    'te_maxpool2_bwd_f32': (C.c_int, [_P, _P, _P, _L, _I, _I, _P]),
-    'te_lpips_normalize_f32': (C.c_int, [_P, _P, _I, _I, _L, _P]),
-    'te_lpips_head_blocks': (C.c_int, [_L]),
-    'te_lpips_head_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
-    'te_lpips_dist_f32': (C.c_int, [_P, _P, _P, _I, _I, _P]),
-    'te_lpips_head_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _P]),
-    'te_lpips_pair_head_fwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _L, _P]),
-    'te_crop_resize_bilinear_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_noise_reg_ws_floats': (C.c_int64, [_P, _I, _I]),
-    'te_noise_reg_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
-    'te_noise_reg_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    'te_noise_normalize_f32': (C.c_int, [_P, _P, _I, _I, _P]),
-    'te_prdc_ws_bytes': (C.c_int64, [_I, _I, _I, _I]),
-    'te_row_sqnorm_f32': (C.c_int, [_P, _P, _I, _I, _P]),
-    'te_prdc_knn_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    'te_prdc_counts_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
-    'te_vgg_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    'te_adaptive_avgpool_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
-    'te_fc_stream_splits': (C.c_int, [_I, _I]),
-    'te_fc_stream_ws_bytes': (C.c_int64, [_L, _I, _I]),
-    'te_fc_stream_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
-    'te_fid_moments_ws_bytes': (C.c_int64, [_L, _I]),
-    'te_fid_moments_f64': (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
-    'te_fid_finalize_f64': (C.c_int, [_P, _P, _P, _P, _L, _I, _P]),
-    'te_gram_f32': (C.c_int, [_P, _P, _I, _I, _P]),
-    'te_svm_smo_f64': (C.c_int, [_P, _P, _P, _P, _P, _I, C.c_double, C.c_double, _L, _P]),
-    'te_svm_coef_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
-    'te_conv2d_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 13 + [_P]),
-    'te_pool3_f32': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'te_resize_bilinear_f32': (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
-    'te_dex_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    'te_cls_score_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
-    'te_attr_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    'te_avgpool2_act_f32': (C.c_int, [_P, _P, _L, _I, _I, _F, _P]),
-    'te_attr_score_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P]),
-    'te_conv2d_res_f32': (C.c_int, [_P, _P, _P, _P, _P] + [_I] * 11 + [_P]),
-    'te_pose_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'te_maxpool3s2p1_f32': (C.c_int, [_P, _P, _L, _I, _I, _P]),
-    'te_alex_stem_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    'te_lpips_unit_f32': (C.c_int, [_P, _P, _I, _I, _L, _P]),
-    'te_lpips_allpairs_ws_floats': (C.c_int64, [_I, _I, _L]),
-    'te_lpips_allpairs_fwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _L, _P]),
-    'te_lpips_allpairs_dist_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
-    'te_conv2d_prelu_f32': (C.c_int, [_P] * 7 + [_I] * 10 + [_P]),
-    'te_id_stem_fwd_f32': (C.c_int, [_P] * 5 + [_I] * 9 + [_P]),
-    'te_se_excite_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    'te_se_scale_add_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 7 + [_P]),
-    'te_rows_unit_f32': (C.c_int, [_P, _P, _L, _I, _P]),
-    'te_rows_dot_f32': (C.c_int, [_P, _P, _P, _L, _I, _P]),
-    # loop-trip queries (host only)
-    'te_upfirdn2d_plan': (C.c_int, [_L] + [_I] * 13 + [_P, _P]),
-    'te_blur_actgrad_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
-    'te_blur_gradact_plan': (C.c_int, [_L] + [_I] * 8 + [_P, _P]),
-    'te_upfirdn2d_direct_cover': (C.c_int64, [_L]),
-    'te_chan_scale_cover': (C.c_int64, [_L, _L, _I]),
-    'te_bias_act_f32_cover': (C.c_int64, [_L, _L, _I, _P]),
-    'te_bias_act_any_cover': (C.c_int64, [_L]),
-    'te_conv_finalize_cover': (C.c_int64, [_L]),
-    'te_small_gemm_splitk_finish_cover': (C.c_int64, [_I, _I]),
-    'te_conv_pack_plan': (C.c_int, [_I, _I, _I, _I, _P, _P]),
-    'te_wgrad_reduce_plan': (C.c_int, [_I, _I, _I, _I, _I, _P, _P]),
-}
-EXPORTS = tuple(_SIGNATURES)
+
+def _header_text():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f'{HEADER_PATH} is missing: the bindings of libte_hip.so are read from it')
+    with open(HEADER_PATH) as f:
+        return f.read()
+
+
+def _prototypes():
+    """(once) ({name: (restype, argtypes)} in header order, TE_ABI_VERSION) of include/te_hip.h"""
+    global _protos
+    if _protos is None:
+        text = _header_text()
+        _protos = _abi.parse(text), _abi.abi_version(text)
+    return _protos
+
+
+def __getattr__(name):
+    if name == 'EXPORTS':           # the entry points' names in header order (read at first use)
+        return tuple(_prototypes()[0])
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
 def lib():
@@ -167,14 +54,18 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -m transeditor_amd.build` '
                                '(there is no CPU / PyTorch fallback for the TransEditor hot path)')
+        protos, version = _prototypes()
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in protos.items():
             if not hasattr(L, name):
                 raise RuntimeError(f'{LIB_PATH} does not export {name}')
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         if L.te_arch() != b'gfx950':
             raise RuntimeError('libte_hip.so was not built for gfx950')
+        if L.te_version() != version:
+            raise RuntimeError(f'{LIB_PATH} has ABI version {L.te_version()} but include/te_hip.h declares {version}: '
+                               'a stale library, rebuild it with `python -m transeditor_amd.build`')
         _lib = L
     return _lib
 
@@ -182,6 +73,22 @@ def lib():
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError(f'{what} failed (code {rc}): {lib().te_last_error_string().decode()}')
+
+
+def _launch(name, *args):
+    """enqueue entry point `name` with `args` on the current stream; a failure raises in that same name"""
+    rc = getattr(_lib or lib(), name)(*args, _stream())
+    if rc:                          # (the one extra Python call per launch is paid for by skipping lib() and _check on success)
+        _check(rc, name)
+
+
+_OPS = []
+
+
+def _op(fn):
+    """marks a tensor-level wrapper that launches: TE_ROCTX=1 runs each of them inside a roctx range (end of this module)"""
+    _OPS.append(fn)
+    return fn
 
 
 _cur_dev = getattr(torch._C, '_cuda_getDevice', torch.cuda.current_device)
@@ -196,24 +103,25 @@ def _on_current_device(t):
                            f'call torch.cuda.set_device (one process per GPU) or wrap the call in torch.cuda.device(...)')
 
 
-def _ptr(t):
+def _ptr(t, dtype=torch.float32, dense=True):
+    """device pointer of t (None: NULL) after the one check every operand gets: on the current GPU, of `dtype`, and contiguous
+    unless the entry point addresses it through explicit strides (dense=False)"""
     if t is None:
         return None
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise RuntimeError(f'te_hip: expected a contiguous fp32 tensor on the GPU, got {t.dtype} {t.device} '
-                           f'contiguous={t.is_contiguous()} (no CPU path exists)')
+    if not (t.is_cuda and t.dtype == dtype and (t.is_contiguous() or not dense)):
+        name = 'fp32' if dtype == torch.float32 else dtype
+        raise RuntimeError(f'te_hip: expected {"a contiguous" if dense else "an"} {name} tensor on the GPU, got {t.dtype} {t.device} '
+                           + (f'contiguous={t.is_contiguous()} ' if dense else '') + '(no CPU path exists)')
     _on_current_device(t)
     return t.data_ptr()
+
+
+_ptr_as = _ptr                  # (t, dtype): an operand that is not fp32
 
 
 def _raw(t):
     """device pointer of a tensor addressed through explicit strides (no contiguity requirement)"""
-    if t is None:
-        return None
-    if not (t.is_cuda and t.dtype == torch.float32):
-        raise RuntimeError(f'te_hip: expected an fp32 tensor on the GPU, got {t.dtype} {t.device} (no CPU path exists)')
-    _on_current_device(t)
-    return t.data_ptr()
+    return _ptr(t, dense=False)
 
 
 def _stream():
@@ -232,34 +140,28 @@ def _aligned16(t):
 _OTHER = {torch.float16: 'f16', torch.float64: 'f64'}       # K1 / K2 also exist in the reference's other two dispatch types
 
 
-def _ptr_as(t, dtype):
-    if t is None:
-        return None
-    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise RuntimeError(f'te_hip: expected a contiguous {dtype} tensor on the GPU, got {t.dtype} {t.device} '
-                           f'contiguous={t.is_contiguous()} (no CPU path exists)')
-    _on_current_device(t)
-    return t.data_ptr()
+def _dispatch(x):
+    """(entry-point suffix, operand dtype) of K1 / K2 for x; anything but half and double goes to the fp32 entry, whose operand
+    check refuses what is not fp32"""
+    return (_OTHER[x.dtype], x.dtype) if x.dtype in _OTHER else ('f32', torch.float32)
 
 
+def _inner(shape):
+    """prod(shape[2:]): the elements per channel of [B,C,...]"""
+    n = 1
+    for d in shape[2:]:
+        n *= d
+    return n
+
+
+@_op
 def bias_act(x, b, ref, act, grad, alpha, scale):
     """out = act(x + b[channel]) * scale; channel = dim 1 (step_b = prod(shape[2:]))."""
     x = x.contiguous()
-    if x.dtype in _OTHER:
-        out = torch.empty_like(x)
-        step_b = 1
-        for d in x.shape[2:]:
-            step_b *= d
-        fn = getattr(lib(), 'te_bias_act_' + _OTHER[x.dtype])
-        _check(fn(_ptr_as(out, x.dtype), _ptr_as(x, x.dtype), _ptr_as(b, x.dtype), _ptr_as(ref, x.dtype), act, grad, alpha, scale,
-                  x.numel(), step_b, b.numel() if b is not None else 1, _stream()), 'te_bias_act_' + _OTHER[x.dtype])
-        return out
+    sfx, dt = _dispatch(x)
     out = torch.empty_like(x)
-    step_b = 1
-    for d in x.shape[2:]:
-        step_b *= d
-    _check(lib().te_bias_act_f32(_ptr(out), _ptr(x), _ptr(b), _ptr(ref), act, grad, alpha, scale,
-                                 x.numel(), step_b, b.numel() if b is not None else 1, _stream()), 'te_bias_act_f32')
+    _launch('te_bias_act_' + sfx, _ptr(out, dt), _ptr(x, dt), _ptr(b, dt), _ptr(ref, dt), act, grad, alpha, scale, x.numel(),
+            _inner(x.shape), b.numel() if b is not None else 1)
     return out
 
 
@@ -273,29 +175,24 @@ def _bias_grad_buffers(want_bias, outer, Cn, inner, device):
             torch.empty(n, device=device, dtype=torch.float32) if n > 0 else None)
 
 
+@_op
 def bias_act_bwd(g, ref, alpha, scale, want_bias=True):
     g = g.contiguous()
     if g.dtype in _OTHER:       # the reference's two steps (fused_act.py:18-38): the kernel in grad mode, then the bias sum
         gi = bias_act(g, None, ref, 3, 1, alpha, scale)
         return gi, (gi.sum(dim=[0] + list(range(2, gi.ndim))) if want_bias else None)
     gi = torch.empty_like(g)
-    Cn = g.shape[1]
-    inner = 1
-    for d in g.shape[2:]:
-        inner *= d
+    Cn, inner = g.shape[1], _inner(g.shape)
     gb, ws = _bias_grad_buffers(want_bias, g.shape[0], Cn, inner, g.device)
-    _check(lib().te_bias_act_bwd_f32(_ptr(gi), _ptr(gb), _ptr(ws), _ptr(g), _ptr(ref), alpha, scale, g.shape[0], Cn, inner,
-                                     _stream()), 'te_bias_act_bwd_f32')
+    _launch('te_bias_act_bwd_f32', _ptr(gi), _ptr(gb), _ptr(ws), _ptr(g), _ptr(ref), alpha, scale, g.shape[0], Cn, inner)
     return gi, gb
 
 
 def bias_act_bwd_rgb_supported(shape):
-    inner = 1
-    for d in shape[2:]:
-        inner *= d
-    return bool(lib().te_bias_act_bwd_rgb_supported(shape[0], shape[1], inner))
+    return bool(lib().te_bias_act_bwd_rgb_supported(shape[0], shape[1], _inner(shape)))
 
 
+@_op
 def bias_act_bwd_rgb(g, ref, grgb, wrgb, srgb, wscale, alpha, scale, want_bias=True):
     """activation gradient with a ToRGB data gradient folded in (see te_hip.h); g may be None.  -> (gi, gb | None)
     The kernel reads g, ref and grgb with 16-byte accesses and the ABI refuses misaligned ones: an operand whose data is not
@@ -303,18 +200,15 @@ def bias_act_bwd_rgb(g, ref, grgb, wrgb, srgb, wscale, alpha, scale, want_bias=T
     ref, grgb = _aligned16(ref.contiguous()), _aligned16(grgb.contiguous())
     g = _aligned16(g.contiguous()) if g is not None else None
     gi = torch.empty_like(ref)
-    Cn = ref.shape[1]
-    inner = 1
-    for d in ref.shape[2:]:
-        inner *= d
+    Cn, inner = ref.shape[1], _inner(ref.shape)
     gb, ws = _bias_grad_buffers(want_bias, ref.shape[0], Cn, inner, ref.device)
-    _check(lib().te_bias_act_bwd_rgb_f32(_ptr(gi), _ptr(gb), _ptr(ws), _ptr(g), _ptr(ref), _ptr(grgb), _ptr(wrgb.contiguous()),
-                                         _ptr(srgb.contiguous()) if srgb is not None else None, wscale, alpha, scale,
-                                         ref.shape[0], Cn, inner, _stream()), 'te_bias_act_bwd_rgb_f32')
+    _launch('te_bias_act_bwd_rgb_f32', _ptr(gi), _ptr(gb), _ptr(ws), _ptr(g), _ptr(ref), _ptr(grgb), _ptr(wrgb.contiguous()),
+            _ptr(srgb.contiguous()) if srgb is not None else None, wscale, alpha, scale, ref.shape[0], Cn, inner)
     return gi, gb
 
 
 # --------------------------------------------------------------------------------------------- K2
+@_op
 def upfirdn2d_raw(x, k, up, down, pad, bias=None, act=0, alpha=0.2, scale=1.0):
     """x [B,C,H,W] -> [B,C,H',W'];  pad = (px0, px1, py0, py1);  up/down = (x, y)."""
     x = x.contiguous()
@@ -326,20 +220,20 @@ def upfirdn2d_raw(x, k, up, down, pad, bias=None, act=0, alpha=0.2, scale=1.0):
     if oh <= 0 or ow <= 0:
         raise RuntimeError(f'upfirdn2d: empty output {oh}x{ow}')
     out = torch.empty(B, Cn, oh, ow, device=x.device, dtype=x.dtype)
-    if x.dtype in _OTHER:
+    sfx, dt = _dispatch(x)
+    if sfx != 'f32':
         if bias is not None or act:
             raise RuntimeError('upfirdn2d: the fused bias / activation epilogue exists in fp32 only')
-        fn = getattr(lib(), 'te_upfirdn2d_' + _OTHER[x.dtype])
-        _check(fn(_ptr_as(out, x.dtype), _ptr_as(x, x.dtype), _ptr_as(k.to(x.dtype).contiguous(), x.dtype), B * Cn, H, W, 1, kh, kw,
-                  up[0], up[1], down[0], down[1], px0, px1, py0, py1, _stream()), 'te_upfirdn2d_' + _OTHER[x.dtype])
-        return out
-    _check(lib().te_upfirdn2d_f32(_ptr(out), _ptr(x), _ptr(k.contiguous()), B * Cn, H, W, 1, kh, kw, up[0], up[1],
-                                  down[0], down[1], px0, px1, py0, py1, _ptr(bias),
-                                  bias.numel() if bias is not None else 1, act, alpha, scale, _stream()),
-           'te_upfirdn2d_f32')
+        k = k.to(dt)                # (the taps in the tensors' own type; the fp32 entry takes fp32 taps only)
+    args = [_ptr(out, dt), _ptr(x, dt), _ptr(k.contiguous(), dt), B * Cn, H, W, 1, kh, kw, up[0], up[1], down[0], down[1],
+            px0, px1, py0, py1]
+    if sfx == 'f32':
+        args += [_ptr(bias), bias.numel() if bias is not None else 1, act, alpha, scale]
+    _launch('te_upfirdn2d_' + sfx, *args)
     return out
 
 
+@_op
 def blur_actgrad(g, ref, k_flipped, pad, alpha, scale):
     """backward of blur + bias + lrelu in one pass: returns (gx, gbias).  g / ref [B,C,H,W]; pad = (px0, px1, py0, py1)."""
     g, ref = g.contiguous(), ref.contiguous()
@@ -351,11 +245,12 @@ def blur_actgrad(g, ref, k_flipped, pad, alpha, scale):
         raise RuntimeError(f'te_blur_actgrad_tiles failed ({tiles})')
     gx = torch.empty(B, Cn, H + py0 + py1 - kh + 1, W + px0 + px1 - kw + 1, device=g.device, dtype=g.dtype)
     partial = torch.empty(B, Cn, tiles, device=g.device, dtype=g.dtype)
-    _check(lib().te_blur_actgrad_f32(_ptr(gx), _ptr(partial), _ptr(g), _ptr(ref), _ptr(k_flipped.contiguous()), B * Cn, H, W,
-                                     kh, kw, px0, px1, py0, py1, alpha, scale, _stream()), 'te_blur_actgrad_f32')
+    _launch('te_blur_actgrad_f32', _ptr(gx), _ptr(partial), _ptr(g), _ptr(ref), _ptr(k_flipped.contiguous()), B * Cn, H, W, kh, kw, px0,
+            px1, py0, py1, alpha, scale)
     return gx, partial.sum(dim=(0, 2))
 
 
+@_op
 def blur_gradact(g, ref, k_flipped, pad, alpha, scale):
     """backward of 'bias + lrelu -> blur' in one pass: (upfirdn2d(g, k_flipped, pad) * slope(ref), gbias).  ref is shaped
     like the result."""
@@ -371,34 +266,35 @@ def blur_gradact(g, ref, k_flipped, pad, alpha, scale):
         raise RuntimeError(f'te_blur_actgrad_tiles failed ({tiles})')
     gx = torch.empty(B, Cn, oh, ow, device=g.device, dtype=g.dtype)
     partial = torch.empty(B, Cn, tiles, device=g.device, dtype=g.dtype)
-    _check(lib().te_blur_gradact_f32(_ptr(gx), _ptr(partial), _ptr(g), _ptr(ref), _ptr(k_flipped.contiguous()), B * Cn, H, W,
-                                     kh, kw, px0, px1, py0, py1, alpha, scale, _stream()), 'te_blur_gradact_f32')
+    _launch('te_blur_gradact_f32', _ptr(gx), _ptr(partial), _ptr(g), _ptr(ref), _ptr(k_flipped.contiguous()), B * Cn, H, W, kh, kw, px0,
+            px1, py0, py1, alpha, scale)
     return gx, partial.sum(dim=(0, 2))
 
 
 # --------------------------------------------------------------------------------------------- F1
+@_op
 def conv_pack(w, kind_pack, wscale=1.0):
     """w [Co,Ci,k,k] (model layout) -> packed Wp[tap][Kp][Mp]."""
     w = w.contiguous()
     Co, Ci, ks, _ = w.shape
     n = lib().te_conv_packed_numel(kind_pack, Co, Ci, ks)
     wp = torch.empty(n, device=w.device, dtype=w.dtype)
-    _check(lib().te_conv_pack_weights_f32(_ptr(wp), _ptr(w), wscale, kind_pack, Co, Ci, ks, _stream()),
-           'te_conv_pack_weights_f32')
+    _launch('te_conv_pack_weights_f32', _ptr(wp), _ptr(w), wscale, kind_pack, Co, Ci, ks)
     return wp
 
 
+@_op
 def conv_pack2(w, kind_a, kind_b, wscale=1.0):
     """both packed layouts of w in one launch -> (wp_a, wp_b)"""
     w = w.contiguous()
     Co, Ci, ks, _ = w.shape
     wa = torch.empty(lib().te_conv_packed_numel(kind_a, Co, Ci, ks), device=w.device, dtype=w.dtype)
     wb = torch.empty(lib().te_conv_packed_numel(kind_b, Co, Ci, ks), device=w.device, dtype=w.dtype)
-    _check(lib().te_conv_pack_weights2_f32(_ptr(wa), kind_a, _ptr(wb), kind_b, _ptr(w), wscale, Co, Ci, ks, _stream()),
-           'te_conv_pack_weights2_f32')
+    _launch('te_conv_pack_weights2_f32', _ptr(wa), kind_a, _ptr(wb), kind_b, _ptr(w), wscale, Co, Ci, ks)
     return wa, wb
 
 
+@_op
 def conv_pack_multi(jobs):
     """jobs: [(wp, w, kind_pack, wscale)] with w [Co,Ci,k,k] dense and wp an already allocated packed buffer of the right
     size: every layout is (re)written in one launch per 64 jobs."""
@@ -409,11 +305,10 @@ def conv_pack_multi(jobs):
         if not (w.is_contiguous() and wp.is_contiguous()):
             raise RuntimeError('te_hip: conv_pack_multi needs dense weights and buffers')
     arr = lambda ty, vals: (ty * n)(*vals)
-    _check(lib().te_conv_pack_weights_multi_f32(
-        n, arr(C.c_void_p, [_ptr(j[0]) for j in jobs]), arr(C.c_void_p, [_ptr(j[1]) for j in jobs]),
-        arr(C.c_float, [float(j[3]) for j in jobs]), arr(C.c_int, [int(j[2]) for j in jobs]),
-        arr(C.c_int, [j[1].shape[0] for j in jobs]), arr(C.c_int, [j[1].shape[1] for j in jobs]),
-        arr(C.c_int, [j[1].shape[2] for j in jobs]), _stream()), 'te_conv_pack_weights_multi_f32')
+    _launch('te_conv_pack_weights_multi_f32', n, arr(C.c_void_p, [_ptr(j[0]) for j in jobs]), arr(C.c_void_p, [_ptr(j[1]) for j in jobs]),
+            arr(C.c_float, [float(j[3]) for j in jobs]), arr(C.c_int, [int(j[2]) for j in jobs]),
+            arr(C.c_int, [j[1].shape[0] for j in jobs]), arr(C.c_int, [j[1].shape[1] for j in jobs]),
+            arr(C.c_int, [j[1].shape[2] for j in jobs]))
 
 
 def wino_ok(B, K, M, H, W):
@@ -470,6 +365,7 @@ def conv_out_shape(kind, B, M, H, W):
     return (B, M, H, W)
 
 
+@_op
 def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, mask_ref=None, mask_gain=1.0):
     """H, W = LOW-resolution size (see te_hip.h).  x [B,K,Hin,Win].  res: residual added after the activation; mask_ref:
     leaky-ReLU gradient mask (saved output of the layer this data gradient lands on) applied last.  The kinds that read
@@ -492,13 +388,12 @@ def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, m
     ws = torch.empty((S,) + tuple(out.shape), device=x.device, dtype=x.dtype) if S > 1 else None
     if kind == CONV_T2S6:          # scratch for the last input column (body kernel -> edge kernel; te_hip.h)
         ws = torch.empty(B * K * H, device=x.device, dtype=x.dtype)
-    _check(lib().te_conv_res_f32(_ptr(out), _ptr(ws), _ptr(x), _ptr(wp), _ptr(isc), _ptr(osc), _ptr(bias),
-                                 _ptr(res), _ptr(mask_ref), mask_gain, act, kind, B, K, M, H, W,
-                                 _stream()),
-           'te_conv_res_f32')
+    _launch('te_conv_res_f32', _ptr(out), _ptr(ws), _ptr(x), _ptr(wp), _ptr(isc), _ptr(osc), _ptr(bias), _ptr(res), _ptr(mask_ref),
+            mask_gain, act, kind, B, K, M, H, W)
     return out
 
 
+@_op
 def wgrad_slabs(g, x, kind, H, W, group=False):
     """correlation slabs [B, S, Co, Ci, taps]; group=True (PLAIN gradient only - nothing per sample is derived from the slabs):
     [B / NB, S, Co, Ci, taps] with NB samples per slab where the plan finds that worthwhile (small images, big weights)"""
@@ -510,14 +405,13 @@ def wgrad_slabs(g, x, kind, H, W, group=False):
         _check(lib().te_wgrad_group_plan(kind, B, Co, Ci, H, W, C.byref(nb), C.byref(sc)), 'te_wgrad_group_plan')
         if nb.value > 1:
             slabs = torch.empty(B // nb.value, sc.value, Co, Ci, taps, device=g.device, dtype=g.dtype)
-            _check(lib().te_wgrad_group_f32(_ptr(slabs), _ptr(g), _ptr(x), kind, B, Co, Ci, H, W, sc.value, nb.value, _stream()),
-                   'te_wgrad_group_f32')
+            _launch('te_wgrad_group_f32', _ptr(slabs), _ptr(g), _ptr(x), kind, B, Co, Ci, H, W, sc.value, nb.value)
             return slabs
     S = lib().te_wgrad_slab_count(kind, B, Co, Ci, H, W)
     if S <= 0:
         raise RuntimeError(f'te_wgrad_slab_count failed ({S})')
     slabs = torch.empty(B, S, Co, Ci, taps, device=g.device, dtype=g.dtype)
-    _check(lib().te_wgrad_f32(_ptr(slabs), _ptr(g), _ptr(x), kind, B, Co, Ci, H, W, S, _stream()), 'te_wgrad_f32')
+    _launch('te_wgrad_f32', _ptr(slabs), _ptr(g), _ptr(x), kind, B, Co, Ci, H, W, S)
     return slabs
 
 
@@ -552,6 +446,7 @@ def wgrad_pair_form(kind, Co, Ci, H, W):
     return bool(lib().te_wgrad_pair_form(kind, Co, Ci, H, W))
 
 
+@_op
 def wgrad_reduce(slabs, w, wscale=1.0, isc=None, osc=None, want_w=True, want_isc=False, want_osc=False):
     B, S, Co, Ci, taps = slabs.shape
     dev, dt = slabs.device, slabs.dtype
@@ -563,8 +458,8 @@ def wgrad_reduce(slabs, w, wscale=1.0, isc=None, osc=None, want_w=True, want_isc
     if n < 0:
         raise RuntimeError(f'te_wgrad_reduce_ws_floats failed ({n})')
     ws = torch.empty(n, device=dev, dtype=dt) if n > 0 else None
-    _check(lib().te_wgrad_reduce_f32(_ptr(gw), _ptr(gisc), _ptr(gosc), _ptr(ws), _ptr(slabs), _ptr(w.contiguous()), wscale,
-                                     _ptr(isc), _ptr(osc), B, S, Co, Ci, taps, _stream()), 'te_wgrad_reduce_f32')
+    _launch('te_wgrad_reduce_f32', _ptr(gw), _ptr(gisc), _ptr(gosc), _ptr(ws), _ptr(slabs), _ptr(w.contiguous()), wscale, _ptr(isc),
+            _ptr(osc), B, S, Co, Ci, taps)
     return gw, gisc, gosc
 
 
@@ -573,37 +468,39 @@ def rgb_supported(M, K, HW):
     return bool(lib().te_rgb_supported(M, K, HW))
 
 
+@_op
 def rgb_fwd(x, w, isc, bias, wscale=1.0):
     """ToRGB forward [B,K,H,W] -> [B,3,H,W].  The kernel reads x with 16-byte accesses: a misaligned x goes in as an aligned copy."""
     x = _aligned16(x.contiguous())
     B, K, H, W = x.shape
     out = torch.empty(B, 3, H, W, device=x.device, dtype=x.dtype)
-    _check(lib().te_rgb_fwd_f32(_ptr(out), _ptr(x), _ptr(w.contiguous()), _ptr(isc), _ptr(bias), wscale, B, K, H * W, _stream()),
-           'te_rgb_fwd_f32')
+    _launch('te_rgb_fwd_f32', _ptr(out), _ptr(x), _ptr(w.contiguous()), _ptr(isc), _ptr(bias), wscale, B, K, H * W)
     return out
 
 
+@_op
 def rgb_dgrad(g, w, isc, K, wscale=1.0):
     """ToRGB data gradient [B,3,H,W] -> [B,K,H,W].  The kernel reads g with 16-byte accesses: a misaligned g goes in as an aligned
     copy."""
     g = _aligned16(g.contiguous())
     B, _, H, W = g.shape
     gx = torch.empty(B, K, H, W, device=g.device, dtype=g.dtype)
-    _check(lib().te_rgb_dgrad_f32(_ptr(gx), _ptr(g), _ptr(w.contiguous()), _ptr(isc), wscale, B, K, H * W, _stream()),
-           'te_rgb_dgrad_f32')
+    _launch('te_rgb_dgrad_f32', _ptr(gx), _ptr(g), _ptr(w.contiguous()), _ptr(isc), wscale, B, K, H * W)
     return gx
 
 
+@_op
 def rgb_wgrad_sum_slabs(g3, x):
     """slabs [B,S,4,K]: rows 0-2 = sum_p g3[b,o,p] x[b,k,p], row 3 = sum_p x[b,k,p]"""
     g3, x = g3.contiguous(), x.contiguous()
     B, K, H, W = x.shape
     S = lib().te_rgb_wgrad_slab_count(B, K, H * W)
     slabs = torch.empty(B, S, 4, K, device=x.device, dtype=x.dtype)
-    _check(lib().te_rgb_wgrad_sum_f32(_ptr(slabs), _ptr(g3), _ptr(x), B, K, H * W, S, _stream()), 'te_rgb_wgrad_sum_f32')
+    _launch('te_rgb_wgrad_sum_f32', _ptr(slabs), _ptr(g3), _ptr(x), B, K, H * W, S)
     return slabs
 
 
+@_op
 def rgb_expand(x3, w3k, bias, act, wscale=1.0):
     """from-RGB stem: x3 [B,3,H,W], w3k [3,K] -> act(wscale * sum_o w3k[o,k] x3[b,o] + bias[k])  [B,K,H,W].  The kernel reads x3
     with 16-byte accesses: a misaligned x3 goes in as an aligned copy."""
@@ -611,11 +508,11 @@ def rgb_expand(x3, w3k, bias, act, wscale=1.0):
     B, _, H, W = x3.shape
     K = w3k.shape[1]
     out = torch.empty(B, K, H, W, device=x3.device, dtype=x3.dtype)
-    _check(lib().te_rgb_expand_f32(_ptr(out), _ptr(x3), _ptr(w3k.contiguous()), _ptr(bias), act, wscale, B, K, H * W, _stream()),
-           'te_rgb_expand_f32')
+    _launch('te_rgb_expand_f32', _ptr(out), _ptr(x3), _ptr(w3k.contiguous()), _ptr(bias), act, wscale, B, K, H * W)
     return out
 
 
+@_op
 def rgb_wgrad_slabs(g, x):
     """correlation slabs [B,S,3,K,1] of the ToRGB weight gradient.  Operands go in as they come: the kernel itself stages a
     misaligned x through its scalar path (the same LDS tile, bit-identical slabs) and reads g element by element."""
@@ -623,11 +520,12 @@ def rgb_wgrad_slabs(g, x):
     B, K, H, W = x.shape
     S = lib().te_rgb_wgrad_slab_count(B, K, H * W)
     slabs = torch.empty(B, S, 3, K, 1, device=x.device, dtype=x.dtype)
-    _check(lib().te_rgb_wgrad_f32(_ptr(slabs), _ptr(g), _ptr(x), B, K, H * W, S, _stream()), 'te_rgb_wgrad_f32')
+    _launch('te_rgb_wgrad_f32', _ptr(slabs), _ptr(g), _ptr(x), B, K, H * W, S)
     return slabs
 
 
 # --------------------------------------------------------------------------------------------- G2/A2
+@_op
 def small_gemm(I, J, K, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alpha=1.0, beta=1.0, act=0, want_pre=False,
                rowsum_scale=None):
     """C[I,J] = act(alpha * A B + beta * bias) + residual with strided operands (see te_hip.h); a / b are the base
@@ -637,22 +535,23 @@ def small_gemm(I, J, K, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alph
     pre = torch.empty_like(c) if want_pre else None
     rs = torch.empty(I, device=a.device, dtype=a.dtype) if rowsum_scale is not None else None
     # a / b are addressed through explicit strides: only device / dtype are checked
-    _check(lib().te_small_gemm_f32(_ptr(c), _ptr(pre), _raw(a), _raw(b), _ptr(bias), _ptr(residual), _ptr(rs),
-                                   rowsum_scale if rowsum_scale is not None else 0.0, I, J, K, sai, sak, sbk, sbj, alpha,
-                                   beta, act, _stream()), 'te_small_gemm_f32')
+    _launch('te_small_gemm_f32', _ptr(c), _ptr(pre), _raw(a), _raw(b), _ptr(bias), _ptr(residual), _ptr(rs),
+            rowsum_scale if rowsum_scale is not None else 0.0, I, J, K, sai, sak, sbk, sbj, alpha, beta, act)
     return c, pre, rs
 
 
+@_op
 def small_gemm_splitk(I, J, K, S, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alpha=1.0, beta=1.0, act=0, want_pre=False):
     """small_gemm for wide reductions: K in S chunks over the grid, fixed-order second pass (see te_hip.h)."""
     c = torch.empty(I, J, device=a.device, dtype=a.dtype)
     pre = torch.empty_like(c) if want_pre else None
     ws = torch.empty(S, I, J, device=a.device, dtype=a.dtype)
-    _check(lib().te_small_gemm_splitk_f32(_ptr(c), _ptr(pre), _ptr(ws), S, _raw(a), _raw(b), _ptr(bias), _ptr(residual), I, J, K,
-                                          sai, sak, sbk, sbj, alpha, beta, act, _stream()), 'te_small_gemm_splitk_f32')
+    _launch('te_small_gemm_splitk_f32', _ptr(c), _ptr(pre), _ptr(ws), S, _raw(a), _raw(b), _ptr(bias), _ptr(residual), I, J, K, sai, sak,
+            sbk, sbj, alpha, beta, act)
     return c, pre
 
 
+@_op
 def minibatch_stddev_fwd(x, group, eps, chunks=1):
     """x [B, C, H, W] -> y [B, C + 1, H, W] (input copied, stddev channel appended); `chunks` > 1: the batch is `chunks`
     independent minibatches laid end to end (one launch each on its slice)"""
@@ -661,11 +560,11 @@ def minibatch_stddev_fwd(x, group, eps, chunks=1):
     y = torch.empty(B, Cn + 1, H, W, device=x.device, dtype=x.dtype)
     Bc = B // chunks
     for c in range(chunks):
-        _check(lib().te_minibatch_stddev_fwd_f32(_ptr(y[c * Bc:(c + 1) * Bc]), _ptr(x[c * Bc:(c + 1) * Bc]), Bc, group, Cn, H * W, eps,
-                                                 _stream()), 'te_minibatch_stddev_fwd_f32')
+        _launch('te_minibatch_stddev_fwd_f32', _ptr(y[c * Bc:(c + 1) * Bc]), _ptr(x[c * Bc:(c + 1) * Bc]), Bc, group, Cn, H * W, eps)
     return y
 
 
+@_op
 def minibatch_stddev_bwd(gy, x, group, eps, chunks=1):
     gy = gy.contiguous()
     B, Cn, H, W = x.shape
@@ -673,20 +572,19 @@ def minibatch_stddev_bwd(gy, x, group, eps, chunks=1):
     Bc = B // chunks
     for c in range(chunks):
         sl = slice(c * Bc, (c + 1) * Bc)
-        _check(lib().te_minibatch_stddev_bwd_f32(_ptr(gx[sl]), _ptr(gy[sl]), _ptr(x[sl]), Bc, group, Cn, H * W, eps, _stream()),
-               'te_minibatch_stddev_bwd_f32')
+        _launch('te_minibatch_stddev_bwd_f32', _ptr(gx[sl]), _ptr(gy[sl]), _ptr(x[sl]), Bc, group, Cn, H * W, eps)
     return gx
 
 
+@_op
 def small_gemm_batched(c, a, b, bias, nz, za, zc, I, J, K, sai, sak, sbk, sbj, sci, scj, zb=0, zbias=0, b_tab=None,
                        bias_tab=None, alpha=1.0, beta=1.0, act=0):
     """nz GEMMs in one launch (see te_hip.h); c is written in place through (zc, sci, scj).  b_tab / bias_tab: lists of
     element offsets relative to b / bias for separately allocated per-z operands."""
     bt = (C.c_int64 * nz)(*b_tab) if b_tab is not None else None
     bit = (C.c_int64 * nz)(*bias_tab) if bias_tab is not None else None
-    _check(lib().te_small_gemm_batched_f32(_raw(c), _raw(a), _raw(b), _raw(bias),
-                                           nz, za, zc, zb, zbias, bt, bit, I, J, K, sai, sak, sbk, sbj, sci, scj, alpha, beta,
-                                           act, _stream()), 'te_small_gemm_batched_f32')
+    _launch('te_small_gemm_batched_f32', _raw(c), _raw(a), _raw(b), _raw(bias), nz, za, zc, zb, zbias, bt, bit, I, J, K, sai, sak, sbk, sbj,
+            sci, scj, alpha, beta, act)
     return c
 
 
@@ -694,19 +592,21 @@ def layer_norm_supported(R, N):
     return bool(lib().te_layer_norm_supported(R, N))
 
 
+@_op
 def layer_norm_fwd(x2, eps):
     """x2 [R, N] contiguous -> (y [R, N], stats [R, 2])"""
     R, N = x2.shape
     y = torch.empty_like(x2)
     stats = torch.empty(R, 2, device=x2.device, dtype=x2.dtype)
-    _check(lib().te_layer_norm_fwd_f32(_ptr(y), _ptr(stats), _ptr(x2), R, N, eps, _stream()), 'te_layer_norm_fwd_f32')
+    _launch('te_layer_norm_fwd_f32', _ptr(y), _ptr(stats), _ptr(x2), R, N, eps)
     return y, stats
 
 
+@_op
 def layer_norm_bwd(g2, y2, stats):
     R, N = y2.shape
     gx = torch.empty_like(y2)
-    _check(lib().te_layer_norm_bwd_f32(_ptr(gx), _ptr(g2), _ptr(y2), _ptr(stats), R, N, _stream()), 'te_layer_norm_bwd_f32')
+    _launch('te_layer_norm_bwd_f32', _ptr(gx), _ptr(g2), _ptr(y2), _ptr(stats), R, N)
     return gx
 
 
@@ -714,43 +614,47 @@ def pixel_norm_supported(B, D, Cn):
     return bool(lib().te_pixel_norm_supported(B, D, Cn))
 
 
+@_op
 def pixel_norm_fwd(x, eps):
     """x [B, D, C] contiguous -> (y, r [B, C])"""
     B, D, Cn = x.shape
     y = torch.empty_like(x)
     r = torch.empty(B, Cn, device=x.device, dtype=x.dtype)
-    _check(lib().te_pixel_norm_fwd_f32(_ptr(y), _ptr(r), _ptr(x), B, D, Cn, eps, _stream()), 'te_pixel_norm_fwd_f32')
+    _launch('te_pixel_norm_fwd_f32', _ptr(y), _ptr(r), _ptr(x), B, D, Cn, eps)
     return y, r
 
 
+@_op
 def pixel_norm_bwd(g, y, r):
     B, D, Cn = y.shape
     gx = torch.empty_like(y)
-    _check(lib().te_pixel_norm_bwd_f32(_ptr(gx), _ptr(g), _ptr(y), _ptr(r), B, D, Cn, _stream()), 'te_pixel_norm_bwd_f32')
+    _launch('te_pixel_norm_bwd_f32', _ptr(gx), _ptr(g), _ptr(y), _ptr(r), B, D, Cn)
     return gx
 
 
 # --------------------------------------------------------------------------------------------- M1
+@_op
 def demod_fwd(w, s, wscale, eps):
     """w [Co,Ci,T] raw weights, s [B,Ci] -> (d [B,Co], wsq [Co,Ci])"""
     Co, Ci, T = w.shape
     B = s.shape[0]
     d = torch.empty(B, Co, device=w.device, dtype=w.dtype)
     wsq = torch.empty(Co, Ci, device=w.device, dtype=w.dtype)
-    _check(lib().te_demod_fwd_f32(_ptr(d), _ptr(wsq), _ptr(w), _ptr(s), wscale, eps, B, Co, Ci, T, _stream()),
-           'te_demod_fwd_f32')
+    _launch('te_demod_fwd_f32', _ptr(d), _ptr(wsq), _ptr(w), _ptr(s), wscale, eps, B, Co, Ci, T)
     return d, wsq
 
 
+@_op
 def demod_from_wsq(wsq, s, eps):
     """d [B,Co] from a cached wsq [Co,Ci] (frozen weights: the 9-tap squares are not recomputed)"""
     Co, Ci = wsq.shape
     B = s.shape[0]
     d = torch.empty(B, Co, device=wsq.device, dtype=wsq.dtype)
-    _check(lib().te_demod_fwd_f32(_ptr(d), None, _ptr(wsq), _ptr(s), 1.0, eps, B, Co, Ci, 0, _stream()), 'te_demod_fwd_f32')
+    _launch('te_demod_fwd_f32', _ptr(d), None, _ptr(wsq), _ptr(s), 1.0, eps, B, Co, Ci, 0)
     return d
 
 
+@_op
 def demod_bwd(gd, d, w, wsq, s, wscale, want_w=True, want_s=True, into=None):
     """into = (gw, gs): accumulate into these existing gradients (either may be None) instead of allocating new ones."""
     Co, Ci, T = w.shape
@@ -760,12 +664,13 @@ def demod_bwd(gd, d, w, wsq, s, wscale, want_w=True, want_s=True, into=None):
     else:
         gw = torch.empty_like(w) if want_w else None
         gs = torch.empty_like(s) if want_s else None
-    _check(lib().te_demod_bwd_f32(_ptr(gw), _ptr(gs), _ptr(gd.contiguous()), _ptr(d), _ptr(w), _ptr(wsq), _ptr(s), wscale,
-                                  B, Co, Ci, T, 1 if into is not None else 0, _stream()), 'te_demod_bwd_f32')
+    _launch('te_demod_bwd_f32', _ptr(gw), _ptr(gs), _ptr(gd.contiguous()), _ptr(d), _ptr(w), _ptr(wsq), _ptr(s), wscale, B, Co, Ci, T,
+            1 if into is not None else 0)
     return gw, gs
 
 
 # --------------------------------------------------------------------------------------------- F2
+@_op
 def attn_fwd(q, k, v, scale, groups):
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     N, M, Cn = q.shape
@@ -773,128 +678,135 @@ def attn_fwd(q, k, v, scale, groups):
     D = Cn // groups
     o = torch.empty_like(q)
     sim = torch.empty(N, groups, M, L, device=q.device, dtype=q.dtype)
-    _check(lib().te_attn_fwd_f32(_ptr(o), _ptr(sim), _ptr(q), _ptr(k), _ptr(v), scale, N, groups, M, L, D, _stream()),
-           'te_attn_fwd_f32')
+    _launch('te_attn_fwd_f32', _ptr(o), _ptr(sim), _ptr(q), _ptr(k), _ptr(v), scale, N, groups, M, L, D)
     return o, sim
 
 
+@_op
 def attn_bwd(go, gsim, q, k, v, sim, scale, groups):
     N, M, Cn = q.shape
     L = k.shape[1]
     gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    _check(lib().te_attn_bwd_f32(_ptr(gq), _ptr(gk), _ptr(gv), _ptr(go.contiguous()),
-                                 _ptr(gsim.contiguous()) if gsim is not None else None, _ptr(q), _ptr(k), _ptr(v),
-                                 _ptr(sim), scale, N, groups, M, L, Cn // groups, _stream()), 'te_attn_bwd_f32')
+    _launch('te_attn_bwd_f32', _ptr(gq), _ptr(gk), _ptr(gv), _ptr(go.contiguous()), _ptr(gsim.contiguous()) if gsim is not None else None,
+            _ptr(q), _ptr(k), _ptr(v), _ptr(sim), scale, N, groups, M, L, Cn // groups)
     return gq, gk, gv
 
 
 # --------------------------------------------------------------------------------------------- T2
+@_op
 def mt_adam(table, chunks, n_tensors, n_chunks, chunk_elems, lr, beta1, beta2, eps, step):
     """table: int64 device tensor [5, n]; chunks: int32 device tensor [2, n_chunks] (see te_hip.h)"""
     _on_current_device(table)
-    _check(lib().te_mt_adam_f32(table.data_ptr(), chunks.data_ptr(), n_tensors, n_chunks, chunk_elems, lr, beta1, beta2, eps,
-                                step, _stream()), 'te_mt_adam_f32')
+    _launch('te_mt_adam_f32', table.data_ptr(), chunks.data_ptr(), n_tensors, n_chunks, chunk_elems, lr, beta1, beta2, eps, step)
 
 
+@_op
 def mt_ema(table, chunks, n_tensors, n_chunks, chunk_elems, decay):
     _on_current_device(table)
-    _check(lib().te_mt_ema_f32(table.data_ptr(), chunks.data_ptr(), n_tensors, n_chunks, chunk_elems, float(decay), _stream()),
-           'te_mt_ema_f32')
+    _launch('te_mt_ema_f32', table.data_ptr(), chunks.data_ptr(), n_tensors, n_chunks, chunk_elems, float(decay))
 
 
 # --------------------------------------------------------------------------------------------- channel scale / dot
+@_op
 def chan_scale(x, s):
     """x [B,C,...] * s[B,C] broadcast over the trailing dims"""
     x, s = x.contiguous(), s.contiguous()
     rows = x.shape[0] * x.shape[1]
     out = torch.empty_like(x)
-    _check(lib().te_chan_scale_f32(_ptr(out), _ptr(x), _ptr(s), rows, x.numel() // max(rows, 1), _stream()), 'te_chan_scale_f32')
+    _launch('te_chan_scale_f32', _ptr(out), _ptr(x), _ptr(s), rows, x.numel() // max(rows, 1))
     return out
 
 
+@_op
 def chan_dot(a, b):
     """sum over the trailing dims of a * b -> [B,C]"""
     a, b = a.contiguous(), b.contiguous()
     rows = a.shape[0] * a.shape[1]
     out = torch.empty(a.shape[0], a.shape[1], device=a.device, dtype=a.dtype)
-    _check(lib().te_chan_dot_f32(_ptr(out), _ptr(a), _ptr(b), rows, a.numel() // max(rows, 1), _stream()), 'te_chan_dot_f32')
+    _launch('te_chan_dot_f32', _ptr(out), _ptr(a), _ptr(b), rows, a.numel() // max(rows, 1))
     return out
 
 
 # --------------------------------------------------------------------------------------------- L1 LPIPS-VGG pieces
+@_op
 def lpips_stem_fwd(x, w, b):
     """ScalingLayer -> conv1_1 -> bias -> ReLU: x [N,3,H,W] -> [N,64,H,W]"""
     x = x.contiguous()
     N, _, H, W = x.shape
     out = torch.empty(N, 64, H, W, device=x.device, dtype=x.dtype)
-    _check(lib().te_lpips_stem_fwd_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(b), N, H, W, _stream()), 'te_lpips_stem_fwd_f32')
+    _launch('te_lpips_stem_fwd_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(b), N, H, W)
     return out
 
 
+@_op
 def lpips_stem_dgrad(g, y1, w):
     """data gradient of the stem w.r.t. the UNSCALED input (relu1_1 mask from its output y1)"""
     g = g.contiguous()
     N, _, H, W = g.shape
     gx = torch.empty(N, 3, H, W, device=g.device, dtype=g.dtype)
-    _check(lib().te_lpips_stem_dgrad_f32(_ptr(gx), _ptr(g), _ptr(y1), _ptr(w), N, H, W, _stream()), 'te_lpips_stem_dgrad_f32')
+    _launch('te_lpips_stem_dgrad_f32', _ptr(gx), _ptr(g), _ptr(y1), _ptr(w), N, H, W)
     return gx
 
 
+@_op
 def maxpool2_fwd(x):
     x = x.contiguous()
     N, Cn, H, W = x.shape
     out = torch.empty(N, Cn, H // 2, W // 2, device=x.device, dtype=x.dtype)
-    _check(lib().te_maxpool2_fwd_f32(_ptr(out), _ptr(x), N * Cn, H, W, _stream()), 'te_maxpool2_fwd_f32')
+    _launch('te_maxpool2_fwd_f32', _ptr(out), _ptr(x), N * Cn, H, W)
     return out
 
 
+@_op
 def maxpool2_bwd(g, x):
     g = g.contiguous()
     N, Cn, H, W = x.shape
     gx = torch.empty_like(x)
-    _check(lib().te_maxpool2_bwd_f32(_ptr(gx), _ptr(g), _ptr(x), N * Cn, H, W, _stream()), 'te_maxpool2_bwd_f32')
+    _launch('te_maxpool2_bwd_f32', _ptr(gx), _ptr(g), _ptr(x), N * Cn, H, W)
     return gx
 
 
+@_op
 def lpips_normalize(x):
     x = x.contiguous()
     out = torch.empty_like(x)
-    _check(lib().te_lpips_normalize_f32(_ptr(out), _ptr(x), x.shape[0], x.shape[1], x.shape[2] * x.shape[3], _stream()),
-           'te_lpips_normalize_f32')
+    _launch('te_lpips_normalize_f32', _ptr(out), _ptr(x), x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
     return out
 
 
+@_op
 def lpips_head_fwd(f, t_hat, w):
     """per-block partial sums [N, blocks] of one layer's head (t_hat: normalised target features, batch N or 1)"""
     f = f.contiguous()
     N, Cn, H, W = f.shape
     nb = lib().te_lpips_head_blocks(H * W)
     partial = torch.empty(N, nb, device=f.device, dtype=f.dtype)
-    _check(lib().te_lpips_head_fwd_f32(_ptr(partial), _ptr(f), _ptr(t_hat), _ptr(w), N, t_hat.shape[0], Cn, H * W, _stream()),
-           'te_lpips_head_fwd_f32')
+    _launch('te_lpips_head_fwd_f32', _ptr(partial), _ptr(f), _ptr(t_hat), _ptr(w), N, t_hat.shape[0], Cn, H * W)
     return partial
 
 
+@_op
 def lpips_dist(partials, hws):
     """d[N] = sum over layers (in order) of the spatial means"""
     L, N = len(partials), partials[0].shape[0]
     d = torch.empty(N, device=partials[0].device, dtype=torch.float32)
     ptrs = (C.c_void_p * L)(*[_ptr(p) for p in partials])
     hw = (C.c_int64 * L)(*hws)
-    _check(lib().te_lpips_dist_f32(_ptr(d), ptrs, hw, L, N, _stream()), 'te_lpips_dist_f32')
+    _launch('te_lpips_dist_f32', _ptr(d), ptrs, hw, L, N)
     return d
 
 
+@_op
 def lpips_head_bwd(gd, f, t_hat, w, gin=None, relu_mask=True):
     f = f.contiguous()
     N, Cn, H, W = f.shape
     gf = torch.empty_like(f)
-    _check(lib().te_lpips_head_bwd_f32(_ptr(gf), _ptr(gin.contiguous()) if gin is not None else None, _ptr(gd.contiguous()), _ptr(f),
-                                       _ptr(t_hat), _ptr(w), N, t_hat.shape[0], Cn, H * W, 1 if relu_mask else 0, _stream()),
-           'te_lpips_head_bwd_f32')
+    _launch('te_lpips_head_bwd_f32', _ptr(gf), _ptr(gin.contiguous()) if gin is not None else None, _ptr(gd.contiguous()), _ptr(f),
+            _ptr(t_hat), _ptr(w), N, t_hat.shape[0], Cn, H * W, 1 if relu_mask else 0)
     return gf
 
 
+@_op
 def lpips_pair_head_fwd(f, w):
     """per-block partial sums [N, blocks] of one layer's head for an interleaved batch f [2N,C,H,W] (images 2n, 2n+1 are a pair)"""
     if f.shape[0] % 2:
@@ -903,10 +815,11 @@ def lpips_pair_head_fwd(f, w):
     N, Cn, H, W = f.shape[0] // 2, f.shape[1], f.shape[2], f.shape[3]
     nb = lib().te_lpips_head_blocks(H * W)
     partial = torch.empty(N, nb, device=f.device, dtype=f.dtype)
-    _check(lib().te_lpips_pair_head_fwd_f32(_ptr(partial), _ptr(f), _ptr(w), N, Cn, H * W, _stream()), 'te_lpips_pair_head_fwd_f32')
+    _launch('te_lpips_pair_head_fwd_f32', _ptr(partial), _ptr(f), _ptr(w), N, Cn, H * W)
     return partial
 
 
+@_op
 def crop_resize_bilinear(img, y0, x0, hc, wc, h, w):
     """window [y0:y0+hc, x0:x0+wc] of img [B,3,H,W], bilinear (align_corners=False) to [B,3,h,w]; hc / h and wc / w integers"""
     img = img.contiguous()
@@ -914,8 +827,7 @@ def crop_resize_bilinear(img, y0, x0, hc, wc, h, w):
     if Cn != 3:
         raise RuntimeError(f'te_hip: crop_resize_bilinear expects [B,3,H,W] images, got {tuple(img.shape)}')
     out = torch.empty(B, 3, h, w, device=img.device, dtype=img.dtype)
-    _check(lib().te_crop_resize_bilinear_f32(_ptr(out), _ptr(img), B, H, W, y0, x0, hc, wc, h, w, _stream()),
-           'te_crop_resize_bilinear_f32')
+    _launch('te_crop_resize_bilinear_f32', _ptr(out), _ptr(img), B, H, W, y0, x0, hc, wc, h, w)
     return out
 
 
@@ -933,6 +845,7 @@ def _noise_list(maps):
     return ptrs, sizes, n, B
 
 
+@_op
 def noise_reg_fwd(maps):
     """-> (loss [1], workspace for noise_reg_bwd)"""
     ptrs, sizes, n, B = _noise_list(maps)
@@ -941,23 +854,24 @@ def noise_reg_fwd(maps):
         raise RuntimeError(f'te_noise_reg_ws_floats failed ({nws})')
     loss = torch.empty(1, device=maps[0].device, dtype=torch.float32)
     ws = torch.empty(nws, device=maps[0].device, dtype=torch.float32)
-    _check(lib().te_noise_reg_fwd_f32(_ptr(loss), _ptr(ws), ptrs, sizes, n, B, _stream()), 'te_noise_reg_fwd_f32')
+    _launch('te_noise_reg_fwd_f32', _ptr(loss), _ptr(ws), ptrs, sizes, n, B)
     return loss, ws
 
 
+@_op
 def noise_reg_bwd(gloss, ws, maps):
     ptrs, sizes, n, B = _noise_list(maps)
     grads = [torch.empty_like(m) for m in maps]
     gptrs = (C.c_void_p * n)(*[_ptr(g) for g in grads])
     tws = torch.empty_like(ws)
-    _check(lib().te_noise_reg_bwd_f32(gptrs, _ptr(tws), _ptr(gloss.reshape(1).contiguous()), _ptr(ws), ptrs, sizes, n, B, _stream()),
-           'te_noise_reg_bwd_f32')
+    _launch('te_noise_reg_bwd_f32', gptrs, _ptr(tws), _ptr(gloss.reshape(1).contiguous()), _ptr(ws), ptrs, sizes, n, B)
     return grads
 
 
+@_op
 def noise_normalize_(maps):
     ptrs, sizes, n, B = _noise_list(maps)
-    _check(lib().te_noise_normalize_f32(ptrs, sizes, n, B, _stream()), 'te_noise_normalize_f32')
+    _launch('te_noise_normalize_f32', ptrs, sizes, n, B)
 
 
 # --------------------------------------------------------------------------------------------- M1 PRDC
@@ -975,14 +889,16 @@ def _prdc_ws(N, M, D, k, device):
     return torch.empty(nb // 4, device=device, dtype=torch.float32)
 
 
+@_op
 def row_sqnorm(x):
     """[N,D] -> the squared row norms [N]"""
     N, D = _features(x, 'row_sqnorm')
     out = torch.empty(N, device=x.device, dtype=torch.float32)
-    _check(lib().te_row_sqnorm_f32(_ptr(out), _ptr(x), N, D, _stream()), 'te_row_sqnorm_f32')
+    _launch('te_row_sqnorm_f32', _ptr(out), _ptr(x), N, D)
     return out
 
 
+@_op
 def prdc_knn(x, nx, k):
     """squared distance of every row of x [N,D] to its k-th nearest other row (element k of the sorted row, diagonal 0) -> [N]"""
     N, D = _features(x, 'prdc_knn')
@@ -990,10 +906,11 @@ def prdc_knn(x, nx, k):
         raise RuntimeError(f'te_hip: prdc_knn expects {N} row norms, got {tuple(nx.shape)}')
     ws = _prdc_ws(N, N, D, k, x.device)
     r2 = torch.empty(N, device=x.device, dtype=torch.float32)
-    _check(lib().te_prdc_knn_f32(_ptr(r2), _ptr(x), _ptr(nx), N, D, k, _ptr(ws), _stream()), 'te_prdc_knn_f32')
+    _launch('te_prdc_knn_f32', _ptr(r2), _ptr(x), _ptr(nx), N, D, k, _ptr(ws))
     return r2
 
 
+@_op
 def prdc_counts(x, nx, rr2, y, ny, rf2):
     """real x [N,D], fake y [M,D], their row norms and squared radii -> (col_count [M] int32, row_any [N] int32, row_min [N])"""
     N, D = _features(x, 'prdc_counts')
@@ -1005,27 +922,29 @@ def prdc_counts(x, nx, rr2, y, ny, rf2):
     col_count = torch.empty(M, device=x.device, dtype=torch.int32)
     row_any = torch.empty(N, device=x.device, dtype=torch.int32)
     row_min = torch.empty(N, device=x.device, dtype=torch.float32)
-    _check(lib().te_prdc_counts_f32(_ptr_as(col_count, torch.int32), _ptr_as(row_any, torch.int32), _ptr(row_min), _ptr(x), _ptr(nx),
-                                    _ptr(rr2), _ptr(y), _ptr(ny), _ptr(rf2), N, M, D, _ptr(ws), _stream()), 'te_prdc_counts_f32')
+    _launch('te_prdc_counts_f32', _ptr_as(col_count, torch.int32), _ptr_as(row_any, torch.int32), _ptr(row_min), _ptr(x), _ptr(nx),
+            _ptr(rr2), _ptr(y), _ptr(ny), _ptr(rf2), N, M, D, _ptr(ws))
     return col_count, row_any, row_min
 
 
 # --------------------------------------------------------------------------------------------- M2 VGG16 fc7 features
+@_op
 def vgg_stem_fwd(x, w, b):
     """conv1_1 -> bias -> ReLU on the raw input (no ScalingLayer): x [N,3,H,W] -> [N,64,H,W]"""
     x = x.contiguous()
     N, _, H, W = x.shape
     out = torch.empty(N, 64, H, W, device=x.device, dtype=x.dtype)
-    _check(lib().te_vgg_stem_fwd_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(b), N, H, W, _stream()), 'te_vgg_stem_fwd_f32')
+    _launch('te_vgg_stem_fwd_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(b), N, H, W)
     return out
 
 
+@_op
 def adaptive_avgpool(x, OH=7, OW=7):
     """torch's adaptive_avg_pool2d: x [N,C,H,W] -> [N,C,OH,OW] (contiguous: .view(N, -1) is the flattened layout)"""
     x = x.contiguous()
     N, Cn, H, W = x.shape
     out = torch.empty(N, Cn, OH, OW, device=x.device, dtype=x.dtype)
-    _check(lib().te_adaptive_avgpool_f32(_ptr(out), _ptr(x), N * Cn, H, W, OH, OW, _stream()), 'te_adaptive_avgpool_f32')
+    _launch('te_adaptive_avgpool_f32', _ptr(out), _ptr(x), N * Cn, H, W, OH, OW)
     return out
 
 
@@ -1037,6 +956,7 @@ def fc_stream_splits(J, K):
     return S
 
 
+@_op
 def fc_stream(a, w, bias, act=0):
     """act(a @ w.T + bias): a [I,K], w [J,K] (torch Linear layout), bias [J] -> [I,J]; act 0 none, 1 ReLU.  The ABI refuses bad shapes
     and misaligned operands; nothing is launched then."""
@@ -1046,7 +966,7 @@ def fc_stream(a, w, bias, act=0):
     nb = lib().te_fc_stream_ws_bytes(I, J, K)
     c = torch.empty(I, J, device=a.device, dtype=a.dtype)
     ws = torch.empty(max(nb, 4) // 4, device=a.device, dtype=a.dtype)        # (nb < 0: the call below names what is wrong)
-    _check(lib().te_fc_stream_f32(_ptr(c), _ptr(ws), _ptr(a), _ptr(w), _ptr(bias), I, J, K, act, _stream()), 'te_fc_stream_f32')
+    _launch('te_fc_stream_f32', _ptr(c), _ptr(ws), _ptr(a), _ptr(w), _ptr(bias), I, J, K, act)
     return c
 
 
@@ -1058,6 +978,7 @@ def fid_moments_ws_bytes(N, D):
     return nb
 
 
+@_op
 def fid_moments(S, s, x, accumulate):
     """S [D,D] fp64 (upper triangle) and s [D] fp64 (+)= the second and first moments of the rows of x [N,D] fp32; in place"""
     N, D = _features(x, 'fid_moments')
@@ -1065,10 +986,11 @@ def fid_moments(S, s, x, accumulate):
         raise RuntimeError(f'te_hip: fid_moments: x {tuple(x.shape)} needs S [{D},{D}] and s [{D}], got {tuple(S.shape)} and {tuple(s.shape)}')
     nb = fid_moments_ws_bytes(N, D)
     ws = torch.empty(nb // 8, device=x.device, dtype=torch.float64) if nb else None
-    _check(lib().te_fid_moments_f64(_ptr_as(S, torch.float64), _ptr_as(s, torch.float64), _ptr_as(ws, torch.float64), _ptr(x), N, D,
-                                    1 if accumulate else 0, _stream()), 'te_fid_moments_f64')
+    _launch('te_fid_moments_f64', _ptr_as(S, torch.float64), _ptr_as(s, torch.float64), _ptr_as(ws, torch.float64), _ptr(x), N, D,
+            1 if accumulate else 0)
 
 
+@_op
 def fid_finalize(S, s, n):
     """the moments of n samples -> (mean [D], cov [D,D]) fp64 on the device: np.mean / np.cov(rowvar=False)"""
     if S.ndim != 2 or S.shape[0] != S.shape[1] or s.shape != (S.shape[0],):
@@ -1076,8 +998,8 @@ def fid_finalize(S, s, n):
     D = S.shape[0]
     mean = torch.empty(D, device=S.device, dtype=torch.float64)
     cov = torch.empty(D, D, device=S.device, dtype=torch.float64)
-    _check(lib().te_fid_finalize_f64(_ptr_as(mean, torch.float64), _ptr_as(cov, torch.float64), _ptr_as(S, torch.float64),
-                                     _ptr_as(s, torch.float64), int(n), D, _stream()), 'te_fid_finalize_f64')
+    _launch('te_fid_finalize_f64', _ptr_as(mean, torch.float64), _ptr_as(cov, torch.float64), _ptr_as(S, torch.float64),
+            _ptr_as(s, torch.float64), int(n), D)
     return mean, cov
 
 
@@ -1095,14 +1017,16 @@ def _labels(y, n, what):
     return y
 
 
+@_op
 def gram(x):
     """x [n,D] -> K = x x^T [n,n], bitwise symmetric"""
     n, D = _features(x, 'gram')
     K = torch.empty(n, n, device=x.device, dtype=torch.float32)
-    _check(lib().te_gram_f32(_ptr(K), _ptr(x), n, D, _stream()), 'te_gram_f32')
+    _launch('te_gram_f32', _ptr(K), _ptr(x), n, D)
     return K
 
 
+@_op
 def svm_smo(K, y, C_=1.0, eps=1e-3, max_iter=1_000_000):
     """the C-SVC dual on the Gram matrix K [n,n] with HOST labels y (+1 / -1) -> (alpha [n] fp64, rho [1] fp64, info [2] int32 =
     (iterations, converged)), all on the device; nothing synchronises"""
@@ -1113,11 +1037,12 @@ def svm_smo(K, y, C_=1.0, eps=1e-3, max_iter=1_000_000):
     alpha = torch.empty(n, device=K.device, dtype=torch.float64)
     rho = torch.empty(1, device=K.device, dtype=torch.float64)
     info = torch.empty(2, device=K.device, dtype=torch.int32)
-    _check(lib().te_svm_smo_f64(_ptr_as(alpha, torch.float64), _ptr_as(rho, torch.float64), _ptr_as(info, torch.int32), _ptr(K),
-                                y.ctypes.data, n, float(C_), float(eps), int(max_iter), _stream()), 'te_svm_smo_f64')
+    _launch('te_svm_smo_f64', _ptr_as(alpha, torch.float64), _ptr_as(rho, torch.float64), _ptr_as(info, torch.int32), _ptr(K),
+            y.ctypes.data, n, float(C_), float(eps), int(max_iter))
     return alpha, rho, info
 
 
+@_op
 def svm_coef(x, alpha, y):
     """w [D] = sum_i alpha_i y_i x[i,:] (fp64 accumulation, one rounding): x [n,D] fp32, alpha [n] fp64, HOST labels y"""
     n, D = _features(x, 'svm_coef')
@@ -1125,7 +1050,7 @@ def svm_coef(x, alpha, y):
         raise RuntimeError(f'te_hip: svm_coef expects {n} alphas, got {tuple(alpha.shape)}')
     y = _labels(y, n, 'svm_coef')
     w = torch.empty(D, device=x.device, dtype=torch.float32)
-    _check(lib().te_svm_coef_f32(_ptr(w), _ptr(x), _ptr_as(alpha, torch.float64), y.ctypes.data, n, D, _stream()), 'te_svm_coef_f32')
+    _launch('te_svm_coef_f32', _ptr(w), _ptr(x), _ptr_as(alpha, torch.float64), y.ctypes.data, n, D)
     return w
 
 
@@ -1148,6 +1073,7 @@ def _slice_out(out, c0, B, Cn, Ho, Wo, like, what):
     return out
 
 
+@_op
 def conv2d(x, w, bias, stride=1, pad=(0, 0), act=0, out=None, c0=0):
     """act(conv2d(x, w, stride, pad) + bias) written into channels [c0, c0 + Co) of `out` [B,Ctot,Ho,Wo] (a new [B,Co,Ho,Wo] tensor
     where out is None): x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co]; act 0 none, 1 ReLU.  The ABI refuses what it does not cover (a
@@ -1158,11 +1084,12 @@ def conv2d(x, w, bias, stride=1, pad=(0, 0), act=0, out=None, c0=0):
     (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
     Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
     out = _slice_out(out, c0, B, Co, max(Ho, 0), max(Wo, 0), x, 'conv2d')
-    _check(lib().te_conv2d_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(bias), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], out.shape[1],
-                               c0, act, _stream()), 'te_conv2d_f32')
+    _launch('te_conv2d_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], out.shape[1], c0,
+            act)
     return out
 
 
+@_op
 def pool3(x, mode, out=None, c0=0):
     """3 x 3 pooling of x [B,C,H,W] into channels [c0, c0 + C) of `out`: POOL3_MAX_S2 (max, stride 2, no padding), POOL3_MAX_S1 (max,
     stride 1, pad 1) or POOL3_AVG_S1 (average, stride 1, pad 1, over the taps inside the image).  Returns out."""
@@ -1171,10 +1098,11 @@ def pool3(x, mode, out=None, c0=0):
     B, Cn, H, W = x.shape
     Ho, Wo = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == POOL3_MAX_S2 else (H, W)
     out = _slice_out(out, c0, B, Cn, max(Ho, 0), max(Wo, 0), x, 'pool3')
-    _check(lib().te_pool3_f32(_ptr(out), _ptr(x), B, Cn, H, W, mode, out.shape[1], c0, _stream()), 'te_pool3_f32')
+    _launch('te_pool3_f32', _ptr(out), _ptr(x), B, Cn, H, W, mode, out.shape[1], c0)
     return out
 
 
+@_op
 def resize_bilinear(x, OH, OW):
     """F.interpolate(x, (OH, OW), mode='bilinear', align_corners=False) of x [B,C,H,W]"""
     if x.ndim != 4:
@@ -1182,7 +1110,7 @@ def resize_bilinear(x, OH, OW):
     x = x.contiguous()
     B, Cn, H, W = x.shape
     out = torch.empty(B, Cn, OH, OW, device=x.device, dtype=x.dtype)
-    _check(lib().te_resize_bilinear_f32(_ptr(out), _ptr(x), B * Cn, H, W, OH, OW, _stream()), 'te_resize_bilinear_f32')
+    _launch('te_resize_bilinear_f32', _ptr(out), _ptr(x), B * Cn, H, W, OH, OW)
     return out
 
 
@@ -1190,16 +1118,18 @@ def resize_bilinear(x, OH, OW):
 CLS_EXPECTATION, CLS_FIRST = 0, 1
 
 
+@_op
 def dex_stem_fwd(img, w, b, crop):
     """RGB [-1, 1] -> BGR byte levels -> centre crop -> conv1_1 -> bias -> ReLU: img [N,3,H,W] -> [N,64,crop,crop].  The ABI refuses a
     crop that does not fit or is not centred (an odd H - crop or W - crop); nothing is launched then."""
     img = img.contiguous()
     N, _, H, W = img.shape
     out = torch.empty(N, 64, max(crop, 0), max(crop, 0), device=img.device, dtype=img.dtype)
-    _check(lib().te_dex_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, crop, _stream()), 'te_dex_stem_fwd_f32')
+    _launch('te_dex_stem_fwd_f32', _ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, crop)
     return out
 
 
+@_op
 def cls_score(a, w, bias, mode, want_prob=False):
     """p = softmax(a @ w.T + bias) over the classes: a [I,K], w [C,K] (torch Linear layout), bias [C] -> score [I] = sum_c (c + 1) p_c
     (CLS_EXPECTATION) or p_0 (CLS_FIRST); want_prob: -> (score, p [I,C]).  The ABI refuses C > 1024, K % 4 != 0 and misaligned
@@ -1209,11 +1139,12 @@ def cls_score(a, w, bias, mode, want_prob=False):
     (I, K), Cn = a.shape, w.shape[0]
     score = torch.empty(I, device=a.device, dtype=a.dtype)
     prob = torch.empty(I, Cn, device=a.device, dtype=a.dtype) if want_prob else None
-    _check(lib().te_cls_score_f32(_ptr(score), _ptr(prob), _ptr(a), _ptr(w), _ptr(bias), I, Cn, K, mode, _stream()), 'te_cls_score_f32')
+    _launch('te_cls_score_f32', _ptr(score), _ptr(prob), _ptr(a), _ptr(w), _ptr(bias), I, Cn, K, mode)
     return (score, prob) if want_prob else score
 
 
 # --------------------------------------------------------------------------------------------- M6 CelebA-HQ attribute classifier
+@_op
 def attr_stem_fwd(img, w, b, R, preprocessed=False):
     """RGB [-1, 1] -> BGR byte levels (preprocessed: img already is) -> f x f box mean, f = S / R -> 1x1 convolution -> bias ->
     leaky ReLU 0.2: img [N,3,S,S], w [C0,3] (scaled), b [C0] -> [N,C0,R,R].  The ABI refuses an S that is no multiple of R and
@@ -1223,11 +1154,11 @@ def attr_stem_fwd(img, w, b, R, preprocessed=False):
     img = img.contiguous()
     N, S, C0 = img.shape[0], img.shape[2], w.shape[0]
     out = torch.empty(N, C0, max(R, 0), max(R, 0), device=img.device, dtype=img.dtype)
-    _check(lib().te_attr_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, S, R, C0, 1 if preprocessed else 0, _stream()),
-           'te_attr_stem_fwd_f32')
+    _launch('te_attr_stem_fwd_f32', _ptr(out), _ptr(img), _ptr(w), _ptr(b), N, S, R, C0, 1 if preprocessed else 0)
     return out
 
 
+@_op
 def avgpool2_act(x, slope=1.0):
     """2 x 2 average pool, then v > 0 ? v : slope * v (slope 1: the plain pool): x [N,C,H,W] -> [N,C,H/2,W/2]"""
     if x.ndim != 4:
@@ -1235,10 +1166,11 @@ def avgpool2_act(x, slope=1.0):
     x = x.contiguous()
     N, Cn, H, W = x.shape
     out = torch.empty(N, Cn, H // 2, W // 2, device=x.device, dtype=x.dtype)
-    _check(lib().te_avgpool2_act_f32(_ptr(out), _ptr(x), N * Cn, H, W, slope, _stream()), 'te_avgpool2_act_f32')
+    _launch('te_avgpool2_act_f32', _ptr(out), _ptr(x), N * Cn, H, W, slope)
     return out
 
 
+@_op
 def attr_score(a, w, bias, slope=0.2, want_logit=True, want_score=True):
     """logit = bias + act(a) @ w, score = 1 / (1 + exp(2 logit)): a [I,K] (dense0's output before its activation), w [K] (scaled),
     bias [1] -> (logit [I] or None, score [I] or None).  The ABI refuses K % 4 != 0 and misaligned operands; nothing is launched
@@ -1248,11 +1180,12 @@ def attr_score(a, w, bias, slope=0.2, want_logit=True, want_score=True):
     I, K = a.shape
     logit = torch.empty(I, device=a.device, dtype=a.dtype) if want_logit else None
     score = torch.empty(I, device=a.device, dtype=a.dtype) if want_score else None
-    _check(lib().te_attr_score_f32(_ptr(logit), _ptr(score), _ptr(a), _ptr(w), _ptr(bias), I, K, slope, _stream()), 'te_attr_score_f32')
+    _launch('te_attr_score_f32', _ptr(logit), _ptr(score), _ptr(a), _ptr(w), _ptr(bias), I, K, slope)
     return logit, score
 
 
 # --------------------------------------------------------------------------------------------- M7 ResNet-18 pose classifier
+@_op
 def conv2d_res(x, w, bias, res, stride=1, pad=(0, 0), act=1):
     """act((conv2d(x, w, stride, pad) + bias) + res), the end of a ResNet BasicBlock: x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co],
     res [B,Co,Ho,Wo] -> a new [B,Co,Ho,Wo] tensor, bitwise relu(conv2d(act=0) + res).  The ABI refuses what te_conv2d_f32 refuses;
@@ -1264,11 +1197,11 @@ def conv2d_res(x, w, bias, res, stride=1, pad=(0, 0), act=1):
     if tuple(res.shape) != (B, Co, Ho, Wo):
         raise RuntimeError(f'te_hip: conv2d_res: the residual must be [{B},{Co},{Ho},{Wo}], got {tuple(res.shape)}')
     out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
-    _check(lib().te_conv2d_res_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(res), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], act,
-                                   _stream()), 'te_conv2d_res_f32')
+    _launch('te_conv2d_res_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(res), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], act)
     return out
 
 
+@_op
 def pose_stem_fwd(img, w, b, crop, preprocessed=False):
     """RGB [-1, 1] -> BGR byte levels (preprocessed: img already is) -> centre crop -> 7x7 stride-2 pad-3 convolution -> bias -> ReLU:
     img [N,3,H,W], w [Co,3,7,7], b [Co] -> [N,Co,Hc,Hc], Hc = (crop - 1) // 2 + 1.  The ABI refuses a crop that does not fit or is not
@@ -1279,11 +1212,11 @@ def pose_stem_fwd(img, w, b, crop, preprocessed=False):
     (N, _, H, W), Co = img.shape, w.shape[0]
     Hc = (max(crop, 1) - 1) // 2 + 1
     out = torch.empty(N, Co, Hc, Hc, device=img.device, dtype=img.dtype)
-    _check(lib().te_pose_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, crop, Co, 1 if preprocessed else 0, _stream()),
-           'te_pose_stem_fwd_f32')
+    _launch('te_pose_stem_fwd_f32', _ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, crop, Co, 1 if preprocessed else 0)
     return out
 
 
+@_op
 def maxpool3s2p1(x):
     """nn.MaxPool2d(3, 2, 1): x [N,C,H,W] -> [N,C,(H - 1) // 2 + 1,(W - 1) // 2 + 1]; the padding never wins, a NaN propagates"""
     if x.ndim != 4:
@@ -1291,11 +1224,12 @@ def maxpool3s2p1(x):
     x = x.contiguous()
     N, Cn, H, W = x.shape
     out = torch.empty(N, Cn, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, dtype=x.dtype)
-    _check(lib().te_maxpool3s2p1_f32(_ptr(out), _ptr(x), N * Cn, H, W, _stream()), 'te_maxpool3s2p1_f32')
+    _launch('te_maxpool3s2p1_f32', _ptr(out), _ptr(x), N * Cn, H, W)
     return out
 
 
 # --------------------------------------------------------------------------------------------- M8 AlexNet LPIPS (diversity score)
+@_op
 def alex_stem_fwd(img, w, b):
     """(x - mu) / sigma -> 11x11 stride-4 pad-2 convolution -> bias -> ReLU: img [N,3,H,W], w [Co,3,11,11], b [Co] ->
     [N,Co,(H - 7) // 4 + 1,(W - 7) // 4 + 1].  The ABI refuses an image below 7 px; nothing is launched then."""
@@ -1305,20 +1239,22 @@ def alex_stem_fwd(img, w, b):
     (N, _, H, W), Co = img.shape, w.shape[0]
     Ho, Wo = conv2d_out_hw(H, W, 11, 11, 4, (2, 2))
     out = torch.empty(N, Co, max(Ho, 0), max(Wo, 0), device=img.device, dtype=img.dtype)
-    _check(lib().te_alex_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, Co, _stream()), 'te_alex_stem_fwd_f32')
+    _launch('te_alex_stem_fwd_f32', _ptr(out), _ptr(img), _ptr(w), _ptr(b), N, H, W, Co)
     return out
 
 
+@_op
 def lpips_unit(f, out=None):
     """f * rsqrt(sum_c f^2 + 1e-10) of f [N,C,H,W] (or [N,C,HW]); out=f normalises in place"""
     if f.ndim not in (3, 4):
         raise RuntimeError(f'te_hip: lpips_unit expects [N,C,H,W] or [N,C,HW], got {tuple(f.shape)}')
     if out is None:
         out = torch.empty_like(f)
-    _check(lib().te_lpips_unit_f32(_ptr(out), _ptr(f), f.shape[0], f.shape[1], f[0, 0].numel(), _stream()), 'te_lpips_unit_f32')
+    _launch('te_lpips_unit_f32', _ptr(out), _ptr(f), f.shape[0], f.shape[1], f[0, 0].numel())
     return out
 
 
+@_op
 def lpips_allpairs_fwd(fh, w):
     """one layer's per-block partials of the all-pairs head for normalised taps fh [N,C,H,W] (or [N,C,HW]) and the head w [C]: a flat
     workspace of te_lpips_allpairs_ws_floats(N, C, HW) floats that lpips_allpairs_dist reads"""
@@ -1329,10 +1265,11 @@ def lpips_allpairs_fwd(fh, w):
     if n < 0:
         raise RuntimeError(f'te_hip: lpips_allpairs_fwd: a group of {N} taps of {HW} pixels is outside the limits (1 <= N < 65536)')
     partial = torch.empty(n, device=fh.device, dtype=fh.dtype)
-    _check(lib().te_lpips_allpairs_fwd_f32(_ptr(partial), _ptr(fh), _ptr(w), N, Cn, HW, _stream()), 'te_lpips_allpairs_fwd_f32')
+    _launch('te_lpips_allpairs_fwd_f32', _ptr(partial), _ptr(fh), _ptr(w), N, Cn, HW)
     return partial
 
 
+@_op
 def lpips_allpairs_dist(partials, shapes, N):
     """D [N,N] = sum over the layers (in order) of the pairs' spatial means; shapes: each layer's (C, HW), as its partials were made"""
     L = len(partials)
@@ -1343,11 +1280,12 @@ def lpips_allpairs_dist(partials, shapes, N):
     for p, (Cn, HW) in zip(partials, shapes):
         if p.numel() != lib().te_lpips_allpairs_ws_floats(N, Cn, HW):
             raise RuntimeError(f'te_hip: lpips_allpairs_dist: {p.numel()} partials are not those of a group of {N} taps [{Cn},{HW}]')
-    _check(lib().te_lpips_allpairs_dist_f32(_ptr(D), ptrs, cs, hw, L, N, _stream()), 'te_lpips_allpairs_dist_f32')
+    _launch('te_lpips_allpairs_dist_f32', _ptr(D), ptrs, cs, hw, L, N)
     return D
 
 
 # --------------------------------------------------------------------------------------------- M9 ArcFace IR-SE50 identity network
+@_op
 def conv2d_prelu(x, w, bias, slope, in_scale=None, in_shift=None, stride=1, pad=(0, 0)):
     """prelu(conv2d(v, w, stride, pad) + bias, slope) with v = in_scale[c] * x + in_shift[c] inside the image and 0 in the padding (both
     None: v = x): x [B,Ci,H,W], w [Co,Ci,kh,kw], bias, slope [Co], in_scale, in_shift [Ci] -> a new [B,Co,Ho,Wo] tensor.  The ABI
@@ -1359,11 +1297,12 @@ def conv2d_prelu(x, w, bias, slope, in_scale=None, in_shift=None, stride=1, pad=
     (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
     Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
     out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
-    _check(lib().te_conv2d_prelu_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), B, Ci, Co, H, W,
-                                     kh, kw, stride, pad[0], pad[1], _stream()), 'te_conv2d_prelu_f32')
+    _launch('te_conv2d_prelu_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), B, Ci, Co, H, W,
+            kh, kw, stride, pad[0], pad[1])
     return out
 
 
+@_op
 def id_stem_fwd(img, w, b, slope, box, pool):
     """the window box = (y0, y1, x0, x1) of img [N,3,H,W] -> adaptive average to pool x pool -> 3x3 pad-1 convolution -> bias -> PReLU:
     w [Co,3,3,3], b, slope [Co] -> [N,Co,pool,pool].  The ABI refuses an empty window and one outside the image; nothing is launched
@@ -1376,21 +1315,22 @@ def id_stem_fwd(img, w, b, slope, box, pool):
     (N, _, H, W), Co = img.shape, w.shape[0]
     y0, y1, x0, x1 = box
     out = torch.empty(N, Co, max(pool, 0), max(pool, 0), device=img.device, dtype=img.dtype)
-    _check(lib().te_id_stem_fwd_f32(_ptr(out), _ptr(img), _ptr(w), _ptr(b), _ptr(slope), N, H, W, y0, y1, x0, x1, pool, Co, _stream()),
-           'te_id_stem_fwd_f32')
+    _launch('te_id_stem_fwd_f32', _ptr(out), _ptr(img), _ptr(w), _ptr(b), _ptr(slope), N, H, W, y0, y1, x0, x1, pool, Co)
     return out
 
 
+@_op
 def se_excite(pooled, w1, w2):
     """sigmoid(relu(pooled @ w1.T) @ w2.T): pooled [B,C], w1 [R,C], w2 [C,R] -> the gates [B,C]"""
     if pooled.ndim != 2 or w1.ndim != 2 or w2.ndim != 2 or w1.shape[1] != pooled.shape[1] or tuple(w2.shape) != (w1.shape[1], w1.shape[0]):
         raise RuntimeError(f'te_hip: se_excite: inconsistent shapes pooled {tuple(pooled.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}')
     (B, Cn), R = pooled.shape, w1.shape[0]
     gate = torch.empty(B, Cn, device=pooled.device, dtype=pooled.dtype)
-    _check(lib().te_se_excite_f32(_ptr(gate), _ptr(pooled), _ptr(w1), _ptr(w2), B, Cn, R, _stream()), 'te_se_excite_f32')
+    _launch('te_se_excite_f32', _ptr(gate), _ptr(pooled), _ptr(w1), _ptr(w2), B, Cn, R)
     return gate
 
 
+@_op
 def se_scale_add(res, gate, sc, stride=1):
     """res * gate[:, :, None, None] + sc[:, :, ::stride, ::stride] (gate None: res + sc[...]): res [B,C,Ho,Wo], gate [B,C],
     sc [B,C,Hs,Ws] -> a new [B,C,Ho,Wo] tensor.  The ABI refuses a shortcut whose size does not match; nothing is launched then."""
@@ -1399,50 +1339,41 @@ def se_scale_add(res, gate, sc, stride=1):
                            f'{None if gate is None else tuple(gate.shape)}, sc {tuple(sc.shape)}')
     (B, Cn, Ho, Wo), (Hs, Ws) = res.shape, sc.shape[2:]
     out = torch.empty_like(res)
-    _check(lib().te_se_scale_add_f32(_ptr(out), _ptr(res), _ptr(gate), _ptr(sc), B, Cn, Ho, Wo, Hs, Ws, stride, _stream()),
-           'te_se_scale_add_f32')
+    _launch('te_se_scale_add_f32', _ptr(out), _ptr(res), _ptr(gate), _ptr(sc), B, Cn, Ho, Wo, Hs, Ws, stride)
     return out
 
 
+@_op
 def rows_unit(a):
     """a / ||a||_2 per row of a [I,D] (the norm's square summed in fp64); a zero row gives NaN"""
     if a.ndim != 2:
         raise RuntimeError(f'te_hip: rows_unit expects [I,D], got {tuple(a.shape)}')
     out = torch.empty_like(a)
-    _check(lib().te_rows_unit_f32(_ptr(out), _ptr(a), a.shape[0], a.shape[1], _stream()), 'te_rows_unit_f32')
+    _launch('te_rows_unit_f32', _ptr(out), _ptr(a), a.shape[0], a.shape[1])
     return out
 
 
+@_op
 def rows_dot(a, b):
     """sum_d a[i,d] * b[i,d] of a, b [I,D] -> [I]"""
     if a.ndim != 2 or tuple(a.shape) != tuple(b.shape):
         raise RuntimeError(f'te_hip: rows_dot expects two [I,D] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}')
     out = torch.empty(a.shape[0], device=a.device, dtype=a.dtype)
-    _check(lib().te_rows_dot_f32(_ptr(out), _ptr(a), _ptr(b), a.shape[0], a.shape[1], _stream()), 'te_rows_dot_f32')
+    _launch('te_rows_dot_f32', _ptr(out), _ptr(a), _ptr(b), a.shape[0], a.shape[1])
     return out
 
 
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
-# TE_ROCTX=1: every tensor-level wrapper above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
+# TE_ROCTX=1: every wrapper marked @_op above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only
 # (torch.cuda.nvtx is backed by roctx on ROCm builds).  Off by default: two extra calls per launch.
 def _install_roctx():
     import functools
     import torch.cuda.nvtx as nvtx
-    names = ['bias_act', 'bias_act_bwd', 'upfirdn2d_raw', 'blur_actgrad', 'blur_gradact', 'conv_pack', 'conv_pack2', 'conv_pack_multi', 'conv',
-             'wgrad_slabs', 'wgrad_reduce', 'rgb_fwd', 'rgb_dgrad', 'rgb_expand', 'rgb_wgrad_slabs', 'small_gemm',
-             'small_gemm_splitk', 'small_gemm_batched', 'minibatch_stddev_fwd', 'minibatch_stddev_bwd',
-             'layer_norm_fwd', 'layer_norm_bwd', 'pixel_norm_fwd', 'pixel_norm_bwd', 'demod_fwd', 'demod_from_wsq', 'demod_bwd',
-             'attn_fwd', 'attn_bwd', 'mt_adam', 'mt_ema', 'chan_scale', 'chan_dot', 'lpips_stem_fwd', 'lpips_stem_dgrad',
-             'maxpool2_fwd', 'maxpool2_bwd', 'lpips_normalize', 'lpips_head_fwd', 'lpips_dist', 'lpips_head_bwd', 'lpips_pair_head_fwd', 'crop_resize_bilinear', 'noise_reg_fwd',
-             'noise_reg_bwd', 'noise_normalize_', 'row_sqnorm', 'prdc_knn', 'prdc_counts', 'vgg_stem_fwd', 'adaptive_avgpool', 'fc_stream',
-             'fid_moments', 'fid_finalize', 'gram', 'svm_smo', 'svm_coef', 'conv2d', 'pool3', 'resize_bilinear', 'dex_stem_fwd', 'cls_score',
-             'attr_stem_fwd', 'avgpool2_act', 'attr_score', 'conv2d_res', 'pose_stem_fwd', 'maxpool3s2p1',
-             'alex_stem_fwd', 'lpips_unit', 'lpips_allpairs_fwd', 'lpips_allpairs_dist',
-             'conv2d_prelu', 'id_stem_fwd', 'se_excite', 'se_scale_add', 'rows_unit', 'rows_dot']
-    g = globals()
 
-    def wrap(fn, name):
+    def wrap(fn):
+        name = fn.__name__
+
         @functools.wraps(fn)
         def run(*a, **k):
             t = next((x for x in a if torch.is_tensor(x)), None)
@@ -1452,9 +1383,8 @@ def _install_roctx():
             finally:
                 nvtx.range_pop()
         return run
-    for n in names:
-        if n in g:
-            g[n] = wrap(g[n], n)
+    for i, fn in enumerate(_OPS):           # the registry then holds what the module exposes
+        _OPS[i] = globals()[fn.__name__] = wrap(fn)
 
 
 ROCTX = os.environ.get('TE_ROCTX') == '1'

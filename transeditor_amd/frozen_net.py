@@ -73,8 +73,7 @@ def check_images(images, who, dims='[B,3,H,W]', square=False, pairs=False):
 
 def _relu_(y):
     """in-place ReLU as te_bias_act_f32 (act 3 = leaky ReLU, alpha 0, scale 1)"""
-    _lib._check(_lib.lib().te_bias_act_f32(_lib._ptr(y), _lib._ptr(y), None, None, 3, 0, 0.0, 1.0, y.numel(), 1, 1, _lib._stream()),
-                'te_bias_act_f32')
+    _lib._launch('te_bias_act_f32', _lib._ptr(y), _lib._ptr(y), None, None, 3, 0, 0.0, 1.0, y.numel(), 1, 1)
     return y
 
 
