@@ -990,6 +990,59 @@ int te_se_scale_add_f32(float* out, const float* res, const float* gate, const f
 int te_rows_unit_f32(float* out, const float* a, int64_t I, int D, te_stream_t stream);
 int te_rows_dot_f32(float* out, const float* a, const float* b, int64_t I, int D, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M10  the dual-space pSp encoder of real-image inversion (pSp/models/encoders/psp_encoders_new.py:35-140
+ * GradualStyleEncoder(50, 'ir_se'), applied by pSp/models/psp_new.py:90-109 pSp.forward).  input_layer and body are M9's
+ * te_conv2d_prelu_f32 and IR-SE units, the two lateral 1x1 convolutions are M4's te_conv2d_f32; here what sits on the backbone
+ * (csrc/psp_heads.hip).  Forward only, NCHW fp32, no atomics, bit-reproducible; an image's outputs are bitwise independent of the batch
+ * it is in.  Every check is made before any launch; nothing is launched on a refusal.
+ *
+ * te_conv2d_heads_f32 (psp_encoders_new.py:11-32 GradualStyleBlock: Conv2d(512, 512, 3, stride=2, padding=1) + LeakyReLU(0.01) chains and
+ * the EqualLinear behind them, :120-136 the loops over styles and spatials; replaces the 138 convolutions, their activations and the
+ * 30 linears, head by head): G convolutions of one shape in one launch,
+ *     out[b, c0 + g*Cg + m, oy, ox] = lrelu_slope(bias[g*Cg + m]
+ *         + sum_{c,ky,kx} w[g, m, c, ky, kx] * x[b, xg(g)*Ci + c, oy*s + ky - py, ox*s + kx - px])                  x = 0 outside the image
+ * xg(g) = 0 when shared != 0 (all heads read the same [B,Ci,H,W] input), else xg(g) = g and x is [B, G*Ci, H, W].  w [G,Cg,Ci,kh,kw],
+ * bias [G*Cg]; out is the channel slice [c0, c0 + G*Cg) of a contiguous [B,Ctot,Ho,Wo]; lrelu_slope(v) = v > 0 ? v : v * slope
+ * (slope = 1 is the identity, a NaN propagates).  kh = kw = 1 on a 1 x 1 plane is the grouped linear layer (the caller folds
+ * EqualLinear's scale into w and bias).  Kernel sizes, strides, padding rules and size limits are te_conv2d_f32's, with Co = G * Cg;
+ * Cg % 64 == 0, else TE_ERR_UNSUPPORTED: a workgroup's 64-channel block then never straddles two heads.
+ * Two routes, chosen from (K = Ci*kh*kw, Ho*Wo) alone, never from B or G:
+ *   unsplit (S = 1): te_conv2d_f32's main loop (csrc/conv2d_body.h) with a gather that adds the head's channel offset and the leaky
+ *     ReLU as the epilogue; the k permutation is untouched, so for every head the result is bitwise
+ *     leaky(te_conv2d_f32(x_g, w_g, b_g, act = 0)).  ws may be NULL.
+ *   split (S > 1), for planes of a few pixels, where G * Cg / 64 workgroups would each walk all of K: the same loop over one of S
+ *     ranges of k (whole 32-deep steps, the ranges in ascending order of k), the bare partial tiles go to the caller's workspace
+ *     ws[S][B][G*Cg][Ho*Wo], a second kernel sums them over s ascending, then adds the bias and applies the leaky ReLU.  A NULL ws or
+ *     ws_bytes below S * B * G*Cg * Ho*Wo * 4 is TE_ERR_WORKSPACE.
+ * splits = 0 takes the rule, S = te_conv2d_heads_splits(Ci, kh, kw, Ho, Wo); splits = n in [1, 16] runs n ranges instead (for
+ * measurements and tests; n ranges must all be non-empty, else TE_ERR_SHAPE).  te_conv2d_heads_ws_bytes is the rule's workspace
+ * (0 where S = 1).  Both helpers return a negative TE_ERR_* on bad arguments.  A NaN input element reaches exactly the outputs of its
+ * own head(s) and image whose window holds it, on both routes.
+ *
+ * te_upsample_add_f32 (psp_encoders_new.py:84-101 _upsample_add; replaces F.interpolate(x, size=(H, W), mode='bilinear',
+ * align_corners=True) + y): x [planes,h,w], y and out [planes,H,W].  Per axis src = o * (in - 1) / (out - 1), and 0 where out == 1,
+ * evaluated exactly in integers as te_resize_bilinear_f32 evaluates its rule: the quotient is the first tap, the remainder over
+ * out - 1 the second tap's weight l1 (rounded once), l0 = 1 - l1; x is mixed first (l1 * b + (l0 * a) with one fma), then y, then
+ * the sum with y[...].  A tap of weight 0 does not enter, so equal sizes give bitwise x + y.  1 <= planes <= 65535, sizes up to 32768,
+ * else TE_ERR_SHAPE.
+ *
+ * te_psp_codes_f32 (psp_encoders_new.py:132-138 torch.stack, adjust_style = EqualLinear(14, 16) over the head axis and the permutes;
+ * psp_new.py:99-107 the latent averages): lat [B, Ns + Np, D] are the heads' latents, the Ns styles first.
+ *     z[b, c, t] = (bz[t] + sum_{j < Ns} A[t, j] * lat[b, j, c]) + z_avg[c, t]           j ascending, one fp32 fma chain from bz[t]
+ *     p[b, c, u] = lat[b, Ns + u, c] + p_avg[c, u]
+ * A [T,Ns] and bz [T] arrive with EqualLinear's scale and lr_mul folded in; z_avg [D,T] and p_avg [D,Np] may each be NULL (nothing is
+ * added then); z is [B,D,T], p is [B,D,Np].  B, Ns, Np, D, T >= 1, else TE_ERR_SHAPE.
+ */
+int te_conv2d_heads_splits(int Ci, int kh, int kw, int Ho, int Wo);
+int64_t te_conv2d_heads_ws_bytes(int64_t B, int G, int Cg, int Ci, int kh, int kw, int Ho, int Wo);
+int te_conv2d_heads_f32(float* out, float* ws, int64_t ws_bytes, const float* x, const float* w, const float* bias, int B, int G, int Ci,
+                        int Cg, int H, int W, int kh, int kw, int s, int py, int px, int Ctot, int c0, int shared, float slope, int splits,
+                        te_stream_t stream);
+int te_upsample_add_f32(float* out, const float* x, const float* y, int64_t planes, int h, int w, int H, int W, te_stream_t stream);
+int te_psp_codes_f32(float* z, float* p, const float* lat, const float* A, const float* bz, const float* z_avg, const float* p_avg,
+                     int64_t B, int Ns, int Np, int D, int T, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1363,6 +1363,63 @@ def rows_dot(a, b):
     return out
 
 
+# --------------------------------------------------------------------------------------------- M10 dual-space pSp encoder
+def conv2d_heads_splits(Ci, kh, kw, Ho, Wo):
+    """the number of k ranges te_conv2d_heads_f32 runs for this (Ci * kh * kw, Ho * Wo); 1 is the unsplit route (no batch or head count enters)"""
+    S = lib().te_conv2d_heads_splits(Ci, kh, kw, Ho, Wo)
+    if S < 0:
+        raise RuntimeError(f'te_conv2d_heads_splits failed ({S}) for Ci={Ci}, a {kh} x {kw} kernel and a {Ho} x {Wo} plane')
+    return S
+
+
+@_op
+def conv2d_heads(x, w, bias, stride=1, pad=(0, 0), shared=False, slope=0.01, out=None, c0=0, splits=0):
+    """G convolutions of one shape in one launch, with bias and leaky ReLU: w [G,Cg,Ci,kh,kw], bias [G*Cg]; x [B,Ci,H,W] (shared: every head
+    reads it) or [B,G*Ci,H,W] (head g reads its own Ci channels); written into channels [c0, c0 + G*Cg) of `out` [B,Ctot,Ho,Wo] (a new
+    [B,G*Cg,Ho,Wo] tensor where out is None).  splits 0: the ABI's rule; n >= 1: n ranges of k (1 is the unsplit route).  The ABI refuses
+    what te_conv2d_f32 refuses and a Cg that is no multiple of 64; nothing is launched then.  Returns out."""
+    if x.ndim != 4 or w.ndim != 5 or bias.ndim != 1 or bias.shape[0] != w.shape[0] * w.shape[1] \
+            or x.shape[1] != w.shape[2] * (1 if shared else w.shape[0]):
+        raise RuntimeError(f'te_hip: conv2d_heads: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, '
+                           f'shared={bool(shared)}')
+    (B, _, H, W), (G, Cg, Ci, kh, kw) = x.shape, w.shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    out = _slice_out(out, c0, B, G * Cg, max(Ho, 0), max(Wo, 0), x, 'conv2d_heads')
+    S = splits if splits else (conv2d_heads_splits(Ci, kh, kw, Ho, Wo) if Ho > 0 and Wo > 0 else 1)
+    ws = torch.empty(S * B * G * Cg * Ho * Wo, device=x.device, dtype=x.dtype) if S > 1 else None
+    _launch('te_conv2d_heads_f32', _ptr(out), _ptr(ws), 0 if ws is None else ws.numel() * 4, _ptr(x), _ptr(w), _ptr(bias), B, G, Ci, Cg, H, W,
+            kh, kw, stride, pad[0], pad[1], out.shape[1], c0, 1 if shared else 0, float(slope), splits)
+    return out
+
+
+@_op
+def upsample_add(x, y):
+    """F.interpolate(x, size=y.shape[2:], mode='bilinear', align_corners=True) + y: x [B,C,h,w], y [B,C,H,W] -> a new [B,C,H,W] tensor"""
+    if x.ndim != 4 or y.ndim != 4 or tuple(x.shape[:2]) != tuple(y.shape[:2]):
+        raise RuntimeError(f'te_hip: upsample_add expects x [B,C,h,w] and y [B,C,H,W], got {tuple(x.shape)} and {tuple(y.shape)}')
+    x, y = x.contiguous(), y.contiguous()
+    (B, Cn, h, w), (H, W) = x.shape, y.shape[2:]
+    out = torch.empty_like(y)
+    _launch('te_upsample_add_f32', _ptr(out), _ptr(x), _ptr(y), B * Cn, h, w, H, W)
+    return out
+
+
+@_op
+def psp_codes(lat, A, bz, Np, z_avg=None, p_avg=None):
+    """the heads' latents lat [B,Ns+Np,D] (styles first) -> (z [B,D,T], p [B,D,Np]): z = adjust_style over the head axis (A [T,Ns], bz [T],
+    scale folded in) + z_avg [D,T], p = the spatial latents + p_avg [D,Np]; either average may be None"""
+    if lat.ndim != 3 or A.ndim != 2 or bz.shape != (A.shape[0],) or lat.shape[1] != A.shape[1] + Np \
+            or z_avg is not None and tuple(z_avg.shape) != (lat.shape[2], A.shape[0]) \
+            or p_avg is not None and tuple(p_avg.shape) != (lat.shape[2], Np):
+        raise RuntimeError(f'te_hip: psp_codes: inconsistent shapes lat {tuple(lat.shape)}, A {tuple(A.shape)}, bz {tuple(bz.shape)}, Np {Np}, '
+                           f'averages {[None if t is None else tuple(t.shape) for t in (z_avg, p_avg)]}')
+    (B, _, D), (T, Ns) = lat.shape, A.shape
+    z = torch.empty(B, D, T, device=lat.device, dtype=lat.dtype)
+    p = torch.empty(B, D, Np, device=lat.device, dtype=lat.dtype)
+    _launch('te_psp_codes_f32', _ptr(z), _ptr(p), _ptr(lat), _ptr(A), _ptr(bz), _ptr(z_avg), _ptr(p_avg), B, Ns, Np, D, T)
+    return z, p
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every wrapper marked @_op above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only

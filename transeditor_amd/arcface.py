@@ -26,7 +26,8 @@ and te_se_scale_add_f32 (res * gate + shortcut).  output_layer is folded exactly
 the Linear - there is no padding there -, BatchNorm1d into its rows and bias; Dropout is the identity in eval mode) and runs as
 te_fc_stream_f32; te_rows_unit_f32 normalises.  Every convolution is the exact-fp32 implicit GEMM of csrc/conv2d_body.h.  An image's
 embedding is bitwise the same whatever batch it is in.  Eval only: there is no backward pass, so IDLoss.forward as a training loss is
-not provided.  Measured deviations and times: profiles/README.md, 'Identity embedding'.
+not provided.  The unit parse and the unit forward live in irse_units.py, which the inversion encoder (psp_encoder.py) runs too.
+Measured deviations and times: profiles/README.md, 'Identity embedding'.
 """
 import argparse
 import json
@@ -36,14 +37,12 @@ import torch
 
 from . import _lib
 from .frozen_net import check_images, no_gpu, resolve, weight_bias
-from .inception_features import fold_bn
+from .irse_units import BN_EPS, bn_affine, check_unit_list, parse_stem, parse_units, reader, register_units, unit_forward
 
-BN_EPS = 1e-5
 BOX = (35, 223, 32, 220)                                              # id_loss.py:18: rows 35:223, columns 32:220
 POOL = 112                                                            # id_loss.py:14
 _NO_GPU = no_gpu('ArcFaceID')
 _HINT = 'not a Backbone state dict: input_layer.*, body.N.res_layer.*, output_layer.*'
-_BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
 
 
 def default_units():
@@ -64,56 +63,13 @@ def parse_state_dict(sd, path='state_dict', units=None, pool=POOL, dtype=torch.f
     """-> dict(stem (w', b', slope), units [dict(cin, depth, stride, scale, shift, w1, slope, w2, b2, fc1, fc2, sc)], fc (w'', b''), keys):
     the batch norms folded as the module docstring says, `keys` the set of keys that were read; ValueError naming the key that is missing,
     has the wrong shape or does not fit the unit list.  dtype=torch.float64: the folded values before their one rounding"""
-    read = set()
-
-    def get(key, shape):
-        read.add(key)
-        return weight_bias(sd, key, None, shape, 'ArcFaceID', path, _HINT)
-
-    def bn(key, c):
-        return [get(f'{key}.{t}', (c,)) for t in _BN_KEYS]
+    get, read = reader(sd, 'ArcFaceID', path, _HINT)
 
     def affine(key, c):
-        """an eval-mode batch norm as (scale, shift) in fp64"""
-        g, b, m, v = (t.detach().double().cpu() for t in bn(key, c))
-        scale = g / torch.sqrt(v + BN_EPS)
-        return scale, b - m * scale
-    w0 = get('input_layer.0.weight', (None, 3, 3, 3))
-    c0 = w0.shape[0]
-    stem = (*fold_bn(w0, *bn('input_layer.1', c0), eps=BN_EPS, dtype=dtype), get('input_layer.2.weight', (c0,)).detach().to(dtype).contiguous())
-    if units is not None:
-        units = [tuple(int(v) for v in u) for u in units]
-        if not units or any(len(u) != 3 or u[0] < 1 or u[1] < 1 or u[2] not in (1, 2) for u in units):
-            raise ValueError(f'ArcFaceID: units must be a list of (in, depth, stride) with stride 1 or 2, got {units!r}')
-    parsed, ci, n = [], c0, 0
-    while f'body.{n}.res_layer.1.weight' in sd or (units is not None and n < len(units)):
-        p = f'body.{n}'
-        w1 = get(f'{p}.res_layer.1.weight', (None, None, 3, 3))
-        depth, cin = w1.shape[:2]
-        if cin != ci:
-            raise ValueError(f'ArcFaceID: {p}.res_layer.1.weight is {tuple(w1.shape)}: the unit takes {cin} channels, the layer before it gives {ci}')
-        stride = 2 if n == 0 or cin != depth else 1
-        if units is not None:
-            if n >= len(units):
-                raise ValueError(f'ArcFaceID: {path} has {p}.res_layer.1.weight, past the {len(units)} units that were named')
-            if units[n][:2] != (cin, depth):
-                raise ValueError(f'ArcFaceID: {p}.res_layer.1.weight is {tuple(w1.shape)}, which is not unit {n} of the list, {units[n]}')
-            stride = units[n][2]
-        scale, shift = affine(f'{p}.res_layer.0', cin)
-        u = dict(cin=cin, depth=depth, stride=stride, scale=scale.to(dtype).contiguous(), shift=shift.to(dtype).contiguous(),
-                 w1=w1.detach().to(dtype).contiguous(), slope=get(f'{p}.res_layer.2.weight', (depth,)).detach().to(dtype).contiguous())
-        u['w2'], u['b2'] = fold_bn(get(f'{p}.res_layer.3.weight', (depth, depth, 3, 3)), *bn(f'{p}.res_layer.4', depth), eps=BN_EPS, dtype=dtype)
-        u['fc1'] = u['fc2'] = u['sc'] = None
-        if f'{p}.res_layer.5.fc1.weight' in sd or f'{p}.res_layer.5.fc2.weight' in sd:
-            fc1 = get(f'{p}.res_layer.5.fc1.weight', (None, depth, 1, 1))
-            fc2 = get(f'{p}.res_layer.5.fc2.weight', (depth, fc1.shape[0], 1, 1))
-            u['fc1'], u['fc2'] = (t.detach().to(dtype).reshape(t.shape[:2]).contiguous() for t in (fc1, fc2))
-        if cin != depth or f'{p}.shortcut_layer.0.weight' in sd:
-            u['sc'] = fold_bn(get(f'{p}.shortcut_layer.0.weight', (depth, cin, 1, 1)), *bn(f'{p}.shortcut_layer.1', depth), eps=BN_EPS, dtype=dtype)
-        parsed.append(u)
-        ci, n = depth, n + 1
-    if not parsed:
-        raise ValueError(f'ArcFaceID: {path} has no body.0.res_layer.1.weight ({_HINT})')
+        return bn_affine(get, key, c)
+    stem = parse_stem(get, dtype)
+    parsed = parse_units(sd, get, stem[0].shape[0], check_unit_list(units, 'ArcFaceID'), 'ArcFaceID', path, _HINT, dtype)
+    ci = parsed[-1]['depth']
     # output_layer: BatchNorm2d(ci) -> Flatten -> Linear(ci * h * h, D) -> BatchNorm1d(D), folded in fp64 and rounded once
     h = _out_side(pool, [(u['cin'], u['depth'], u['stride']) for u in parsed])
     read.add('output_layer.3.bias')
@@ -151,38 +107,16 @@ class ArcFaceID(torch.nn.Module):
         state_dict, path = resolve(path, state_dict, 'ArcFaceID', 'ArcFace IR-SE weight')
         net = parse_state_dict(state_dict, path, units, pool)
         self.box, self.pool, self.keys, self.affine = box, pool, frozenset(net['keys']), net['affine']
-        self.units = tuple((u['cin'], u['depth'], u['stride']) for u in net['units'])
-        self.se = tuple(u['fc1'] is not None for u in net['units'])
         self.dim = net['fc'][0].shape[0]
         for name, t in zip(('stem_w', 'stem_b', 'stem_slope', 'fc_w', 'fc_b'), (*net['stem'], *net['fc'])):
             self.register_buffer(name, t)
-        for i, u in enumerate(net['units']):
-            for k in ('scale', 'shift', 'w1', 'slope', 'w2', 'b2', 'fc1', 'fc2'):
-                if u[k] is not None:
-                    self.register_buffer(f'u{i}_{k}', u[k])
-            self.register_buffer(f'u{i}_zero', torch.zeros(u['depth']))             # the first convolution has no bias
-            if u['sc'] is not None:
-                self.register_buffer(f'u{i}_sc_w', u['sc'][0])
-                self.register_buffer(f'u{i}_sc_b', u['sc'][1])
+        register_units(self, net['units'])
         self.eval()
         if torch.cuda.is_available():
             self.to('cuda')
 
     def _unit(self, i, x):
-        """bottleneck_IR(_SE).forward.  An activation is dropped once its last reader has run: the first convolution's output when the
-        second has read it, the unit's input (or its convolved shortcut) and the residual branch after the final addition."""
-        def g(k):
-            return getattr(self, f'u{i}_{k}', None)
-        stride = self.units[i][2]
-        t = _lib.conv2d_prelu(x, g('w1'), g('zero'), g('slope'), g('scale'), g('shift'), 1, (1, 1))
-        r = _lib.conv2d(t, g('w2'), g('b2'), stride, (1, 1), act=0)
-        del t
-        gate = None
-        if self.se[i]:
-            gate = _lib.se_excite(_lib.adaptive_avgpool(r, 1, 1).view(r.shape[0], -1), g('fc1'), g('fc2'))
-        if g('sc_w') is not None:
-            x, stride = _lib.conv2d(x, g('sc_w'), g('sc_b'), stride, (0, 0), act=0), 1
-        return _lib.se_scale_add(r, gate, x, stride)
+        return unit_forward(self, i, x)
 
     @torch.no_grad()
     def embed(self, images):

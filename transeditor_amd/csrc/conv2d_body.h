@@ -1,7 +1,9 @@
 // The implicit-GEMM kernel of the general fp32 convolution as a template, shared by te_conv2d_f32 (conv2d.hip) and the ResNet entry points
-// (resnet.hip: te_conv2d_res_f32, te_pose_stem_fwd_f32) and the AlexNet stem (lpips_alex.hip: te_alex_stem_fwd_f32), written once.  Two compile-time policies make the variants:
+// (resnet.hip: te_conv2d_res_f32, te_pose_stem_fwd_f32), the AlexNet stem (lpips_alex.hip: te_alex_stem_fwd_f32), the IR-SE unit (irse.hip) and the
+// grouped head convolutions (psp_heads.hip), written once.  Compile-time policies make the variants:
 //     the gather   : where a tap of the patch comes from (GatherPlain: x[b, c, iy, ix] of a dense [B,Ci,H,W] tensor), and
-//     the epilogue : what happens to acc + bias before the store (EpiBiasAct: the activation).
+//     the epilogue : what happens to acc + bias before the store (EpiBiasAct: the activation),
+//     the part     : which range of k the workgroup runs and where the tile goes (PartWhole: all of it, into `out`; psp_heads.hip splits).
 // Everything else - the tile shapes, the LDS layout, the order of k inside an output's one fp32 fma chain (the permutation of
 // gemm_nt_f32.h: lane half h feeds k = 8q + 4h + u of every 32-deep step to MFMA (q, u)) - is the same for all of them, so two variants
 // that gather the same values produce the same accumulators bit for bit.  The description of the loop is at the top of conv2d.hip.
@@ -84,6 +86,19 @@ struct EpiBiasAct {
     }
 };
 
+// the part of the k chain a workgroup runs and where its tile goes: the whole chain, bias added, into `out`.  A split launch (psp_heads.hip)
+// names another range of k and another destination; the order of k inside the range is the same
+struct PartWhole {
+    template <class Args>
+    static __device__ __forceinline__ int k_begin(const Args& a) { return 0; }
+    template <class Args>
+    static __device__ __forceinline__ int k_end(const Args& a) { return a.K; }
+    template <class Args>
+    static __device__ __forceinline__ float* out(const Args& a) { return a.out; }
+    template <class Args>
+    static __device__ __forceinline__ float finish(const Args& a, float acc, int m) { return acc + a.bias[m]; }
+};
+
 // NPT consecutive k (from k0, wave-uniform) of the thread's pixel: the tap (c, iy0 + ky, ix0 + kx) or 0
 template <int NPT, class Gather, class Args>
 __device__ __forceinline__ void gather(float (&r)[NPT], const Pixel& px, const Args& a, int k0) {
@@ -106,7 +121,7 @@ __device__ __forceinline__ void gather(float (&r)[NPT], const Pixel& px, const A
 
 // The kernel.  `Args` is ConvArgs or a struct derived from it that carries what the policies need.  PROF_ONLY lines exist in
 // conv2d.hip's profiling build alone (it owns the buffer they write).
-template <int BN, bool AL, class Gather, class Epi, class Args>
+template <int BN, bool AL, class Gather, class Epi, class Part = PartWhole, class Args = ConvArgs>
 __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
     constexpr int NACC = BN / 64;                // 32 x 32 tiles per wave along the pixels
     constexpr int NPT = BN * BK / NT;            // patch elements per thread and step: 8 or 16 consecutive k
@@ -142,12 +157,13 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
         for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
     f32x4 rw[2];
     float rx[NPT];
-    load_weights<AL>(rw, a.w, m0, a.Co, a.K, 0);
-    gather<NPT, Gather>(rx, px, a, kg * NPT);
+    const int kb = Part::k_begin(a), ke = Part::k_end(a);
+    load_weights<AL>(rw, a.w, m0, a.Co, a.K, kb);
+    gather<NPT, Gather>(rx, px, a, kb + kg * NPT);
     const float* wp = Ws + (wm * 32 + c) * LD + 4 * h;
     const float* xp = Xs + (wn * (BN / 2) + c) * LD + 4 * h;
     PROF_ONLY(unsigned long long pc[3] = {0, 0, 0}; unsigned long long tlast = __builtin_readcyclecounter();)
-    for (int kk = 0; kk < a.K; kk += BK) {
+    for (int kk = kb; kk < ke; kk += BK) {
         __syncthreads();                                     // the previous step's LDS reads are done
         {
             const int t = threadIdx.x;
@@ -161,7 +177,7 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
         }
         __syncthreads();
         PROF_LAP(pc[0]);
-        if (kk + BK < a.K) {                                 // in flight behind the MFMAs below
+        if (kk + BK < ke) {                                   // in flight behind the MFMAs below
             load_weights<AL>(rw, a.w, m0, a.Co, a.K, kk + BK);
             gather<NPT, Gather>(rx, px, a, kk + BK + kg * NPT);
         }
@@ -190,12 +206,12 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
         if (p >= a.P) continue;
         const int64_t b = p / HoWo;
         const int r = (int)(p - b * HoWo);
-        float* dst = a.out + (b * a.Ctot + a.c0) * HoWo + r;
+        float* dst = Part::out(a) + (b * a.Ctot + a.c0) * HoWo + r;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
             if (m < a.Co) {
-                float v = acc[i][e] + a.bias[m];
+                float v = Part::finish(a, acc[i][e], m);
                 v = Epi::apply(a, v, dst, m, HoWo);
                 dst[(int64_t)m * HoWo] = v;
             }
