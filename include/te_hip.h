@@ -162,7 +162,8 @@ int te_upfirdn2d_f64(double* out, const double* x, const double* k, int64_t majo
                             of conv_transpose2d(stride 2), :318 */
 
 #define TE_CONV_T2S6 7   /* TE_CONV_T2 with its products on the bf16 matrix pipe (three-piece split, fp32-equivalent like TE_CONV_3X3W6): the body
-                            cells [0,H) x [0,W) in csrc/t2s6.hip, the last output row and column through the fp32 kernel.
+                            cells [0,H) x [0,W) by t2s6_kernel / t2s6q_kernel, the last output row and column by t2_edge_kernel (plain fp32
+                            arithmetic on the fp32 copy of the weights in the same packed buffer), all in csrc/t2s6.hip.
                             Shapes: te_conv_t2s6_supported; weights packed TE_PACK_T6FWD / TE_PACK_T6SWAP; never split; no residual / mask.
                             Reference: conv_transpose2d(stride 2) of ModulatedConv2d.forward, model_spatial_query.py:310-321 */
 

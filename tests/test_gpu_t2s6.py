@@ -1,5 +1,5 @@
 """TE_CONV_T2S6: the transposed 3x3 / stride 2 convolution on the bf16 matrix pipe (csrc/t2s6.hip: body cells, three bf16 pieces per
-fp32 operand, six exact piece products per multiply-add, fp32 accumulation; last output row / column through the fp32 kernel from the
+fp32 operand, six exact piece products per multiply-add, fp32 accumulation; last output row / column from t2_edge_kernel, plain fp32 arithmetic on the
 plain copy of the weights in the same packed buffer) against fp64 torch and against the fp32 kernel (TE_CONV_T2) - both weight layouts
 (forward of the generator's up-sampling layers, conv_transpose2d(stride 2) of ModulatedConv2d.forward, model_spatial_query.py:310-321;
 data gradient of the discriminator's down-sampling convolutions, :765-779), style scale at staging, demodulation scale / bias /
@@ -37,7 +37,7 @@ def test_split_bf16_transposed_conv_vs_fp64(B, K, M, H, W):
     print(f'split-bf16 transposed {K}->{M} @{H}x{W}: max {rel_err(got, want):.2e} (fp32 kernel {rel_err(direct, want):.2e}), L2 {l2(got):.2e} ({l2(direct):.2e})')
     assert rel_err(got, want) < 5e-6
     assert l2(got) < 2.5 * l2(direct) + 1e-7
-    # the border rows / columns on their own (the halo of the body tiles and the two fp32 regions)
+    # the border rows / columns on their own (the halo of the body tiles and the last output row and column of t2_edge_kernel)
     for sl in ((slice(None), slice(None), slice(0, 2)), (slice(None), slice(None), slice(2 * H - 1, None)),
                (slice(None), slice(None), slice(None), slice(0, 2)), (slice(None), slice(None), slice(None), slice(2 * W - 1, None))):
         assert rel_err(got[sl], want[sl]) < 5e-6

@@ -1,5 +1,5 @@
 """TE_CONV_T2S6 (the transposed 3x3 / stride 2 convolution on the bf16 matrix pipe, three-piece split; last output row / column
-through the fp32 kernel) against fp64 torch and the fp32 kernel (TE_CONV_T2): error and time at the FFHQ-256 / batch-16 layer shapes
+from t2_edge_kernel, plain fp32 arithmetic) against fp64 torch and the fp32 kernel (TE_CONV_T2): error and time at the FFHQ-256 / batch-16 layer shapes
 and at small shapes, both weight layouts.      python tools/t2s6_check.py"""
 import math
 import os

@@ -113,6 +113,20 @@ __device__ __forceinline__ bool split6_tile_list(int ntiles, int nt8, int mblock
     return lo < hi;
 }
 
+// ---- a body shared by two kernels (s2s6.hip: the ping-pong and the two-image form of the kind are one function template, the kernels
+// the runtime sees are thin __global__ wrappers).  The body is declared `__device__ __attribute__((optnone))` and called as
+// `[[clang::always_inline]] body<...>(p);` (the attribute at the call takes precedence): the optimiser leaves the stand-alone function
+// alone, lambdas included, and the code is optimised once, inside its kernel, as if it had been written there.  A plain __forceinline__
+// body is optimised on its own first and again after inlining; the passes are not idempotent, and the kernels came out further from
+// the code that was measured (s2s6_kernel<false>: 156 VGPRs against 163, 49 s_waitcnt against 37; profiles/refactor_split6_forms_isa.txt
+// has every form that was tried and what is left with this one).  t2s6.hip keeps its two kernels written out: merged the same way, its
+// two-image kernel was 0.7 - 0.9 % slower in small launches in both timing visits (profiles/refactor_split6_forms_time.txt).
+
+// ---- host: which form of a kind to launch.  form_sel = the kind's form hook counted from its two-image default: 0 = ping-pong, 1 = the
+// two-image form where M % 128 == 0 and its grid (blocks_q: half as many blocks) still gives every CU a block, 2 = the two-image form
+// wherever M % 128 == 0 (tests)
+inline bool split6_two_image(int form_sel, int M, int64_t blocks_q) { return form_sel >= 1 && M % 128 == 0 && (form_sel == 2 || blocks_q >= te::kNumCU); }
+
 // ---- host: one launch of a kernel that needs more than 64 KB of dynamic LDS.  hipFuncSetAttribute is done once per (kernel, device):
 // one flag per instantiation of this template, i.e. per kernel.
 template <auto KERNEL, class Args>

@@ -683,7 +683,7 @@ int te_t2s6_launch(float* out, const float* in, const float* U, const float* isc
     const size_t lds = 2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4;
     const int form = g_t2_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
-    if (form >= 1 && M % (2 * BM) == 0 && (form == 2 || blocks_q >= te::kNumCU)) {
+    if (split6_two_image(form, M, blocks_q)) {
         a.mblocks = M / (2 * BM);
         SPLIT6_LAUNCH_ISC(t2s6q_kernel, isc, dim3((unsigned)blocks_q), WT, lds, s, a);
     } else {

@@ -806,7 +806,7 @@ int te_wino6_launch(float* out, const float* in, const float* U, const float* is
     const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
     const int form = g_w6_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
-    if (form >= 2 && M % (2 * BM) == 0 && W >= TW && (form == 3 || blocks_q >= te::kNumCU)) {     // (W == 16: the ping-pong kernel only)
+    if (W >= TW && split6_two_image(form - 1, M, blocks_q)) {     // (forms 2 / 3 of te_conv_wino6_form; W == 16: the ping-pong kernel only)
         a.mblocks = M / (2 * BM);
         // the tile walk: a block takes a run of consecutive tiles of its XCD and carries the pipeline across them (wino6q_kernel).
         const int nt8c = (int)te::cdiv(a.ntiles, 8);                   // tiles of the fullest XCD
