@@ -173,6 +173,7 @@ int te_upfirdn2d_f64(double* out, const double* x, const double* k, int64_t majo
                             (isc, osc, bias, mask_ref must be NULL, act 0).  Shapes: te_conv_p1s6_supported; weights packed
                             TE_PACK_P6FWD / TE_PACK_P6DGRAD; never split.
                             Reference: F.conv2d of EqualConv2d (1x1) in ResBlock.skip, model_spatial_query.py:173-181, :780-798 */
+#define TE_CONV_KINDS 9   /* number of kinds: valid values are 0 .. TE_CONV_KINDS - 1 */
 
 /* how te_conv_pack_weights_f32 reads the source weight w[Co][Ci][kh][kw] (model layout,
  * ModulatedConv2d.weight[0]) */
@@ -194,6 +195,7 @@ int te_upfirdn2d_f64(double* out, const double* x, const double* k, int64_t majo
 #define TE_PACK_P6FWD 11  /* TE_CONV_1X1S6, M = Co, K = Ci (1x1 weights): P6[K/16][piece][M/32][64 lanes][8 bf16] (3 K M bf16; Co % 32 == 0,
                              Ci % 16 == 0)                                                                                                */
 #define TE_PACK_P6DGRAD 12 /* TE_CONV_1X1S6 as data gradient: M = Ci, K = Co (Ci % 32 == 0, Co % 16 == 0)                                  */
+#define TE_PACK_KINDS 13   /* number of layouts: valid values are 0 .. TE_PACK_KINDS - 1 */
 
 int64_t te_conv_packed_numel(int kind_pack, int Co, int Ci, int ksize);
 int te_conv_pack_weights_f32(float* wp, const float* w, float wscale, int kind_pack, int Co, int Ci,
@@ -297,7 +299,8 @@ int te_wgrad_pair_form(int kind, int Co, int Ci, int H, int W);
  * form, nine taps x six products - W % 16 == 0; round 6: kind TE_CONV_1X1 with Co % 128 == 0, Ci % 128 == 0, W % 16 == 0).
  * te_wgrad_split_bf16(0 | 1): process-wide switch (environment TE_SPLIT_BF16 at load time), returns the previous value; any other
  * argument only queries.  With the switch on, te_wgrad_f32 / te_wgrad_group_f32 take the kernel where it applies and the fp32
- * kernel elsewhere; te_wgrad_slab_count and te_wgrad_group_plan plan their chunks from the same switch. */
+ * kernel elsewhere; te_wgrad_slab_count and te_wgrad_group_plan plan their chunks for the kernel that te_wgrad6_form (below) names,
+ * so they follow the same switch. */
 int te_wgrad_split_supported(int kind, int Co, int Ci, int H, int W);
 int te_wgrad_split_bf16(int on);
 /* Round 6: form of the split transposed-kind kernel - 1 (default): a block owns 64 channels of the (2H+1) x (2W+1) tensor x 128 of the
@@ -393,7 +396,8 @@ int te_blur_gradact_f32(float* gx, float* partial, const float* g, const float* 
                         te_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Loop-trip queries (host only, nothing is launched; each calls the grid function of the launch it describes).  Many kernels
+ * Loop-trip queries (host only, nothing is launched; each calls the grid function of the launch it describes, and the three FIR plans
+ * check their arguments with the validator of their launch).  Many kernels
  * launch fewer blocks than they have work and loop inside the block; these say how often, so that a test can assert the trips
  * it relies on (tests/loop_trips.py).
  *   te_upfirdn2d_plan / te_blur_actgrad_plan / te_blur_gradact_plan: what te_upfirdn2d_f32 / te_blur_actgrad_f32 /
@@ -409,7 +413,9 @@ int te_blur_gradact_f32(float* gx, float* partial, const float* g, const float* 
  *     walks the tiles blockIdx.x, blockIdx.x + *blocks, ...).
  *   te_wgrad_reduce_plan: second pass of the dW output of te_wgrad_reduce_f32 (16-byte aligned tensors): *parts partial tensors
  *     (1: no second pass), *cover elements per trip of its grid.
- * Negative TE_ERR_* on bad arguments. */
+ * Negative TE_ERR_* on bad arguments.  The three FIR plans refuse what their launch refuses, with the launch's code (for example
+ * TE_ERR_UNSUPPORTED for taps other than 4 x 4 in the two blur plans), and a launch of no planes (major == 0) with TE_ERR_SHAPE; the two
+ * blur plans do not apply their launches' limits on the plane count and the plane size. */
 int te_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
                       int pad_x0, int pad_x1, int pad_y0, int pad_y1, int* zgroups, int* tiles);
 int te_blur_actgrad_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,

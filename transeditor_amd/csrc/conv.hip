@@ -841,32 +841,40 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const PackJobs 
     else pack_tiles<1>(q, tile);
 }
 
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline int pow2ceil(int v) { return 1 << ilog2(v); }
-inline int roundup(int v, int m) { return (v + m - 1) / m * m; }
+using te::ilog2; using te::pow2ceil; using te::roundup;
+
+// One descriptor per TE_PACK_* layout, in the order of te_hip.h: all the host needs to size and check a packing job.  M = Co, K = Ci when
+// `fwd` (else swapped); `taps` the layout needs (ANY_TAPS: 1 or 9); `padded`: Kp, Mp = K, M rounded up to KPAD, MPAD (else Kp = K, Mp = M);
+// M % mmul == 0 and K % kmul == 0 are required; the layout is a fragment-order part of bf16_per_km bf16 per K M (three pieces per value,
+// never padded; 0: none), then - 16-byte aligned, t6_plain_offset - an fp32 part of f32_per_km floats per Kp Mp (PER_TAP: one per tap; 0: none)
+constexpr int ANY_TAPS = 0, PER_TAP = -1;
+struct PackDesc { bool fwd; int taps; bool padded; int mmul, kmul, bf16_per_km, f32_per_km; };
+constexpr PackDesc PACKS[TE_PACK_KINDS] = {
+    {true, ANY_TAPS, true, 1, 1, 0, PER_TAP}, {false, ANY_TAPS, true, 1, 1, 0, PER_TAP}, {false, ANY_TAPS, true, 1, 1, 0, PER_TAP},   // FWD, DGRAD, SWAP
+    {true, 9, false, 8, 8, 0, 12}, {false, 9, false, 8, 8, 0, 12},                  // WFWD, WDGRAD: U[K/8][ky][component][8][M]
+    {true, 9, false, 32, 32, 36, 0}, {false, 9, false, 32, 32, 36, 0},              // W6FWD, W6DGRAD: [K/16][piece][ky][component][M/32][64 lanes][8 bf16]
+    {true, 9, false, 32, 16, 27, 0}, {false, 9, false, 32, 16, 27, 0},              // S6FWD, S6SWAP: [K/16][piece][tap][M/32][64 lanes][8 bf16]
+    {true, 9, true, 32, 16, 27, PER_TAP}, {false, 9, true, 32, 16, 27, PER_TAP},    // T6FWD, T6SWAP: the S6 layout, then the plain one (edge kernel of TE_CONV_T2S6)
+    {true, 1, false, 32, 16, 3, 0}, {false, 1, false, 32, 16, 3, 0},                // P6FWD, P6DGRAD: [K/16][piece][M/32][64 lanes][8 bf16]
+};
+static_assert(!PACKS[TE_PACK_SWAP].fwd && PACKS[TE_PACK_P6DGRAD].taps == 1 && PACKS[TE_PACK_T6SWAP].bf16_per_km == 27, "PACKS follows the order of te_hip.h; t6_plain_offset (device side) is written for 27 K M bf16");
+inline bool pack_kind_ok(int kind_pack) { return kind_pack >= 0 && kind_pack < TE_PACK_KINDS; }
+// te_conv_packed_numel has no way to refuse: a kind outside the table is sized like TE_PACK_SWAP, as it always was
+inline const PackDesc& pack_desc(int kind_pack) { return PACKS[pack_kind_ok(kind_pack) ? kind_pack : TE_PACK_SWAP]; }
 
 struct PackDims { int K, M, Kp, Mp, ntap; };
-inline bool pack_is_wino6(int kind_pack) { return kind_pack == TE_PACK_W6FWD || kind_pack == TE_PACK_W6DGRAD; }
-inline bool pack_is_s6(int kind_pack) { return kind_pack == TE_PACK_S6FWD || kind_pack == TE_PACK_S6SWAP; }
-inline bool pack_is_t6(int kind_pack) { return kind_pack == TE_PACK_T6FWD || kind_pack == TE_PACK_T6SWAP; }
-inline bool pack_is_p6(int kind_pack) { return kind_pack == TE_PACK_P6FWD || kind_pack == TE_PACK_P6DGRAD; }
-inline bool pack_is_wino(int kind_pack) { return kind_pack == TE_PACK_WFWD || kind_pack == TE_PACK_WDGRAD || pack_is_wino6(kind_pack); }
 inline PackDims pack_dims(int kind_pack, int Co, int Ci, int ksize) {
-    PackDims d;
-    d.ntap = ksize * ksize;
-    const bool fwd = kind_pack == TE_PACK_FWD || kind_pack == TE_PACK_WFWD || kind_pack == TE_PACK_W6FWD || kind_pack == TE_PACK_S6FWD ||
-                     kind_pack == TE_PACK_T6FWD || kind_pack == TE_PACK_P6FWD;
-    d.M = fwd ? Co : Ci;
-    d.K = fwd ? Ci : Co;
-    // the Winograd layouts (fp32: U[K/8][ky][component][8][M], K % 8 == 0 and M % 8 == 0) and the split fragment-order layouts (W6 / S6 /
-    // P6: [K/16][piece][...][M/32][64 lanes][8 bf16], M % 32 == 0 and K % 16 == 0 - 32 for W6) are not padded: pack_launch checks the multiples
-    if (pack_is_wino(kind_pack) || pack_is_s6(kind_pack) || pack_is_p6(kind_pack)) {
-        d.Kp = d.K; d.Mp = d.M;
-    } else {
-        d.Kp = roundup(d.K, KPAD);
-        d.Mp = roundup(d.M, MPAD);
-    }
-    return d;
+    const PackDesc& pd = pack_desc(kind_pack);
+    const int M = pd.fwd ? Co : Ci, K = pd.fwd ? Ci : Co;
+    return {K, M, pd.padded ? roundup(K, KPAD) : K, pd.padded ? roundup(M, MPAD) : M, ksize * ksize};
+}
+// First guess of a region's cell tile: TW x TH cells of NS samples fill the block tile of `cells` cells.  conv_plan counts a launch's blocks,
+// and from them the split-K count, with this guess as it stands; add_region may still halve TH for the staging budget (and then takes NS from
+// the halved tile), so it can launch more blocks than the plan counted.  Deliberate: the un-shrunk count is what fixes today's split counts.
+struct CellTile { int TW, TH, NS; };
+inline CellTile first_cell_tile(int cells, int rh, int rw) {
+    const int TW = std::min(32, pow2ceil(rw)), TH = std::min(pow2ceil(rh), cells / TW);
+    return {TW, TH, cells / (TW * TH)};
 }
 
 template <int KIND, int TC>
@@ -876,21 +884,14 @@ int add_region(ConvArgs& a, int ri0, int rj0, int rh, int rw, int& nblocks, size
     constexpr int NTILE = tile_cells<KIND, TC>();
     ConvArgs::Region& g = a.reg[a.nreg];
     g.ri0 = ri0; g.rj0 = rj0; g.rh = rh; g.rw = rw;
-    constexpr int NSP_ = Cfg<KIND, TC>::NSP;
-    auto tile_in = [](int th, int tw) {        // input-tile elements of one sample
-        if (KIND == TE_CONV_3X3) return (th + 2) * (tw + 2);
-        if (KIND == TE_CONV_S2) return (2 * th + 1) * (2 * tw + 1);
-        if (KIND == TE_CONV_T2) return (th + 1) * (tw + 1);
-        return th * tw;
-    };
     constexpr int NSP = Cfg<KIND, TC>::NSP, NQ = Cfg<KIND, TC>::NQ;
     auto in_rows = [](int th) { return KIND == TE_CONV_3X3 ? th + 2 : (KIND == TE_CONV_S2 ? 2 * th + 1 : (KIND == TE_CONV_T2 ? th + 1 : th)); };
     auto in_cols = [](int tw) { return KIND == TE_CONV_3X3 ? tw + 2 : (KIND == TE_CONV_S2 ? 2 * tw + 1 : (KIND == TE_CONV_T2 ? tw + 1 : tw)); };
-    g.TW = std::min(32, pow2ceil(rw));
-    g.TH = std::min(pow2ceil(rh), NTILE / g.TW);
+    const CellTile t0 = first_cell_tile(NTILE, rh, rw);
+    g.TW = t0.TW; g.TH = t0.TH;
     g.xo = 0; g.nseg = 0;
     if (!fast) {
-        while (g.TH > 1 && tile_in(g.TH, g.TW) > NSP_ * NTHREADS) g.TH >>= 1;   // thin edge regions: one sample must fit
+        while (g.TH > 1 && in_rows(g.TH) * in_cols(g.TW) > NSP * NTHREADS) g.TH >>= 1;   // thin edge regions: one sample must fit
     } else {
         // FAST staging: rows of 16-byte segments; the kinds with a left halo column start their rows 3 columns early so
         // that no segment straddles the left image border.  NQ (segment, channel) pairs per thread must cover a stage.
@@ -1004,16 +1005,46 @@ int launch_regions_tc(ConvArgs a, const int (*regions)[4], int n, hipStream_t s)
 
 inline int tile_class(int M) { return M >= 96 ? 0 : (M >= 48 ? 1 : 2); }
 
-template <int KIND>
-int launch_regions(const ConvArgs& a, const int (*regions)[4], int n, hipStream_t s, int tc) {
+// the one runtime -> constexpr dispatch over a kind's tile classes: f(std::integral_constant<int, TC>)
+template <int KIND, class F>
+auto with_tile_class(int tc, F&& f) {
     if constexpr (KIND == TE_CONV_1X1) {
-        if (tc == 3) return launch_regions_tc<KIND, 3>(a, regions, n, s);
+        if (tc == 3) return f(std::integral_constant<int, 3>{});
     }
     switch (tc) {
-        case 0: return launch_regions_tc<KIND, 0>(a, regions, n, s);
-        case 1: return launch_regions_tc<KIND, 1>(a, regions, n, s);
-        default: return launch_regions_tc<KIND, 2>(a, regions, n, s);
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        default: return f(std::integral_constant<int, 2>{});
     }
+}
+
+template <int KIND>
+int launch_regions(const ConvArgs& a, const int (*regions)[4], int n, hipStream_t s, int tc) {
+    return with_tile_class<KIND>(tc, [&](auto TC) { return launch_regions_tc<KIND, decltype(TC)::value>(a, regions, n, s); });
+}
+
+// (KC, BM, cells per block tile) of the kernels' own tables for a runtime (kind, tile class)
+struct TileDims { int KC, BM, cells; };
+template <int KIND>
+TileDims tile_dims_of(int tc) {
+    return with_tile_class<KIND>(tc, [](auto TC) { return TileDims{Cfg<KIND, decltype(TC)::value>::KC, tile_bm<KIND, decltype(TC)::value>(), tile_cells<KIND, decltype(TC)::value>()}; });
+}
+inline TileDims tile_dims(int kind, int tc) {
+    return kind == TE_CONV_T2 ? tile_dims_of<TE_CONV_T2>(tc) : kind == TE_CONV_S2 ? tile_dims_of<TE_CONV_S2>(tc)
+         : kind == TE_CONV_1X1 ? tile_dims_of<TE_CONV_1X1>(tc) : tile_dims_of<TE_CONV_3X3>(tc);
+}
+
+// transposed conv on images up to this many cells per side runs as ONE padded (H+1) x (W+1) region; larger ones as body +
+// last column + last row (round 3: 16 -> 8, the 8x8 -> 17x17 layer filled 42 % of its padded tiles: 152 -> 106 us at
+// 512 -> 512, batch 16)
+constexpr int T2_PAD_LIMIT = 8;
+
+// cell regions {ri0, rj0, rh, rw} of a launch, the main one first (conv_plan sizes the split on it); returns their number
+inline int conv_regions(int kind, int H, int W, int (*r)[4]) {
+    const bool t2 = kind == TE_CONV_T2, padded = t2 && (W + 1 <= T2_PAD_LIMIT || H + 1 <= T2_PAD_LIMIT);      // small images: one padded region
+    const int all[3][4] = {{0, 0, H + padded, W + padded}, {0, W, H + 1, 1}, {H, 0, 1, W}};                 // body, last column (+corner), last row
+    std::copy(&all[0][0], &all[0][0] + 12, &r[0][0]);
+    return (t2 && !padded) ? 3 : 1;
 }
 
 }  // namespace
@@ -1022,12 +1053,11 @@ PROF_READBACK(conv)
 PROF_CLEAR(conv)
 
 extern "C" int64_t te_conv_packed_numel(int kind_pack, int Co, int Ci, int ksize) {
+    const PackDesc& pd = pack_desc(kind_pack);
     const PackDims d = pack_dims(kind_pack, Co, Ci, ksize);
-    // (the split layouts: 3 pieces x 12 x K x M bf16 = 18 K M floats)
-    if (pack_is_s6(kind_pack)) return ((int64_t)27 * d.Kp * d.Mp + 1) / 2;          // 3 pieces x 9 taps x K x M bf16
-    if (pack_is_p6(kind_pack)) return ((int64_t)3 * d.Kp * d.Mp + 1) / 2;           // 3 pieces x K x M bf16
-    if (pack_is_t6(kind_pack)) return t6_plain_offset(d.K, d.M) + (int64_t)d.ntap * d.Kp * d.Mp;
-    return (int64_t)(pack_is_wino6(kind_pack) ? 18 : (pack_is_wino(kind_pack) ? 12 : d.ntap)) * d.Kp * d.Mp;
+    const int64_t split = ((int64_t)pd.bf16_per_km * d.K * d.M + 1) / 2;            // floats of the fragment-order part
+    if (!pd.f32_per_km) return split;
+    return (pd.bf16_per_km ? t6_plain_offset(d.K, d.M) : 0) + (int64_t)(pd.f32_per_km == PER_TAP ? d.ntap : pd.f32_per_km) * d.Kp * d.Mp;
 }
 
 // 32 x 32 tiles of a packing job and the capped grid.x of a launch whose biggest job has `biggest` tiles: a block walks the tiles
@@ -1038,15 +1068,39 @@ static unsigned pack_grid_x(int64_t biggest) { return (unsigned)std::min<int64_t
 // blocks along x of a single-job packing launch and the job's tile count (host only)
 extern "C" int te_conv_pack_plan(int kind_pack, int Co, int Ci, int ksize, int* blocks, int* tiles) {
     if (!blocks || !tiles) return TE_ERR_NULL;
-    if (Co <= 0 || Ci <= 0 || (ksize != 1 && ksize != 3) || kind_pack < 0 || kind_pack > 12) return TE_ERR_SHAPE;
+    if (Co <= 0 || Ci <= 0 || (ksize != 1 && ksize != 3) || !pack_kind_ok(kind_pack)) return TE_ERR_SHAPE;
     const int64_t t = pack_job_tiles(pack_dims(kind_pack, Co, Ci, ksize));
     *tiles = (int)t;
     *blocks = (int)pack_grid_x(t);
     return 0;
 }
 
+// every packing entry point runs the tiled multi-job kernel (1, 2 or up to 64 layouts per launch)
 static int pack_launch(const char* what, int n, float* const* wp, const float* const* w, const float* wscale, const int* kind_pack,
-                       const int* Co, const int* Ci, const int* ksize, hipStream_t s);
+                       const int* Co, const int* Ci, const int* ksize, hipStream_t s) {
+    TE_REQUIRE(n >= 0 && (n == 0 || (wp && w && wscale && kind_pack && Co && Ci && ksize)), TE_ERR_NULL, "%s: NULL table", what);
+    for (int base = 0; base < n; base += 64) {
+        const int cnt = std::min(64, n - base);
+        PackJobs P{};
+        int64_t biggest = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const int e = base + i;
+            TE_REQUIRE(wp[e] && w[e], TE_ERR_NULL, "%s: NULL pointer in job %d", what, e);
+            TE_REQUIRE(Co[e] > 0 && Ci[e] > 0 && (ksize[e] == 1 || ksize[e] == 3), TE_ERR_SHAPE, "%s: bad dims in job %d", what, e);
+            TE_REQUIRE(pack_kind_ok(kind_pack[e]), TE_ERR_UNSUPPORTED, "%s: bad kind in job %d", what, e);
+            const PackDims d = pack_dims(kind_pack[e], Co[e], Ci[e], ksize[e]);
+            const PackDesc& pd = pack_desc(kind_pack[e]);
+            TE_REQUIRE((pd.taps == ANY_TAPS || d.ntap == pd.taps) && d.M % pd.mmul == 0 && d.K % pd.kmul == 0, TE_ERR_UNSUPPORTED,
+                       "%s: layout %d needs a weight of %d tap(s) with M %% %d == 0 and K %% %d == 0 (job %d)", what, kind_pack[e], pd.taps, pd.mmul, pd.kmul, e);
+            P.j[i] = PackJob{wp[e], w[e], wscale[e], kind_pack[e], Ci[e], d.ntap, d.K, d.M, d.Kp, d.Mp};
+            biggest = std::max<int64_t>(biggest, pack_job_tiles(d));
+        }
+        // one block per 32 x 32 tile of the biggest job (512 x 512: 256 blocks); small jobs walk their few tiles and exit
+        dim3 grid(pack_grid_x(biggest), (unsigned)cnt);
+        pack_weights_multi_kernel<<<grid, 256, 0, s>>>(P);
+    }
+    return te::launch_status(what);
+}
 
 extern "C" int te_conv_pack_weights_f32(float* wp, const float* w, float wscale, int kind_pack, int Co, int Ci, int ksize,
                                         te_stream_t stream_) {
@@ -1068,47 +1122,6 @@ extern "C" int te_conv_pack_weights_multi_f32(int n, float* const* wp, const flo
     return pack_launch("te_conv_pack_weights_multi_f32", n, wp, w, wscale, kind_pack, Co, Ci, ksize, (hipStream_t)stream_);
 }
 
-// every packing entry point runs the tiled multi-job kernel (1, 2 or up to 64 layouts per launch)
-static int pack_launch(const char* what, int n, float* const* wp, const float* const* w, const float* wscale, const int* kind_pack,
-                       const int* Co, const int* Ci, const int* ksize, hipStream_t s) {
-    TE_REQUIRE(n >= 0 && (n == 0 || (wp && w && wscale && kind_pack && Co && Ci && ksize)), TE_ERR_NULL, "%s: NULL table", what);
-    for (int base = 0; base < n; base += 64) {
-        const int cnt = std::min(64, n - base);
-        PackJobs P{};
-        int64_t biggest = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const int e = base + i;
-            TE_REQUIRE(wp[e] && w[e], TE_ERR_NULL, "%s: NULL pointer in job %d", what, e);
-            TE_REQUIRE(Co[e] > 0 && Ci[e] > 0 && (ksize[e] == 1 || ksize[e] == 3), TE_ERR_SHAPE, "%s: bad dims in job %d", what, e);
-            TE_REQUIRE(kind_pack[e] >= 0 && kind_pack[e] <= 12, TE_ERR_UNSUPPORTED, "%s: bad kind in job %d", what, e);
-            TE_REQUIRE(!pack_is_p6(kind_pack[e]) || (ksize[e] == 1 && (kind_pack[e] == TE_PACK_P6FWD ? (Co[e] % 32 == 0 && Ci[e] % 16 == 0)
-                                                                                                    : (Ci[e] % 32 == 0 && Co[e] % 16 == 0))),
-                       TE_ERR_UNSUPPORTED, "te_conv_pack_weights: the split layouts of TE_CONV_1X1S6 need a 1x1 weight with M %% 32 == 0 and K %% 16 == 0");
-            TE_REQUIRE(!pack_is_t6(kind_pack[e]) || (ksize[e] == 3 && (kind_pack[e] == TE_PACK_T6FWD ? (Co[e] % 32 == 0 && Ci[e] % 16 == 0)
-                                                                                                    : (Ci[e] % 32 == 0 && Co[e] % 16 == 0))),
-                       TE_ERR_UNSUPPORTED, "te_conv_pack_weights: the split layouts of TE_CONV_T2S6 need a 3x3 weight with M %% 32 == 0 and K %% 16 == 0");
-            TE_REQUIRE(!pack_is_s6(kind_pack[e]) || (ksize[e] == 3 && (kind_pack[e] == TE_PACK_S6FWD ? (Co[e] % 32 == 0 && Ci[e] % 16 == 0)
-                                                                                                    : (Ci[e] % 32 == 0 && Co[e] % 16 == 0))),
-                       TE_ERR_UNSUPPORTED, "te_conv_pack_weights: the split layouts of TE_CONV_S2S6 need a 3x3 weight with M %% 32 == 0 and K %% 16 == 0");
-            TE_REQUIRE(!pack_is_wino6(kind_pack[e]) || (ksize[e] == 3 && Co[e] % 32 == 0 && Ci[e] % 32 == 0), TE_ERR_UNSUPPORTED,
-                       "%s: the split Winograd layouts need 3x3 taps and channel counts that are multiples of 32 (job %d)", what, e);
-            TE_REQUIRE(!pack_is_wino(kind_pack[e]) || (ksize[e] == 3 && Co[e] % 8 == 0 && Ci[e] % 8 == 0), TE_ERR_UNSUPPORTED,
-                       "%s: the Winograd layouts need 3x3 taps and channel counts that are multiples of 8 (job %d)", what, e);
-            const PackDims d = pack_dims(kind_pack[e], Co[e], Ci[e], ksize[e]);
-            P.j[i] = PackJob{wp[e], w[e], wscale[e], kind_pack[e], Ci[e], d.ntap, d.K, d.M, d.Kp, d.Mp};
-            biggest = std::max<int64_t>(biggest, pack_job_tiles(d));
-        }
-        // one block per 32 x 32 tile of the biggest job (512 x 512: 256 blocks); small jobs walk their few tiles and exit
-        dim3 grid(pack_grid_x(biggest), (unsigned)cnt);
-        pack_weights_multi_kernel<<<grid, 256, 0, s>>>(P);
-    }
-    return te::launch_status(what);
-}
-
-// transposed conv on images up to this many cells per side runs as ONE padded (H+1) x (W+1) region; larger ones as body +
-// last column + last row (round 3: 16 -> 8, the 8x8 -> 17x17 layer filled 42 % of its padded tiles: 152 -> 106 us at
-// 512 -> 512, batch 16)
-constexpr int T2_PAD_LIMIT = 8;
 // the split-K plan: fewest stages a split keeps, blocks per CU it aims at
 constexpr int SPLITK_MINSTAGES = 4, SPLITK_BLOCKS = 2;
 
@@ -1126,23 +1139,22 @@ static ConvPlan conv_plan(int kind, int B, int K, int M, int H, int W) {
     // (narrower tile classes for the 4x4 / 8x8 layers were measured and lose: 3x3 512->512 @4x4 65 -> 112 (64 rows) / 119 us (32 rows),
     // profiles/experiments/r03_tiny_tile_class.log)
     pl.tc = tc;
-    const int KC = t2k ? (tc == 0 ? T2_KC0 : 16) : 8;
-    const int BM = t2k ? (tc == 2 ? 32 : 64) : (tc == 0 ? 128 : (tc == 1 ? 64 : 32));
+    const TileDims td = tile_dims(kind, tc);
     // split the channel loop when the image is too small to give every CU a tile (4x4 ... 16x16 layers); the
-    // split count comes from the real tile geometry of the main region and is shared by every region of the launch
-    const int ntile = t2k ? (tc == 1 ? 64 : 128) : ((tc == 0 || (kind == TE_CONV_S2 && tc == 1)) ? 128 : 256);      // cells per block tile of the chosen tile class
-    int rh = H, rw = W;
-    if (t2k && (W + 1 <= T2_PAD_LIMIT || H + 1 <= T2_PAD_LIMIT)) { rh = H + 1; rw = W + 1; }
-    const int TW = std::min(32, pow2ceil(rw)), TH = std::min(pow2ceil(rh), ntile / TW), NS = ntile / (TW * TH);
-    const int64_t base_blocks = (int64_t)te::cdiv(rw, TW) * te::cdiv(rh, TH) * te::cdiv(B, NS) * te::cdiv(M, BM);
-    const int stages = Kp / KC;
+    // split count comes from the tile geometry of the main region and is shared by every region of the launch
+    int r[3][4];
+    conv_regions(kind, H, W, r);
+    const int rh = r[0][2], rw = r[0][3];
+    const CellTile t = first_cell_tile(td.cells, rh, rw);
+    const int64_t base_blocks = (int64_t)te::cdiv(rw, t.TW) * te::cdiv(rh, t.TH) * te::cdiv(B, t.NS) * te::cdiv(M, td.BM);
+    const int stages = Kp / td.KC;
     int ks = 1;
     if (base_blocks < te::kNumCU) ks = (int)std::min<int64_t>(te::cdiv(SPLITK_BLOCKS * te::kNumCU, base_blocks), std::max(1, stages / SPLITK_MINSTAGES));
     pl.ksplit = std::max(1, ks);
-    pl.kchunk = (int)te::cdiv(stages, pl.ksplit) * KC;
+    pl.kchunk = (int)te::cdiv(stages, pl.ksplit) * td.KC;
     pl.ksplit = (int)te::cdiv(Kp, pl.kchunk);
     // 1x1 on images that fill the chip, channel count a multiple of 64: the deep-stage FAST class
-    if (kind == TE_CONV_1X1 && tc == 0 && pl.ksplit == 1 && NS == 1 && K % 64 == 0) pl.tc = 3;
+    if (kind == TE_CONV_1X1 && tc == 0 && pl.ksplit == 1 && t.NS == 1 && K % 64 == 0) pl.tc = 3;
     return pl;
 }
 
@@ -1157,7 +1169,7 @@ extern "C" int64_t te_conv_finalize_cover(int64_t outputs) {
 }
 
 extern "C" int te_conv_splitk_count(int kind, int B, int K, int M, int H, int W) {
-    if (B <= 0 || K <= 0 || M <= 0 || H <= 0 || W <= 0 || kind < 0 || kind > 8) return TE_ERR_SHAPE;
+    if (B <= 0 || K <= 0 || M <= 0 || H <= 0 || W <= 0 || kind < 0 || kind >= TE_CONV_KINDS) return TE_ERR_SHAPE;
     if (kind == TE_CONV_3X3W || kind == TE_CONV_3X3W6 || kind == TE_CONV_S2S6 || kind == TE_CONV_T2S6 || kind == TE_CONV_1X1S6) return 1;
     return conv_plan(kind, B, K, M, H, W).ksplit;
 }
@@ -1170,7 +1182,7 @@ extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const flo
                "te_conv_res_f32: no residual / mask epilogue for the transposed kind");
     TE_REQUIRE(B > 0 && K > 0 && M > 0 && H > 0 && W > 0, TE_ERR_SHAPE, "te_conv_f32: bad dims");
     TE_REQUIRE(act == 0 || act == 3 || act == 4, TE_ERR_UNSUPPORTED, "te_conv_f32: act must be 0, 3 or 4");
-    TE_REQUIRE(kind >= 0 && kind <= 8, TE_ERR_UNSUPPORTED, "te_conv_f32: unknown kind %d", kind);
+    TE_REQUIRE(kind >= 0 && kind < TE_CONV_KINDS, TE_ERR_UNSUPPORTED, "te_conv_f32: unknown kind %d", kind);
     hipStream_t s = (hipStream_t)stream_;
     if (kind == TE_CONV_1X1S6) {
         TE_REQUIRE(!isc && !osc && !bias && !mask_ref && act == 0, TE_ERR_UNSUPPORTED,
@@ -1194,41 +1206,22 @@ extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const flo
     a.out = out; a.ws = ws; a.in = in; a.wp = wp; a.isc = isc; a.osc = osc; a.bias = bias; a.res = res; a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
     a.B = B; a.K = K; a.M = M; a.Kp = roundup(K, KPAD); a.Mp = roundup(M, MPAD); a.H = H; a.W = W;
     const ConvPlan pl = conv_plan(kind, B, K, M, H, W);
-    const int tc = pl.tc;
     a.ksplit = pl.ksplit; a.kchunk = pl.kchunk;
     if (a.ksplit > 1 && !a.ws) {       // no workspace (te_conv_f32): the channel loop is not split - slower on 4x4 ... 16x16 images,
         a.ksplit = 1;                  // but no atomics anywhere: every result of this library is bit-reproducible
         a.kchunk = a.Kp;
     }
     if (a.ksplit == 1) a.ws = nullptr;
+    int r[3][4];
+    const int n = conv_regions(kind, H, W, r);
+    a.Hi = a.Ho = H; a.Wi = a.Wo = W;
     int rc = 0;
     switch (kind) {
-        case TE_CONV_3X3: {
-            a.Hi = a.Ho = H; a.Wi = a.Wo = W;
-            const int r[1][4] = {{0, 0, H, W}};
-            // (a 128 x 256 block tile, NBW = 4, measured the same 133 TF/s: the kernel sits at the clock-limited peak)
-            rc = launch_regions<TE_CONV_3X3>(a, r, 1, s, tc);
-        } break;
-        case TE_CONV_1X1: {
-            a.Hi = a.Ho = H; a.Wi = a.Wo = W;
-            const int r[1][4] = {{0, 0, H, W}};
-            rc = launch_regions<TE_CONV_1X1>(a, r, 1, s, tc);
-        } break;
-        case TE_CONV_S2: {
-            a.Hi = 2 * H + 1; a.Wi = 2 * W + 1; a.Ho = H; a.Wo = W;
-            const int r[1][4] = {{0, 0, H, W}};
-            rc = launch_regions<TE_CONV_S2>(a, r, 1, s, tc);
-        } break;
-        default: {      // TE_CONV_T2
-            a.Hi = H; a.Wi = W; a.Ho = 2 * H + 1; a.Wo = 2 * W + 1;
-            if (W + 1 <= T2_PAD_LIMIT || H + 1 <= T2_PAD_LIMIT) {
-                const int r[1][4] = {{0, 0, H + 1, W + 1}};                       // small images: one padded region
-                rc = launch_regions<TE_CONV_T2>(a, r, 1, s, tc);
-            } else {
-                const int r[3][4] = {{0, 0, H, W}, {0, W, H + 1, 1}, {H, 0, 1, W}};  // body, last column (+corner), last row
-                rc = launch_regions<TE_CONV_T2>(a, r, 3, s, tc);
-            }
-        } break;
+        // (3x3: a 128 x 256 block tile, NBW = 4, measured the same 133 TF/s: the kernel sits at the clock-limited peak)
+        case TE_CONV_3X3: rc = launch_regions<TE_CONV_3X3>(a, r, n, s, pl.tc); break;
+        case TE_CONV_1X1: rc = launch_regions<TE_CONV_1X1>(a, r, n, s, pl.tc); break;
+        case TE_CONV_S2: a.Hi = 2 * H + 1; a.Wi = 2 * W + 1; rc = launch_regions<TE_CONV_S2>(a, r, n, s, pl.tc); break;
+        default: a.Ho = 2 * H + 1; a.Wo = 2 * W + 1; rc = launch_regions<TE_CONV_T2>(a, r, n, s, pl.tc); break;      // TE_CONV_T2
     }
     if (rc) return rc;
     if (a.ksplit > 1 && (a.ws || osc || bias || act)) {

@@ -21,6 +21,10 @@ inline int launch_status(const char* what) {
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }      // ceil(log2 v)
+inline int pow2ceil(int v) { return 1 << ilog2(v); }
+inline int roundup(int v, int m) { return (v + m - 1) / m * m; }
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // torch's relu: a NaN fails both comparisons and propagates

@@ -522,22 +522,16 @@ void launch_blur44(float* out, const float* x, const float* k, const float* b, c
                    float* partial) {
     FirParams q = p;
     dim3 grid(blur44_grid(q), 1u, 1u);
-    const int d = (-p.pad_x0) & 3;
-    if (q.ext_x || q.ext_y) {
-        switch (d) {
-            case 0: blur44_kernel<AG, 0, true><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            case 1: blur44_kernel<AG, 1, true><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            case 2: blur44_kernel<AG, 2, true><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            default: blur44_kernel<AG, 3, true><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+    auto go = [&](auto EXT) {       // EXT: the launch has an extra column / row (the +1 rule); D = (-pad_x0) & 3
+        switch ((-p.pad_x0) & 3) {
+            case 0: blur44_kernel<AG, 0, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+            case 1: blur44_kernel<AG, 1, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+            case 2: blur44_kernel<AG, 2, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+            default: blur44_kernel<AG, 3, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
         }
-    } else {
-        switch (d) {
-            case 0: blur44_kernel<AG, 0, false><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            case 1: blur44_kernel<AG, 1, false><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            case 2: blur44_kernel<AG, 2, false><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            default: blur44_kernel<AG, 3, false><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-        }
-    }
+    };
+    if (q.ext_x || q.ext_y) go(std::true_type{});
+    else go(std::false_type{});
 }
 
 // which kernel a te_upfirdn2d_f32 problem takes (shared by the launch and te_upfirdn2d_plan)
@@ -561,18 +555,61 @@ inline FirParams fir_geometry(int64_t major, int in_h, int in_w, int minor, int 
     p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.minor = minor; p.major = major;
     return p;
 }
-inline FirParams blur_bwd_geometry(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
-    FirParams p{};
-    p.in_h = in_h; p.in_w = in_w;
-    p.out_h = in_h + pad_y0 + pad_y1 - kh + 1;
-    p.out_w = in_w + pad_x0 + pad_x1 - kw + 1;
-    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
-    p.up_x = p.up_y = p.down_x = p.down_y = 1; p.minor = 1; p.major = major;
-    return p;
-}
 // te_blur_actgrad_f32 takes the blur kernel unless a row is narrower than one 16-byte group
 inline bool actgrad_blur44(const FirParams& p) { return p.in_w >= 4; }
+// grid of a fused blur backward pass; fills q like blur44_grid / tile_grid (shared by the launch, the plans and te_blur_actgrad_tiles)
+inline unsigned blur_bwd_grid(FirParams& q) { return actgrad_blur44(q) ? blur44_grid(q) : tile_grid(q); }
 
+// Argument conditions and geometry of a general upfirdn2d problem, shared by the three launches and te_upfirdn2d_plan (which has no
+// epilogue to check): one place says what is refused and with which code.  major == 0 passes (an empty launch).
+int fir_problem(const char* what, FirParams& p, int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x,
+                int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, bool has_bias = false, int64_t size_b = 1, int act = 0) {
+    TE_REQUIRE(major >= 0 && in_h > 0 && in_w > 0 && minor > 0 && kh > 0 && kw > 0, TE_ERR_SHAPE, "%s: bad dims", what);
+    TE_REQUIRE(up_x > 0 && up_y > 0 && down_x > 0 && down_y > 0, TE_ERR_SHAPE, "%s: up/down must be > 0", what);
+    TE_REQUIRE(act == 0 || act == 3, TE_ERR_UNSUPPORTED, "%s: act must be 0 or 3", what);
+    TE_REQUIRE(!(has_bias || act) || minor == 1, TE_ERR_UNSUPPORTED, "%s: fused epilogue needs minor == 1", what);
+    TE_REQUIRE(!has_bias || size_b > 0, TE_ERR_SHAPE, "%s: bias given but size_b <= 0", what);
+    p = fir_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+    TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "%s: empty output (%d x %d)", what, p.out_h, p.out_w);
+    return 0;
+}
+
+// The same for the two fused blur backward passes (up = down = 1, 4 x 4 taps), shared by their launch and their plans.  min_w: the
+// narrowest row the pass takes (te_blur_gradact_f32 has the blur kernel only: one 16-byte group); nonneg_pads: te_blur_actgrad_f32
+// refuses negative pads, because every input element has to be staged by some tile for the bias gradient.
+int blur_bwd_problem(const char* what, FirParams& p, int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0,
+                     int pad_y1, int min_w, bool nonneg_pads) {
+    TE_REQUIRE(major >= 0 && in_h > 0 && in_w >= min_w, TE_ERR_SHAPE, "%s: bad dims (in_w >= %d)", what, min_w);
+    TE_REQUIRE(kh == 4 && kw == 4, TE_ERR_UNSUPPORTED, "%s: 4x4 taps only", what);
+    TE_REQUIRE(!nonneg_pads || (pad_x0 >= 0 && pad_x1 >= 0 && pad_y0 >= 0 && pad_y1 >= 0), TE_ERR_UNSUPPORTED,
+               "%s: pads must be >= 0 (every input element has to be staged by some tile)", what);
+    p = fir_geometry(major, in_h, in_w, 1, kh, kw, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1);
+    TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "%s: empty output", what);
+    return 0;
+}
+
+// body of te_blur_actgrad_f32 (MODE 1) and te_blur_gradact_f32 (MODE 2)
+template <int MODE>
+int blur_bwd_launch(const char* what, float* gx, float* partial, const float* g, const float* ref, const float* k, int64_t major, int in_h,
+                    int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1, float alpha, float scale, hipStream_t s,
+                    int min_w, bool nonneg_pads) {
+    TE_REQUIRE(gx && partial && g && ref && k, TE_ERR_NULL, "%s: NULL pointer", what);
+    FirParams p;
+    if (const int rc = blur_bwd_problem(what, p, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, min_w, nonneg_pads)) return rc;
+    p.size_b = 1; p.act = 0; p.alpha = alpha; p.scale = scale;
+    if (major == 0) return 0;
+    TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "%s: too many planes", what);
+    TE_REQUIRE((int64_t)in_h * in_w * 4 < 0x7FFFFFFF, TE_ERR_UNSUPPORTED, "%s: plane too large", what);
+    if (MODE == 2 || actgrad_blur44(p)) {
+        launch_blur44<MODE>(gx, g, k, nullptr, p, s, ref, partial);
+    } else {
+        dim3 grid(tile_grid(p), 1u, 1u);
+        fir_tile_kernel<1, 1, 4, 4, true><<<grid, 256, 0, s>>>(gx, g, k, nullptr, p, ref, partial);
+    }
+    return te::launch_status(what);
+}
+
+// what a plan hands out: the grid function has filled q
 inline int plan_out(const FirParams& q, bool walks, int* zgroups, int* tiles) {
     *zgroups = walks ? q.zgroups : 0;
     *tiles = walks ? q.tiles_x * q.tiles_y : 0;
@@ -581,50 +618,26 @@ inline int plan_out(const FirParams& q, bool walks, int* zgroups, int* tiles) {
 
 }  // namespace
 
+// tiles per plane of both fused blur backward passes (only the output size is checked: the launches check the rest)
 extern "C" int te_blur_actgrad_tiles(int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
-    const int oh = in_h + pad_y0 + pad_y1 - kh + 1, ow = in_w + pad_x0 + pad_x1 - kw + 1;
-    if (oh <= 0 || ow <= 0) return TE_ERR_SHAPE;
-    if (in_w < 4) return (int)(te::cdiv(ow, TOW) * te::cdiv(oh, TOH));     // narrower than one 16-byte group: generic tile kernel
-    return blur44_tiles(ow, BOW) * blur44_tiles(oh, BOH);
+    FirParams p = fir_geometry(1, in_h, in_w, 1, kh, kw, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1);
+    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
+    blur_bwd_grid(p);
+    return p.tiles_x * p.tiles_y;
 }
 
 extern "C" int te_blur_actgrad_f32(float* gx, float* partial, const float* g, const float* ref, const float* k, int64_t major,
                                    int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                    float alpha, float scale, te_stream_t stream_) {
-    TE_REQUIRE(gx && partial && g && ref && k, TE_ERR_NULL, "te_blur_actgrad_f32: NULL pointer");
-    TE_REQUIRE(major >= 0 && in_h > 0 && in_w > 0, TE_ERR_SHAPE, "te_blur_actgrad_f32: bad dims");
-    TE_REQUIRE(kh == 4 && kw == 4, TE_ERR_UNSUPPORTED, "te_blur_actgrad_f32: 4x4 taps only");
-    TE_REQUIRE(pad_x0 >= 0 && pad_x1 >= 0 && pad_y0 >= 0 && pad_y1 >= 0, TE_ERR_UNSUPPORTED,
-               "te_blur_actgrad_f32: pads must be >= 0 (every input element has to be staged by some tile)");
-    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
-    TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "te_blur_actgrad_f32: empty output");
-    p.size_b = 1; p.act = 0; p.alpha = alpha; p.scale = scale;
-    if (major == 0) return 0;
-    TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "te_blur_actgrad_f32: too many planes");
-    TE_REQUIRE((int64_t)in_h * in_w * 4 < 0x7FFFFFFF, TE_ERR_UNSUPPORTED, "te_blur_actgrad_f32: plane too large");
-    if (actgrad_blur44(p)) {
-        launch_blur44<1>(gx, g, k, nullptr, p, (hipStream_t)stream_, ref, partial);
-    } else {
-        dim3 grid(tile_grid(p), 1u, 1u);
-        fir_tile_kernel<1, 1, 4, 4, true><<<grid, 256, 0, (hipStream_t)stream_>>>(gx, g, k, nullptr, p, ref, partial);
-    }
-    return te::launch_status("te_blur_actgrad_f32");
+    return blur_bwd_launch<1>("te_blur_actgrad_f32", gx, partial, g, ref, k, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, alpha,
+                              scale, (hipStream_t)stream_, 1, true);
 }
 
 extern "C" int te_blur_gradact_f32(float* gx, float* partial, const float* g, const float* ref, const float* k, int64_t major,
                                    int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                    float alpha, float scale, te_stream_t stream_) {
-    TE_REQUIRE(gx && partial && g && ref && k, TE_ERR_NULL, "te_blur_gradact_f32: NULL pointer");
-    TE_REQUIRE(major >= 0 && in_h > 0 && in_w >= 4, TE_ERR_SHAPE, "te_blur_gradact_f32: bad dims (in_w >= 4)");
-    TE_REQUIRE(kh == 4 && kw == 4, TE_ERR_UNSUPPORTED, "te_blur_gradact_f32: 4x4 taps only");
-    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
-    TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "te_blur_gradact_f32: empty output");
-    p.size_b = 1; p.act = 0; p.alpha = alpha; p.scale = scale;
-    if (major == 0) return 0;
-    TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "te_blur_gradact_f32: too many planes");
-    TE_REQUIRE((int64_t)in_h * in_w * 4 < 0x7FFFFFFF, TE_ERR_UNSUPPORTED, "te_blur_gradact_f32: plane too large");
-    launch_blur44<2>(gx, g, k, nullptr, p, (hipStream_t)stream_, ref, partial);
-    return te::launch_status("te_blur_gradact_f32");
+    return blur_bwd_launch<2>("te_blur_gradact_f32", gx, partial, g, ref, k, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, alpha,
+                              scale, (hipStream_t)stream_, 4, false);
 }
 
 // half / double (the reference dispatches its kernel over AT_DISPATCH_FLOATING_TYPES_AND_HALF, upfirdn2d_kernel.cu:57-58,
@@ -661,15 +674,8 @@ template <typename T, typename A>
 int upfirdn2d_any(T* out, const T* x, const T* k, int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y,
                   int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, te_stream_t stream_, const char* what) {
     TE_REQUIRE(out && x && k, TE_ERR_NULL, "%s: out/x/k is NULL", what);
-    TE_REQUIRE(major >= 0 && in_h > 0 && in_w > 0 && minor > 0 && kh > 0 && kw > 0, TE_ERR_SHAPE, "%s: bad dims", what);
-    TE_REQUIRE(up_x > 0 && up_y > 0 && down_x > 0 && down_y > 0, TE_ERR_SHAPE, "%s: up/down must be > 0", what);
-    FirParams p{};
-    p.in_h = in_h; p.in_w = in_w;
-    p.out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
-    p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
-    TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "%s: empty output (%d x %d)", what, p.out_h, p.out_w);
-    p.pad_x0 = pad_x0; p.pad_y0 = pad_y0; p.kh = kh; p.kw = kw;
-    p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.minor = minor; p.major = major;
+    FirParams p;
+    if (const int rc = fir_problem(what, p, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1)) return rc;
     if (major == 0) return 0;
     const int64_t total = major * p.out_h * p.out_w * minor;
     const int grid = fir_direct_grid(total);
@@ -697,14 +703,10 @@ extern "C" int te_upfirdn2d_f32(float* out, const float* x, const float* k, int6
                                 int pad_y0, int pad_y1, const float* b, int64_t size_b, int act, float alpha,
                                 float scale, te_stream_t stream_) {
     TE_REQUIRE(out && x && k, TE_ERR_NULL, "te_upfirdn2d_f32: out/x/k is NULL");
-    TE_REQUIRE(major >= 0 && in_h > 0 && in_w > 0 && minor > 0 && kh > 0 && kw > 0, TE_ERR_SHAPE,
-               "te_upfirdn2d_f32: bad dims");
-    TE_REQUIRE(up_x > 0 && up_y > 0 && down_x > 0 && down_y > 0, TE_ERR_SHAPE, "te_upfirdn2d_f32: up/down must be > 0");
-    TE_REQUIRE(act == 0 || act == 3, TE_ERR_UNSUPPORTED, "te_upfirdn2d_f32: act must be 0 or 3");
-    TE_REQUIRE(!(b || act) || minor == 1, TE_ERR_UNSUPPORTED, "te_upfirdn2d_f32: fused epilogue needs minor == 1");
-    TE_REQUIRE(!b || size_b > 0, TE_ERR_SHAPE, "te_upfirdn2d_f32: bias given but size_b <= 0");
-    FirParams p = fir_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
-    TE_REQUIRE(p.out_h > 0 && p.out_w > 0, TE_ERR_SHAPE, "te_upfirdn2d_f32: empty output (%d x %d)", p.out_h, p.out_w);
+    FirParams p;
+    if (const int rc = fir_problem("te_upfirdn2d_f32", p, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0,
+                                   pad_y1, b != nullptr, size_b, act))
+        return rc;
     p.size_b = (int)size_b; p.act = act; p.alpha = alpha; p.scale = (b || act) ? scale : 1.f;
     if (major == 0) return 0;
     hipStream_t s = (hipStream_t)stream_;
@@ -728,37 +730,34 @@ extern "C" int te_upfirdn2d_f32(float* out, const float* x, const float* k, int6
 extern "C" int te_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
                                  int pad_x0, int pad_x1, int pad_y0, int pad_y1, int* zgroups, int* tiles) {
     if (!zgroups || !tiles) return TE_ERR_NULL;
-    if (major <= 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
-        return TE_ERR_SHAPE;
-    FirParams p = fir_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
-    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
-    switch (fir_route(p)) {
-        case FIR_BLUR44: blur44_grid(p); return plan_out(p, true, zgroups, tiles);
-        case FIR_TILE_UP2:
-        case FIR_TILE_DOWN2: tile_grid(p); return plan_out(p, true, zgroups, tiles);
-        default: return plan_out(p, false, zgroups, tiles);
-    }
+    FirParams p;
+    if (const int rc = fir_problem("te_upfirdn2d_plan", p, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1))
+        return rc;
+    if (major == 0) return TE_ERR_SHAPE;      // nothing is launched: there is no plan
+    const FirRoute route = fir_route(p);
+    if (route == FIR_BLUR44) blur44_grid(p);
+    else if (route != FIR_DIRECT) tile_grid(p);
+    return plan_out(p, route != FIR_DIRECT, zgroups, tiles);
+}
+
+static int blur_bwd_plan(const char* what, int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                         int* zgroups, int* tiles, int min_w, bool nonneg_pads) {
+    if (!zgroups || !tiles) return TE_ERR_NULL;
+    FirParams p;
+    if (const int rc = blur_bwd_problem(what, p, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, min_w, nonneg_pads)) return rc;
+    if (major == 0) return TE_ERR_SHAPE;      // nothing is launched: there is no plan
+    blur_bwd_grid(p);
+    return plan_out(p, true, zgroups, tiles);
 }
 
 extern "C" int te_blur_actgrad_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                     int* zgroups, int* tiles) {
-    if (!zgroups || !tiles) return TE_ERR_NULL;
-    if (major <= 0 || in_h <= 0 || in_w <= 0 || kh != 4 || kw != 4 || pad_x0 < 0 || pad_x1 < 0 || pad_y0 < 0 || pad_y1 < 0) return TE_ERR_SHAPE;
-    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
-    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
-    if (actgrad_blur44(p)) blur44_grid(p);
-    else tile_grid(p);
-    return plan_out(p, true, zgroups, tiles);
+    return blur_bwd_plan("te_blur_actgrad_plan", major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, zgroups, tiles, 1, true);
 }
 
 extern "C" int te_blur_gradact_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                     int* zgroups, int* tiles) {
-    if (!zgroups || !tiles) return TE_ERR_NULL;
-    if (major <= 0 || in_h <= 0 || in_w < 4 || kh != 4 || kw != 4) return TE_ERR_SHAPE;
-    FirParams p = blur_bwd_geometry(major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1);
-    if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
-    blur44_grid(p);
-    return plan_out(p, true, zgroups, tiles);
+    return blur_bwd_plan("te_blur_gradact_plan", major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, zgroups, tiles, 4, false);
 }
 
 extern "C" int64_t te_upfirdn2d_direct_cover(int64_t outputs) {

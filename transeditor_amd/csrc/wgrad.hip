@@ -490,16 +490,21 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
 // block tile: 8 waves (128 x 64 channels) by default; narrow layers (both channel counts <= 64, the 512 / 1024 px
 // generator tail) use the 4-wave 64 x 64 tile so half of the plain-operand rows are not zero padding
 
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline int pow2ceil(int v) { return 1 << ilog2(v); }
+using te::ilog2; using te::pow2ceil;
 inline unsigned magic(unsigned d) { return (unsigned)(((1ull << 32) + d - 1) / d); }   // exact floor(e/d) for e < 2^16, d < 2^16
+
+// cell tile of a stage, TW x TH <= ncell cells: the launch, the chunk planners and te_wgrad_pair_form all take it from here.  (A k-step
+// multiplies two horizontally adjacent cells: 1-pixel-wide images get a second, masked column.)
+struct CellTile { int TW, TH; };
+inline CellTile cell_tile(int ncell, int H, int W) {
+    const int TW = std::max(2, std::min(32, pow2ceil(W)));
+    return {TW, std::max(1, std::min(pow2ceil(H), ncell / TW))};
+}
 
 template <int KIND>
 bool fill_geometry(WgArgs& a) {
-    constexpr int NCELL = WK<KIND>::NCELL;
-    a.TW = std::max(2, std::min(32, pow2ceil(a.W)));      // a k-step multiplies two horizontally adjacent cells: 1-pixel-wide
-                                                          // images get a second, masked column
-    a.TH = std::max(1, std::min(pow2ceil(a.H), NCELL / a.TW));
+    const CellTile t = cell_tile(WK<KIND>::NCELL, a.H, a.W);
+    a.TW = t.TW; a.TH = t.TH;
     a.NC = a.TH * a.TW;                            // cells per stage (<= NCELL)
     a.lgTW = ilog2(a.TW);
     a.lgNC = ilog2(a.NC);
@@ -556,11 +561,9 @@ int launch_wgrad(WgArgs a, hipStream_t s) {
     return 0;
 }
 
-inline int n_cell_tiles(int kind, int H, int W) {
-    const int ncell = (kind == TE_CONV_T2) ? 32 : 64;
-    const int TW = std::max(2, std::min(32, pow2ceil(W)));
-    const int TH = std::max(1, std::min(pow2ceil(H), ncell / TW));
-    return ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+inline int n_cell_tiles(int kind, int H, int W) {      // (a kind without a kernel counts like the 3x3 one)
+    const CellTile t = cell_tile(kind == TE_CONV_T2 ? WK<TE_CONV_T2>::NCELL : (kind == TE_CONV_1X1 ? WK<TE_CONV_1X1>::NCELL : WK<TE_CONV_3X3>::NCELL), H, W);
+    return ((W + t.TW - 1) / t.TW) * ((H + t.TH - 1) / t.TH);
 }
 
 // ------------------------------------------------------------------------------------------------ reduce
@@ -892,30 +895,35 @@ inline int reduce_w_nchunk(int B, int S, int64_t E, bool vec) {
 
 PROF_READBACK(wgrad)
 
-extern "C" int te_wgrad_split_bf16(int on);
-extern "C" int te_wgrad_split_supported(int kind, int Co, int Ci, int H, int W);
+// What the chunk planners know of a launch.  per_sample is an ESTIMATE of its blocks per sample, cdiv(Co Ci, block tile), and not the grid's
+// cdiv(Co, .) * cdiv(Ci, .), which is larger for channel tails: the number fixes S and so the summation order, it stays.  Which kernel runs
+// is te_wgrad6_form's decision (csrc/wgrad6.hip: what the launch dispatches on), asked for per-sample slabs - a group is only formed where
+// its NB samples stay inside the same 32-bit offset limit.  rounds = blocks per CU the split aims at: the 8-wave 3x3 / T2 blocks own a CU
+// (two 68 KB operand images), so ONE round of them does the same work as two with half the slab bytes for the reducer (same-box A/B, round 3:
+// +0.8 % / +1.2 % on the kernels, half the te_wgrad_reduce traffic of the narrow layers); the light 1x1 blocks share a CU and want two.
+struct BlockEstimate { int64_t per_sample; int samples_per_block, rounds; };
+static BlockEstimate block_estimate(int kind, int B, int Co, int Ci, int H, int W) {
+    const int form = te_wgrad6_form(kind, B, Co, Ci, H, W, 1);
+    return {form == TE_WG6_1X1 ? (int64_t)(Co / 128) * (Ci / 128)                          // wgrad6p_kernel: 128 x 128 channel blocks
+                               : te::cdiv((int64_t)Co * Ci, (pick_nwp(Co, Ci) * 32) * QCH),
+            form == TE_WG6_3X3_PAIR ? 2 : 1,                                               // one block per PAIR of samples and chunk (Co == Ci == 32)
+            kind == TE_CONV_1X1 ? 2 : 1};
+}
+// chunks per slab so that `slabs` slabs of at most `tiles` cell tiles give every CU its rounds of blocks
+static int split_chunks(const BlockEstimate& e, int64_t slabs, int64_t tiles) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(te::cdiv((int64_t)e.rounds * te::kNumCU, e.per_sample * slabs), tiles));
+}
 
 extern "C" int te_wgrad_pair_form(int kind, int Co, int Ci, int H, int W) {
     if (kind != TE_CONV_3X3 || Co <= 0 || Ci <= 0 || H <= 0 || W <= 0) return 0;
-    const int TW = std::max(2, std::min(32, pow2ceil(W))), TH = std::max(1, std::min(pow2ceil(H), 64 / TW));
-    return pair_form_3x3(Co, Ci, TH * TW) ? 1 : 0;
+    const CellTile t = cell_tile(WK<TE_CONV_3X3>::NCELL, H, W);
+    return pair_form_3x3(Co, Ci, t.TH * t.TW) ? 1 : 0;
 }
 
 extern "C" int te_wgrad_slab_count(int kind, int B, int Co, int Ci, int H, int W) {
     if (B <= 0 || Co <= 0 || Ci <= 0 || H <= 0 || W <= 0) return TE_ERR_SHAPE;
-    const int tiles = n_cell_tiles(kind, H, W);
-    int64_t mn = te::cdiv((int64_t)Co * Ci, (pick_nwp(Co, Ci) * 32) * QCH) * (int64_t)B;
-    // the sample-pair form of csrc/wgrad6.hip (Co == Ci == 32) runs one block per PAIR of samples and chunk
-    if (te_wgrad_split_bf16(-1) == 1 && te_wgrad_split_supported(kind, Co, Ci, H, W) == 2 && B % 2 == 0) mn = B / 2;
-    // the split 1x1 kernel (wgrad6p_kernel, round 6) has 128 x 128 channel blocks
-    if (kind == TE_CONV_1X1 && te_wgrad_split_bf16(-1) == 1 && te_wgrad_split_supported(kind, Co, Ci, H, W) == 1) mn = (int64_t)(Co / 128) * (Ci / 128) * B;
-    // blocks per CU the split aims at: the 8-wave 3x3 / T2 blocks own a CU (two 68 KB operand images), so ONE round of them
-    // does the same work as two with half the slab bytes for the reducer (same-box A/B, round 3: +0.8 % / +1.2 % on the
-    // kernels, half the te_wgrad_reduce traffic of the narrow layers); the light 1x1 blocks share a CU and want two
-    const int rounds = (kind == TE_CONV_1X1) ? 2 : 1;
-    int64_t S = te::cdiv((int64_t)rounds * te::kNumCU, mn);
-    S = std::max<int64_t>(1, std::min<int64_t>(S, tiles));
-    return (int)S;
+    const BlockEstimate e = block_estimate(kind, B, Co, Ci, H, W);
+    return split_chunks(e, B / e.samples_per_block, n_cell_tiles(kind, H, W));
 }
 
 // Plan of the GROUPED form (te_wgrad_group_f32): *NB samples share a slab, *S chunks per group.  Grouping pays where the slabs
@@ -925,21 +933,16 @@ extern "C" int te_wgrad_slab_count(int kind, int B, int Co, int Ci, int H, int W
 // NB = the largest divisor of B that still leaves every CU a block; 1 when a sample alone already splits into chunks.
 extern "C" int te_wgrad_group_plan(int kind, int B, int Co, int Ci, int H, int W, int* NB_out, int* S_out) {
     if (B <= 0 || Co <= 0 || Ci <= 0 || H <= 0 || W <= 0 || !NB_out || !S_out) return TE_ERR_SHAPE;
-    const int tiles = n_cell_tiles(kind, H, W);
-    int64_t mn1 = te::cdiv((int64_t)Co * Ci, (pick_nwp(Co, Ci) * 32) * QCH);
-    if (kind == TE_CONV_1X1 && te_wgrad_split_bf16(-1) == 1 && te_wgrad_split_supported(kind, Co, Ci, H, W) == 1) mn1 = (int64_t)(Co / 128) * (Ci / 128);
+    const BlockEstimate e = block_estimate(kind, B, Co, Ci, H, W);      // (the sample-pair form keeps per-sample slabs: it is not grouped)
     const int64_t per_sample = std::max<int64_t>((int64_t)Co * (kind == TE_CONV_T2 ? (2 * H + 1) * (2 * W + 1) : H * W), (int64_t)Ci * H * W) * 4;
     int NB = 1;
     // whole channel blocks only: the 16-byte staging path masks a channel tail through the END of the sample's buffer range, and
     // a group's range continues into the next sample
     if (te_wgrad_slab_count(kind, B, Co, Ci, H, W) == 1 && Co % 128 == 0 && Ci % 128 == 0) {
         for (int d = 2; d <= B; ++d)
-            if (B % d == 0 && (B / d) * mn1 >= te::kNumCU && (int64_t)d * per_sample < (int64_t)OOB) NB = d;
+            if (B % d == 0 && (B / d) * e.per_sample >= te::kNumCU && (int64_t)d * per_sample < (int64_t)OOB) NB = d;
     }
-    const int64_t mn = mn1 * (B / NB);
-    int64_t S = te::cdiv((int64_t)((kind == TE_CONV_1X1) ? 2 : 1) * te::kNumCU, mn);
-    S = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)tiles * NB));
-    *NB_out = NB; *S_out = (int)S;
+    *NB_out = NB; *S_out = split_chunks(e, B / NB, (int64_t)n_cell_tiles(kind, H, W) * NB);
     return 0;
 }
 
