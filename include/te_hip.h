@@ -933,8 +933,8 @@ int te_lpips_allpairs_dist_f32(float* D, const float* const* partial, const int*
  * AdaptiveAvgPool2d((112, 112)); pSp/scripts/calc_id_loss_parallel.py:58-67 takes the paired dot products).  The second convolution of
  * a unit (3x3, stride 1 or 2, its batch norm folded in) and the 1x1 stride-s shortcut convolution are M4's te_conv2d_f32 with act 0,
  * the squeeze is M2's te_adaptive_avgpool_f32 with OH = OW = 1, and output_layer (BatchNorm2d, Dropout in eval mode, Flatten, Linear,
- * BatchNorm1d, folded exactly by the caller) is M2's te_fc_stream_f32 with act 0; here what is left (csrc/irse.hip).  Forward only
- * (IDLoss.forward as a loss and every backward pass are not provided), NCHW fp32, no atomics, no workspace, bit-reproducible; an
+ * BatchNorm1d, folded exactly by the caller) is M2's te_fc_stream_f32 with act 0; here what is left (csrc/irse.hip).  The forward
+ * pass (the backward pass with respect to the image, for IDLoss.forward as a loss, is M9b), NCHW fp32, no atomics, no workspace, bit-reproducible; an
  * image's result is bitwise independent of the batch it is in.  Nothing is launched on a refusal.
  *
  * te_conv2d_prelu_f32 (helpers.py:86-90, :108-112: BatchNorm2d(in_channel), Conv2d(in_channel, depth, 3, 1, 1, bias=False), PReLU(depth);
@@ -996,6 +996,71 @@ int te_se_scale_add_f32(float* out, const float* res, const float* gate, const f
                         te_stream_t stream);
 int te_rows_unit_f32(float* out, const float* a, int64_t I, int D, te_stream_t stream);
 int te_rows_dot_f32(float* out, const float* a, const float* b, int64_t I, int D, te_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * M9b  the identity network as a LOSS (pSp/criteria/id_loss.py:23-45 IDLoss.forward, one of the three losses of
+ * pSp/training/coach_new.py): its backward pass with respect to the input image, which the reference leaves to torch autograd.  The
+ * network is frozen: there is no weight gradient and no training-mode batch norm.  Every operator of M9 is linear in its input except
+ * the PReLU, the SE gate and the final normalisation; the Linear backwards is M2's te_fc_stream_f32 on the transposed folded weight.
+ * NCHW fp32, no atomics, bit-reproducible, an image's gradient is bitwise independent of the batch it is in; nothing is launched on a
+ * refusal (csrc/irse_bwd.hip; the two *_keep entry points are csrc/irse.hip's).
+ *
+ * te_conv2d_prelu_keep_f32, te_id_stem_keep_f32 (the forward of a differentiable pass): te_conv2d_prelu_f32 and te_id_stem_fwd_f32 with
+ * one more output, pre [B,Co,Ho,Wo] = t, the value the PReLU is applied to.  With a negative slope a positive output does not tell
+ * the branch, so the backward pass reads it from pre.  out has the bits of the entry point without `_keep`; refusals are the same, and
+ * a NULL pre is TE_ERR_NULL.
+ *
+ * te_conv2d_dgrad_f32 (replaces autograd's conv2d backward w.r.t. the input, with what follows it): the data gradient of te_conv2d_f32 /
+ * te_conv2d_prelu_f32 for x [B,Ci,H,W], w [Co,Ci,kh,kw], stride s, padding (py, px); g [B,Co,Ho,Wo] -> gx [B,Ci,H,W]:
+ *     acc[b,ci,y,x] = sum over (co,ky,kx) with y = s*oy - py + ky, x = s*ox - px + kx of g[b,co,oy,ox] * w[co,ci,ky,kx]
+ *     pre != NULL :  gx = pre[b,ci,y,x] > 0 ? acc : acc * slope[ci]        PReLU' of the layer the gradient enters; torch's rule: 0, -0
+ *                                                                           and NaN take the slope.  in_scale and add must be NULL
+ *     pre == NULL :  gx = in_scale[ci] * acc + a                           each term optional (one fma where both are given);
+ *                    a = add[b, ci, y / add_s, x / add_s] where add_s divides y and x, else 0:  add [B,Ci,(H-1)/add_s+1,(W-1)/add_s+1].
+ *                    add_s = 2 is the adjoint of MaxPool2d(1, 2) (te_se_scale_add_f32's shortcut), add_s = 1 a plain tensor (the
+ *                    convolution shortcut's gradient); in_scale is the leading batch norm's gradient (its shift and the zero padding
+ *                    drop out)
+ * The weight arrives as the adjoint GEMM reads it, made once by the caller.  Per axis and output parity r < s the taps that reach
+ * rows y = s*yy + r are k = k0 + s*j, k0 = (r + p) % s, j < n = ceil((k_size - k0) / s).  wt holds, for (ry, rx) = (0,0), (0,1), (1,0), (1,1)
+ * (s = 1: the one phase), a block [Ci, Co, ny, nx] with the taps flipped: wt[ci,co,jy,jx] = w[co, ci, k0y + s*(ny-1-jy), k0x + s*(nx-1-jx)].
+ * Each phase is a dense stride-1 implicit GEMM over g on te_conv2d_f32's main loop (csrc/conv2d_body.h, the k order of the forward
+ * family) with K = Co*ny*nx, stored with a pitch of s; a 3x3 stride-2 layer is the sub-kernels 1x1, 1x2, 2x1 and 2x2, none of whose
+ * taps is a zero of the zero-inserted plane; a phase no tap reaches (the odd ones of a 1x1 stride-2 layer) receives the epilogue of 0.
+ * A NaN in g reaches exactly the inputs whose window holds it.  1 <= kh, kw <= 7 and s in {1, 2}, else TE_ERR_UNSUPPORTED (also for
+ * pre together with in_scale or add, and add_s outside {1, 2}); padding >= the kernel, Ho or Wo < 1, non-positive sizes, an image of g or
+ * gx past 31 bits: TE_ERR_SHAPE; a NULL gx, g or wt, or exactly one of pre and slope: TE_ERR_NULL.
+ *
+ * te_se_bwd_f32 (helpers.py:57-73 SEModule backwards): out = r * gate + shortcut, gate = sigmoid(w2 relu(w1 pooled)), pooled = mean(r).
+ *     ggate[b,c] = sum_hw gout * r                                  one wave per plane: a chain per lane, a fixed butterfly
+ *     gh[b,r]    = hidden[b,r] > 0 ? sum_c w2[c,r] * ggate[b,c] * gate[b,c] * (1 - gate[b,c]) : 0      hidden recomputed as te_se_excite_f32
+ *     gmean[b,c] = (sum_r w1[r,c] * gh[b,r]) / (Ho*Wo)              one latency-shaped workgroup per image, r ascending
+ *     gr         = gout * gate[b,c] + gmean[b,c]                    one fma; 16 bytes per thread where Ho*Wo % 4 == 0 and aligned
+ * gout, r, gr [B,C,Ho,Wo]; gate, pooled [B,C]; w1 [R,C], w2 [C,R]; ws 2*B*C floats (ggate, gmean).  The shortcut's gradient is gout
+ * itself.  Limits are te_se_excite_f32's, a plane below 2^31 and 2^40 elements, else TE_ERR_SHAPE.
+ *
+ * te_id_stem_bwd_f32 (the adjoint of te_id_stem_fwd_f32): g [N,Co,Pn,Pn], pre the stem's kept pre-activation, wt the stem weight
+ * [Co,3,3,3] in te_conv2d_dgrad_f32's layout ([3, Co*9], flipped); gimg [N,3,H,W]; ws N*3*Pn*Pn floats.  g * PReLU'(pre) (in the gather)
+ * goes through the data gradient of the 3x3 convolution to the pooled plane in ws; then AdaptiveAvgPool2d and the crop backwards as a
+ * GATHER: an image pixel inside the window sums the pooled windows [floor(i L / Pn), ceil((i + 1) L / Pn)) that contain it (at most
+ * 2 x 2 where L >= Pn), each divided by its count, rows then columns ascending; a pixel outside the window is exactly 0.  Refusals
+ * are te_id_stem_fwd_f32's.
+ *
+ * te_rows_unit_bwd_f32 (helpers.py:16-19 l2_norm backwards): e = a / norm; ga[i,:] = (ge[i,:] - e[i,:] * <e[i,:], ge[i,:]>) / norm_i, the
+ * dot product and the norm's square in fp64 in te_rows_dot_f32's shape, each rounded to fp32 once.  Limits are te_rows_unit_f32's.
+ */
+int te_conv2d_prelu_keep_f32(float* out, float* pre, const float* x, const float* w, const float* bias, const float* slope,
+                             const float* in_scale, const float* in_shift, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py,
+                             int px, te_stream_t stream);
+int te_id_stem_keep_f32(float* out, float* pre, const float* img, const float* w, const float* b, const float* slope, int N, int H, int W,
+                        int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream);
+int te_conv2d_dgrad_f32(float* gx, const float* g, const float* wt, const float* pre, const float* slope, const float* in_scale,
+                        const float* add, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int add_s,
+                        te_stream_t stream);
+int te_se_bwd_f32(float* gr, float* ws, const float* gout, const float* r, const float* gate, const float* pooled, const float* w1,
+                  const float* w2, int B, int C, int R, int Ho, int Wo, te_stream_t stream);
+int te_id_stem_bwd_f32(float* gimg, float* ws, const float* g, const float* wt, const float* pre, const float* slope, int N, int H, int W,
+                       int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream);
+int te_rows_unit_bwd_f32(float* ga, const float* ge, const float* e, const float* a, int64_t I, int D, te_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * M10  the dual-space pSp encoder of real-image inversion (pSp/models/encoders/psp_encoders_new.py:35-140

@@ -1285,21 +1285,40 @@ def lpips_allpairs_dist(partials, shapes, N):
 
 
 # --------------------------------------------------------------------------------------------- M9 ArcFace IR-SE50 identity network
+def _conv2d_prelu(who, keep, x, w, bias, slope, in_scale, in_shift, stride, pad):
+    if x.ndim != 4 or w.ndim != 4 or x.shape[1] != w.shape[1] or bias.shape != (w.shape[0],) or slope.shape != (w.shape[0],) \
+            or any(t is not None and t.shape != (x.shape[1],) for t in (in_scale, in_shift)):
+        raise RuntimeError(f'te_hip: {who}: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, '
+                           f'slope {tuple(slope.shape)}, affine {[None if t is None else tuple(t.shape) for t in (in_scale, in_shift)]}')
+    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
+    pre = [torch.empty_like(out)] if keep else []
+    _launch(f'te_{who}_f32', _ptr(out), *map(_ptr, pre), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), B, Ci, Co, H, W,
+            kh, kw, stride, pad[0], pad[1])
+    return (out, *pre) if keep else out
+
+
 @_op
 def conv2d_prelu(x, w, bias, slope, in_scale=None, in_shift=None, stride=1, pad=(0, 0)):
     """prelu(conv2d(v, w, stride, pad) + bias, slope) with v = in_scale[c] * x + in_shift[c] inside the image and 0 in the padding (both
     None: v = x): x [B,Ci,H,W], w [Co,Ci,kh,kw], bias, slope [Co], in_scale, in_shift [Ci] -> a new [B,Co,Ho,Wo] tensor.  The ABI
     refuses what te_conv2d_f32 refuses and an affine given by half; nothing is launched then."""
-    if x.ndim != 4 or w.ndim != 4 or x.shape[1] != w.shape[1] or bias.shape != (w.shape[0],) or slope.shape != (w.shape[0],) \
-            or any(t is not None and t.shape != (x.shape[1],) for t in (in_scale, in_shift)):
-        raise RuntimeError(f'te_hip: conv2d_prelu: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, '
-                           f'slope {tuple(slope.shape)}, affine {[None if t is None else tuple(t.shape) for t in (in_scale, in_shift)]}')
-    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
-    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
-    out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
-    _launch('te_conv2d_prelu_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), B, Ci, Co, H, W,
-            kh, kw, stride, pad[0], pad[1])
-    return out
+    return _conv2d_prelu('conv2d_prelu', False, x, w, bias, slope, in_scale, in_shift, stride, pad)
+
+
+def _id_stem(who, keep, img, w, b, slope, box, pool):
+    if img.ndim != 4 or img.shape[1] != 3 or w.ndim != 4 or tuple(w.shape[1:]) != (3, 3, 3) or b.shape != (w.shape[0],) \
+            or slope.shape != (w.shape[0],):
+        raise RuntimeError(f'te_hip: {who}: inconsistent shapes img {tuple(img.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}, '
+                           f'slope {tuple(slope.shape)}')
+    img = img.contiguous()
+    (N, _, H, W), Co = img.shape, w.shape[0]
+    y0, y1, x0, x1 = box
+    out = torch.empty(N, Co, max(pool, 0), max(pool, 0), device=img.device, dtype=img.dtype)
+    pre = [torch.empty_like(out)] if keep else []
+    _launch(f'te_{who}_f32', _ptr(out), *map(_ptr, pre), _ptr(img), _ptr(w), _ptr(b), _ptr(slope), N, H, W, y0, y1, x0, x1, pool, Co)
+    return (out, *pre) if keep else out
 
 
 @_op
@@ -1307,16 +1326,7 @@ def id_stem_fwd(img, w, b, slope, box, pool):
     """the window box = (y0, y1, x0, x1) of img [N,3,H,W] -> adaptive average to pool x pool -> 3x3 pad-1 convolution -> bias -> PReLU:
     w [Co,3,3,3], b, slope [Co] -> [N,Co,pool,pool].  The ABI refuses an empty window and one outside the image; nothing is launched
     then."""
-    if img.ndim != 4 or img.shape[1] != 3 or w.ndim != 4 or tuple(w.shape[1:]) != (3, 3, 3) or b.shape != (w.shape[0],) \
-            or slope.shape != (w.shape[0],):
-        raise RuntimeError(f'te_hip: id_stem_fwd: inconsistent shapes img {tuple(img.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}, '
-                           f'slope {tuple(slope.shape)}')
-    img = img.contiguous()
-    (N, _, H, W), Co = img.shape, w.shape[0]
-    y0, y1, x0, x1 = box
-    out = torch.empty(N, Co, max(pool, 0), max(pool, 0), device=img.device, dtype=img.dtype)
-    _launch('te_id_stem_fwd_f32', _ptr(out), _ptr(img), _ptr(w), _ptr(b), _ptr(slope), N, H, W, y0, y1, x0, x1, pool, Co)
-    return out
+    return _id_stem('id_stem_fwd', False, img, w, b, slope, box, pool)
 
 
 @_op
@@ -1361,6 +1371,104 @@ def rows_dot(a, b):
     out = torch.empty(a.shape[0], device=a.device, dtype=a.dtype)
     _launch('te_rows_dot_f32', _ptr(out), _ptr(a), _ptr(b), a.shape[0], a.shape[1])
     return out
+
+
+# --------------------------------------------------------------------------------------------- M9b the identity network's backward pass
+@_op
+def conv2d_prelu_keep(x, w, bias, slope, in_scale=None, in_shift=None, stride=1, pad=(0, 0)):
+    """conv2d_prelu that also returns the pre-activation: -> (out, pre), out bitwise conv2d_prelu's, out = prelu(pre, slope)"""
+    return _conv2d_prelu('conv2d_prelu_keep', True, x, w, bias, slope, in_scale, in_shift, stride, pad)
+
+
+@_op
+def id_stem_keep(img, w, b, slope, box, pool):
+    """id_stem_fwd that also returns the pre-activation: -> (out, pre)"""
+    return _id_stem('id_stem_keep', True, img, w, b, slope, box, pool)
+
+
+def dgrad_phases(k, stride, pad):
+    """per output parity r < stride of one axis: (k0, n), the taps k0, k0 + stride, ... (n of them) of a kernel of size k that reach the
+    rows y = stride * yy + r of the data gradient (y = stride * oy - pad + tap)"""
+    out = []
+    for r in range(stride):
+        k0 = (r + pad) % stride
+        out.append((k0, (k - k0 + stride - 1) // stride if k0 < k else 0))
+    return out
+
+
+def dgrad_weight(w, stride=1, pad=(0, 0)):
+    """w [Co,Ci,kh,kw] -> the flat weight conv2d_dgrad reads (made once per layer: the network is frozen): for each output phase
+    (ry, rx), ry-major, the block [Ci, Co, ny, nx] of the taps that reach it, flipped (te_hip.h, te_conv2d_dgrad_f32).  Stride 1 is the
+    one block [Ci, Co*kh*kw].  Plain torch: runs on whatever device w is on."""
+    blocks = []
+    for k0y, ny in dgrad_phases(w.shape[2], stride, pad[0]):
+        for k0x, nx in dgrad_phases(w.shape[3], stride, pad[1]):
+            sub = w[:, :, k0y::stride, k0x::stride]
+            assert tuple(sub.shape[2:]) == (ny, nx)
+            blocks.append(sub.flip(2, 3).transpose(0, 1).reshape(-1))
+    return torch.cat(blocks).contiguous()
+
+
+@_op
+def conv2d_dgrad(g, wt, x_shape, kernel, stride=1, pad=(0, 0), pre=None, slope=None, in_scale=None, add=None, add_stride=1):
+    """the data gradient of conv2d / conv2d_prelu: g [B,Co,Ho,Wo], wt = dgrad_weight(w, stride, pad), x_shape = (B, Ci, H, W) of the
+    forward's input, kernel = (kh, kw) -> gx [B,Ci,H,W].  pre [B,Ci,H,W] with slope [Ci]: gx = acc * PReLU'(pre).  Else
+    gx = in_scale[ci] * acc + add[:, :, y / add_stride, x / add_stride] (where add_stride divides y and x), each term optional."""
+    B, Ci, H, W = x_shape
+    kh, kw = kernel
+    if g.ndim != 4 or g.shape[0] != B or wt.ndim != 1 or (pre is not None and tuple(pre.shape) != (B, Ci, H, W)) \
+            or any(t is not None and tuple(t.shape) != (Ci,) for t in (slope, in_scale)) \
+            or tuple(g.shape[2:]) != conv2d_out_hw(H, W, kh, kw, stride, pad) \
+            or wt.numel() != Ci * g.shape[1] * sum(a[1] for a in dgrad_phases(kh, stride, pad[0])) * sum(a[1] for a in dgrad_phases(kw, stride, pad[1])) \
+            or (add is not None and tuple(add.shape) != (B, Ci, (H - 1) // max(add_stride, 1) + 1, (W - 1) // max(add_stride, 1) + 1)):
+        raise RuntimeError(f'te_hip: conv2d_dgrad: inconsistent shapes g {tuple(g.shape)}, wt {tuple(wt.shape)}, x {tuple(x_shape)}, a {kh} x {kw} '
+                           f'kernel, stride {stride}, pad {tuple(pad)}, pre {None if pre is None else tuple(pre.shape)}, add '
+                           f'{None if add is None else tuple(add.shape)} read with stride {add_stride}')
+    gx = torch.empty(B, Ci, H, W, device=g.device, dtype=g.dtype)
+    _launch('te_conv2d_dgrad_f32', _ptr(gx), _ptr(g), _ptr(wt), _ptr(pre), _ptr(slope), _ptr(in_scale), _ptr(add), B, Ci, g.shape[1], H, W,
+            kh, kw, stride, pad[0], pad[1], add_stride)
+    return gx
+
+
+@_op
+def se_bwd(gout, r, gate, pooled, w1, w2):
+    """the gradient of r in out = r * gate + shortcut with gate = se_excite(pooled, w1, w2), pooled = the plane means of r:
+    gout, r [B,C,Ho,Wo], gate, pooled [B,C], w1 [R,C], w2 [C,R] -> gr [B,C,Ho,Wo]"""
+    if gout.ndim != 4 or gout.shape != r.shape or tuple(gate.shape) != tuple(gout.shape[:2]) or gate.shape != pooled.shape or w1.ndim != 2 \
+            or w1.shape[1] != gate.shape[1] or tuple(w2.shape) != (w1.shape[1], w1.shape[0]):
+        raise RuntimeError(f'te_hip: se_bwd: inconsistent shapes gout {tuple(gout.shape)}, r {tuple(r.shape)}, gate {tuple(gate.shape)}, pooled '
+                           f'{tuple(pooled.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}')
+    B, Cn, Ho, Wo = gout.shape
+    gr = torch.empty_like(gout)
+    ws = torch.empty(2 * B * Cn, device=gout.device, dtype=gout.dtype)
+    _launch('te_se_bwd_f32', _ptr(gr), _ptr(ws), _ptr(gout), _ptr(r), _ptr(gate), _ptr(pooled), _ptr(w1), _ptr(w2), B, Cn, w1.shape[0], Ho, Wo)
+    return gr
+
+
+@_op
+def id_stem_bwd(g, wt, pre, slope, img_shape, box, pool):
+    """the adjoint of id_stem_fwd: g, pre [N,Co,pool,pool], wt = dgrad_weight(the stem weight, 1, (1, 1)), slope [Co], img_shape = (N, 3, H, W)
+    -> the image's gradient [N,3,H,W], exactly 0 outside the box"""
+    N, _, H, W = img_shape
+    if g.ndim != 4 or g.shape != pre.shape or g.shape[0] != N or tuple(g.shape[2:]) != (pool, pool) or slope.shape != (g.shape[1],) \
+            or wt.shape != (27 * g.shape[1],) or img_shape[1] != 3:
+        raise RuntimeError(f'te_hip: id_stem_bwd: inconsistent shapes g {tuple(g.shape)}, pre {tuple(pre.shape)}, wt {tuple(wt.shape)}, slope '
+                           f'{tuple(slope.shape)}, image {tuple(img_shape)}, pool {pool}')
+    y0, y1, x0, x1 = box
+    gimg = torch.empty(N, 3, H, W, device=g.device, dtype=g.dtype)
+    ws = torch.empty(N * 3 * pool * pool, device=g.device, dtype=g.dtype)
+    _launch('te_id_stem_bwd_f32', _ptr(gimg), _ptr(ws), _ptr(g), _ptr(wt), _ptr(pre), _ptr(slope), N, H, W, y0, y1, x0, x1, pool, g.shape[1])
+    return gimg
+
+
+@_op
+def rows_unit_bwd(ge, e, a):
+    """l2_norm backwards: e = rows_unit(a), ge the gradient of e -> the gradient of a, (ge - e <e, ge>) / ||a||, per row of [I,D]"""
+    if a.ndim != 2 or tuple(ge.shape) != tuple(a.shape) or tuple(e.shape) != tuple(a.shape):
+        raise RuntimeError(f'te_hip: rows_unit_bwd expects three [I,D] tensors of one shape, got {tuple(ge.shape)}, {tuple(e.shape)}, {tuple(a.shape)}')
+    ga = torch.empty_like(a)
+    _launch('te_rows_unit_bwd_f32', _ptr(ga), _ptr(ge), _ptr(e), _ptr(a), a.shape[0], a.shape[1])
+    return ga
 
 
 # --------------------------------------------------------------------------------------------- M10 dual-space pSp encoder

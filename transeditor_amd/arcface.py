@@ -25,19 +25,30 @@ and te_se_excite_f32 (the gates), the shortcut (the unit's input read with the s
 and te_se_scale_add_f32 (res * gate + shortcut).  output_layer is folded exactly on the host in fp64 (BatchNorm2d into the columns of
 the Linear - there is no padding there -, BatchNorm1d into its rows and bias; Dropout is the identity in eval mode) and runs as
 te_fc_stream_f32; te_rows_unit_f32 normalises.  Every convolution is the exact-fp32 implicit GEMM of csrc/conv2d_body.h.  An image's
-embedding is bitwise the same whatever batch it is in.  Eval only: there is no backward pass, so IDLoss.forward as a training loss is
-not provided.  The unit parse and the unit forward live in irse_units.py, which the inversion encoder (psp_encoder.py) runs too.
-Measured deviations and times: profiles/README.md, 'Identity embedding'.
+embedding is bitwise the same whatever batch it is in.  The unit parse and the unit forward live in irse_units.py, which the inversion
+encoder (psp_encoder.py) runs too.  Measured deviations and times: profiles/README.md, 'Identity embedding'.
+
+    e = net.embed_grad(images)                                      # the same bits, and a gradient for `images`
+
+The network is frozen (eval-mode batch norms, no weight gradient), but it has a backward pass with respect to its input: embed_grad is
+the same chain as one once-differentiable autograd.Function (_Embed, written as lpips._Distance is) on the kernels of csrc/irse_bwd.hip:
+te_rows_unit_bwd_f32, te_fc_stream_f32 on the transposed folded weight, irse_units.unit_backward per unit (te_se_bwd_f32 and
+te_conv2d_dgrad_f32, a stride-2 layer in its four output phases) and te_id_stem_bwd_f32.  The forward keeps per unit the first
+convolution's pre-activation and, for the gate, the residual branch, the gates and the pooled vector; nothing else.  id_loss.IDLoss
+is the reference's training loss on it.  Times: profiles/README.md, 'Identity loss'.
 """
 import argparse
 import json
 import sys
 
 import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .frozen_net import check_images, no_gpu, resolve, weight_bias
-from .irse_units import BN_EPS, bn_affine, check_unit_list, parse_stem, parse_units, reader, register_units, unit_forward
+from .irse_units import (BN_EPS, bn_affine, check_unit_list, parse_stem, parse_units, reader, register_units, unit_backward, unit_forward,
+                         unit_forward_keep)
 
 BOX = (35, 223, 32, 220)                                              # id_loss.py:18: rows 35:223, columns 32:220
 POOL = 112                                                            # id_loss.py:14
@@ -96,6 +107,37 @@ def parse_state_dict(sd, path='state_dict', units=None, pool=POOL, dtype=torch.f
     return dict(stem=stem, units=parsed, fc=fc, keys=read, affine=has[0], side=h)
 
 
+class _Embed(Function):
+    """e = ArcFaceID.embed(images), bit for bit; backward -> the gradient w.r.t. images (the network is frozen)"""
+
+    @staticmethod
+    def forward(ctx, images, net):
+        a, stem_pre = _lib.id_stem_keep(images, net.stem_w, net.stem_b, net.stem_slope, net.box, net.pool)
+        kept = []
+        for i in range(len(net.units)):
+            a, k = unit_forward_keep(net, i, a)
+            kept.append(k)
+        f = _lib.fc_stream(a.view(a.shape[0], -1), net.fc_w, net.fc_b, act=0)
+        e = _lib.rows_unit(f)
+        ctx.net, ctx.kept, ctx.stem_pre, ctx.rows, ctx.shapes = net, kept, stem_pre, (e, f), (tuple(images.shape), tuple(a.shape))
+        return e
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ge):
+        net, kept = ctx.net, ctx.kept
+        image_shape, feature_shape = ctx.shapes
+        stem_wt, fc_wt, fc_zero = net._backward_weights()
+        g = _lib.rows_unit_bwd(ge.contiguous(), *ctx.rows)
+        g = _lib.fc_stream(g, fc_wt, fc_zero, act=0).view(feature_shape)          # the Linear backwards: the transposed folded weight
+        for i in range(len(net.units) - 1, -1, -1):
+            g = unit_backward(net, i, kept[i], g)
+            kept[i] = None
+        gimg = _lib.id_stem_bwd(g, stem_wt, ctx.stem_pre, net.stem_slope, image_shape, net.box, net.pool)
+        ctx.kept = ctx.stem_pre = ctx.rows = None
+        return gimg, None
+
+
 class ArcFaceID(torch.nn.Module):
     def __init__(self, path=None, state_dict=None, box=BOX, pool=POOL, units=None):
         super().__init__()
@@ -133,6 +175,25 @@ class ArcFaceID(torch.nn.Module):
         return _lib.rows_unit(_lib.fc_stream(a.view(a.shape[0], -1), self.fc_w, self.fc_b, act=0))
 
     forward = embed
+
+    def _backward_weights(self):
+        """(made once per device: the weights never change) the stem weight in _lib.conv2d_dgrad's layout, the transposed folded Linear
+        [C * h * h, D] and its zero bias"""
+        cache = self.__dict__.setdefault('_bwd_weights', {})
+        if self.fc_w.device not in cache:
+            cache[self.fc_w.device] = (_lib.dgrad_weight(self.stem_w, 1, (1, 1)), self.fc_w.t().contiguous(),
+                                       torch.zeros(self.fc_w.shape[1], device=self.fc_w.device))
+        return cache[self.fc_w.device]
+
+    def embed_grad(self, images):
+        """embed with a backward pass: [B,3,S,S] in [-1, 1] -> [B,D] fp32 unit rows, bitwise embed's, differentiable w.r.t. images (once)"""
+        check_images(images, 'ArcFaceID', '[B,3,S,S]', square=True)
+        S = images.shape[2]
+        if self.box[1] > S or self.box[3] > S:
+            raise ValueError(f'ArcFaceID: the box {self.box} does not lie inside a {S} px image')
+        if not images.is_cuda:
+            raise RuntimeError(_NO_GPU)
+        return _Embed.apply(images.float(), self)
 
     @torch.no_grad()
     def similarity(self, a, b):

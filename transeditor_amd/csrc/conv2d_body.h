@@ -3,7 +3,8 @@
 // grouped head convolutions (psp_heads.hip), written once.  Compile-time policies make the variants:
 //     the gather   : where a tap of the patch comes from (GatherPlain: x[b, c, iy, ix] of a dense [B,Ci,H,W] tensor), and
 //     the epilogue : what happens to acc + bias before the store (EpiBiasAct: the activation),
-//     the part     : which range of k the workgroup runs and where the tile goes (PartWhole: all of it, into `out`; psp_heads.hip splits).
+//     the part     : which range of k the workgroup runs and where the tile goes (PartWhole: all of it, into `out`; psp_heads.hip splits;
+//                    irse_bwd.hip stores a phase of a stride-2 data gradient with a pitch of 2: the destination is the part's DestDense or its own).
 // Everything else - the tile shapes, the LDS layout, the order of k inside an output's one fp32 fma chain (the permutation of
 // gemm_nt_f32.h: lane half h feeds k = 8q + 4h + u of every 32-deep step to MFMA (q, u)) - is the same for all of them, so two variants
 // that gather the same values produce the same accumulators bit for bit.  The description of the loop is at the top of conv2d.hip.
@@ -86,9 +87,17 @@ struct EpiBiasAct {
     }
 };
 
+// where pixel r of image b of the tile goes and the pitch between two of its channels: the slice [c0, c0 + Co) of a dense [B,Ctot,Ho,Wo]
+struct DestDense {
+    template <class Args>
+    static __device__ __forceinline__ float* dest(const Args& a, float* out, int64_t b, int r, int HoWo) { return out + (b * a.Ctot + a.c0) * HoWo + r; }
+    template <class Args>
+    static __device__ __forceinline__ int pitch(const Args& a, int HoWo) { return HoWo; }
+};
+
 // the part of the k chain a workgroup runs and where its tile goes: the whole chain, bias added, into `out`.  A split launch (psp_heads.hip)
 // names another range of k and another destination; the order of k inside the range is the same
-struct PartWhole {
+struct PartWhole : DestDense {
     template <class Args>
     static __device__ __forceinline__ int k_begin(const Args& a) { return 0; }
     template <class Args>
@@ -206,14 +215,15 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
         if (p >= a.P) continue;
         const int64_t b = p / HoWo;
         const int r = (int)(p - b * HoWo);
-        float* dst = Part::out(a) + (b * a.Ctot + a.c0) * HoWo + r;
+        float* dst = Part::dest(a, Part::out(a), b, r, HoWo);
+        const int cp = Part::pitch(a, HoWo);                 // the epilogue's `HoWo`: the element is dst[m * cp]
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
             if (m < a.Co) {
                 float v = Part::finish(a, acc[i][e], m);
-                v = Epi::apply(a, v, dst, m, HoWo);
-                dst[(int64_t)m * HoWo] = v;
+                v = Epi::apply(a, v, dst, m, cp);
+                dst[(int64_t)m * cp] = v;
             }
         }
     }

@@ -10,8 +10,9 @@
 //
 // Both convolutions are the main loop of conv2d_body.h with other policies.  The batch norm in front of the padded convolution is a
 // GATHER (a tap inside the image is scale[c] * x + shift[c], a tap of the padding is 0: the shift cannot be a bias, the padded taps
-// do not carry it), PReLU is an epilogue; the stem's gather averages the tap's window of the full image on the way into LDS.  Forward
-// only, no atomics, no workspace, every reduction a fixed-order chain or a fixed-shape tree.
+// do not carry it), PReLU is an epilogue; the stem's gather averages the tap's window of the full image on the way into LDS.  The
+// forward pass; te_conv2d_prelu_keep_f32 and te_id_stem_keep_f32 are the same two kernels with an epilogue that also stores the
+// pre-activation, for the backward pass of irse_bwd.hip.  No atomics, no workspace, every reduction a fixed-order chain or a fixed-shape tree.
 #include "te_common.h"
 #include "conv2d_body.h"
 
@@ -24,6 +25,7 @@ struct PreluArgs : ConvArgs {
     const float* in_scale;       // [Ci] or NULL (then in_shift is NULL too)
     const float* in_shift;
     const float* slope;          // [Co]
+    float* pre;                  // the *_keep entry points: where t goes, in the layout of out
 };
 
 struct IdStemArgs : PreluArgs {  // H = W = Pn: the convolution sees the pooled plane
@@ -70,17 +72,33 @@ struct EpiPrelu {
     }
 };
 
-template <int BN, class Gather, class Args>
+// the same, and t itself goes to pre: what the backward pass (irse_bwd.hip) takes the PReLU branch from.  With a negative slope a
+// positive output does not tell the branch, so the differentiable forward keeps t; out has the bits EpiPrelu gives
+struct EpiPreluKeep {
+    template <class Args>
+    static __device__ __forceinline__ float apply(const Args& a, float v, const float* dst, int m, int HoWo) {
+        a.pre[(dst - a.out) + (int64_t)m * HoWo] = v;
+        return v > 0.f ? v : __fmul_rn(a.slope[m], v);
+    }
+};
+
+template <int BN, class Gather, class Epi, class Args>
 void launch_conv(const Args& a, bool al, hipStream_t st) {
     const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (al) conv2d_kernel<BN, true, Gather, EpiPrelu><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false, Gather, EpiPrelu><<<grid, NT, 0, st>>>(a);
+    if (al) conv2d_kernel<BN, true, Gather, Epi><<<grid, NT, 0, st>>>(a);
+    else conv2d_kernel<BN, false, Gather, Epi><<<grid, NT, 0, st>>>(a);
 }
 
+// (a.pre set: the keeping epilogue)
 template <class Gather, class Args>
 void launch_either(const Args& a, bool al, hipStream_t st) {
-    if (wide_grid(a.P, a.Co)) launch_conv<128, Gather>(a, al, st);
-    else launch_conv<64, Gather>(a, al, st);
+    if (a.pre) {
+        if (wide_grid(a.P, a.Co)) launch_conv<128, Gather, EpiPreluKeep>(a, al, st);
+        else launch_conv<64, Gather, EpiPreluKeep>(a, al, st);
+    } else {
+        if (wide_grid(a.P, a.Co)) launch_conv<128, Gather, EpiPrelu>(a, al, st);
+        else launch_conv<64, Gather, EpiPrelu>(a, al, st);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------ squeeze-and-excitation
@@ -195,38 +213,67 @@ __global__ __launch_bounds__(64) void rows_dot_kernel(float* __restrict__ out, c
 
 }  // namespace
 
-extern "C" int te_conv2d_prelu_f32(float* out, const float* x, const float* w, const float* bias, const float* slope, const float* in_scale,
-                                   const float* in_shift, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px,
-                                   te_stream_t stream) {
-    TE_REQUIRE(out && x && w && bias && slope, TE_ERR_NULL, "te_conv2d_prelu_f32: NULL pointer");
-    TE_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), TE_ERR_NULL,
-               "te_conv2d_prelu_f32: in_scale and in_shift must both be given or both be NULL");
+namespace {
+
+// te_conv2d_prelu_f32 (pre == NULL) and te_conv2d_prelu_keep_f32
+int conv2d_prelu(const char* who, float* out, float* pre, const float* x, const float* w, const float* bias, const float* slope,
+                 const float* in_scale, const float* in_shift, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px,
+                 te_stream_t stream) {
+    TE_REQUIRE(out && x && w && bias && slope, TE_ERR_NULL, "%s: NULL pointer", who);
+    TE_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), TE_ERR_NULL, "%s: in_scale and in_shift must both be given or both be NULL", who);
     PreluArgs a;
-    a.out = out; a.x = x; a.w = w; a.bias = bias; a.slope = slope; a.in_scale = in_scale; a.in_shift = in_shift;
-    if (const int rc = fill_args(a, "te_conv2d_prelu_f32", B, Ci, Co, H, W, kh, kw, s, py, px, Co, 0, 0)) return rc;
+    a.out = out; a.x = x; a.w = w; a.bias = bias; a.slope = slope; a.in_scale = in_scale; a.in_shift = in_shift; a.pre = pre;
+    if (const int rc = fill_args(a, who, B, Ci, Co, H, W, kh, kw, s, py, px, Co, 0, 0)) return rc;
     const bool al = a.K % 4 == 0 && te::aligned16(w);
     hipStream_t st = (hipStream_t)stream;
     if (in_scale) launch_either<GatherAffine>(a, al, st);
     else launch_either<GatherPlain>(a, al, st);
-    return te::launch_status("te_conv2d_prelu_f32");
+    return te::launch_status(who);
+}
+
+// te_id_stem_fwd_f32 (pre == NULL) and te_id_stem_keep_f32
+int id_stem(const char* who, float* out, float* pre, const float* img, const float* w, const float* b, const float* slope, int N, int H, int W,
+            int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream) {
+    TE_REQUIRE(out && img && w && b && slope, TE_ERR_NULL, "%s: NULL pointer", who);
+    TE_REQUIRE(N >= 1 && N < 65536 && H >= 1 && W >= 1 && Co >= 1, TE_ERR_SHAPE, "%s: 1 <= N < 65536 and positive H, W, Co (got %d, %d, %d, %d)", who,
+               N, H, W, Co);
+    TE_REQUIRE(y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W, TE_ERR_SHAPE,
+               "%s: the window [%d, %d) x [%d, %d) must be non-empty and inside the %d x %d image", who, y0, y1, x0, x1, H, W);
+    TE_REQUIRE(Pn >= 1 && Pn <= 32768 && y1 - y0 <= 32768 && x1 - x0 <= 32768, TE_ERR_SHAPE,
+               "%s: 1 <= Pn <= 32768 and a window of at most 32768 x 32768 (got Pn = %d, %d x %d)", who, Pn, y1 - y0, x1 - x0);
+    TE_REQUIRE((int64_t)3 * H * W <= 0x7fffffff, TE_ERR_SHAPE, "%s: one image (3 * H * W) must fit 31 bits", who);
+    IdStemArgs a;
+    a.out = out; a.x = img; a.w = w; a.bias = b; a.slope = slope; a.in_scale = nullptr; a.in_shift = nullptr; a.pre = pre;
+    if (const int rc = fill_args(a, who, N, 3, Co, Pn, Pn, 3, 3, 1, 1, 1, Co, 0, 0)) return rc;
+    a.IH = H; a.IW = W; a.y0 = y0; a.x0 = x0; a.Lh = y1 - y0; a.Lw = x1 - x0;
+    launch_either<GatherPooled>(a, false, (hipStream_t)stream);                  // K = 27: the unaligned weight path
+    return te::launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int te_conv2d_prelu_f32(float* out, const float* x, const float* w, const float* bias, const float* slope, const float* in_scale,
+                                   const float* in_shift, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px,
+                                   te_stream_t stream) {
+    return conv2d_prelu("te_conv2d_prelu_f32", out, nullptr, x, w, bias, slope, in_scale, in_shift, B, Ci, Co, H, W, kh, kw, s, py, px, stream);
+}
+
+extern "C" int te_conv2d_prelu_keep_f32(float* out, float* pre, const float* x, const float* w, const float* bias, const float* slope,
+                                        const float* in_scale, const float* in_shift, int B, int Ci, int Co, int H, int W, int kh, int kw, int s,
+                                        int py, int px, te_stream_t stream) {
+    TE_REQUIRE(pre, TE_ERR_NULL, "te_conv2d_prelu_keep_f32: NULL pointer");
+    return conv2d_prelu("te_conv2d_prelu_keep_f32", out, pre, x, w, bias, slope, in_scale, in_shift, B, Ci, Co, H, W, kh, kw, s, py, px, stream);
 }
 
 extern "C" int te_id_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, const float* slope, int N, int H, int W,
                                   int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream) {
-    TE_REQUIRE(out && img && w && b && slope, TE_ERR_NULL, "te_id_stem_fwd_f32: NULL pointer");
-    TE_REQUIRE(N >= 1 && N < 65536 && H >= 1 && W >= 1 && Co >= 1, TE_ERR_SHAPE,
-               "te_id_stem_fwd_f32: 1 <= N < 65536 and positive H, W, Co (got %d, %d, %d, %d)", N, H, W, Co);
-    TE_REQUIRE(y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W, TE_ERR_SHAPE,
-               "te_id_stem_fwd_f32: the window [%d, %d) x [%d, %d) must be non-empty and inside the %d x %d image", y0, y1, x0, x1, H, W);
-    TE_REQUIRE(Pn >= 1 && Pn <= 32768 && y1 - y0 <= 32768 && x1 - x0 <= 32768, TE_ERR_SHAPE,
-               "te_id_stem_fwd_f32: 1 <= Pn <= 32768 and a window of at most 32768 x 32768 (got Pn = %d, %d x %d)", Pn, y1 - y0, x1 - x0);
-    TE_REQUIRE((int64_t)3 * H * W <= 0x7fffffff, TE_ERR_SHAPE, "te_id_stem_fwd_f32: one image (3 * H * W) must fit 31 bits");
-    IdStemArgs a;
-    a.out = out; a.x = img; a.w = w; a.bias = b; a.slope = slope; a.in_scale = nullptr; a.in_shift = nullptr;
-    if (const int rc = fill_args(a, "te_id_stem_fwd_f32", N, 3, Co, Pn, Pn, 3, 3, 1, 1, 1, Co, 0, 0)) return rc;
-    a.IH = H; a.IW = W; a.y0 = y0; a.x0 = x0; a.Lh = y1 - y0; a.Lw = x1 - x0;
-    launch_either<GatherPooled>(a, false, (hipStream_t)stream);                  // K = 27: the unaligned weight path
-    return te::launch_status("te_id_stem_fwd_f32");
+    return id_stem("te_id_stem_fwd_f32", out, nullptr, img, w, b, slope, N, H, W, y0, y1, x0, x1, Pn, Co, stream);
+}
+
+extern "C" int te_id_stem_keep_f32(float* out, float* pre, const float* img, const float* w, const float* b, const float* slope, int N, int H,
+                                   int W, int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream) {
+    TE_REQUIRE(pre, TE_ERR_NULL, "te_id_stem_keep_f32: NULL pointer");
+    return id_stem("te_id_stem_keep_f32", out, pre, img, w, b, slope, N, H, W, y0, y1, x0, x1, Pn, Co, stream);
 }
 
 extern "C" int te_se_excite_f32(float* gate, const float* pooled, const float* w1, const float* w2, int B, int C, int R, te_stream_t stream) {

@@ -1,0 +1,338 @@
+// The backward pass of the ArcFace IR-SE50 identity network (irse.hip) with respect to its INPUT: the network is frozen, so there is no
+// weight gradient and no training-mode batch norm.  What pSp/criteria/id_loss.py:23-45 IDLoss.forward needs from torch autograd:
+//
+//     te_conv2d_dgrad_f32    : the data gradient of te_conv2d_f32 / te_conv2d_prelu_f32, with the PReLU' or the affine + add epilogue
+//     te_se_bwd_f32          : SEModule and the gated product backwards: gout, r, gate, pooled -> the gradient of r
+//     te_id_stem_bwd_f32     : PReLU', the stem convolution, AdaptiveAvgPool2d and the crop backwards, to the image
+//     te_rows_unit_bwd_f32   : l2_norm backwards
+//
+// The adjoint of a convolution is a convolution: te_conv2d_dgrad_f32 and the stem run the main loop of conv2d_body.h (the k order of the
+// forward family) over the incoming gradient, on a weight the host transposed and flipped once.  A stride-2 layer is NOT a gather over
+// the zero-inserted plane (three of four taps there are zeros the MFMA would multiply): its four output phases (y % 2, x % 2) are four
+// dense stride-1 implicit GEMMs over g with the sub-kernels 1x1, 1x2, 2x1 and 2x2 of the 3x3, each stored with a pitch of 2 (PartPhase).
+// No atomics; every reduction is a fixed-order chain or a fixed-shape tree; an image's gradient is bitwise independent of its batch.
+#include "te_common.h"
+#include "conv2d_body.h"
+#include "wave_dot.h"
+
+namespace {
+
+using namespace te::conv2d;
+
+// ------------------------------------------------------------------------------------------------------ the data gradient
+// The loop's view of one phase: its "input" is g [B,Co,Ho,Wo] (Ci, H, W of ConvArgs), its "output channels" are the forward's input
+// channels (Co of ConvArgs), its pixels the Hp x Wp outputs of the phase (Ho, Wo of ConvArgs), stride 1.
+struct DgradArgs : ConvArgs {
+    const float* pre;            // [B,Cx,GH,GW] or NULL: the PReLU' epilogue
+    const float* slope;          // [Cx]
+    const float* in_scale;       // [Cx] or NULL
+    const float* add;            // [B,Cx,AH,AW] or NULL
+    int GH, GW;                  // the plane of gx
+    int ds, ry, rx;              // the phase: gx rows ry, ry + ds, ..., columns rx, rx + ds, ...
+    int as, AH, AW;              // add is read at (y / as, x / as) where as divides y and x
+};
+
+struct PartPhase {
+    static __device__ __forceinline__ int k_begin(const DgradArgs& a) { return 0; }
+    static __device__ __forceinline__ int k_end(const DgradArgs& a) { return a.K; }
+    static __device__ __forceinline__ float* out(const DgradArgs& a) { return a.out; }
+    static __device__ __forceinline__ float finish(const DgradArgs& a, float acc, int m) { return acc; }
+    static __device__ __forceinline__ float* dest(const DgradArgs& a, float* out, int64_t b, int r, int HoWo) {
+        const int oy = r / a.Wo, ox = r - oy * a.Wo;
+        return out + b * a.Co * a.GH * a.GW + (oy * a.ds + a.ry) * a.GW + ox * a.ds + a.rx;
+    }
+    static __device__ __forceinline__ int pitch(const DgradArgs& a, int HoWo) { return a.GH * a.GW; }
+};
+
+// pre given : gx = acc * (pre > 0 ? 1 : slope[m])      torch's rule: pre == 0, -0 and NaN take the slope
+// else      : gx = in_scale[m] * acc + add             each term optional; one fma where both are there
+struct EpiDgrad {
+    static __device__ __forceinline__ float apply(const DgradArgs& a, float v, const float* dst, int m, int GHW) {
+        const int64_t at = dst - a.out;                      // plane 0 of the image: (b * Cx) * GHW + y * GW + x
+        if (a.pre) return a.pre[at + (int64_t)m * GHW] > 0.f ? v : __fmul_rn(v, a.slope[m]);
+        float t = 0.f;
+        if (a.add) {
+            const int64_t plane0 = at / GHW;
+            const int rem = (int)(at - plane0 * GHW);
+            const int y = rem / a.GW, x = rem - y * a.GW;
+            if (a.as == 1) t = a.add[at + (int64_t)m * GHW];
+            else if (y % a.as == 0 && x % a.as == 0) t = a.add[((plane0 + m) * a.AH + y / a.as) * a.AW + x / a.as];
+        }
+        if (a.in_scale) return a.add ? fmaf(a.in_scale[m], v, t) : __fmul_rn(a.in_scale[m], v);
+        return a.add ? __fadd_rn(v, t) : v;
+    }
+};
+
+template <int BN, class Gather, class Epi, class Args>
+void launch_phase(const Args& a, hipStream_t st) {
+    const bool al = a.K % 4 == 0 && te::aligned16(a.w);
+    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
+    if (al) conv2d_kernel<BN, true, Gather, Epi, PartPhase, Args><<<grid, NT, 0, st>>>(a);
+    else conv2d_kernel<BN, false, Gather, Epi, PartPhase, Args><<<grid, NT, 0, st>>>(a);
+}
+
+// the taps ky = k0 + s j (j < n) that reach output rows of parity r, and the padding of the phase's stride-1 convolution over g with
+// those taps flipped: row y = s yy + r reads g rows yy - pad + j', j' = n - 1 - j
+struct Phase { int k0, n, pad; };
+inline Phase phase_of(int r, int k, int s, int p) {
+    Phase f;
+    f.k0 = (r + p) % s;
+    f.n = f.k0 < k ? (k - f.k0 + s - 1) / s : 0;
+    f.pad = f.n - 1 - (r + p - f.k0) / s;
+    return f;
+}
+
+// every phase of a data gradient on the loop, with gather `Gather` over g.  `a` arrives with out, x, pre, slope, in_scale, add, as, AH, AW
+// set; the weight holds the phases (ry, rx) = (0, 0), (0, 1), (1, 0), (1, 1) one behind the other, each [Cx, Co * ny * nx]
+template <class Gather, class Args>
+void launch_dgrad(Args a, const float* wt, int B, int Cx, int Co, int H, int W, int kh, int kw, int s, int py, int px, int Ho, int Wo,
+                  hipStream_t st) {
+    a.Co = Cx; a.H = Ho; a.W = Wo; a.s = 1; a.GH = H; a.GW = W; a.ds = s; a.Ctot = Cx; a.c0 = 0; a.act = 0; a.bias = nullptr;
+    for (int ry = 0; ry < s; ++ry)
+        for (int rx = 0; rx < s; ++rx) {
+            const Phase fy = phase_of(ry, kh, s, py), fx = phase_of(rx, kw, s, px);
+            const int Hp = (H - ry + s - 1) / s, Wp = (W - rx + s - 1) / s;
+            const bool empty = fy.n == 0 || fx.n == 0;       // no tap reaches this phase: the loop runs no step and the epilogue sees 0
+            a.w = wt;
+            a.Ci = empty ? 0 : Co; a.kh = empty ? 1 : fy.n; a.kw = empty ? 1 : fx.n; a.K = a.Ci * a.kh * a.kw;
+            a.py = empty ? 0 : fy.pad; a.px = empty ? 0 : fx.pad;
+            a.Ho = Hp; a.Wo = Wp; a.P = (int64_t)B * Hp * Wp; a.ry = ry; a.rx = rx;
+            wt += (int64_t)Cx * a.K;
+            if (a.P == 0) continue;
+            if (wide_grid(a.P, a.Co)) launch_phase<128, Gather, EpiDgrad>(a, st);
+            else launch_phase<64, Gather, EpiDgrad>(a, st);
+        }
+}
+
+// the checks of te_conv2d_dgrad_f32 and te_id_stem_bwd_f32; -> Ho, Wo
+int check_dgrad(const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int& Ho, int& Wo) {
+    TE_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, TE_ERR_SHAPE, "%s: B, Ci, Co, H, W must be positive (got %d, %d, %d, %d, %d)", who,
+               B, Ci, Co, H, W);
+    TE_REQUIRE(kh >= 1 && kh <= kMaxKernel && kw >= 1 && kw <= kMaxKernel, TE_ERR_UNSUPPORTED, "%s: 1 <= kh, kw <= %d (got %d x %d)", who,
+               kMaxKernel, kh, kw);
+    TE_REQUIRE(s == 1 || s == 2, TE_ERR_UNSUPPORTED, "%s: the stride must be 1 or 2 (got %d)", who, s);
+    TE_REQUIRE(py >= 0 && py < kh && px >= 0 && px < kw, TE_ERR_SHAPE, "%s: 0 <= py < kh and 0 <= px < kw (got padding %d, %d for a %d x %d kernel)",
+               who, py, px, kh, kw);
+    TE_REQUIRE(H + 2 * py >= kh && W + 2 * px >= kw, TE_ERR_SHAPE, "%s: a %d x %d kernel with padding %d, %d does not fit a %d x %d image", who, kh,
+               kw, py, px, H, W);
+    Ho = (H + 2 * py - kh) / s + 1;
+    Wo = (W + 2 * px - kw) / s + 1;
+    TE_REQUIRE((int64_t)Ci * H * W <= 0x7fffffff && (int64_t)Co * Ho * Wo <= 0x7fffffff && (int64_t)Co * kh * kw <= 0x7fffffff - BK,
+               TE_ERR_SHAPE, "%s: one image of gx (Ci * H * W), one of g (Co * Ho * Wo) and Co * kh * kw must fit 31 bits", who);
+    TE_REQUIRE(te::cdiv((int64_t)B * H * W, 64) <= 0x7fffffff && te::cdiv(Ci, BM) <= 65535, TE_ERR_SHAPE,
+               "%s: too many outputs (%lld pixels, %d channels)", who, (long long)B * H * W, Ci);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------ squeeze-and-excitation
+using te::wave_sum;              // (float: wave_dot.h)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// ggate[plane] = sum_hw gout * r: one wave per plane, lane l takes i = l, l + 64, ... as one fma chain, the lanes meet in a butterfly
+__global__ __launch_bounds__(256) void se_ggate_kernel(float* __restrict__ ggate, const float* __restrict__ gout, const float* __restrict__ r,
+                                                       int64_t planes, int HW) {
+    const int lane = threadIdx.x & 63;
+    const int64_t plane = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (plane >= planes) return;
+    const float* g = gout + plane * HW;
+    const float* q = r + plane * HW;
+    float acc = 0.f;
+    for (int i = lane; i < HW; i += 64) acc = fmaf(g[i], q[i], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) ggate[plane] = acc;
+}
+
+// One workgroup of four waves per image, as se_excite_kernel.  Step 1: the hidden units again, with se_excite_kernel's arithmetic (they
+// are not kept).  Step 2: a live hidden unit's gradient is one wave's dot product over the channels of w2[:, r] with
+// gz[c] = ggate[c] * gate[c] * (1 - gate[c]); a dead one (hidden <= 0 or NaN: torch's threshold rule) gets 0.  Step 3: a thread per
+// channel, one fma chain over r ascending, divided by the plane: what every pixel of r[b,c] receives through the mean.
+constexpr int kSeThreads = 256;
+constexpr int kSeMaxR = 1024;
+
+__global__ __launch_bounds__(kSeThreads) void se_bwd_kernel(float* __restrict__ gmean, const float* __restrict__ ggate,
+                                                            const float* __restrict__ gate, const float* __restrict__ pooled,
+                                                            const float* __restrict__ w1, const float* __restrict__ w2, int C, int R, float hw) {
+    __shared__ float hidden[kSeMaxR];
+    __shared__ float gh[kSeMaxR];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const float* p = pooled + (int64_t)blockIdx.x * C;
+    const float* gg = ggate + (int64_t)blockIdx.x * C;
+    const float* gt = gate + (int64_t)blockIdx.x * C;
+    for (int r = wid; r < R; r += kSeThreads / 64) {
+        const float* w = w1 + (int64_t)r * C;
+        float acc = 0.f;
+        for (int k = lane; k < C; k += 64) acc = fmaf(w[k], p[k], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) hidden[r] = acc;
+    }
+    __syncthreads();
+    for (int r = wid; r < R; r += kSeThreads / 64) {
+        float acc = 0.f;
+        for (int c = lane; c < C; c += 64) {
+            const float s = gt[c];
+            acc = fmaf(w2[(int64_t)c * R + r], gg[c] * (s * (1.f - s)), acc);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) gh[r] = hidden[r] > 0.f ? acc : 0.f;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += kSeThreads) {
+        float z = 0.f;
+        for (int r = 0; r < R; ++r) z = fmaf(w1[(int64_t)r * C + c], gh[r], z);
+        gmean[(int64_t)blockIdx.x * C + c] = __fdiv_rn(z, hw);
+    }
+}
+
+// gr = gout * gate[plane] + gmean[plane], one fma; four consecutive elements of a plane per thread (HW % 4 == 0) or one
+template <bool VEC>
+__global__ __launch_bounds__(256) void se_gr_kernel(float* __restrict__ gr, const float* __restrict__ gout, const float* __restrict__ gate,
+                                                    const float* __restrict__ gmean, int64_t items, int per_plane) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= items) return;
+    const int64_t plane = t / per_plane;
+    const float s = gate[plane], m = gmean[plane];
+    if (VEC) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(gout + 4 * t);
+        f32x4 o;
+        o.x = fmaf(g.x, s, m); o.y = fmaf(g.y, s, m); o.z = fmaf(g.z, s, m); o.w = fmaf(g.w, s, m);
+        *reinterpret_cast<f32x4*>(gr + 4 * t) = o;
+    } else {
+        gr[t] = fmaf(gout[t], s, m);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ the stem
+struct StemBwdArgs : DgradArgs {
+    const float* spre;           // the stem's kept pre-activation, in the layout of g
+    const float* sslope;         // [Co]
+};
+
+// a tap of g * PReLU'(pre): the product with the slope is one rounding; c is wave-uniform
+struct GatherPreluGrad {
+    static __device__ __forceinline__ const float* image(const StemBwdArgs& a, int64_t b) { return a.x + b * a.Ci * a.H * a.W; }
+    static __device__ __forceinline__ int plane(const StemBwdArgs& a) { return a.H * a.W; }
+    static __device__ __forceinline__ float tap(const float* img, const StemBwdArgs& a, int HW, int c, int iy, int ix) {
+        const int at = c * HW + iy * a.W + ix;
+        const float g = img[at];
+        return a.spre[(img - a.x) + at] > 0.f ? g : __fmul_rn(g, a.sslope[c]);
+    }
+};
+
+// AdaptiveAvgPool2d and the crop backwards as a GATHER: an image pixel sums the pooled windows [floor(i L / Pn), ceil((i + 1) L / Pn))
+// that contain it (at most 2 x 2 of them where L >= Pn), each divided by its count, rows then columns ascending; 0 outside the box
+__global__ __launch_bounds__(256) void stem_unpool_kernel(float* __restrict__ gimg, const float* __restrict__ gp, int64_t total, int H, int W,
+                                                          int y0, int x0, int Lh, int Lw, int Pn) {
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const int x = (int)(o % W) - x0, y = (int)(o / W % H) - y0;
+    const int64_t plane = o / W / H;
+    float s = 0.f;
+    if ((unsigned)y < (unsigned)Lh && (unsigned)x < (unsigned)Lw) {
+        const int ia = y * Pn / Lh, ib = ((y + 1) * Pn - 1) / Lh;              // (Pn, L <= 32768: the products fit)
+        const int ja = x * Pn / Lw, jb = ((x + 1) * Pn - 1) / Lw;
+        const float* src = gp + plane * Pn * Pn;
+        for (int i = ia; i <= ib; ++i) {
+            const int rows = ((i + 1) * Lh + Pn - 1) / Pn - i * Lh / Pn;
+            for (int j = ja; j <= jb; ++j) {
+                const int cols = ((j + 1) * Lw + Pn - 1) / Pn - j * Lw / Pn;
+                s = __fadd_rn(s, __fdiv_rn(src[i * Pn + j], (float)(rows * cols)));
+            }
+        }
+    }
+    gimg[o] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------ the rows
+// Row i = blockIdx.x, one wave, rows_dot_kernel's shape: <e, ge> and the norm's square are fp64 chains per lane and fp64 butterflies
+__global__ __launch_bounds__(64) void rows_unit_bwd_kernel(float* __restrict__ ga, const float* __restrict__ ge, const float* __restrict__ e,
+                                                           const float* __restrict__ a, int D) {
+    const int lane = threadIdx.x;
+    const int64_t at = (int64_t)blockIdx.x * D;
+    double dot = 0.0, sq = 0.0;
+    for (int d = lane; d < D; d += 64) {
+        const double v = a[at + d];
+        dot = fma((double)e[at + d], (double)ge[at + d], dot);
+        sq = fma(v, v, sq);
+    }
+    const float dt = (float)wave_sum(dot);
+    const float norm = (float)sqrt(wave_sum(sq));
+    for (int d = lane; d < D; d += 64) ga[at + d] = __fdiv_rn(fmaf(-e[at + d], dt, ge[at + d]), norm);
+}
+
+}  // namespace
+
+extern "C" int te_conv2d_dgrad_f32(float* gx, const float* g, const float* wt, const float* pre, const float* slope, const float* in_scale,
+                                   const float* add, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int add_s,
+                                   te_stream_t stream) {
+    TE_REQUIRE(gx && g && wt, TE_ERR_NULL, "te_conv2d_dgrad_f32: NULL pointer");
+    TE_REQUIRE((pre == nullptr) == (slope == nullptr), TE_ERR_NULL, "te_conv2d_dgrad_f32: pre and slope must both be given or both be NULL");
+    TE_REQUIRE(!pre || (!in_scale && !add), TE_ERR_UNSUPPORTED, "te_conv2d_dgrad_f32: the PReLU' epilogue (pre) takes neither in_scale nor add");
+    TE_REQUIRE(!add || add_s == 1 || add_s == 2, TE_ERR_UNSUPPORTED, "te_conv2d_dgrad_f32: add_s must be 1 or 2 (got %d)", add_s);
+    int Ho, Wo;
+    if (const int rc = check_dgrad("te_conv2d_dgrad_f32", B, Ci, Co, H, W, kh, kw, s, py, px, Ho, Wo)) return rc;
+    DgradArgs a;
+    a.out = gx; a.x = g; a.pre = pre; a.slope = slope; a.in_scale = in_scale; a.add = add;
+    a.as = add ? add_s : 1; a.AH = (H - 1) / a.as + 1; a.AW = (W - 1) / a.as + 1;
+    launch_dgrad<GatherPlain>(a, wt, B, Ci, Co, H, W, kh, kw, s, py, px, Ho, Wo, (hipStream_t)stream);
+    return te::launch_status("te_conv2d_dgrad_f32");
+}
+
+extern "C" int te_se_bwd_f32(float* gr, float* ws, const float* gout, const float* r, const float* gate, const float* pooled, const float* w1,
+                             const float* w2, int B, int C, int R, int Ho, int Wo, te_stream_t stream) {
+    TE_REQUIRE(gr && ws && gout && r && gate && pooled && w1 && w2, TE_ERR_NULL, "te_se_bwd_f32: NULL pointer");
+    TE_REQUIRE(B >= 1 && C >= 1 && R >= 1 && R <= kSeMaxR && (int64_t)C * R <= 0x7fffffff && Ho >= 1 && Wo >= 1 && (int64_t)Ho * Wo <= 0x7fffffff,
+               TE_ERR_SHAPE, "te_se_bwd_f32: B, C, Ho, Wo >= 1, 1 <= R <= %d, C * R and Ho * Wo below 2^31 (got %d, %d, %d, %d, %d)", kSeMaxR, B, C,
+               R, Ho, Wo);
+    const int64_t planes = (int64_t)B * C;
+    const int HW = Ho * Wo;
+    TE_REQUIRE(planes <= ((int64_t)1 << 40) / HW && te::cdiv(planes, 4) <= 0x7fffffff, TE_ERR_SHAPE,
+               "te_se_bwd_f32: at most 2^40 elements (got %lld planes of %d x %d)", (long long)planes, Ho, Wo);
+    hipStream_t st = (hipStream_t)stream;
+    float* ggate = ws;
+    float* gmean = ws + planes;
+    se_ggate_kernel<<<(unsigned)te::cdiv(planes, 4), 256, 0, st>>>(ggate, gout, r, planes, HW);
+    se_bwd_kernel<<<(unsigned)B, kSeThreads, 0, st>>>(gmean, ggate, gate, pooled, w1, w2, C, R, (float)HW);
+    if (HW % 4 == 0 && te::aligned16(gr) && te::aligned16(gout)) {
+        const int64_t items = planes * HW / 4;
+        se_gr_kernel<true><<<(unsigned)te::cdiv(items, 256), 256, 0, st>>>(gr, gout, gate, gmean, items, HW / 4);
+    } else {
+        const int64_t items = planes * HW;
+        se_gr_kernel<false><<<(unsigned)te::cdiv(items, 256), 256, 0, st>>>(gr, gout, gate, gmean, items, HW);
+    }
+    return te::launch_status("te_se_bwd_f32");
+}
+
+extern "C" int te_id_stem_bwd_f32(float* gimg, float* ws, const float* g, const float* wt, const float* pre, const float* slope, int N, int H,
+                                  int W, int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream) {
+    TE_REQUIRE(gimg && ws && g && wt && pre && slope, TE_ERR_NULL, "te_id_stem_bwd_f32: NULL pointer");
+    TE_REQUIRE(N >= 1 && N < 65536 && H >= 1 && W >= 1 && Co >= 1, TE_ERR_SHAPE,
+               "te_id_stem_bwd_f32: 1 <= N < 65536 and positive H, W, Co (got %d, %d, %d, %d)", N, H, W, Co);
+    TE_REQUIRE(y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W, TE_ERR_SHAPE,
+               "te_id_stem_bwd_f32: the window [%d, %d) x [%d, %d) must be non-empty and inside the %d x %d image", y0, y1, x0, x1, H, W);
+    TE_REQUIRE(Pn >= 1 && Pn <= 32768 && y1 - y0 <= 32768 && x1 - x0 <= 32768, TE_ERR_SHAPE,
+               "te_id_stem_bwd_f32: 1 <= Pn <= 32768 and a window of at most 32768 x 32768 (got Pn = %d, %d x %d)", Pn, y1 - y0, x1 - x0);
+    TE_REQUIRE((int64_t)3 * H * W <= 0x7fffffff && te::cdiv((int64_t)N * 3 * H * W, 256) <= 0x7fffffff, TE_ERR_SHAPE,
+               "te_id_stem_bwd_f32: one image (3 * H * W) must fit 31 bits and the batch 2^39 elements");
+    int Ho, Wo;
+    if (const int rc = check_dgrad("te_id_stem_bwd_f32", N, 3, Co, Pn, Pn, 3, 3, 1, 1, 1, Ho, Wo)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StemBwdArgs a;
+    a.out = ws; a.x = g; a.pre = nullptr; a.slope = nullptr; a.in_scale = nullptr; a.add = nullptr; a.as = 1; a.AH = Pn; a.AW = Pn;
+    a.spre = pre; a.sslope = slope;
+    launch_dgrad<GatherPreluGrad>(a, wt, N, 3, Co, Pn, Pn, 3, 3, 1, 1, 1, Ho, Wo, st);
+    const int64_t total = (int64_t)N * 3 * H * W;
+    stem_unpool_kernel<<<(unsigned)te::cdiv(total, 256), 256, 0, st>>>(gimg, ws, total, H, W, y0, x0, y1 - y0, x1 - x0, Pn);
+    return te::launch_status("te_id_stem_bwd_f32");
+}
+
+extern "C" int te_rows_unit_bwd_f32(float* ga, const float* ge, const float* e, const float* a, int64_t I, int D, te_stream_t stream) {
+    TE_REQUIRE(ga && ge && e && a, TE_ERR_NULL, "te_rows_unit_bwd_f32: NULL pointer");
+    TE_REQUIRE(I >= 1 && I <= 0x7fffffff && D >= 1, TE_ERR_SHAPE, "te_rows_unit_bwd_f32: 1 <= I < 2^31 and D >= 1 (got %lld, %d)", (long long)I, D);
+    rows_unit_bwd_kernel<<<(unsigned)I, 64, 0, (hipStream_t)stream>>>(ga, ge, e, a, D);
+    return te::launch_status("te_rows_unit_bwd_f32");
+}

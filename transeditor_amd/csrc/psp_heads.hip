@@ -56,7 +56,7 @@ struct EpiPartial {
 };
 
 // range blockIdx.z of the k chain; the bare accumulators go to ws[blockIdx.z][B][G * Cg][Ho * Wo] (Ctot = Co, c0 = 0 there)
-struct PartSplit {
+struct PartSplit : DestDense {
     static __device__ __forceinline__ int k_begin(const HeadsArgs& a) { return blockIdx.z * a.kper; }
     static __device__ __forceinline__ int k_end(const HeadsArgs& a) { return min(a.K, (int)(blockIdx.z + 1) * a.kper); }
     static __device__ __forceinline__ float* out(const HeadsArgs& a) { return a.out + blockIdx.z * a.part; }

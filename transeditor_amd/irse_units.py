@@ -127,3 +127,60 @@ def unit_forward(mod, i, x):
     if g('sc_w') is not None:
         x, stride = _lib.conv2d(x, g('sc_w'), g('sc_b'), stride, (0, 0), act=0), 1
     return _lib.se_scale_add(r, gate, x, stride)
+
+
+# ------------------------------------------------------------------------------------------------------------ the backward pass
+# With respect to the unit's INPUT only: the networks are frozen.  unit_forward_keep is unit_forward (the same bits) that also returns
+# what unit_backward reads: the first convolution's pre-activation (the PReLU branch cannot be read from its output: slopes may be
+# negative) and, where the unit has a gate, the residual branch, the gates and the pooled vector.  Everything else is dropped.
+def dgrad_weights(mod, i):
+    """(made once per unit and device: the weights never change) the unit's convolutions in _lib.conv2d_dgrad's layout:
+    dict(w1, w2, sc or None)"""
+    cache = mod.__dict__.setdefault('_dgrad_weights', {})
+    w1 = getattr(mod, f'u{i}_w1')
+    key = (i, w1.device)
+    if key not in cache:
+        stride, sc = mod.units[i][2], getattr(mod, f'u{i}_sc_w', None)
+        cache[key] = dict(w1=_lib.dgrad_weight(w1, 1, (1, 1)), w2=_lib.dgrad_weight(getattr(mod, f'u{i}_w2'), stride, (1, 1)),
+                          sc=None if sc is None else _lib.dgrad_weight(sc, stride, (0, 0)))
+    return cache[key]
+
+
+def unit_forward_keep(mod, i, x):
+    """-> (the unit's output, bitwise unit_forward's; (pre, r, gate, pooled) for unit_backward: r, gate, pooled None without a gate)"""
+    def g(k):
+        return getattr(mod, f'u{i}_{k}', None)
+    stride = mod.units[i][2]
+    t, pre = _lib.conv2d_prelu_keep(x, g('w1'), g('zero'), g('slope'), g('scale'), g('shift'), 1, (1, 1))
+    r = _lib.conv2d(t, g('w2'), g('b2'), stride, (1, 1), act=0)
+    del t
+    gate = pooled = None
+    if mod.se[i]:
+        pooled = _lib.adaptive_avgpool(r, 1, 1).view(r.shape[0], -1)
+        gate = _lib.se_excite(pooled, g('fc1'), g('fc2'))
+    if g('sc_w') is not None:
+        x, stride = _lib.conv2d(x, g('sc_w'), g('sc_b'), stride, (0, 0), act=0), 1
+    out = _lib.se_scale_add(r, gate, x, stride)
+    return out, (pre, r if mod.se[i] else None, gate, pooled)
+
+
+def unit_backward(mod, i, kept, gout):
+    """the gradient of the unit's input from the gradient of its output [B,depth,Ho,Wo] and what unit_forward_keep kept.  The shortcut
+    takes gout as it is; the residual branch goes back through the gate (te_se_bwd_f32), the second convolution and the PReLU (one
+    te_conv2d_dgrad_f32, stride 2 in its four phases), then the first convolution, whose epilogue applies the leading batch norm's scale
+    and adds the shortcut's gradient: gout spread with the stride (the adjoint of MaxPool2d(1, s)) or the shortcut convolution's own
+    data gradient."""
+    def g(k):
+        return getattr(mod, f'u{i}_{k}', None)
+    pre, r, gate, pooled = kept
+    cin, depth, stride = mod.units[i]
+    B, _, H, W = pre.shape                                                      # the first convolution has stride 1: the input's plane
+    wt = dgrad_weights(mod, i)
+    gout = gout.contiguous()
+    gr = _lib.se_bwd(gout, r, gate, pooled, g('fc1'), g('fc2')) if mod.se[i] else gout
+    gt = _lib.conv2d_dgrad(gr, wt['w2'], (B, depth, H, W), (3, 3), stride, (1, 1), pre=pre, slope=g('slope'))
+    del gr
+    add, add_stride = gout, stride
+    if wt['sc'] is not None:
+        add, add_stride = _lib.conv2d_dgrad(gout, wt['sc'], (B, cin, H, W), (1, 1), stride, (0, 0)), 1
+    return _lib.conv2d_dgrad(gt, wt['w1'], (B, cin, H, W), (3, 3), 1, (1, 1), in_scale=g('scale'), add=add, add_stride=add_stride)
