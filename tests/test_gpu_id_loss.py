@@ -277,6 +277,21 @@ def test_stem_bwd(S, box, Pn, N, Co):
     assert torch.equal(one, got[:1])
 
 
+def test_stem_bwd_wide_tile_equals_the_narrow_one():
+    """a pool of 112 is 98 workgroups of 128 pixels per image (the gradient has 3 channels: one block): six images are 588, above
+    kWideGridMin = 512, and take the 128-pixel tile; an image alone runs on the 64-pixel one.  The same bits."""
+    from transeditor_amd import _lib
+    S, box, Pn, N, Co = 116, (2, 114, 2, 114), 112, 6, 8
+    w, _, slope = (t.to(DEV) for t in _stem_weights(Co, 19))
+    gen = torch.Generator().manual_seed(23)
+    g, pre = (torch.randn(N, Co, Pn, Pn, generator=gen).to(DEV) for _ in range(2))
+    wt = _lib.dgrad_weight(w, 1, (1, 1))
+    full = _lib.id_stem_bwd(g, wt, pre, slope, (N, 3, S, S), box, Pn)
+    for i in range(N):
+        assert torch.equal(full[i:i + 1], _lib.id_stem_bwd(g[i:i + 1].contiguous(), wt, pre[i:i + 1].contiguous(), slope, (1, 3, S, S), box, Pn)), i
+    assert bool((full[:, :, 2:114, 2:114] != 0).all())
+
+
 @pytest.mark.parametrize('D', [4, 512, 515])
 def test_rows_unit_bwd(D):
     """ga = (ge - e <e, ge>) / ||a|| elementwise against fp64 on the same fp32 e and a: 2^-24 (|e <e, ge>| / ||a|| + 3 |ga|): the dot

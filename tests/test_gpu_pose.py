@@ -202,6 +202,22 @@ def test_stem_against_fp64():
 
 
 @pytest.mark.parametrize('preprocessed', [False, True])
+def test_stem_wide_tile_equals_the_narrow_one(preprocessed):
+    """a crop of 255 is 128 x 128 outputs, 128 workgroups of 128 pixels per image at Co = 64: four images are 512, kWideGridMin, and take
+    the 128-pixel tile; an image alone runs on the 64-pixel one.  The same bits, from the RGB image and from the BGR levels."""
+    from transeditor_amd import _lib
+    N, H, W, crop, Co = 4, 255, 255, 255, 64
+    w, b = (t.to(DEV) for t in _stem_weights(Co, 13))
+    x = _stem_input(N, H, W, crop, 17)
+    x = (_levels(x) if preprocessed else x).to(DEV)
+    full = _lib.pose_stem_fwd(x, w, b, crop, preprocessed)
+    assert full.shape == (N, Co, 128, 128)
+    for i in range(N):
+        assert torch.equal(full[i:i + 1], _lib.pose_stem_fwd(x[i:i + 1].contiguous(), w, b, crop, preprocessed)), i
+    assert float((full > 0).float().mean()) > 0.2
+
+
+@pytest.mark.parametrize('preprocessed', [False, True])
 def test_stem_nan_pixel_reaches_its_windows(preprocessed):
     from transeditor_amd import _lib
     N, H, W, crop, Co = 1, 44, 40, 30, 64

@@ -80,6 +80,19 @@ def test_heads_unsplit_writes_its_slice_only():
     assert not bool((got[:, 5:5 + 128] == SENTINEL).any())
 
 
+def test_heads_unsplit_wide_tile_equals_the_narrow_one():
+    """two heads of 64 channels on a 128 x 128 plane: one image is 128 x 2 = 256 workgroups of 128 pixels, below kWideGridMin = 512, and
+    runs on the 64-pixel tile; two images are 512 and take the 128-pixel one.  K = 72 is unsplit by the rule.  The same bits."""
+    from transeditor_amd import _lib
+    x, w, b = (t.to(DEV) for t in _heads_case(2, 2, 8, 64, 128, 3, 1, 41))
+    assert _lib.conv2d_heads_splits(8, 3, 3, 128, 128) == 1
+    full = _lib.conv2d_heads(x, w, b, 1, (1, 1), True, SLOPE)
+    assert full.shape == (2, 128, 128, 128)
+    for i in range(2):
+        assert torch.equal(full[i:i + 1], _lib.conv2d_heads(x[i:i + 1].contiguous(), w, b, 1, (1, 1), True, SLOPE)), i
+    assert 0.2 < float((full < 0).float().mean()) < 0.8
+
+
 def test_heads_slope_one_is_the_identity_and_a_nan_propagates():
     from transeditor_amd import _lib
     x, w, b = _heads_case(2, 2, 8, 64, 4, 3, 0, 77)

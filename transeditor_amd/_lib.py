@@ -1073,19 +1073,25 @@ def _slice_out(out, c0, B, Cn, Ho, Wo, like, what):
     return out
 
 
+def _conv2d_geometry(who, x, w, bias, stride, pad, out=None, c0=0, also=None, more=''):
+    """the x / w / bias check of the ops on the conv2d loop (`also`: what else the op needs to hold, `more`: its part of the message) ->
+    (B, Ci, Co, H, W, kh, kw, stride, py, px) as the ABI takes them, the output tensor (_slice_out) and (Ho, Wo), which the ABI refuses
+    where they are not positive"""
+    if x.ndim != 4 or w.ndim != 4 or bias.ndim != 1 or x.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0] or (also and not also()):
+        raise RuntimeError(f'te_hip: {who}: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}{more}')
+    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    return (B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1]), _slice_out(out, c0, B, Co, max(Ho, 0), max(Wo, 0), x, who), (Ho, Wo)
+
+
 @_op
 def conv2d(x, w, bias, stride=1, pad=(0, 0), act=0, out=None, c0=0):
     """act(conv2d(x, w, stride, pad) + bias) written into channels [c0, c0 + Co) of `out` [B,Ctot,Ho,Wo] (a new [B,Co,Ho,Wo] tensor
     where out is None): x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co]; act 0 none, 1 ReLU.  The ABI refuses what it does not cover (a
     stride above 2, a kernel above 7 x 7, padding >= the kernel, an empty output, a slice past Ctot); nothing is launched then.
     Returns out."""
-    if x.ndim != 4 or w.ndim != 4 or bias.ndim != 1 or x.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0]:
-        raise RuntimeError(f'te_hip: conv2d: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
-    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
-    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
-    out = _slice_out(out, c0, B, Co, max(Ho, 0), max(Wo, 0), x, 'conv2d')
-    _launch('te_conv2d_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], out.shape[1], c0,
-            act)
+    geo, out, _ = _conv2d_geometry('conv2d', x, w, bias, stride, pad, out, c0)
+    _launch('te_conv2d_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), *geo, out.shape[1], c0, act)
     return out
 
 
@@ -1190,14 +1196,10 @@ def conv2d_res(x, w, bias, res, stride=1, pad=(0, 0), act=1):
     """act((conv2d(x, w, stride, pad) + bias) + res), the end of a ResNet BasicBlock: x [B,Ci,H,W], w [Co,Ci,kh,kw], bias [Co],
     res [B,Co,Ho,Wo] -> a new [B,Co,Ho,Wo] tensor, bitwise relu(conv2d(act=0) + res).  The ABI refuses what te_conv2d_f32 refuses;
     nothing is launched then."""
-    if x.ndim != 4 or w.ndim != 4 or bias.ndim != 1 or x.shape[1] != w.shape[1] or bias.shape[0] != w.shape[0]:
-        raise RuntimeError(f'te_hip: conv2d_res: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
-    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
-    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
-    if tuple(res.shape) != (B, Co, Ho, Wo):
-        raise RuntimeError(f'te_hip: conv2d_res: the residual must be [{B},{Co},{Ho},{Wo}], got {tuple(res.shape)}')
-    out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
-    _launch('te_conv2d_res_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(res), B, Ci, Co, H, W, kh, kw, stride, pad[0], pad[1], act)
+    geo, out, (Ho, Wo) = _conv2d_geometry('conv2d_res', x, w, bias, stride, pad)
+    if tuple(res.shape) != (*out.shape[:2], Ho, Wo):
+        raise RuntimeError(f'te_hip: conv2d_res: the residual must be [{out.shape[0]},{out.shape[1]},{Ho},{Wo}], got {tuple(res.shape)}')
+    _launch('te_conv2d_res_f32', _ptr(out), _ptr(x), _ptr(w), _ptr(bias), _ptr(res), *geo, act)
     return out
 
 
@@ -1286,16 +1288,12 @@ def lpips_allpairs_dist(partials, shapes, N):
 
 # --------------------------------------------------------------------------------------------- M9 ArcFace IR-SE50 identity network
 def _conv2d_prelu(who, keep, x, w, bias, slope, in_scale, in_shift, stride, pad):
-    if x.ndim != 4 or w.ndim != 4 or x.shape[1] != w.shape[1] or bias.shape != (w.shape[0],) or slope.shape != (w.shape[0],) \
-            or any(t is not None and t.shape != (x.shape[1],) for t in (in_scale, in_shift)):
-        raise RuntimeError(f'te_hip: {who}: inconsistent shapes x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, '
-                           f'slope {tuple(slope.shape)}, affine {[None if t is None else tuple(t.shape) for t in (in_scale, in_shift)]}')
-    (B, Ci, H, W), (Co, _, kh, kw) = x.shape, w.shape
-    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
-    out = torch.empty(B, Co, max(Ho, 0), max(Wo, 0), device=x.device, dtype=x.dtype)
+    geo, out, _ = _conv2d_geometry(
+        who, x, w, bias, stride, pad,
+        also=lambda: slope.shape == (w.shape[0],) and all(t is None or t.shape == (x.shape[1],) for t in (in_scale, in_shift)),
+        more=f', slope {tuple(slope.shape)}, affine {[None if t is None else tuple(t.shape) for t in (in_scale, in_shift)]}')
     pre = [torch.empty_like(out)] if keep else []
-    _launch(f'te_{who}_f32', _ptr(out), *map(_ptr, pre), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), B, Ci, Co, H, W,
-            kh, kw, stride, pad[0], pad[1])
+    _launch(f'te_{who}_f32', _ptr(out), *map(_ptr, pre), _ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(in_scale), _ptr(in_shift), *geo)
     return (out, *pre) if keep else out
 
 

@@ -19,8 +19,8 @@
 // Taps outside the image, pixels >= P, channels >= Co and k >= K are zeros.  No im2col tensor, no workspace, no split of K, no atomics.
 // An output element is one chain over k ascending in the permutation of gemm_nt_f32.h (lane half h feeds k = 8q + 4h + u of every step
 // to MFMA (q, u)), which depends on nothing but K: an image's outputs are bitwise the same whatever batch and whatever tile it is in.
-// The kernel itself is the template conv2d_kernel<BN, AL, Gather, Epilogue> of conv2d_body.h, which resnet.hip instantiates with other
-// gathers and epilogues; te_conv2d_f32 is <GatherPlain, EpiBiasAct>.
+// The kernel itself is the template conv2d_kernel<BN, AL, Gather, Epilogue> of conv2d_body.h, which the other networks instantiate with
+// other gathers and epilogues through the same launch(); te_conv2d_f32 is <GatherPlain, EpiBiasAct>.
 #include "te_common.h"
 
 #ifdef CONV2D_PROF   // experimental builds: per-wave cycle counts of the three phases of the K loop, read back with te_debug_conv2d_prof
@@ -100,13 +100,6 @@ __global__ __launch_bounds__(256) void resize_kernel(float* __restrict__ out, co
     out[plane * OH * OW + i] = ly0 * (lx0 * ra[xa] + lx1 * ra[xb]) + ly1 * (lx0 * rb[xa] + lx1 * rb[xb]);
 }
 
-template <int BN>
-void launch_conv(const ConvArgs& a, bool al, hipStream_t st) {
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (al) conv2d_kernel<BN, true, GatherPlain, EpiBiasAct><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false, GatherPlain, EpiBiasAct><<<grid, NT, 0, st>>>(a);
-}
-
 }  // namespace
 
 extern "C" int te_conv2d_f32(float* out, const float* x, const float* w, const float* bias, int B, int Ci, int Co, int H, int W, int kh,
@@ -115,10 +108,7 @@ extern "C" int te_conv2d_f32(float* out, const float* x, const float* w, const f
     ConvArgs a;
     a.out = out; a.x = x; a.w = w; a.bias = bias;
     if (const int rc = fill_args(a, "te_conv2d_f32", B, Ci, Co, H, W, kh, kw, s, py, px, Ctot, c0, act)) return rc;
-    const bool al = a.K % 4 == 0 && te::aligned16(w);
-    hipStream_t st = (hipStream_t)stream;
-    if (wide_grid(a.P, Co)) launch_conv<128>(a, al, st);
-    else launch_conv<64>(a, al, st);
+    launch<GatherPlain, EpiBiasAct>(a, (hipStream_t)stream);
     return te::launch_status("te_conv2d_f32");
 }
 

@@ -1,6 +1,14 @@
-// The implicit-GEMM kernel of the general fp32 convolution as a template, shared by te_conv2d_f32 (conv2d.hip) and the ResNet entry points
-// (resnet.hip: te_conv2d_res_f32, te_pose_stem_fwd_f32), the AlexNet stem (lpips_alex.hip: te_alex_stem_fwd_f32), the IR-SE unit (irse.hip) and the
-// grouped head convolutions (psp_heads.hip), written once.  Compile-time policies make the variants:
+// The implicit-GEMM kernel of the general fp32 convolution as a template, with its launch and its checks, written once for every frozen
+// network that runs it:
+//     conv2d.hip      te_conv2d_f32 (Inception-v3 and the plain layers of all the others)
+//     resnet.hip      te_conv2d_res_f32, te_pose_stem_fwd_f32 (the ResNet-18 pose scorer)
+//     lpips_alex.hip  te_alex_stem_fwd_f32
+//     irse.hip        te_conv2d_prelu[_keep]_f32, te_id_stem_{fwd,keep}_f32 (ArcFace IR-SE50)
+//     irse_bwd.hip    te_conv2d_dgrad_f32, te_id_stem_bwd_f32 (its backward pass: the adjoint is the same loop over the gradient)
+//     psp_heads.hip   te_conv2d_heads_f32 (the pSp encoder's grouped heads)
+// A new network on this loop adds a gather, an epilogue and an entry point, and no launcher: the entry point checks what is its own,
+// fills its Args (ConvArgs or a struct derived from it; fill_args does the shared checks and the shared fields) and calls
+// launch<Gather, Epi[, Part]>(a, stream).  Compile-time policies make the variants:
 //     the gather   : where a tap of the patch comes from (GatherPlain: x[b, c, iy, ix] of a dense [B,Ci,H,W] tensor), and
 //     the epilogue : what happens to acc + bias before the store (EpiBiasAct: the activation),
 //     the part     : which range of k the workgroup runs and where the tile goes (PartWhole: all of it, into `out`; psp_heads.hip splits;
@@ -232,11 +240,28 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const Args a) {
 // BN = 128 where that still fills the chip, else 64 (the result does not depend on the choice)
 inline bool wide_grid(int64_t P, int Co) { return te::cdiv(P, 128) * te::cdiv(Co, BM) >= kWideGridMin; }
 
-// the checks and the fill of ConvArgs that every entry point on this loop shares; `who` names the entry point in the messages.
-// The loop itself takes any kernel size and stride; `max_kernel` and `stride4` are the entry point's own limits (the AlexNet stem of
-// lpips_alex.hip is 11 x 11 with stride 4, every other entry point keeps 7 x 7 and strides 1 and 2).
-inline int fill_args(ConvArgs& a, const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int Ctot, int c0,
-                     int act, int max_kernel = kMaxKernel, bool stride4 = false) {
+template <int BN, bool ALIGNED, class Gather, class Epi, class Part, class Args>
+void launch_tile(const Args& a, int S, hipStream_t st) {
+    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM), (unsigned)S);
+    if (ALIGNED && a.K % 4 == 0 && te::aligned16(a.w)) conv2d_kernel<BN, ALIGNED, Gather, Epi, Part, Args><<<grid, NT, 0, st>>>(a);
+    else conv2d_kernel<BN, false, Gather, Epi, Part, Args><<<grid, NT, 0, st>>>(a);
+}
+
+// THE launch of the loop: the tile (wide_grid), the weight loads (16-byte ones where K % 4 == 0 and w is aligned) and the grid, S
+// workgroups deep for a part that splits the k chain.  The library holds the kernel forms that the two flags allow and no others:
+// ALIGNED = false for an entry point whose K is fixed and no multiple of 4 (the pose and AlexNet stems; the identity stem has always
+// carried its unused aligned forms and goes on doing so), WIDE = false for one that was tuned at BN = 64 alone (the heads' split part).
+template <class Gather, class Epi, class Part = PartWhole, bool ALIGNED = true, bool WIDE = true, class Args>
+void launch(const Args& a, hipStream_t st, int S = 1) {
+    if (WIDE && wide_grid(a.P, a.Co)) launch_tile<WIDE ? 128 : 64, ALIGNED, Gather, Epi, Part>(a, S, st);
+    else launch_tile<64, ALIGNED, Gather, Epi, Part>(a, S, st);
+}
+
+// The geometry of a convolution, checked: -> Ho, Wo.  `who` names the entry point in the messages.  The loop itself takes any kernel
+// size and stride; `max_kernel` and `stride4` are the entry point's own limits (the AlexNet stem of lpips_alex.hip is 11 x 11 with
+// stride 4, every other entry point keeps 7 x 7 and strides 1 and 2).
+inline int check_geometry(const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int& Ho, int& Wo,
+                          int max_kernel = kMaxKernel, bool stride4 = false) {
     TE_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, TE_ERR_SHAPE, "%s: B, Ci, Co, H, W must be positive (got %d, %d, %d, %d, %d)", who,
                B, Ci, Co, H, W);
     TE_REQUIRE(kh >= 1 && kh <= max_kernel && kw >= 1 && kw <= max_kernel, TE_ERR_UNSUPPORTED, "%s: 1 <= kh, kw <= %d (got %d x %d)", who,
@@ -244,19 +269,37 @@ inline int fill_args(ConvArgs& a, const char* who, int B, int Ci, int Co, int H,
     TE_REQUIRE(s == 1 || s == 2 || (stride4 && s == 4), TE_ERR_UNSUPPORTED, "%s: the stride must be 1 or 2 (got %d)", who, s);
     TE_REQUIRE(py >= 0 && py < kh && px >= 0 && px < kw, TE_ERR_SHAPE,
                "%s: 0 <= py < kh and 0 <= px < kw (got padding %d, %d for a %d x %d kernel)", who, py, px, kh, kw);
-    TE_REQUIRE(act == 0 || act == 1, TE_ERR_UNSUPPORTED, "%s: act must be 0 (none) or 1 (ReLU), got %d", who, act);
     TE_REQUIRE(H + 2 * py >= kh && W + 2 * px >= kw, TE_ERR_SHAPE,
                "%s: a %d x %d kernel with padding %d, %d does not fit a %d x %d image (Ho, Wo >= 1)", who, kh, kw, py, px, H, W);
+    Ho = (H + 2 * py - kh) / s + 1;
+    Wo = (W + 2 * px - kw) / s + 1;
+    return 0;
+}
+
+// What the loop indexes with an int and what the grid can hold, for a launch that gathers kh x kw patches of [B,Ci,H,W] images into
+// Co channels of Ho x Wo pixels.  The data gradient (irse_bwd.hip) runs the loop the other way round and calls this with the roles swapped.
+inline int check_limits(const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int Ho, int Wo) {
+    TE_REQUIRE((int64_t)Ci * H * W <= 0x7fffffff && (int64_t)Ci * kh * kw <= 0x7fffffff - BK && (int64_t)Ho * Wo <= 0x7fffffff, TE_ERR_SHAPE,
+               "%s: one image (%d * %d * %d), a patch (%d * %d * %d) and a plane of pixels (%d * %d) must fit 31 bits", who, Ci, H, W, Ci, kh, kw,
+               Ho, Wo);
+    const int64_t P = (int64_t)B * Ho * Wo;
+    TE_REQUIRE(te::cdiv(P, 64) <= 0x7fffffff && te::cdiv(Co, BM) <= 65535, TE_ERR_SHAPE, "%s: too many outputs (%lld pixels, %d channels)", who,
+               (long long)P, Co);
+    return 0;
+}
+
+// the checks and the fill of ConvArgs that every forward entry point on this loop shares
+inline int fill_args(ConvArgs& a, const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int Ctot, int c0,
+                     int act, int max_kernel = kMaxKernel, bool stride4 = false) {
+    int Ho, Wo;
+    if (const int rc = check_geometry(who, B, Ci, Co, H, W, kh, kw, s, py, px, Ho, Wo, max_kernel, stride4)) return rc;
+    TE_REQUIRE(act == 0 || act == 1, TE_ERR_UNSUPPORTED, "%s: act must be 0 (none) or 1 (ReLU), got %d", who, act);
     TE_REQUIRE(c0 >= 0 && Ctot >= 1 && (int64_t)c0 + Co <= Ctot, TE_ERR_SHAPE, "%s: the slice [%d, %d + %d) is outside the %d output channels",
                who, c0, c0, Co, Ctot);
-    const int Ho = (H + 2 * py - kh) / s + 1, Wo = (W + 2 * px - kw) / s + 1;
-    TE_REQUIRE((int64_t)Ci * H * W <= 0x7fffffff && (int64_t)Ci * kh * kw <= 0x7fffffff - BK && (int64_t)Ho * Wo <= 0x7fffffff, TE_ERR_SHAPE,
-               "%s: one image (Ci * H * W), Ci * kh * kw and Ho * Wo must fit 31 bits", who);
+    if (const int rc = check_limits(who, B, Ci, Co, H, W, kh, kw, Ho, Wo)) return rc;
     a.P = (int64_t)B * Ho * Wo;
     a.Ci = Ci; a.Co = Co; a.H = H; a.W = W; a.kh = kh; a.kw = kw; a.s = s; a.py = py; a.px = px;
     a.Ho = Ho; a.Wo = Wo; a.Ctot = Ctot; a.c0 = c0; a.act = act; a.K = Ci * kh * kw;
-    TE_REQUIRE(te::cdiv(a.P, 64) <= 0x7fffffff && te::cdiv(Co, BM) <= 65535, TE_ERR_SHAPE, "%s: too many outputs (%lld pixels, %d channels)", who,
-               (long long)a.P, Co);
     return 0;
 }
 

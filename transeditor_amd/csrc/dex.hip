@@ -82,11 +82,7 @@ __global__ __launch_bounds__(kHeadThreads) void cls_score_kernel(float* __restri
 extern "C" int te_dex_stem_fwd_f32(float* out, const float* img, const float* w, const float* b, int N, int H, int W, int crop,
                                    te_stream_t stream) {
     TE_REQUIRE(out && img && w && b, TE_ERR_NULL, "te_dex_stem_fwd_f32: NULL pointer");
-    TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536, TE_ERR_SHAPE, "te_dex_stem_fwd_f32: bad dims");
-    TE_REQUIRE(crop >= 1 && crop <= H && crop <= W && crop <= 32768, TE_ERR_SHAPE,
-               "te_dex_stem_fwd_f32: the crop (%d) must be positive and fit the %d x %d image", crop, H, W);
-    TE_REQUIRE((H - crop) % 2 == 0 && (W - crop) % 2 == 0, TE_ERR_SHAPE,
-               "te_dex_stem_fwd_f32: a centre crop of %d needs H - crop and W - crop even (got %d x %d)", crop, H, W);
+    if (const int rc = te::check_centre_crop("te_dex_stem_fwd_f32", N, H, W, crop, 64)) return rc;      // (conv1_1 has 64 channels)
     te::launch_vgg_stem<StemByteBgr>(out, img, w, b, N, H, W, crop, crop, (H - crop) / 2, (W - crop) / 2, stream);
     return te::launch_status("te_dex_stem_fwd_f32");
 }

@@ -15,10 +15,13 @@
 // pre-activation, for the backward pass of irse_bwd.hip.  No atomics, no workspace, every reduction a fixed-order chain or a fixed-shape tree.
 #include "te_common.h"
 #include "conv2d_body.h"
+#include "irse_common.h"
 
 namespace {
 
 using namespace te::conv2d;
+using namespace te::irse;
+using te::wave_sum;
 
 // ------------------------------------------------------------------------------------------------------ the two convolutions
 struct PreluArgs : ConvArgs {
@@ -49,8 +52,9 @@ struct GatherPooled {
     }
     static __device__ __forceinline__ int plane(const IdStemArgs& a) { return a.IH * a.IW; }
     static __device__ __forceinline__ float tap(const float* img, const IdStemArgs& a, int HW, int c, int iy, int ix) {
-        const int ya = iy * a.Lh / a.H, yb = ((iy + 1) * a.Lh + a.H - 1) / a.H;         // (Pn, Lh <= 32768: the products fit)
-        const int xa = ix * a.Lw / a.W, xb = ((ix + 1) * a.Lw + a.W - 1) / a.W;
+        int ya, yb, xa, xb;
+        te::adaptive_window<int>(iy, a.Lh, a.H, ya, yb);                                // (Pn, Lh <= 32768: the products fit)
+        te::adaptive_window<int>(ix, a.Lw, a.W, xa, xb);
         const float* src = img + c * HW;
         float s = 0.f;
         bool first = true;
@@ -82,55 +86,25 @@ struct EpiPreluKeep {
     }
 };
 
-template <int BN, class Gather, class Epi, class Args>
-void launch_conv(const Args& a, bool al, hipStream_t st) {
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (al) conv2d_kernel<BN, true, Gather, Epi><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false, Gather, Epi><<<grid, NT, 0, st>>>(a);
-}
-
 // (a.pre set: the keeping epilogue)
 template <class Gather, class Args>
-void launch_either(const Args& a, bool al, hipStream_t st) {
-    if (a.pre) {
-        if (wide_grid(a.P, a.Co)) launch_conv<128, Gather, EpiPreluKeep>(a, al, st);
-        else launch_conv<64, Gather, EpiPreluKeep>(a, al, st);
-    } else {
-        if (wide_grid(a.P, a.Co)) launch_conv<128, Gather, EpiPrelu>(a, al, st);
-        else launch_conv<64, Gather, EpiPrelu>(a, al, st);
-    }
+void launch_either(const Args& a, hipStream_t st) {
+    if (a.pre) launch<Gather, EpiPreluKeep>(a, st);
+    else launch<Gather, EpiPrelu>(a, st);
 }
 
 // ------------------------------------------------------------------------------------------------------ squeeze-and-excitation
 // One workgroup of four waves per image.  Step 1: the waves split the R hidden units; a unit is one wave's dot product over the C
 // pooled values (lane l takes k = l, l + 64, ... as one fma chain, the lanes' sums meet in a butterfly), ReLU -> LDS.  Step 2: a
 // thread per channel (c = t, t + 256, ...): one fma chain over the R hidden units in ascending order, then the sigmoid with the
-// exponential of the NEGATIVE magnitude, so nothing overflows.  Nothing depends on B.
-constexpr int kSeThreads = 256;
-constexpr int kSeMaxR = 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
+// exponential of the NEGATIVE magnitude, so nothing overflows.  Nothing depends on B.  (A unit is se_unit of irse_common.h.)
 __global__ __launch_bounds__(kSeThreads) void se_excite_kernel(float* __restrict__ gate, const float* __restrict__ pooled,
                                                                const float* __restrict__ w1, const float* __restrict__ w2, int C, int R) {
     __shared__ float hidden[kSeMaxR];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const float* p = pooled + (int64_t)blockIdx.x * C;
     for (int r = wid; r < R; r += kSeThreads / 64) {
-        const float* w = w1 + (int64_t)r * C;
-        float acc = 0.f;
-        for (int k = lane; k < C; k += 64) acc = fmaf(w[k], p[k], acc);
-        acc = wave_sum(acc);
+        const float acc = se_unit(p, w1, C, r, lane);
         if (lane == 0) hidden[r] = te::relu_nan(acc);
     }
     __syncthreads();
@@ -224,10 +198,9 @@ int conv2d_prelu(const char* who, float* out, float* pre, const float* x, const 
     PreluArgs a;
     a.out = out; a.x = x; a.w = w; a.bias = bias; a.slope = slope; a.in_scale = in_scale; a.in_shift = in_shift; a.pre = pre;
     if (const int rc = fill_args(a, who, B, Ci, Co, H, W, kh, kw, s, py, px, Co, 0, 0)) return rc;
-    const bool al = a.K % 4 == 0 && te::aligned16(w);
     hipStream_t st = (hipStream_t)stream;
-    if (in_scale) launch_either<GatherAffine>(a, al, st);
-    else launch_either<GatherPlain>(a, al, st);
+    if (in_scale) launch_either<GatherAffine>(a, st);
+    else launch_either<GatherPlain>(a, st);
     return te::launch_status(who);
 }
 
@@ -235,18 +208,12 @@ int conv2d_prelu(const char* who, float* out, float* pre, const float* x, const 
 int id_stem(const char* who, float* out, float* pre, const float* img, const float* w, const float* b, const float* slope, int N, int H, int W,
             int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream) {
     TE_REQUIRE(out && img && w && b && slope, TE_ERR_NULL, "%s: NULL pointer", who);
-    TE_REQUIRE(N >= 1 && N < 65536 && H >= 1 && W >= 1 && Co >= 1, TE_ERR_SHAPE, "%s: 1 <= N < 65536 and positive H, W, Co (got %d, %d, %d, %d)", who,
-               N, H, W, Co);
-    TE_REQUIRE(y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W, TE_ERR_SHAPE,
-               "%s: the window [%d, %d) x [%d, %d) must be non-empty and inside the %d x %d image", who, y0, y1, x0, x1, H, W);
-    TE_REQUIRE(Pn >= 1 && Pn <= 32768 && y1 - y0 <= 32768 && x1 - x0 <= 32768, TE_ERR_SHAPE,
-               "%s: 1 <= Pn <= 32768 and a window of at most 32768 x 32768 (got Pn = %d, %d x %d)", who, Pn, y1 - y0, x1 - x0);
-    TE_REQUIRE((int64_t)3 * H * W <= 0x7fffffff, TE_ERR_SHAPE, "%s: one image (3 * H * W) must fit 31 bits", who);
+    if (const int rc = check_id_window(who, N, H, W, y0, y1, x0, x1, Pn, Co)) return rc;
     IdStemArgs a;
     a.out = out; a.x = img; a.w = w; a.bias = b; a.slope = slope; a.in_scale = nullptr; a.in_shift = nullptr; a.pre = pre;
     if (const int rc = fill_args(a, who, N, 3, Co, Pn, Pn, 3, 3, 1, 1, 1, Co, 0, 0)) return rc;
     a.IH = H; a.IW = W; a.y0 = y0; a.x0 = x0; a.Lh = y1 - y0; a.Lw = x1 - x0;
-    launch_either<GatherPooled>(a, false, (hipStream_t)stream);                  // K = 27: the unaligned weight path
+    launch_either<GatherPooled>(a, (hipStream_t)stream);                         // K = 27 takes the unaligned weight path
     return te::launch_status(who);
 }
 

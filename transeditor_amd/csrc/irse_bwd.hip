@@ -13,11 +13,12 @@
 // No atomics; every reduction is a fixed-order chain or a fixed-shape tree; an image's gradient is bitwise independent of its batch.
 #include "te_common.h"
 #include "conv2d_body.h"
-#include "wave_dot.h"
+#include "irse_common.h"
 
 namespace {
 
 using namespace te::conv2d;
+using namespace te::irse;
 
 // ------------------------------------------------------------------------------------------------------ the data gradient
 // The loop's view of one phase: its "input" is g [B,Co,Ho,Wo] (Ci, H, W of ConvArgs), its "output channels" are the forward's input
@@ -63,14 +64,6 @@ struct EpiDgrad {
     }
 };
 
-template <int BN, class Gather, class Epi, class Args>
-void launch_phase(const Args& a, hipStream_t st) {
-    const bool al = a.K % 4 == 0 && te::aligned16(a.w);
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (al) conv2d_kernel<BN, true, Gather, Epi, PartPhase, Args><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false, Gather, Epi, PartPhase, Args><<<grid, NT, 0, st>>>(a);
-}
-
 // the taps ky = k0 + s j (j < n) that reach output rows of parity r, and the padding of the phase's stride-1 convolution over g with
 // those taps flipped: row y = s yy + r reads g rows yy - pad + j', j' = n - 1 - j
 struct Phase { int k0, n, pad; };
@@ -99,39 +92,20 @@ void launch_dgrad(Args a, const float* wt, int B, int Cx, int Co, int H, int W, 
             a.Ho = Hp; a.Wo = Wp; a.P = (int64_t)B * Hp * Wp; a.ry = ry; a.rx = rx;
             wt += (int64_t)Cx * a.K;
             if (a.P == 0) continue;
-            if (wide_grid(a.P, a.Co)) launch_phase<128, Gather, EpiDgrad>(a, st);
-            else launch_phase<64, Gather, EpiDgrad>(a, st);
+            launch<Gather, EpiDgrad, PartPhase>(a, st);
         }
 }
 
-// the checks of te_conv2d_dgrad_f32 and te_id_stem_bwd_f32; -> Ho, Wo
+// the checks of te_conv2d_dgrad_f32 and te_id_stem_bwd_f32 on the forward layer's geometry; -> Ho, Wo.  The loop runs the other way
+// round: it gathers g [B,Co,Ho,Wo] into the Ci channels of gx; the epilogue indexes one image of gx with an int
 int check_dgrad(const char* who, int B, int Ci, int Co, int H, int W, int kh, int kw, int s, int py, int px, int& Ho, int& Wo) {
-    TE_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, TE_ERR_SHAPE, "%s: B, Ci, Co, H, W must be positive (got %d, %d, %d, %d, %d)", who,
-               B, Ci, Co, H, W);
-    TE_REQUIRE(kh >= 1 && kh <= kMaxKernel && kw >= 1 && kw <= kMaxKernel, TE_ERR_UNSUPPORTED, "%s: 1 <= kh, kw <= %d (got %d x %d)", who,
-               kMaxKernel, kh, kw);
-    TE_REQUIRE(s == 1 || s == 2, TE_ERR_UNSUPPORTED, "%s: the stride must be 1 or 2 (got %d)", who, s);
-    TE_REQUIRE(py >= 0 && py < kh && px >= 0 && px < kw, TE_ERR_SHAPE, "%s: 0 <= py < kh and 0 <= px < kw (got padding %d, %d for a %d x %d kernel)",
-               who, py, px, kh, kw);
-    TE_REQUIRE(H + 2 * py >= kh && W + 2 * px >= kw, TE_ERR_SHAPE, "%s: a %d x %d kernel with padding %d, %d does not fit a %d x %d image", who, kh,
-               kw, py, px, H, W);
-    Ho = (H + 2 * py - kh) / s + 1;
-    Wo = (W + 2 * px - kw) / s + 1;
-    TE_REQUIRE((int64_t)Ci * H * W <= 0x7fffffff && (int64_t)Co * Ho * Wo <= 0x7fffffff && (int64_t)Co * kh * kw <= 0x7fffffff - BK,
-               TE_ERR_SHAPE, "%s: one image of gx (Ci * H * W), one of g (Co * Ho * Wo) and Co * kh * kw must fit 31 bits", who);
-    TE_REQUIRE(te::cdiv((int64_t)B * H * W, 64) <= 0x7fffffff && te::cdiv(Ci, BM) <= 65535, TE_ERR_SHAPE,
-               "%s: too many outputs (%lld pixels, %d channels)", who, (long long)B * H * W, Ci);
-    return 0;
+    if (const int rc = check_geometry(who, B, Ci, Co, H, W, kh, kw, s, py, px, Ho, Wo)) return rc;
+    TE_REQUIRE((int64_t)Ci * H * W <= 0x7fffffff, TE_ERR_SHAPE, "%s: one image of gx (%d * %d * %d) must fit 31 bits", who, Ci, H, W);
+    return check_limits(who, B, Co, Ci, Ho, Wo, kh, kw, H, W);
 }
 
 // ------------------------------------------------------------------------------------------------------ squeeze-and-excitation
-using te::wave_sum;              // (float: wave_dot.h)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+using te::wave_sum;
 
 // ggate[plane] = sum_hw gout * r: one wave per plane, lane l takes i = l, l + 64, ... as one fma chain, the lanes meet in a butterfly
 __global__ __launch_bounds__(256) void se_ggate_kernel(float* __restrict__ ggate, const float* __restrict__ gout, const float* __restrict__ r,
@@ -147,13 +121,10 @@ __global__ __launch_bounds__(256) void se_ggate_kernel(float* __restrict__ ggate
     if (lane == 0) ggate[plane] = acc;
 }
 
-// One workgroup of four waves per image, as se_excite_kernel.  Step 1: the hidden units again, with se_excite_kernel's arithmetic (they
-// are not kept).  Step 2: a live hidden unit's gradient is one wave's dot product over the channels of w2[:, r] with
+// One workgroup of four waves per image, as se_excite_kernel.  Step 1: the hidden units again, by se_excite_kernel's own se_unit (they
+// are not kept), before the ReLU.  Step 2: a live hidden unit's gradient is one wave's dot product over the channels of w2[:, r] with
 // gz[c] = ggate[c] * gate[c] * (1 - gate[c]); a dead one (hidden <= 0 or NaN: torch's threshold rule) gets 0.  Step 3: a thread per
 // channel, one fma chain over r ascending, divided by the plane: what every pixel of r[b,c] receives through the mean.
-constexpr int kSeThreads = 256;
-constexpr int kSeMaxR = 1024;
-
 __global__ __launch_bounds__(kSeThreads) void se_bwd_kernel(float* __restrict__ gmean, const float* __restrict__ ggate,
                                                             const float* __restrict__ gate, const float* __restrict__ pooled,
                                                             const float* __restrict__ w1, const float* __restrict__ w2, int C, int R, float hw) {
@@ -164,10 +135,7 @@ __global__ __launch_bounds__(kSeThreads) void se_bwd_kernel(float* __restrict__ 
     const float* gg = ggate + (int64_t)blockIdx.x * C;
     const float* gt = gate + (int64_t)blockIdx.x * C;
     for (int r = wid; r < R; r += kSeThreads / 64) {
-        const float* w = w1 + (int64_t)r * C;
-        float acc = 0.f;
-        for (int k = lane; k < C; k += 64) acc = fmaf(w[k], p[k], acc);
-        acc = wave_sum(acc);
+        const float acc = se_unit(p, w1, C, r, lane);
         if (lane == 0) hidden[r] = acc;
     }
     __syncthreads();
@@ -233,10 +201,10 @@ __global__ __launch_bounds__(256) void stem_unpool_kernel(float* __restrict__ gi
     const int64_t plane = o / W / H;
     float s = 0.f;
     if ((unsigned)y < (unsigned)Lh && (unsigned)x < (unsigned)Lw) {
-        const int ia = y * Pn / Lh, ib = ((y + 1) * Pn - 1) / Lh;              // (Pn, L <= 32768: the products fit)
+        const int ia = y * Pn / Lh, ib = ((y + 1) * Pn - 1) / Lh;              // the windows' inverse (Pn, L <= 32768: the products fit)
         const int ja = x * Pn / Lw, jb = ((x + 1) * Pn - 1) / Lw;
         const float* src = gp + plane * Pn * Pn;
-        for (int i = ia; i <= ib; ++i) {
+        for (int i = ia; i <= ib; ++i) {                     // (its own copy of te::adaptive_window's bounds: the call changes the instruction stream)
             const int rows = ((i + 1) * Lh + Pn - 1) / Pn - i * Lh / Pn;
             for (int j = ja; j <= jb; ++j) {
                 const int cols = ((j + 1) * Lw + Pn - 1) / Pn - j * Lw / Pn;
@@ -310,13 +278,8 @@ extern "C" int te_se_bwd_f32(float* gr, float* ws, const float* gout, const floa
 extern "C" int te_id_stem_bwd_f32(float* gimg, float* ws, const float* g, const float* wt, const float* pre, const float* slope, int N, int H,
                                   int W, int y0, int y1, int x0, int x1, int Pn, int Co, te_stream_t stream) {
     TE_REQUIRE(gimg && ws && g && wt && pre && slope, TE_ERR_NULL, "te_id_stem_bwd_f32: NULL pointer");
-    TE_REQUIRE(N >= 1 && N < 65536 && H >= 1 && W >= 1 && Co >= 1, TE_ERR_SHAPE,
-               "te_id_stem_bwd_f32: 1 <= N < 65536 and positive H, W, Co (got %d, %d, %d, %d)", N, H, W, Co);
-    TE_REQUIRE(y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W, TE_ERR_SHAPE,
-               "te_id_stem_bwd_f32: the window [%d, %d) x [%d, %d) must be non-empty and inside the %d x %d image", y0, y1, x0, x1, H, W);
-    TE_REQUIRE(Pn >= 1 && Pn <= 32768 && y1 - y0 <= 32768 && x1 - x0 <= 32768, TE_ERR_SHAPE,
-               "te_id_stem_bwd_f32: 1 <= Pn <= 32768 and a window of at most 32768 x 32768 (got Pn = %d, %d x %d)", Pn, y1 - y0, x1 - x0);
-    TE_REQUIRE((int64_t)3 * H * W <= 0x7fffffff && te::cdiv((int64_t)N * 3 * H * W, 256) <= 0x7fffffff, TE_ERR_SHAPE,
+    if (const int rc = check_id_window("te_id_stem_bwd_f32", N, H, W, y0, y1, x0, x1, Pn, Co)) return rc;
+    TE_REQUIRE(te::cdiv((int64_t)N * 3 * H * W, 256) <= 0x7fffffff, TE_ERR_SHAPE,
                "te_id_stem_bwd_f32: one image (3 * H * W) must fit 31 bits and the batch 2^39 elements");
     int Ho, Wo;
     if (const int rc = check_dgrad("te_id_stem_bwd_f32", N, 3, Co, Pn, Pn, 3, 3, 1, 1, 1, Ho, Wo)) return rc;

@@ -33,12 +33,6 @@ struct GatherScaled {
     }
 };
 
-template <int BN>
-void launch_stem(const ConvArgs& a, hipStream_t st) {
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    conv2d_kernel<BN, false, GatherScaled, EpiBiasAct><<<grid, NT, 0, st>>>(a);      // K = 363: the unaligned weight path
-}
-
 // ------------------------------------------------------------------------------------------------ the unit normalisation
 // A block is 16 waves over a tile of PT = min(256, HW rounded up to 64) pixels, as pair_head_kernel (lpips.hip): PT / 64 waves side
 // by side along the pixels, the other factor CG = 1024 / PT splits the channel loop.  Pass 1: each thread's sum of squares over its
@@ -231,9 +225,7 @@ extern "C" int te_alex_stem_fwd_f32(float* out, const float* x, const float* w, 
     ConvArgs a;
     a.out = out; a.x = x; a.w = w; a.bias = b;
     if (const int rc = fill_args(a, "te_alex_stem_fwd_f32", N, 3, Co, H, W, 11, 11, 4, 2, 2, Co, 0, 1, 11, true)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (wide_grid(a.P, Co)) launch_stem<128>(a, st);
-    else launch_stem<64>(a, st);
+    launch<GatherScaled, EpiBiasAct, PartWhole, false>(a, (hipStream_t)stream);                  // K = 363: the unaligned weight path
     return te::launch_status("te_alex_stem_fwd_f32");
 }
 

@@ -63,13 +63,6 @@ struct PartSplit : DestDense {
     static __device__ __forceinline__ float finish(const HeadsArgs& a, float acc, int m) { return acc; }
 };
 
-template <int BN, class Epi, class Part>
-void launch_heads(const HeadsArgs& a, bool al, int S, hipStream_t st) {
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM), (unsigned)S);
-    if (al) conv2d_kernel<BN, true, GatherHeads, Epi, Part><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false, GatherHeads, Epi, Part><<<grid, NT, 0, st>>>(a);
-}
-
 // out[b, c0 + m, r] = leaky(((ws[0] + ws[1]) + ... + ws[S - 1]) + bias[m]); one thread per output element
 __global__ __launch_bounds__(256) void heads_reduce_kernel(float* __restrict__ out, const float* __restrict__ ws, const float* __restrict__ bias,
                                                            int64_t total, int64_t part, int Co, int HoWo, int S, int Ctot, int c0, float slope) {
@@ -195,11 +188,9 @@ extern "C" int te_conv2d_heads_f32(float* out, float* ws, int64_t ws_bytes, cons
     a.Cg = Cg; a.kper = per * BK; a.slope = slope;
     a.part = (int64_t)B * a.Co * HoWo;
     TE_REQUIRE(a.part <= ((int64_t)1 << 56) / (4 * kMaxSplits), TE_ERR_SHAPE, "te_conv2d_heads_f32: too many outputs (%lld)", (long long)a.part);
-    const bool al = a.K % 4 == 0 && te::aligned16(w);
     hipStream_t st = (hipStream_t)stream;
     if (S == 1) {
-        if (wide_grid(a.P, a.Co)) launch_heads<128, EpiLeaky, PartWhole>(a, al, 1, st);
-        else launch_heads<64, EpiLeaky, PartWhole>(a, al, 1, st);
+        launch<GatherHeads, EpiLeaky>(a, st);
         return te::launch_status("te_conv2d_heads_f32");
     }
     TE_REQUIRE(ws && ws_bytes >= S * a.part * 4, TE_ERR_WORKSPACE, "te_conv2d_heads_f32: %d ranges of k need a workspace of %lld bytes (got %lld)", S,
@@ -207,7 +198,7 @@ extern "C" int te_conv2d_heads_f32(float* out, float* ws, int64_t ws_bytes, cons
     TE_REQUIRE(te::cdiv(a.part, 256) <= 0x7fffffff, TE_ERR_SHAPE, "te_conv2d_heads_f32: too many outputs (%lld)", (long long)a.part);
     HeadsArgs p = a;
     p.out = ws; p.Ctot = a.Co; p.c0 = 0;
-    launch_heads<64, EpiPartial, PartSplit>(p, al, S, st);
+    launch<GatherHeads, EpiPartial, PartSplit, true, false>(p, st, S);                            // the rule splits planes of one 64-pixel tile: BN = 64 alone
     heads_reduce_kernel<<<(unsigned)te::cdiv(a.part, 256), 256, 0, st>>>(out, ws, bias, a.part, a.part, a.Co, (int)HoWo, S, Ctot, c0, slope);
     return te::launch_status("te_conv2d_heads_f32");
 }

@@ -74,20 +74,6 @@ __global__ __launch_bounds__(256) void maxpool3s2p1_kernel(float* __restrict__ o
     out[o] = v;
 }
 
-template <int BN>
-void launch_res(const ResArgs& a, bool al, hipStream_t st) {
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (al) conv2d_kernel<BN, true, GatherPlain, EpiResidual><<<grid, NT, 0, st>>>(a);
-    else conv2d_kernel<BN, false, GatherPlain, EpiResidual><<<grid, NT, 0, st>>>(a);
-}
-
-template <int BN>
-void launch_stem(const StemArgs& a, bool byte, hipStream_t st) {
-    const dim3 grid((unsigned)te::cdiv(a.P, BN), (unsigned)te::cdiv(a.Co, BM));
-    if (byte) conv2d_kernel<BN, false, GatherCrop<true>, EpiBiasAct><<<grid, NT, 0, st>>>(a);      // K = 147: the unaligned weight path
-    else conv2d_kernel<BN, false, GatherCrop<false>, EpiBiasAct><<<grid, NT, 0, st>>>(a);
-}
-
 }  // namespace
 
 extern "C" int te_conv2d_res_f32(float* out, const float* x, const float* w, const float* bias, const float* res, int B, int Ci, int Co, int H,
@@ -96,10 +82,7 @@ extern "C" int te_conv2d_res_f32(float* out, const float* x, const float* w, con
     ResArgs a;
     a.out = out; a.x = x; a.w = w; a.bias = bias; a.res = res;
     if (const int rc = fill_args(a, "te_conv2d_res_f32", B, Ci, Co, H, W, kh, kw, s, py, px, Co, 0, act)) return rc;
-    const bool al = a.K % 4 == 0 && te::aligned16(w);
-    hipStream_t st = (hipStream_t)stream;
-    if (wide_grid(a.P, Co)) launch_res<128>(a, al, st);
-    else launch_res<64>(a, al, st);
+    launch<GatherPlain, EpiResidual>(a, (hipStream_t)stream);
     return te::launch_status("te_conv2d_res_f32");
 }
 
@@ -108,20 +91,15 @@ extern "C" int te_pose_stem_fwd_f32(float* out, const float* img, const float* w
     TE_REQUIRE(out && img && w && b, TE_ERR_NULL, "te_pose_stem_fwd_f32: NULL pointer");
     TE_REQUIRE(preprocessed == 0 || preprocessed == 1, TE_ERR_UNSUPPORTED,
                "te_pose_stem_fwd_f32: preprocessed must be 0 (RGB in [-1, 1]) or 1 (BGR byte levels), got %d", preprocessed);
-    TE_REQUIRE(N > 0 && H > 0 && W > 0 && N < 65536 && Co >= 1, TE_ERR_SHAPE,
-               "te_pose_stem_fwd_f32: 1 <= N < 65536 and positive H, W, Co (got %d, %d, %d, %d)", N, H, W, Co);
-    TE_REQUIRE(crop >= 1 && crop <= H && crop <= W && crop <= 32768, TE_ERR_SHAPE,
-               "te_pose_stem_fwd_f32: the crop (%d) must be positive and fit the %d x %d image", crop, H, W);
-    TE_REQUIRE((H - crop) % 2 == 0 && (W - crop) % 2 == 0, TE_ERR_SHAPE,
-               "te_pose_stem_fwd_f32: a centre crop of %d needs H - crop and W - crop even (got %d x %d)", crop, H, W);
+    if (const int rc = te::check_centre_crop("te_pose_stem_fwd_f32", N, H, W, crop, Co)) return rc;
     TE_REQUIRE((int64_t)3 * H * W <= 0x7fffffff, TE_ERR_SHAPE, "te_pose_stem_fwd_f32: one image (3 * H * W) must fit 31 bits");
     StemArgs a;
     a.out = out; a.x = img; a.w = w; a.bias = b;
     if (const int rc = fill_args(a, "te_pose_stem_fwd_f32", N, 3, Co, crop, crop, 7, 7, 2, 3, 3, Co, 0, 1)) return rc;
     a.IH = H; a.IW = W; a.y0 = (H - crop) / 2; a.x0 = (W - crop) / 2;
     hipStream_t st = (hipStream_t)stream;
-    if (wide_grid(a.P, Co)) launch_stem<128>(a, preprocessed == 0, st);
-    else launch_stem<64>(a, preprocessed == 0, st);
+    if (preprocessed == 0) launch<GatherCrop<true>, EpiBiasAct, PartWhole, false>(a, st);        // K = 147: the unaligned weight path
+    else launch<GatherCrop<false>, EpiBiasAct, PartWhole, false>(a, st);
     return te::launch_status("te_pose_stem_fwd_f32");
 }
 

@@ -30,6 +30,14 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // torch's relu: a NaN fails both comparisons and propagates
 __device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 
+// AdaptiveAvgPool's window of output i where L inputs become P outputs: [lo, hi) = [floor(i L / P), ceil((i + 1) L / P)).  T is the
+// type of the products: int64_t, or int where the caller's limits (P, L <= 32768) make them fit
+template <class T>
+__device__ __forceinline__ void adaptive_window(int i, int L, int P, int& lo, int& hi) {
+    lo = (int)((T)i * L / P);
+    hi = (int)(((T)(i + 1) * L + P - 1) / P);
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE property: do it once per (kernel, device), safely from
 // any host thread (the autograd engine's backward threads call the ABI concurrently; setting it twice is harmless).
 inline void allow_big_lds(std::atomic<uint64_t>& done, const void* fn, int bytes) {

@@ -150,8 +150,9 @@ __global__ __launch_bounds__(256) void adaptive_avgpool_kernel(float* __restrict
     if (o >= total) return;
     const int ox = (int)(o % OW), oy = (int)(o / OW % OH);
     const int64_t p = o / OW / OH;
-    const int y0 = (int)((int64_t)oy * H / OH), y1 = (int)(((int64_t)(oy + 1) * H + OH - 1) / OH);
-    const int x0 = (int)((int64_t)ox * W / OW), x1 = (int)(((int64_t)(ox + 1) * W + OW - 1) / OW);
+    int y0, y1, x0, x1;
+    te::adaptive_window<int64_t>(oy, H, OH, y0, y1);
+    te::adaptive_window<int64_t>(ox, W, OW, x0, x1);
     const float* src = x + p * H * W;
     float s = 0.f;
     bool first = true;

@@ -1,4 +1,5 @@
-// One wave's reductions and its row dot product, shared by the score heads (csrc/dex.hip, csrc/celeba_attr.hip).
+// One wave's reductions and its row dot product, shared by the score heads (csrc/dex.hip, csrc/celeba_attr.hip) and the IR-SE50
+// identity network (csrc/irse.hip, csrc/irse_bwd.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,12 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // all 64 lanes end with the same value: a butterfly whose shape does not depend on the data
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
