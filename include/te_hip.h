@@ -1063,6 +1063,43 @@ int te_id_stem_bwd_f32(float* gimg, float* ws, const float* g, const float* wt, 
 int te_rows_unit_bwd_f32(float* ga, const float* ge, const float* e, const float* a, int64_t I, int D, te_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * M8b  the AlexNet LPIPS as a LOSS (pSp/criteria/lpips/lpips.py:29-35 LPIPS('alex').forward with networks.py:35-84 and utils.py:6-8, the
+ * lpips_lambda term of pSp/training/coach_new.py:285-320 calc_loss): its backward pass with respect to the first image, which the
+ * reference leaves to torch autograd.  This LPIPS normalises a tap as x / (sqrt(sum_c x^2) + 1e-10), eps BESIDE the root: its heads are
+ * L1's te_lpips_normalize_f32 / te_lpips_head_fwd_f32 / te_lpips_head_bwd_f32 (not M8's te_lpips_unit_f32), the forward trunk is M8's
+ * te_alex_stem_fwd_f32 with M4's te_pool3_f32 and te_conv2d_f32, the data gradients of conv2 ... conv5 are M9b's te_conv2d_dgrad_f32;
+ * here the two adjoints that are left (csrc/lpips_alex_bwd.hip).  The network is frozen: there is no weight gradient.  NCHW fp32, no
+ * atomics, no workspace, fixed-order sums: bit-reproducible, and an image's gradient is bitwise independent of the batch it is in.
+ * Nothing is launched on a refusal.
+ *
+ * te_pool3s2_max_bwd_f32 (the adjoint of te_pool3_f32 mode 0 = nn.MaxPool2d(3, 2), features[2] and [5] of torchvision's alexnet): x, gx
+ * `planes` planes of H x W, g `planes` planes of Ho x Wo, Ho = (H - 3) / 2 + 1, Wo likewise.  The windows overlap, so this is a GATHER:
+ * an input pixel lies in at most 2 x 2 windows; for each it recomputes the argmax from x and it sums the g of the windows whose argmax
+ * it is, window rows then columns ascending, from 0.  The argmax rule is torch's: the scan is ky, then kx, ascending, and a later
+ * element replaces the current one only if it is greater or is a NaN, so the first of equal maxima wins and the last NaN of a window
+ * takes its gradient.  ALL of gx is written: a pixel that wins no window, and the last row / column where (H - 3) % 2 == 1 (W
+ * likewise), which no window reaches, are exactly 0.  TE_ERR_NULL for a NULL pointer; TE_ERR_SHAPE for planes, H or W < 1, H < 3 or
+ * W < 3 (as the forward), a plane past 31 bits or more than 2^31 - 1 blocks of 256 pixels.
+ *
+ * te_alex_stem_dgrad_f32 (the adjoint of te_alex_stem_fwd_f32 without its ReLU: the caller's g is already masked, which
+ * te_lpips_head_bwd_f32 does): g [N,Co,Ho,Wo], Ho = (H - 7) / 4 + 1, Wo likewise; gimg [N,3,H,W], the gradient of the UNSCALED image:
+ *     gimg[n,c,y,x] = (sum over (o,ky,kx) with y + 2 - ky = 4 oy, x + 2 - kx = 4 ox, 0 <= oy < Ho, 0 <= ox < Wo
+ *                      of w[o,c,ky,kx] * g[n,o,oy,ox]) / sigma[c]             sigma (0.458, 0.448, 0.450)
+ * the sum one fma chain from 0 over o, then ky, then kx ascending, the division one correctly rounded fp32 step (torch's backward of
+ * (x - mu) / sigma; mu and the zero padding drop out).  Per axis and output parity r < 4 the taps that reach rows y = 4 yy + r are
+ * k = k0 + 4 j, k0 = (r + 2) % 4, j < n = (3, 2, 3, 3)[r], read from the gradient rows yy + (r + 2) / 4 - j: 16 dense phases with
+ * sub-kernels of 3 x 3 down to 2 x 2, never a walk over the zero-inserted plane.  wt holds, for ry = 0 ... 3, a block [Co, ny, 11, 3]:
+ *     wt[ry][o, jy, kx, c] = w[o, c, k0(ry) + 4 jy, kx]                       363 Co floats, made once by the caller
+ * (rows split by phase, columns whole: a lane owns the four column phases of its position, because together they read four
+ * neighbouring gradient columns; the weight index is uniform over a wave, which owns one ry).  A pixel that no window reaches is
+ * exactly 0 (column 29 of a 30-wide image: its taps kx = 3, 7 ask for ox = 7, 6 >= Wo = 6).  A NaN in g reaches exactly the pixels one
+ * of whose taps reads it, on all three channels.  Limits are te_alex_stem_fwd_f32's: TE_ERR_NULL for a NULL pointer; TE_ERR_SHAPE for
+ * N < 1, N >= 65536, H, W or Co < 1, H + 4 < 11 or W + 4 < 11, 3 * H * W or Co * Ho * Wo past 31 bits.
+ */
+int te_pool3s2_max_bwd_f32(float* gx, const float* g, const float* x, int64_t planes, int H, int W, te_stream_t stream);
+int te_alex_stem_dgrad_f32(float* gimg, const float* g, const float* wt, int N, int H, int W, int Co, te_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * M10  the dual-space pSp encoder of real-image inversion (pSp/models/encoders/psp_encoders_new.py:35-140
  * GradualStyleEncoder(50, 'ir_se'), applied by pSp/models/psp_new.py:90-109 pSp.forward).  input_layer and body are M9's
  * te_conv2d_prelu_f32 and IR-SE units, the two lateral 1x1 convolutions are M4's te_conv2d_f32; here what sits on the backbone

@@ -1469,6 +1469,44 @@ def rows_unit_bwd(ge, e, a):
     return ga
 
 
+# --------------------------------------------------------------------------------------------- M8b AlexNet LPIPS as a loss
+@_op
+def pool3s2_max_bwd(g, x):
+    """MaxPool2d(3, 2) backwards (the adjoint of pool3 with POOL3_MAX_S2): x [B,C,H,W] the pool's input, g [B,C,Ho,Wo] -> gx [B,C,H,W],
+    every element written; torch's tie rule (the first of equal maxima takes the gradient)"""
+    if x.ndim != 4 or g.ndim != 4 or tuple(g.shape) != (x.shape[0], x.shape[1], max((x.shape[2] - 3) // 2 + 1, 0), max((x.shape[3] - 3) // 2 + 1, 0)):
+        raise RuntimeError(f'te_hip: pool3s2_max_bwd: inconsistent shapes g {tuple(g.shape)}, x {tuple(x.shape)}')
+    B, Cn, H, W = x.shape
+    gx = torch.empty_like(x, memory_format=torch.contiguous_format)
+    _launch('te_pool3s2_max_bwd_f32', _ptr(gx), _ptr(g), _ptr(x), B * Cn, H, W)
+    return gx
+
+
+ALEX_STEM_ROW_TAPS = tuple((2 + r) % 4 for r in range(4))          # k0 of the output rows y = 4 yy + r: (2, 3, 0, 1)
+
+
+def alex_stem_dgrad_weight(w):
+    """w [Co,3,11,11] -> the flat weight alex_stem_dgrad reads (made once: the network is frozen): for each row phase ry < 4 the block
+    [Co, ny, 11, 3] of the kernel rows k0 + 4 jy that reach the rows y = 4 yy + ry (te_hip.h, te_alex_stem_dgrad_f32).  Plain torch:
+    runs on whatever device w is on."""
+    if w.ndim != 4 or tuple(w.shape[1:]) != (3, 11, 11):
+        raise RuntimeError(f'te_hip: alex_stem_dgrad_weight expects [Co,3,11,11], got {tuple(w.shape)}')
+    return torch.cat([w[:, :, k0::4, :].permute(0, 2, 3, 1).reshape(-1) for k0 in ALEX_STEM_ROW_TAPS]).contiguous()
+
+
+@_op
+def alex_stem_dgrad(g, wt, img_shape):
+    """the adjoint of alex_stem_fwd without its ReLU: g [N,Co,Ho,Wo] (already masked), wt = alex_stem_dgrad_weight(w), img_shape =
+    (N, 3, H, W) -> the UNSCALED image's gradient [N,3,H,W]"""
+    N, _, H, W = img_shape
+    if g.ndim != 4 or g.shape[0] != N or img_shape[1] != 3 or tuple(g.shape[2:]) != conv2d_out_hw(H, W, 11, 11, 4, (2, 2)) \
+            or wt.shape != (363 * g.shape[1],):
+        raise RuntimeError(f'te_hip: alex_stem_dgrad: inconsistent shapes g {tuple(g.shape)}, wt {tuple(wt.shape)}, image {tuple(img_shape)}')
+    gimg = torch.empty(N, 3, H, W, device=g.device, dtype=g.dtype)
+    _launch('te_alex_stem_dgrad_f32', _ptr(gimg), _ptr(g), _ptr(wt), N, H, W, g.shape[1])
+    return gimg
+
+
 # --------------------------------------------------------------------------------------------- M10 dual-space pSp encoder
 def conv2d_heads_splits(Ci, kh, kw, Ho, Wo):
     """the number of k ranges te_conv2d_heads_f32 runs for this (Ci * kh * kw, Ho * Wo); 1 is the unsplit route (no batch or head count enters)"""
