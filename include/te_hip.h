@@ -222,6 +222,25 @@ int te_conv_f32(float* out, const float* in, const float* wp, const float* isc, 
  * second kernel sums them in a fixed order (DETERMINISTIC, no atomics, no memset).  te_conv_f32 itself (no workspace)
  * never splits (same result up to summation order, slower on 4x4 ... 16x16 images). */
 int te_conv_splitk_count(int kind, int B, int K, int M, int H, int W);
+/* Which form of the fp32 direct kernel (conv_mfma_kernel<KIND, TC, HAS_ISC, MS, OCC, FAST, EPI>, csrc/conv.hip) a launch runs, on which
+ * cell tiles and grid (host only, nothing is launched: the answer is the plan that te_conv_res_f32 itself makes and then launches).
+ * kind: TE_CONV_3X3, TE_CONV_T2, TE_CONV_S2 or TE_CONV_1X1 (the other kinds: TE_ERR_UNSUPPORTED).  has_isc: style scales given;
+ * epi: 0 none, 1 residual, 2 mask, 3 both; with_ws: a split-K workspace is given (te_conv_ws_f32 / te_conv_res_f32 with ws), 0 = te_conv_f32.
+ * form[TE_CONV_FORM_INTS]:
+ *   [0] tc            tile class that launches (0, 1, 2: the block tiles for M >= 96, >= 48, below; 3: the deep-stage 1x1, which exists as FAST only)
+ *   [1] fast          the FAST kernel (whole stages, 16-byte row segments)        [2] ms   the kernel's multi-sample TEMPLATE flag
+ *   [3] multi_sample  some tile holds more than one sample (with ms == 0: the plain kernel's run-time path)
+ *   [4] occ           waves per SIMD the kernel is compiled for                   [5] ksplit  splits that launch (1 without workspace)
+ *   [6] nreg          cell regions (T2 beyond the padded sizes: body, last column, last row)
+ *   [7] ntiles  [8] nbody (tiles of the first region, dealt to the XCDs in 8 bands)  [9] mblocks  [10] grid x (blocks; some may have no tile)
+ *   then per region r at TE_CONV_FORM_HEAD + r * TE_CONV_FORM_REGION: TW, TH, NS (samples a tile has room for), NSv (samples staged),
+ *   tiles_x, tiles_y, tapmask, TH0 (rows of the tile before the staging budget halved them); zeros past nreg.
+ * TE_ERR_NULL / TE_ERR_SHAPE on bad arguments, and the launch's own refusals with the launch's code (an epilogue with style scales or on
+ * the strided / transposed kinds, a tile beyond the staging budget: TE_ERR_UNSUPPORTED); a refusal leaves form untouched. */
+#define TE_CONV_FORM_HEAD 11
+#define TE_CONV_FORM_REGION 8
+#define TE_CONV_FORM_INTS (TE_CONV_FORM_HEAD + 3 * TE_CONV_FORM_REGION)
+int te_conv_form(int kind, int B, int K, int M, int H, int W, int has_isc, int epi, int with_ws, int* form);
 /* 1 if TE_CONV_3X3W covers the problem: K % 8 == 0, W % 32 == 0, and M % 128 == 0 with H % 4 == 0, or M % 64 == 0 with
  * H % 8 == 0, or M % 32 == 0 with H % 16 == 0 (block tile = 128 / 64 / 32 output channels x 4 / 8 / 16 rows x 32 columns):
  * every 3x3 stride-1 layer of the generator and discriminator from 32x32 up incl. the 32 / 64-channel tail of FFHQ-1024; the

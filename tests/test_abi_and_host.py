@@ -61,6 +61,7 @@ def test_bindings_pinned_by_hand():
         'te_upfirdn2d_f32': (I, [P, P, P, L, I, I, I, I, I, I, I, I, I, I, I, I, I, P, L, I, F, F, P]),
         'te_small_gemm_batched_f32': (I, [P, P, P, P, I, L, L, L, L, P, P, I, I, I, L, L, L, L, L, L, F, F, I, P]),
         'te_wgrad_group_plan': (I, [I, I, I, I, I, I, P, P]),
+        'te_conv_form': (I, [I, I, I, I, I, I, I, I, I, P]),
         'te_lpips_allpairs_dist_f32': (I, [P, P, P, P, I, I, P]),
         'te_conv2d_prelu_f32': (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
         'te_fid_moments_f64': (I, [P, P, P, P, L, I, I, P]),
@@ -75,7 +76,7 @@ def test_bindings_pinned_by_hand():
 def test_every_binding_has_the_declared_number_of_arguments(libpath):
     from transeditor_amd import _lib
     declared = _declared_prototypes()
-    assert tuple(declared) == _lib.EXPORTS and len(declared) >= 134          # header order
+    assert tuple(declared) == _lib.EXPORTS and len(declared) >= 148          # header order
     L = _lib.lib()
     for name, params in declared.items():
         n = 0 if params.strip() == 'void' else params.count(',') + 1       # (no nested parentheses: every comma is top-level)

@@ -62,8 +62,9 @@ def _randn(shape, seed, dtype=torch.float32):
     return torch.randn(shape, generator=g, device=DEV, dtype=torch.float32).to(dtype)
 
 
-def _within(entry, what, got, ref, bound, keep=None):
-    """assert |got - ref| <= bound elementwise (where `keep`), after recording max err / bound and the left-out share"""
+def _within(entry, what, got, ref, bound, keep=None, results=RESULTS):
+    """assert |got - ref| <= bound elementwise (where `keep`), after recording max err / bound and the left-out share (in `results`: this
+    module's report, or that of another module which shares the check)"""
     err = (got.double() - ref).abs()
     ratio = err / bound.clamp_min(1e-300)
     left = 0.0
@@ -71,7 +72,7 @@ def _within(entry, what, got, ref, bound, keep=None):
         left = 1.0 - float(keep.double().mean())
         ratio = torch.where(keep, ratio, torch.zeros_like(ratio))
     worst = float(ratio.max())
-    RESULTS.append((entry.name, what, worst, left))
+    results.append((entry.name, what, worst, left))
     print(f'{entry.name} {what}: max err / bound {worst:.4f}, left out {left:.1e}')
     assert torch.isfinite(got).all()
     assert left <= KINK_CAP, f'{entry.name} {what}: {left:.2e} of the elements sit on the kink'

@@ -365,9 +365,28 @@ def conv_out_shape(kind, B, M, H, W):
     return (B, M, H, W)
 
 
+CONV_FORM_HEAD = ('tc', 'fast', 'ms', 'multi_sample', 'occ', 'ksplit', 'nreg', 'ntiles', 'nbody', 'mblocks', 'grid_x')      # te_conv_form (te_hip.h)
+CONV_FORM_REGION = ('TW', 'TH', 'NS', 'NSv', 'tiles_x', 'tiles_y', 'tapmask', 'TH0')
+CONV_EPI = {'none': 0, 'res': 1, 'mask': 2, 'both': 3}
+
+
+def conv_form(kind, B, K, M, H, W, has_isc=False, epi='none', with_ws=True):
+    """the form of the fp32 direct kernel that conv() launches for this problem (host only): a dict of CONV_FORM_HEAD plus 'regions', a list of
+    nreg dicts of CONV_FORM_REGION; the negative TE_ERR_* code where the launch refuses the combination"""
+    buf = (C.c_int * (len(CONV_FORM_HEAD) + 3 * len(CONV_FORM_REGION)))()
+    rc = lib().te_conv_form(kind, B, K, M, H, W, int(has_isc), CONV_EPI[epi], int(with_ws), buf)
+    if rc:
+        return rc
+    v, h, r = list(buf), len(CONV_FORM_HEAD), len(CONV_FORM_REGION)
+    form = dict(zip(CONV_FORM_HEAD, v[:h]))
+    form['regions'] = [dict(zip(CONV_FORM_REGION, v[h + i * r:h + (i + 1) * r])) for i in range(form['nreg'])]
+    return form
+
+
 @_op
-def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, mask_ref=None, mask_gain=1.0):
-    """H, W = LOW-resolution size (see te_hip.h).  x [B,K,Hin,Win].  res: residual added after the activation; mask_ref:
+def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, mask_ref=None, mask_gain=1.0, split=True):
+    """H, W = LOW-resolution size (see te_hip.h).  x [B,K,Hin,Win].  split=False: no split-K workspace is handed over (what
+    te_conv_f32 launches: the channel loop is not split).  res: residual added after the activation; mask_ref:
     leaky-ReLU gradient mask (saved output of the layer this data gradient lands on) applied last.  The kinds that read
     residual / mask (and TE_CONV_1X1S6 its input) with 16-byte accesses get aligned copies of misaligned operands."""
     x = x.contiguous()
@@ -385,7 +404,7 @@ def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, m
     if S < 1:
         raise RuntimeError(f'te_conv_splitk_count failed ({S})')
     # small images split the channel loop over the grid: per-split slabs + fixed-order sum (deterministic, graph-capturable)
-    ws = torch.empty((S,) + tuple(out.shape), device=x.device, dtype=x.dtype) if S > 1 else None
+    ws = torch.empty((S,) + tuple(out.shape), device=x.device, dtype=x.dtype) if S > 1 and split else None
     if kind == CONV_T2S6:          # scratch for the last input column (body kernel -> edge kernel; te_hip.h)
         ws = torch.empty(B * K * H, device=x.device, dtype=x.dtype)
     _launch('te_conv_res_f32', _ptr(out), _ptr(ws), _ptr(x), _ptr(wp), _ptr(isc), _ptr(osc), _ptr(bias), _ptr(res), _ptr(mask_ref),

@@ -929,42 +929,54 @@ int add_region(ConvArgs& a, int ri0, int rj0, int rh, int rw, int& nblocks, size
     return 0;
 }
 
+// The form of a launch: which instantiation of conv_mfma_kernel runs, on which grid.  plan_regions_tc decides it (and lays the regions
+// out in ConvArgs); launch_planned_tc dispatches on nothing else, and te_conv_form reports it.
+struct ConvForm {
+    int tc;                  // tile class that launches (the deep-stage class 3 falls back to 0 when the launch is not FAST)
+    bool has_isc, ms, epi;   // the kernel's template flags.  ms: multi-sample tiles AND a kernel form that tells them apart at compile time
+    bool fast;
+    int occ;                 // waves per SIMD the kernel is compiled for
+    bool multi_sample;       // some region stages more than one sample per tile (without style scales or epilogue stages a run-time path)
+    int nblocks;             // cell tiles of all regions (0: nothing to launch)
+    size_t lds_floats;
+    unsigned grid_x;
+    int th0[3];              // per region: rows of the first cell-tile guess, before the staging budget halves them
+};
+
 template <int KIND, int TC, bool HAS_ISC, bool MS, int OCC, bool FAST, bool EPI>
-void launch_f(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s) {
-    constexpr int BM = tile_bm<KIND, TC>();
+void launch_f(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
     te::allow_big_lds(attr_done, (const void*)conv_mfma_kernel<KIND, TC, HAS_ISC, MS, OCC, FAST, EPI>, 128 * 1024);
-    ConvArgs b = a;
-    b.ntiles = nblocks; b.mblocks = (int)te::cdiv(a.M, BM);
-    b.nbody = (a.nreg > 1) ? a.reg[1].first_block : nblocks;
-    b.nt8 = te::xcd_banded() ? (int)te::cdiv(b.nbody, 8) : 0;
-    const int64_t per_xcd = b.nt8 ? b.nt8 + te::cdiv(nblocks - b.nbody, 8) : te::cdiv(nblocks, 8);
-    dim3 grid((unsigned)(per_xcd * 8 * b.mblocks), 1u, (unsigned)a.ksplit);
-    conv_mfma_kernel<KIND, TC, HAS_ISC, MS, OCC, FAST, EPI><<<grid, NTHREADS, lds_floats * sizeof(float), s>>>(b);
+    dim3 grid(f.grid_x, 1u, (unsigned)a.ksplit);
+    conv_mfma_kernel<KIND, TC, HAS_ISC, MS, OCC, FAST, EPI><<<grid, NTHREADS, f.lds_floats * sizeof(float), s>>>(a);
 }
 
 template <int KIND, int TC> constexpr bool have_fast() { return TC == 3 || KIND != TE_CONV_1X1; }
 
 template <int KIND, int TC, bool HAS_ISC, bool MS, int OCC, bool EPI>
-void launch_o(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s, bool fast) {
+void launch_o(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
     constexpr bool HAVE_FAST = have_fast<KIND, TC>() && !MS;
-    if (HAVE_FAST && fast) launch_f<KIND, TC, HAS_ISC, MS, OCC, HAVE_FAST, EPI>(a, nblocks, lds_floats, s);
-    else launch_f<KIND, TC, HAS_ISC, MS, OCC, false, EPI>(a, nblocks, lds_floats, s);
+    if (HAVE_FAST && f.fast) launch_f<KIND, TC, HAS_ISC, MS, OCC, HAVE_FAST, EPI>(a, f, s);
+    else launch_f<KIND, TC, HAS_ISC, MS, OCC, false, EPI>(a, f, s);
 }
+
+// 3 waves/SIMD variant only for the plain 3x3 at the 128-row tile (the only one whose register budget is near 168); the
+// epilogue-stage variants take the 2-wave budget (their extra loads do not fit 168 registers).  (Compiled for 2 waves the plain 3x3
+// 128-row tile measured 135.7 against 140.1 TFLOP/s with the FAST kernel.)
+template <int KIND, int TC> constexpr bool can3(bool ms) { return ((KIND == TE_CONV_3X3 && TC == 0 && !ms) || (KIND == TE_CONV_T2 && TC == 1 && !ms)); }
 
 template <int KIND, int TC, bool HAS_ISC, bool MS, bool EPI = false>
-void launch_t(const ConvArgs& a, int nblocks, size_t lds_floats, hipStream_t s, bool fast) {
-    // 3 waves/SIMD variant only for the plain 3x3 at the 128-row tile (the only one whose register budget is near 168); the
-    // epilogue-stage variants take the 2-wave budget (their extra loads do not fit 168 registers).  (Compiled for 2 waves the plain 3x3
-    // 128-row tile measured 135.7 against 140.1 TFLOP/s with the FAST kernel.)
-    constexpr bool CAN3 = ((KIND == TE_CONV_3X3 && TC == 0 && !MS) || (KIND == TE_CONV_T2 && TC == 1 && !MS));
-    if (CAN3) launch_o<KIND, TC, HAS_ISC, MS, CAN3 ? 3 : 2, EPI>(a, nblocks, lds_floats, s, fast);
-    else launch_o<KIND, TC, HAS_ISC, MS, 2, EPI>(a, nblocks, lds_floats, s, fast);
+void launch_t(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
+    constexpr bool CAN3 = can3<KIND, TC>(MS);
+    if (CAN3) launch_o<KIND, TC, HAS_ISC, MS, CAN3 ? 3 : 2, EPI>(a, f, s);
+    else launch_o<KIND, TC, HAS_ISC, MS, 2, EPI>(a, f, s);
 }
 
-// regions: list of {ri0, rj0, rh, rw}
+// The planning half of a launch.  regions: list of {ri0, rj0, rh, rw}.  Lays the regions out in `a`, fills the grid fields of `a` (the
+// kernel's block -> work mapping) and decides the form `f`.  Launches nothing and reads no device memory: of the pointers in `a` only
+// isc, res and mref are looked at, and only for being NULL or not.
 template <int KIND, int TC>
-int launch_regions_tc(ConvArgs a, const int (*regions)[4], int n, hipStream_t s) {
+int plan_regions_tc(ConvArgs& a, const int (*regions)[4], int n, ConvForm& f) {
     constexpr int KC = Cfg<KIND, TC>::KC;
     int nblocks = 0;
     size_t lds_floats = 0;
@@ -985,22 +997,45 @@ int launch_regions_tc(ConvArgs a, const int (*regions)[4], int n, hipStream_t s)
                a.reg[0].NS == 1 && a.reg[0].TW >= 4;      // TW >= 4: row segments never straddle the left image border
         if (!fast) break;
     }
+    f = ConvForm{};
+    f.tc = TC;
     if (nblocks == 0) return 0;
-    if (TC == 3 && !fast) return launch_regions_tc<KIND, 0>(a, regions, n, s);      // the deep-stage class exists as a FAST kernel only
-    if (a.res || a.mref) {
-        if constexpr (KIND == TE_CONV_3X3 || KIND == TE_CONV_1X1) {
-            if (a.isc) return te::fail(TE_ERR_UNSUPPORTED, "te_conv_res_f32: residual / mask epilogue exists for unmodulated launches only");
-            if (ms) launch_t<KIND, TC, false, true, true>(a, nblocks, lds_floats, s, fast);
-            else launch_t<KIND, TC, false, false, true>(a, nblocks, lds_floats, s, fast);
-            return 0;
-        } else {
+    if (TC == 3 && !fast) return plan_regions_tc<KIND, 0>(a, regions, n, f);      // the deep-stage class exists as a FAST kernel only
+    f.epi = a.res || a.mref;
+    if (f.epi) {
+        if (KIND != TE_CONV_3X3 && KIND != TE_CONV_1X1)
             return te::fail(TE_ERR_UNSUPPORTED, "te_conv_res_f32: residual / mask epilogue exists for the 3x3 and 1x1 kinds only");
-        }
+        if (a.isc) return te::fail(TE_ERR_UNSUPPORTED, "te_conv_res_f32: residual / mask epilogue exists for unmodulated launches only");
     }
-    if (!a.isc) launch_t<KIND, TC, false, false>(a, nblocks, lds_floats, s, fast);
-    else if (ms) launch_t<KIND, TC, true, true>(a, nblocks, lds_floats, s, fast);
-    else launch_t<KIND, TC, true, false>(a, nblocks, lds_floats, s, fast);
+    f.has_isc = a.isc != nullptr;
+    f.multi_sample = ms;
+    f.ms = ms && (f.epi || f.has_isc);       // a plain launch has one kernel form for both and takes the multi-sample path at run time
+    f.fast = fast;
+    f.occ = can3<KIND, TC>(f.ms) ? 3 : 2;
+    f.nblocks = nblocks;
+    f.lds_floats = lds_floats;
+    for (int i = 0; i < a.nreg; ++i) f.th0[i] = first_cell_tile(tile_cells<KIND, TC>(), a.reg[i].rh, a.reg[i].rw).TH;
+    a.ntiles = nblocks; a.mblocks = (int)te::cdiv(a.M, tile_bm<KIND, TC>());
+    a.nbody = (a.nreg > 1) ? a.reg[1].first_block : nblocks;
+    a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.nbody, 8) : 0;
+    const int64_t per_xcd = a.nt8 ? a.nt8 + te::cdiv(nblocks - a.nbody, 8) : te::cdiv(nblocks, 8);
+    f.grid_x = (unsigned)(per_xcd * 8 * a.mblocks);
     return 0;
+}
+
+// The launching half: the instantiation that `f` names, on the grid that `f` names.
+template <int KIND, int TC>
+void launch_planned_tc(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
+    if (f.epi) {
+        if constexpr (KIND == TE_CONV_3X3 || KIND == TE_CONV_1X1) {
+            if (f.ms) launch_t<KIND, TC, false, true, true>(a, f, s);
+            else launch_t<KIND, TC, false, false, true>(a, f, s);
+        }
+        return;
+    }
+    if (!f.has_isc) launch_t<KIND, TC, false, false>(a, f, s);
+    else if (f.ms) launch_t<KIND, TC, true, true>(a, f, s);
+    else launch_t<KIND, TC, true, false>(a, f, s);
 }
 
 inline int tile_class(int M) { return M >= 96 ? 0 : (M >= 48 ? 1 : 2); }
@@ -1019,8 +1054,13 @@ auto with_tile_class(int tc, F&& f) {
 }
 
 template <int KIND>
-int launch_regions(const ConvArgs& a, const int (*regions)[4], int n, hipStream_t s, int tc) {
-    return with_tile_class<KIND>(tc, [&](auto TC) { return launch_regions_tc<KIND, decltype(TC)::value>(a, regions, n, s); });
+int plan_regions(ConvArgs& a, const int (*regions)[4], int n, int tc, ConvForm& f) {
+    return with_tile_class<KIND>(tc, [&](auto TC) { return plan_regions_tc<KIND, decltype(TC)::value>(a, regions, n, f); });
+}
+
+template <int KIND>
+void launch_planned(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
+    with_tile_class<KIND>(f.tc, [&](auto TC) { launch_planned_tc<KIND, decltype(TC)::value>(a, f, s); });
 }
 
 // (KC, BM, cells per block tile) of the kernels' own tables for a runtime (kind, tile class)
@@ -1174,6 +1214,54 @@ extern "C" int te_conv_splitk_count(int kind, int B, int K, int M, int H, int W)
     return conv_plan(kind, B, K, M, H, W).ksplit;
 }
 
+// The planning half of te_conv_res_f32 for the four fp32 kinds: everything of the launch that does not touch the device.  `a` comes in with its
+// pointers (of which only ws, isc, res and mref matter here, and only as NULL or not) and leaves as the kernel's argument; `f` names the kernel.
+static int conv_plan_launch(ConvArgs& a, ConvForm& f, int kind, int B, int K, int M, int H, int W) {
+    a.B = B; a.K = K; a.M = M; a.Kp = roundup(K, KPAD); a.Mp = roundup(M, MPAD); a.H = H; a.W = W;
+    const ConvPlan pl = conv_plan(kind, B, K, M, H, W);
+    a.ksplit = pl.ksplit; a.kchunk = pl.kchunk;
+    if (a.ksplit > 1 && !a.ws) {       // no workspace (te_conv_f32): the channel loop is not split - slower on 4x4 ... 16x16 images,
+        a.ksplit = 1;                  // but no atomics anywhere: every result of this library is bit-reproducible
+        a.kchunk = a.Kp;
+    }
+    if (a.ksplit == 1) a.ws = nullptr;
+    int r[3][4];
+    const int n = conv_regions(kind, H, W, r);
+    a.Hi = a.Ho = H; a.Wi = a.Wo = W;
+    switch (kind) {
+        // (3x3: a 128 x 256 block tile, NBW = 4, measured the same 133 TF/s: the kernel sits at the clock-limited peak)
+        case TE_CONV_3X3: return plan_regions<TE_CONV_3X3>(a, r, n, pl.tc, f);
+        case TE_CONV_1X1: return plan_regions<TE_CONV_1X1>(a, r, n, pl.tc, f);
+        case TE_CONV_S2: a.Hi = 2 * H + 1; a.Wi = 2 * W + 1; return plan_regions<TE_CONV_S2>(a, r, n, pl.tc, f);
+        default: a.Ho = 2 * H + 1; a.Wo = 2 * W + 1; return plan_regions<TE_CONV_T2>(a, r, n, pl.tc, f);      // TE_CONV_T2
+    }
+}
+
+// what te_conv_res_f32 would launch (host only): conv_plan_launch's answer, written out
+extern "C" int te_conv_form(int kind, int B, int K, int M, int H, int W, int has_isc, int epi, int with_ws, int* form) {
+    if (!form) return TE_ERR_NULL;
+    if (B <= 0 || K <= 0 || M <= 0 || H <= 0 || W <= 0 || kind < 0 || kind >= TE_CONV_KINDS || epi < 0 || epi > 3) return TE_ERR_SHAPE;
+    if (kind != TE_CONV_3X3 && kind != TE_CONV_T2 && kind != TE_CONV_S2 && kind != TE_CONV_1X1) return TE_ERR_UNSUPPORTED;
+    static float present;              // stands for "this operand is given": the plan compares the pointers with NULL and reads nothing
+    ConvArgs a{};
+    a.ws = with_ws ? &present : nullptr;
+    a.isc = has_isc ? &present : nullptr;
+    a.res = (epi & 1) ? &present : nullptr;
+    a.mref = (epi & 2) ? &present : nullptr;
+    ConvForm f;
+    const int rc = conv_plan_launch(a, f, kind, B, K, M, H, W);
+    if (rc) return rc;
+    const int head[TE_CONV_FORM_HEAD] = {f.tc, f.fast, f.ms, f.multi_sample, f.occ, a.ksplit, a.nreg, a.ntiles, a.nbody, a.mblocks, (int)f.grid_x};
+    std::copy(head, head + TE_CONV_FORM_HEAD, form);
+    std::fill(form + TE_CONV_FORM_HEAD, form + TE_CONV_FORM_INTS, 0);
+    for (int i = 0; i < a.nreg; ++i) {
+        const ConvArgs::Region& g = a.reg[i];
+        const int reg[TE_CONV_FORM_REGION] = {g.TW, g.TH, g.NS, g.NSv, g.tiles_x, g.tiles_y, g.tapmask, f.th0[i]};
+        std::copy(reg, reg + TE_CONV_FORM_REGION, form + TE_CONV_FORM_HEAD + i * TE_CONV_FORM_REGION);
+    }
+    return 0;
+}
+
 extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const float* wp, const float* isc, const float* osc,
                                const float* bias, const float* res, const float* mask_ref, float mask_gain, int act, int kind,
                                int B, int K, int M, int H, int W, te_stream_t stream_) {
@@ -1204,26 +1292,15 @@ extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const flo
     }
     ConvArgs a{};
     a.out = out; a.ws = ws; a.in = in; a.wp = wp; a.isc = isc; a.osc = osc; a.bias = bias; a.res = res; a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
-    a.B = B; a.K = K; a.M = M; a.Kp = roundup(K, KPAD); a.Mp = roundup(M, MPAD); a.H = H; a.W = W;
-    const ConvPlan pl = conv_plan(kind, B, K, M, H, W);
-    a.ksplit = pl.ksplit; a.kchunk = pl.kchunk;
-    if (a.ksplit > 1 && !a.ws) {       // no workspace (te_conv_f32): the channel loop is not split - slower on 4x4 ... 16x16 images,
-        a.ksplit = 1;                  // but no atomics anywhere: every result of this library is bit-reproducible
-        a.kchunk = a.Kp;
-    }
-    if (a.ksplit == 1) a.ws = nullptr;
-    int r[3][4];
-    const int n = conv_regions(kind, H, W, r);
-    a.Hi = a.Ho = H; a.Wi = a.Wo = W;
-    int rc = 0;
-    switch (kind) {
-        // (3x3: a 128 x 256 block tile, NBW = 4, measured the same 133 TF/s: the kernel sits at the clock-limited peak)
-        case TE_CONV_3X3: rc = launch_regions<TE_CONV_3X3>(a, r, n, s, pl.tc); break;
-        case TE_CONV_1X1: rc = launch_regions<TE_CONV_1X1>(a, r, n, s, pl.tc); break;
-        case TE_CONV_S2: a.Hi = 2 * H + 1; a.Wi = 2 * W + 1; rc = launch_regions<TE_CONV_S2>(a, r, n, s, pl.tc); break;
-        default: a.Ho = 2 * H + 1; a.Wo = 2 * W + 1; rc = launch_regions<TE_CONV_T2>(a, r, n, s, pl.tc); break;      // TE_CONV_T2
-    }
+    ConvForm f;
+    const int rc = conv_plan_launch(a, f, kind, B, K, M, H, W);
     if (rc) return rc;
+    if (f.nblocks) switch (kind) {
+        case TE_CONV_3X3: launch_planned<TE_CONV_3X3>(a, f, s); break;
+        case TE_CONV_1X1: launch_planned<TE_CONV_1X1>(a, f, s); break;
+        case TE_CONV_S2: launch_planned<TE_CONV_S2>(a, f, s); break;
+        default: launch_planned<TE_CONV_T2>(a, f, s); break;      // TE_CONV_T2
+    }
     if (a.ksplit > 1 && (a.ws || osc || bias || act)) {
         const int plane = a.Ho * a.Wo;
         const int64_t total = (int64_t)B * M * plane;
