@@ -29,7 +29,8 @@ from .op.attention import attention_core
 from .op.fir_act import blur_bias_act
 from .op.layernorm import pixel_norm, sample_layer_norm
 from .op.linear import linear_fused, shared_input_linears
-from .op.modconv import latent_producer_section, modconv, _STATE as _modconv_state
+from .op.modconv import modconv
+from .op.recorded import latent_producer_section, _STATE as _modconv_state
 from .op.resblock import resblock
 from .op import modulation, styled_rgb
 from .op.stddev import minibatch_stddev

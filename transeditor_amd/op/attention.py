@@ -10,6 +10,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from .linear import bmm
+from .recorded import recorded_backward
 
 
 def _torch_expr(q, k, v, scale, groups):
@@ -38,14 +39,8 @@ class _AttnCore(Function):
     def backward(ctx, go, gsim):
         q, k, v, sim = ctx.saved_tensors
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                q, k, v = q.view_as(q), k.view_as(k), v.view_as(v)   # aliases: partial derivatives only
-                o2, sim2 = _torch_expr(q, k, v, ctx.scale, ctx.groups)
-                outs, gouts = [o2], [go if go is not None else torch.zeros_like(o2)]
-                if gsim is not None:
-                    outs.append(sim2)
-                    gouts.append(gsim)
-                gq, gk, gv = torch.autograd.grad(outs, (q, k, v), gouts, create_graph=True, allow_unused=True)
+            gq, gk, gv = recorded_backward(lambda q, k, v: _torch_expr(q, k, v, ctx.scale, ctx.groups), (q, k, v),
+                                           ctx.needs_input_grad[:3], (go, gsim))
             return gq, gk, gv, None, None
         if go is None:
             go = torch.zeros_like(q)

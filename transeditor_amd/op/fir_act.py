@@ -11,6 +11,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from .fused_act import fused_leaky_relu
+from .recorded import recorded_backward
 from .upfirdn2d import upfirdn2d, _geometry, flipped_taps
 
 
@@ -29,10 +30,9 @@ class _BlurBiasAct(Function):
         x, kernel, bias, out = ctx.saved_tensors
         pad = ctx.pad
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                xa, ba = x.view_as(x), bias.view_as(bias)          # aliases: partial derivatives only
-                y = fused_leaky_relu(upfirdn2d(xa, kernel, pad=pad), ba)
-                gx, gb = torch.autograd.grad(y, (xa, ba), g, create_graph=True, allow_unused=True)
+            need = ctx.needs_input_grad
+            gx, gb = recorded_backward(lambda x, bias: fused_leaky_relu(upfirdn2d(x, kernel, pad=pad), bias),
+                                       (x, bias), (need[0], need[2]), g)
             return gx, None, gb, None
         pad4 = (pad[0], pad[1], pad[0], pad[1])
         _, g_pad = _geometry(x.shape[2:], kernel.shape, (1, 1), (1, 1), pad4)

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from .. import _lib
+from .recorded import recorded_backward
 
 EPS = 1e-5
 
@@ -24,10 +25,7 @@ class _SampleLayerNorm(Function):
     def backward(ctx, g):
         x, y, stats = ctx.saved_tensors
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                xa = x.view_as(x)
-                gx, = torch.autograd.grad(F.layer_norm(xa, xa.shape[1:], eps=EPS), xa, g, create_graph=True)
-            return gx
+            return recorded_backward(lambda x: F.layer_norm(x, x.shape[1:], eps=EPS), (x,), ctx.needs_input_grad, g)[0]
         return _lib.layer_norm_bwd(g.reshape(y.shape).contiguous(), y, stats).view(x.shape)
 
 
@@ -57,10 +55,7 @@ class _PixelNorm(Function):
     def backward(ctx, g):
         x, y, r = ctx.saved_tensors
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                xa = x.view_as(x)
-                gx, = torch.autograd.grad(_pixel_norm_expr(xa, 1), xa, g, create_graph=True)
-            return gx
+            return recorded_backward(lambda x: _pixel_norm_expr(x, 1), (x,), ctx.needs_input_grad, g)[0]
         return _lib.pixel_norm_bwd(g.contiguous(), y, r)
 
 

@@ -14,7 +14,8 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from .. import _lib
-from .modconv import _STATE as _modconv_state
+from .fused_act import fused_leaky_relu
+from .recorded import _STATE, recorded_backward
 
 _ACT = {None: 0, 'gelu': 1, 'lrelu': 3}
 MAX_K = 1024          # widest reduction of the single-pass kernel; beyond it the split-K form (discriminator's 8192-wide linear)
@@ -150,7 +151,6 @@ def _closed_expr(x, weight, bias, alpha, beta, act, residual):
     N, K = weight.shape
     y = _LinFwd.apply(x.reshape(-1, K), weight, alpha).reshape(*x.shape[:-1], N)
     if act == 'lrelu':
-        from .fused_act import fused_leaky_relu
         y2 = y.reshape(-1, N)
         y = fused_leaky_relu(y2, None if bias is None else (bias * beta if beta != 1.0 else bias)).reshape(y.shape)
     else:
@@ -190,12 +190,8 @@ class _Linear(Function):
         alpha, beta, act = ctx.cfg
         need = ctx.needs_input_grad
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                al = [None if t is None else t.view_as(t) for t in (x, weight, bias, residual)]
-                y = _closed_expr(al[0], al[1], al[2], alpha, beta, act, al[3])
-                ins = [t for t, n in zip(al, need[:4]) if n and t is not None]
-                gs = iter(torch.autograd.grad(y, ins, gy, create_graph=True, allow_unused=True))
-            return tuple(next(gs) if (n and t is not None) else None for t, n in zip(al, need[:4])) + (None, None, None)
+            r = recorded_backward(lambda x, w, b, res: _closed_expr(x, w, b, alpha, beta, act, res), (x, weight, bias, residual), need[:4], gy)
+            return tuple(r) + (None, None, None)
         N, K = weight.shape
         g = gy.reshape(-1, N).contiguous()
         # the skip connection hands on the DENSE gradient: a strided one (the permute in front of adjust_style makes the first)
@@ -236,7 +232,7 @@ def linear_fused(x, weight, bias=None, alpha=1.0, beta=1.0, act=None, residual=N
     if weight.shape[1] > MAX_K and not _ksplit(weight.shape[1]):
         raise RuntimeError(f'te_hip: linear layer with {weight.shape[1]} inputs: reductions wider than {MAX_K} must split into '
                            f'chunks of <= {MAX_K} that are multiples of 8 (no library fallback)')
-    if _modconv_state.second_order and torch.is_grad_enabled():
+    if _STATE.second_order and torch.is_grad_enabled():
         # the caller announced a create_graph backward (regulariser steps): build the differentiable form right away
         return _closed_expr(x, weight, bias, alpha, beta, act, residual)
     return _Linear.apply(x, weight, bias, residual, alpha, beta, act)
@@ -273,14 +269,10 @@ class _SharedInputLinears(Function):
         need = ctx.needs_input_grad
         J, K = weights[0].shape
         if torch.is_grad_enabled():              # recorded backward: layer by layer through the closed trio
-            with torch.enable_grad():
-                xa = x.view_as(x)
-                pa = [p.view_as(p) for p in params]
-                ys = [_closed_expr(xa, pa[z], pa[nz + z], alpha, beta, None, None) for z in range(nz)]
-                ins = [t for t, f in zip([xa] + pa, [need[0]] + list(need[4:])) if f]
-                res = iter(torch.autograd.grad(ys, ins, list(gs), create_graph=True, allow_unused=True))
-            gx = next(res) if need[0] else None
-            return (gx, None, None, None) + tuple(next(res) if f else None for f in need[4:])
+            def build(x, *pa):
+                return [_closed_expr(x, pa[z], pa[nz + z], alpha, beta, None, None) for z in range(nz)]
+            r = recorded_backward(build, [x] + params, need[:1] + need[4:], gs)
+            return (r[0], None, None, None) + tuple(r[1:])
         x2 = x.reshape(-1, K).contiguous()
         R = x2.shape[0]
         g = torch.stack([t.reshape(R, J) for t in gs])                      # [nz, R, J]
@@ -311,7 +303,7 @@ def shared_input_linears(x, mods):
     kernel applies (fp32 on the GPU, <= 16 layers, reduction <= MAX_K, not inside second_order())."""
     m0 = mods[0]
     ok = (x.is_cuda and x.dtype == torch.float32 and 1 < len(mods) <= 16 and m0.weight.shape[1] <= MAX_K
-          and not _modconv_state.second_order
+          and not _STATE.second_order
           and all(m.activation is None and m.bias is not None and m.weight.shape == m0.weight.shape and m.scale == m0.scale
                   and m.lr_mul == m0.lr_mul and m.weight.is_contiguous() and m.bias.is_contiguous() for m in mods))
     if not ok:

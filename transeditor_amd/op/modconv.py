@@ -15,9 +15,13 @@ Two layers of autograd functions:
   built on them is differentiable to any order (R1 / path-length regularisers).
 * ``modconv`` (``_ModConvFused``) — the fast path: scales, bias and activation fused into the
   kernels, a hand-written backward that produces dx, dW, ds, dd from ONE data-gradient conv and
-  ONE correlation pass (per-sample slabs + te_wgrad_reduce).  When its backward is itself being
-  recorded (create_graph=True) it re-derives the gradients through the differentiable trio,
-  so double backward stays exact.
+  ONE correlation pass (per-sample slabs + te_wgrad_reduce; ``_modconv_bwd``).  When its backward
+  is itself being recorded (create_graph) it re-derives the gradients through the differentiable
+  trio (``recorded_backward``), so double backward stays exact.
+
+The hints of the regulariser steps (``second_order()``, ``no_weight_grads()``) and their per-thread
+state live in op/recorded.py and are re-exported here; the two weight caches below keep their fields
+on the same state object.
 
 kinds: '3x3' (stride 1, pad 1), '1x1', 'up' (3x3 transposed stride 2 -> (2H+1)x(2W+1); the blur
 that follows in the reference, model_spatial_query.py:318-321, is a separate upfirdn2d), 'down' (3x3 stride 2,
@@ -25,115 +29,18 @@ pad 0 over a (2H+1)x(2W+1) input -> HxW: the discriminator's blurred downsamplin
 adjoint kernel pair of 'up').
 """
 import contextlib
-
 import os
 
 import torch
 from torch.autograd import Function
 
 from .. import _lib
-from .chanscale import chan_scale
+from .chanscale import _ChanDot, chan_scale
 from .fused_act import fused_leaky_relu
-
-# Hints for the regulariser steps (R1, path length), which differentiate twice.  Both are optional: without them the
-# fused Function recomputes its forward through the differentiable pieces when its backward turns out to be recorded.
-#
-# Threading: forward passes may run concurrently from several Python threads (the reference's metrics wrap the generator in
-# nn.DataParallel; te_hip.h promises thread-safe entry points), so `second_order` and the frozen-weight cache are
-# THREAD-LOCAL.  `skip_w` cannot be: it is read inside backward functions, which the autograd engine runs on its own
-# per-device thread.  It therefore lives on a small token object (`_Graph`) that every `second_order()` context creates and
-# every node built inside it keeps (`ctx.graph`); `no_weight_grads()` flips the flag on the calling thread's most recent
-# token (and on the process-wide default token that nodes built outside any `second_order()` context share).
-import threading
-
-
-class _Graph:
-    __slots__ = ('skip_w',)
-
-    def __init__(self):
-        self.skip_w = False
-
-
-_DEFAULT_GRAPH = _Graph()
-
-
-class _Local(threading.local):
-    """per-thread state with dict-style access (`_STATE['second_order']`); every thread starts from the defaults"""
-
-    def __init__(self):
-        self.second_order = False
-        self.second_wrt = None               # second_order(wrt=...): where the recorded backward will stop
-        self.graph = _DEFAULT_GRAPH          # token of the current / most recent second_order() context of this thread
-        self.frozen_on = False
-        self.frozen_cache = None
-        self.pack_cache = None               # dict while a packed_weights_cache() context is open on this thread
-
-    def __getitem__(self, k):
-        if k == 'skip_w':
-            return self.graph.skip_w or _DEFAULT_GRAPH.skip_w
-        return getattr(self, k)
-
-    def __eq__(self, other):                 # (tests compare against a plain dict)
-        return {'second_order': self.second_order, 'skip_w': self['skip_w']} == other
-
-
-_STATE = _Local()
-
-
-def current_graph():
-    """token the nodes created right now belong to (see the threading note above)"""
-    return _STATE.graph if _STATE.second_order else _DEFAULT_GRAPH
-
-
-@contextlib.contextmanager
-def second_order(wrt=None):
-    """Forward passes inside this context are built from the any-order differentiable pieces right away (the caller knows
-    a create_graph backward follows), which saves the forward recomputation inside the recorded backward.
-    `wrt='latent'`: the recorded backward will stop at the generator's W+ latent (path-length regulariser,
-    train_spatial_query.py:92-105 with `return_latents=True`), so everything that PRODUCES the latent - mapping networks,
-    attention blocks, adjust_style - is differentiated once only and keeps its fused first-order nodes
-    (Generator.forward suspends the hint for that section)."""
-    old = (_STATE.second_order, _STATE.graph, _STATE.second_wrt)
-    _STATE.second_order, _STATE.graph, _STATE.second_wrt = True, _Graph(), wrt
-    try:
-        yield _STATE.graph
-    finally:
-        _STATE.second_order = old[0]         # (the token stays current for the no_weight_grads() that follows the forward)
-        _STATE.second_wrt = old[2]
-        if old[0]:
-            _STATE.graph = old[1]
-
-
-@contextlib.contextmanager
-def latent_producer_section():
-    """Generator.forward wraps the part that produces the latent in this: under second_order(wrt='latent') the hint is off
-    inside (see there); otherwise nothing changes."""
-    if not (_STATE.second_order and _STATE.second_wrt == 'latent'):
-        yield
-        return
-    _STATE.second_order = False
-    try:
-        yield
-    finally:
-        _STATE.second_order = True
-
-
-@contextlib.contextmanager
-def no_weight_grads():
-    """Around `autograd.grad(..., inputs=<activations / latents>, create_graph=True)`: the first-order weight gradients
-    of the convolutions are not among the requested inputs, so their correlation passes are skipped (autograd cannot tell
-    a Python Function which of its outputs are consumed).  Do NOT use around a backward that accumulates into weights.
-    Applies to the graph built by this thread's most recent `second_order()` forward and to nodes built outside any such
-    context (those share one process-wide token: hint-less double backward is not meant to run concurrently)."""
-    toks = {id(t): t for t in (_STATE.graph, _DEFAULT_GRAPH)}.values()
-    old = [(t, t.skip_w) for t in toks]
-    for t in toks:
-        t.skip_w = True
-    try:
-        yield
-    finally:
-        for t, o in old:
-            t.skip_w = o
+# the hints of the regulariser steps live in op/recorded.py (state, threading note); callers reach them through this module too
+from .recorded import (_DEFAULT_GRAPH, _STATE, current_graph, latent_producer_section, no_weight_grads, recorded_backward,      # noqa: F401
+                       second_order, weights_skipped)
+from .style import demod
 
 
 # Frozen-weight cache (inference-only pipeline, SURVEY §8f.3): inside `frozen_weights()` a forward that needs no gradient
@@ -458,7 +365,7 @@ class _ConvFwd(Function):
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        skip_w = ctx.graph.skip_w or _DEFAULT_GRAPH.skip_w
+        skip_w = weights_skipped(ctx.graph)
         with cache_of(ctx):
             gx = _ConvDgrad.apply(gy, w, ctx.kind, ctx.wscale) if ctx.needs_input_grad[0] else None
             gw = _ConvWgrad.apply(gy, x, ctx.kind, w.shape[2], ctx.wscale) if (ctx.needs_input_grad[1] and not skip_w) else None
@@ -565,7 +472,6 @@ def _rgb_ok(kind, Co, Ci, x_like, osc, act=False):
 
 
 def _chan_dot(a, b):
-    from .chanscale import _ChanDot
     return _ChanDot.apply(a.contiguous(), b.contiguous())
 
 
@@ -586,7 +492,7 @@ class _MCFwd(Function):
     def backward(ctx, gy):
         x, w, s, d, y = ctx.saved_tensors
         need = ctx.needs_input_grad
-        skip_w = ctx.graph.skip_w or _DEFAULT_GRAPH.skip_w
+        skip_w = weights_skipped(ctx.graph)
         with cache_of(ctx):
             gx = _MCDgrad.apply(gy, w, s, d, ctx.kind, ctx.wscale) if (need[0] or need[2]) else None
             gw = _MCWgrad.apply(gy, x, s, d, ctx.kind, w.shape[2], ctx.wscale) if (need[1] and not skip_w) else None
@@ -678,6 +584,40 @@ def _composite(x, w, isc, osc, bias, act, kind, wscale=1.0):
     return y
 
 
+def _modconv_bwd(g, x, w, isc, osc, kind, wscale, need, wp_bwd=None, rgb=False, wsq=None):
+    """First-order backward of the modulated convolution y = osc (.) conv(isc (.) x, wscale w) from g = dL/dy (contiguous) ->
+    (gx, gw, gisc, gosc): ONE data-gradient convolution (wp_bwd: its packed weights and kind as the forward planned them; rgb: the
+    ToRGB streaming kernels), ONE correlation pass into per-sample slabs, the slab reducer.  need: flags for (x, w, isc, osc).
+    wsq (te_demod_fwd_f32's squares): osc is the demodulation coefficient of (w, isc) computed inside the node, so its gradient is
+    chained into gw / gisc in place and gosc comes back None.  Shared by _ModConvFused and op/styled_rgb.py::_ModConvRGB."""
+    gx = gw = gisc = gosc = None
+    if need[0] and rgb:
+        gx = _lib.rgb_dgrad(g, w.reshape(w.shape[0], w.shape[1]), isc, x.shape[1], wscale)
+    elif need[0]:
+        gx = _dgrad_raw(g, w, kind, isc=osc, osc=isc, wscale=wscale, wp=wp_bwd)
+    if need[1] or (need[2] and isc is not None) or (need[3] and osc is not None):
+        slabs = _lib.rgb_wgrad_slabs(g, x) if rgb else _wgrad_raw(g, x, kind)
+        if kind == 'down' and isc is None and osc is None:        # the discriminator's convolutions
+            gw = _slab_sum(slabs, kind).reshape(w.shape) if need[1] else None
+            if gw is not None and wscale != 1.0:
+                gw = gw * wscale
+            return gx, gw, None, None
+        if kind == 'down':       # modulated (ModulatedConv2d(downsample=True)): slabs come as [B,S,Ci,Co,taps]
+            slabs = slabs.sum(dim=1).transpose(1, 2).contiguous().unsqueeze(1)
+        w3 = w.reshape(w.shape[0], w.shape[1], -1)
+        dm = wsq is not None
+        gw, gisc, gosc = _lib.wgrad_reduce(slabs, w3, wscale, isc, osc,
+                                           want_w=need[1], want_isc=need[2] and isc is not None,
+                                           want_osc=(need[3] or dm) and osc is not None)
+        if dm:       # chain through d = demod(w, isc): its dW / d style are added to gw / gisc in place
+            if gw is not None or gisc is not None:
+                _lib.demod_bwd(gosc, osc, w3, wsq, isc, wscale, into=(gw, gisc))
+            gosc = None
+        if gw is not None:
+            gw = gw.reshape(w.shape)
+    return gx, gw, gisc, gosc
+
+
 class _ModConvFused(Function):
     @staticmethod
     def forward(ctx, x, w, isc, osc, bias, act, kind, wscale, demod_eps):
@@ -724,23 +664,13 @@ class _ModConvFused(Function):
         act, kind, wscale = ctx.act, ctx.kind, ctx.wscale
         need = ctx.needs_input_grad
         if torch.is_grad_enabled():
-            # double backward requested: differentiate the composite built from the closed trio
-            # The inputs may depend on each other in the OUTER graph (osc = demod is a function of isc = style
-            # scale): differentiate w.r.t. fresh aliases so each returned gradient is the PARTIAL derivative,
-            # while everything stays connected to the original tensors for the next differentiation.
-            with torch.enable_grad():
-                al = [None if t is None else t.view_as(t) for t in (x, w, isc, osc, bias)]
-                if ctx.demod is not None:          # osc is a function of (w, isc) inside this node
-                    from .style import demod as _demod
-                    al[3] = _demod(al[1], al[2], wscale, ctx.demod[0])
-                    need = tuple(need[:3]) + (False,) + tuple(need[4:])
-                y = _composite(al[0], al[1], al[2], al[3], al[4], act, kind, wscale)
-                if _DEFAULT_GRAPH.skip_w:        # (a node of the fused path was built outside second_order(): default token)
-                    need = (need[0], False) + tuple(need[2:])
-                ins = [t for t, n in zip(al, need[:5]) if n and t is not None]
-                gs = iter(torch.autograd.grad(y, ins, g, create_graph=True, allow_unused=True))
-            return tuple(next(gs) if (n and t is not None) else None
-                         for t, n in zip(al, need[:5])) + (None, None, None, None)
+            # double backward requested: differentiate the composite built from the closed trio (op/recorded.py)
+            dm = ctx.demod is not None           # osc is then a function of (w, isc) inside this node, rebuilt from their aliases
+
+            def build(x, w, isc, osc, bias):
+                return _composite(x, w, isc, demod(w, isc, wscale, ctx.demod[0]) if dm else osc, bias, act, kind, wscale)
+            nd = (need[0], need[1] and not weights_skipped()) + need[2:5]      # (built outside second_order(): default token)
+            return tuple(recorded_backward(build, (x, w, isc, None if dm else osc, bias), nd, g)) + (None,) * 4
         g = g.contiguous()
         g_bias = None
         if act:
@@ -754,31 +684,8 @@ class _ModConvFused(Function):
                 gw = _lib.rgb_wgrad_slabs(x, g).sum(dim=(0, 1)).reshape(3, w.shape[0]).t().reshape(w.shape)
                 gw = gw * wscale if wscale != 1.0 else gw
             return gx, gw, None, None, g_bias, None, None, None, None
-        if ctx.rgb:
-            gx = _lib.rgb_dgrad(g, w.reshape(w.shape[0], w.shape[1]), isc, x.shape[1], wscale) if need[0] else None
-        else:
-            gx = _dgrad_raw(g, w, kind, isc=osc, osc=isc, wscale=wscale, wp=ctx.wp_bwd) if need[0] else None
-        gw = gisc = gosc = None
-        if need[1] or (need[2] and isc is not None) or (need[3] and osc is not None):
-            slabs = _lib.rgb_wgrad_slabs(g, x) if ctx.rgb else _wgrad_raw(g, x, kind)
-            if kind == 'down' and isc is None and osc is None:        # the discriminator's convolutions
-                gw = _slab_sum(slabs, kind).reshape(w.shape) if need[1] else None
-                if gw is not None and wscale != 1.0:
-                    gw = gw * wscale
-                return gx, gw, None, None, g_bias, None, None, None, None
-            if kind == 'down':       # modulated (ModulatedConv2d(downsample=True)): slabs come as [B,S,Ci,Co,taps]
-                slabs = slabs.sum(dim=1).transpose(1, 2).contiguous().unsqueeze(1)
-            w3 = w.reshape(w.shape[0], w.shape[1], -1)
-            dm = ctx.demod is not None
-            gw, gisc, gosc = _lib.wgrad_reduce(slabs, w3, wscale, isc, osc,
-                                               want_w=need[1], want_isc=need[2] and isc is not None,
-                                               want_osc=(need[3] or dm) and osc is not None)
-            if dm:       # chain through d = demod(w, isc): its dW / d style are added to gw / gisc in place
-                if gw is not None or gisc is not None:
-                    _lib.demod_bwd(gosc, osc, w3, ctx.demod[1], isc, wscale, into=(gw, gisc))
-                gosc = None
-            if gw is not None:
-                gw = gw.reshape(w.shape)
+        wsq = ctx.demod[1] if ctx.demod is not None else None
+        gx, gw, gisc, gosc = _modconv_bwd(g, x, w, isc, osc, kind, wscale, need[:4], getattr(ctx, 'wp_bwd', None), ctx.rgb, wsq)
         return gx, gw, gisc, gosc, g_bias, None, None, None, None
 
 
@@ -791,12 +698,10 @@ def modconv(x, w, isc=None, osc=None, bias=None, act=False, kind='3x3', wscale=1
     if demod_eps is not None and (osc is not None or isc is None or isc.shape[0] > 64 or w.shape[1] > 8192):
         if osc is not None or isc is None:
             raise RuntimeError('modconv: demod_eps needs isc and excludes an explicit osc')
-        from .style import demod as _demod
-        osc, demod_eps = _demod(w, isc, float(wscale), demod_eps), None      # shapes the demod kernels do not cover
+        osc, demod_eps = demod(w, isc, float(wscale), demod_eps), None      # shapes the demod kernels do not cover
     if _STATE.second_order and torch.is_grad_enabled():
         if demod_eps is not None:
-            from .style import demod as _demod
-            osc = _demod(w, isc, float(wscale), demod_eps)
+            osc = demod(w, isc, float(wscale), demod_eps)
         return _composite(x, w, isc, osc, bias, act, kind, float(wscale))
     isc = isc.contiguous() if isc is not None else None
     osc = osc.contiguous() if osc is not None else None

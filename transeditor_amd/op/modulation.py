@@ -18,6 +18,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from .linear import _closed_expr
+from .recorded import recorded_backward
 
 
 def _offsets(ts):
@@ -78,14 +79,10 @@ class _BatchedModulation(Function):
         need = ctx.needs_input_grad
         B, Z, K = lat_g.shape
         if torch.is_grad_enabled():              # recorded backward: layer by layer through the closed trio
-            with torch.enable_grad():
-                la = lat_g.view_as(lat_g)
-                pa = [p.view_as(p) for p in params]
-                ys = [_closed_expr(la[:, z], pa[z], pa[n + z], alpha, beta, None, None) for z in range(n)]
-                ins = [t for t, f in zip([la] + pa, [need[0]] + list(need[4:])) if f]
-                res = iter(torch.autograd.grad(ys, ins, list(gs), create_graph=True, allow_unused=True))
-            glat = next(res) if need[0] else None
-            return (glat, None, None, None) + tuple(next(res) if f else None for f in need[4:])
+            def build(la, *pa):
+                return [_closed_expr(la[:, z], pa[z], pa[n + z], alpha, beta, None, None) for z in range(n)]
+            r = recorded_backward(build, [lat_g] + params, need[:1] + need[4:], gs)
+            return (r[0], None, None, None) + tuple(r[1:])
         lat_g = lat_g.contiguous()
         glat = torch.empty_like(lat_g) if need[0] else None
         gws, gbs = [None] * n, [None] * n

@@ -26,6 +26,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from .modconv import _act_code, _composite, _dgrad_raw, _wgrad_plain, cache_of, keep_cache, packed_route
+from .recorded import recorded_backward
 from .upfirdn2d import _geometry, flipped_taps, upfirdn2d
 
 _SQRT2 = math.sqrt(2.0)
@@ -93,18 +94,11 @@ class _ResBlock(Function):
         x, w1, b1, w2, b2, ws, k_main, k_skip, y1, yb, y2, xs, img, w0, b0 = ctx.saved_tensors
         s1, s2, ss, pad_main, pad_skip, gain, pm, ps, s0, need_x = ctx.cfg
         need = ctx.needs_input_grad
-        if torch.is_grad_enabled():          # double backward requested: differentiate the composite (partial derivatives
-            with torch.enable_grad():        # w.r.t. fresh aliases, everything stays connected for the next order)
-                src = (img if ctx.stem else x, w1, b1, w2, b2, ws)
-                al = [t.view_as(t) for t in src]
-                st = [w0.view_as(w0), b0.view_as(b0)] if ctx.stem else [None, None]
-                y = resblock_composite(*al, k_main, k_skip, s1, s2, ss, pad_main, pad_skip, gain, st[0], st[1], s0)
-                flags = list(need[:6]) + ([need[14], need[15]] if ctx.stem else [])
-                ins = [t for t, n in zip(al + (st if ctx.stem else []), flags) if n]
-                gs = iter(torch.autograd.grad(y, ins, g, create_graph=True, allow_unused=True))
-            first = tuple(next(gs) if n else None for n in need[:6])
-            tail = (next(gs) if need[14] else None, next(gs) if need[15] else None) if ctx.stem else (None, None)
-            return first + (None,) * 8 + tail + (None,)
+        if torch.is_grad_enabled():          # double backward requested: differentiate the composite (op/recorded.py)
+            def build(x, w1, b1, w2, b2, ws, w0, b0):          # (w0, b0 are None without the stem)
+                return resblock_composite(x, w1, b1, w2, b2, ws, k_main, k_skip, s1, s2, ss, pad_main, pad_skip, gain, w0, b0, s0)
+            r = recorded_backward(build, (img if ctx.stem else x, w1, b1, w2, b2, ws, w0, b0), need[:6] + need[14:16], g)
+            return tuple(r[:6]) + (None,) * 8 + (r[6], r[7], None)
         bwd1, bwd2, bwds = ctx.packs
         g = g.contiguous()
         front = need_x or need[1] or need[2]

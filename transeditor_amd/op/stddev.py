@@ -7,6 +7,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
+from .recorded import recorded_backward
 
 EPS = 1e-8
 
@@ -31,9 +32,7 @@ class _Stddev(Function):
     def backward(ctx, gy):
         x, = ctx.saved_tensors
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                xa = x.view_as(x)
-                gx, = torch.autograd.grad(_torch_expr(xa, ctx.group, 1, ctx.chunks), xa, gy, create_graph=True)
+            gx, = recorded_backward(lambda x: _torch_expr(x, ctx.group, 1, ctx.chunks), (x,), ctx.needs_input_grad[:1], gy)
             return gx, None, None
         return _lib.minibatch_stddev_bwd(gy, x.contiguous(), ctx.group, EPS, ctx.chunks), None, None
 

@@ -9,6 +9,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from .linear import _LinFwd
+from .recorded import recorded_backward
 
 
 def _torch_expr(w, s, wscale, eps):
@@ -34,11 +35,7 @@ class _Demod(Function):
         wscale, eps = ctx.cfg
         need = ctx.needs_input_grad
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                wa, sa = w.view_as(w), s.view_as(s)
-                ins = [t for t, n in zip((wa, sa), need[:2]) if n]
-                gs = iter(torch.autograd.grad(_torch_expr(wa, sa, wscale, eps), ins, gd, create_graph=True))
-            return tuple(next(gs) if n else None for n in need[:2]) + (None, None)
+            return tuple(recorded_backward(lambda w, s: _torch_expr(w, s, wscale, eps), (w, s), need[:2], gd)) + (None, None)
         w3 = w.reshape(w.shape[0], w.shape[1], -1).contiguous()
         gw, gs = _lib.demod_bwd(gd, d, w3, wsq, s.contiguous(), wscale, want_w=need[0], want_s=need[1])
         return (gw.reshape(w.shape) if gw is not None else None), gs, None, None

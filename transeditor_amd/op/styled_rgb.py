@@ -10,15 +10,17 @@ activation-gradient pass of the convolution (reads two, writes one): 28 bytes pe
 gradient is three multiply-adds per element inside the activation-gradient pass (te_bias_act_bwd_rgb_f32): 12 bytes per
 element, and the last layer - whose activation feeds ToRGB only - reads no upstream gradient at all.
 
-Everything else is the fused modulated-convolution backward of op/modconv.py (one data-gradient convolution, one
-correlation pass, the slab reducer, the demodulation chain).  A recorded backward (create_graph) differentiates the
-any-order composite of the same two layers; under `second_order()` the model does not build this node.
+Everything else is the fused modulated-convolution backward of op/modconv.py (`_modconv_bwd`: one data-gradient convolution,
+one correlation pass, the slab reducer, the demodulation chain).  A recorded backward (create_graph) differentiates the
+any-order composite of the same two layers (op/recorded.py); under `second_order()` the model does not build this node.
 """
 import torch
 from torch.autograd import Function
 
 from .. import _lib
-from .modconv import _DEFAULT_GRAPH, _composite, _dgrad_raw, _fwd_raw, _wgrad_raw, cache_of, keep_cache
+from .modconv import _composite, _fwd_raw, _modconv_bwd, cache_of, keep_cache
+from .recorded import recorded_backward, weights_skipped
+from .style import demod
 
 _SQRT2 = 2 ** 0.5
 
@@ -58,25 +60,14 @@ class _ModConvRGB(Function):
         wscale, eps, wscale_r = ctx.cfg
         need = ctx.needs_input_grad
         if torch.is_grad_enabled():
-            # recorded backward: the composite of the two layers w.r.t. fresh aliases (partial derivatives only)
-            with torch.enable_grad():
-                from .style import demod as _demod
-                al = [t.view_as(t) for t in (x, w, s, bias, wr, sr, br)]
-                ac = _composite(al[0], al[1], al[2], _demod(al[1], al[2], wscale, eps), al[3], True, '3x3', wscale)
-                rc = _composite(ac, al[4], al[5], None, al[6], False, '1x1', wscale_r)
-                outs, gouts = [], []
-                if ga is not None:
-                    outs.append(ac)
-                    gouts.append(ga)
-                if grgb is not None:
-                    outs.append(rc)
-                    gouts.append(grgb)
-                nd = list(need[:7])
-                if _DEFAULT_GRAPH.skip_w:
-                    nd[1] = nd[4] = False
-                ins = [t for t, n in zip(al, nd) if n]
-                gs = iter(torch.autograd.grad(outs, ins, gouts, create_graph=True, allow_unused=True))
-            return tuple(next(gs) if n else None for n in nd) + (None, None, None)
+            # recorded backward: the composite of the two layers (op/recorded.py)
+            def build(x, w, s, bias, wr, sr, br):
+                ac = _composite(x, w, s, demod(w, s, wscale, eps), bias, True, '3x3', wscale)
+                return ac, _composite(ac, wr, sr, None, br, False, '1x1', wscale_r)
+            nd = list(need[:7])
+            if weights_skipped():
+                nd[1] = nd[4] = False
+            return tuple(recorded_backward(build, (x, w, s, bias, wr, sr, br), nd, (ga, grgb))) + (None, None, None)
         Co = w.shape[0]
         gwr = gsr = gbr = None
         if grgb is not None:
@@ -99,16 +90,8 @@ class _ModConvRGB(Function):
                 gr = _lib.rgb_dgrad(grgb, wr.reshape(3, Co), sr, Co, wscale_r)
                 gt = gr if gt is None else gt + gr
             g, gb = _lib.bias_act_bwd(gt, a, 0.2, _SQRT2, want_bias=need[3])
-        # the modulated convolution's backward: one data-gradient convolution, one correlation pass, one reducer
-        gx = _dgrad_raw(g, w, '3x3', isc=d, osc=s, wscale=wscale, wp=ctx.wp_bwd) if need[0] else None
-        gw = gs = None
-        if need[1] or need[2]:
-            slabs = _wgrad_raw(g, x, '3x3')
-            w3 = w.reshape(Co, w.shape[1], -1)
-            gw, gs, gd = _lib.wgrad_reduce(slabs, w3, wscale, s, d, want_w=need[1], want_isc=need[2], want_osc=True)
-            _lib.demod_bwd(gd, d, w3, wsq, s, wscale, into=(gw, gs))      # chain through d = demod(w, s), accumulated in place
-            if gw is not None:
-                gw = gw.reshape(w.shape)
+        # the modulated convolution's backward, its demodulation chain included
+        gx, gw, gs, _ = _modconv_bwd(g, x, w, s, d, '3x3', wscale, (need[0], need[1], need[2], False), ctx.wp_bwd, wsq=wsq)
         return gx, gw, gs, gb, gwr, gsr, gbr, None, None, None
 
 

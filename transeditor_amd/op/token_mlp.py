@@ -15,6 +15,7 @@ from torch.autograd import Function
 from .. import _lib
 from .fused_act import fused_leaky_relu
 from .linear import bmm
+from .recorded import recorded_backward
 
 
 def _torch_expr(x, weights, biases, scale, lr_mul):
@@ -60,14 +61,8 @@ class _TokenMLP(Function):
         weights, biases = params[:T], params[T:]
         need = ctx.needs_input_grad
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                xa = x.view_as(x)
-                pa = [p.view_as(p) for p in params]
-                out = _torch_expr(xa, pa[:T], pa[T:], scale, lr_mul)
-                ins = [t for t, n in zip([xa] + pa, [need[0]] + list(need[4:])) if n]
-                gs = iter(torch.autograd.grad(out, ins, gy, create_graph=True, allow_unused=True))
-            gx = next(gs) if need[0] else None
-            return (gx, None, None, None) + tuple(next(gs) if n else None for n in need[4:])
+            r = recorded_backward(lambda x, *pa: _torch_expr(x, pa[:T], pa[T:], scale, lr_mul), [x] + params, need[:1] + need[4:], gy)
+            return (r[0], None, None, None) + tuple(r[1:])
         x = x.contiguous()
         B, D, Cn = x.shape
         N = weights[0].shape[0]
