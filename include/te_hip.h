@@ -538,6 +538,25 @@ int te_mt_adam_f32(const int64_t* table, const int32_t* chunks, int n_tensors, i
                    double beta1, double beta2, double eps, int step, te_stream_t stream);
 int te_mt_ema_f32(const int64_t* table, const int32_t* chunks, int n_tensors, int n_chunks, int chunk_elems, double decay,
                   te_stream_t stream);
+/* Ranger = RAdam + Lookahead + gradient centralisation (reference pSp/training/ranger.py:79-165, the encoder's optimiser,
+ * pSp/training/coach_new.py:225-233; one parameter at a time and about fifteen element-wise launches each there).
+ *   table[7][n] (int64) = param ptr, grad ptr (0 = no gradient: tensor skipped), exp_avg ptr, exp_avg_sq ptr, slow_buffer ptr,
+ *                         numel, L.  L = numel / shape[0] where the reference centralises the gradient (ranger.py:118-119: the mean
+ *                         over every dim but the first is subtracted), 0 where it does not.
+ *   work[3][n_work] (int32) = tensor index, first row, row count: a block owns whole rows of L elements (L == 0: "rows" of
+ *                         tile_elems elements, no mean).  Rows of L <= tile_elems come in groups of at most tile_elems elements;
+ *                         a longer row is an entry of its own.  Every row of a tensor must be in exactly one entry.
+ * Per element, fp32, one rounding per operation (ranger.py:118-163):  g' = g - mean(row);  v = v beta2 + (1 - beta2) g' g';
+ *   m = m beta1 + (1 - beta1) g';  decay != 0: p += -decay p;  rectified: p += -step_lr m / (sqrt(v) + eps), else p += -step_lr m;
+ *   lookahead: slow += alpha (p - slow), p = slow (slow_buffer is neither read nor written otherwise).  p.grad is not modified.
+ * The schedule is the caller's: step_lr = step_size * lr and decay = weight_decay * lr are formed in double on the host, as are
+ * the two branch flags.  A row's sum is a fixed function of L and the element index (the order: csrc/optim.hip), so results do not
+ * depend on alignment, on the work map's grouping, or on the other tensors.  16-byte accesses where every pointer of the tensor
+ * sits at the same offset inside its 16 bytes.  tile_elems: a multiple of 4, 2048 <= tile_elems <= 8184; 0 <= beta < 1, eps > 0,
+ * 0 <= alpha <= 1, else TE_ERR_SHAPE and nothing is launched. */
+int te_mt_ranger_f32(const int64_t* table, const int32_t* work, int n_tensors, int n_work, int tile_elems, double step_lr,
+                     double decay, double beta1, double beta2, double eps, double alpha, int rectified, int lookahead,
+                     te_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-(sample, channel) scaling of an activation tensor and its adjoint: the elementwise pieces of the any-order composite

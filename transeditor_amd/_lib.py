@@ -725,6 +725,14 @@ def mt_ema(table, chunks, n_tensors, n_chunks, chunk_elems, decay):
     _launch('te_mt_ema_f32', table.data_ptr(), chunks.data_ptr(), n_tensors, n_chunks, chunk_elems, float(decay))
 
 
+@_op
+def mt_ranger(table, work, n_tensors, n_work, tile_elems, step_lr, decay, beta1, beta2, eps, alpha, rectified, lookahead):
+    """table: int64 device tensor [7, n]; work: int32 device tensor [3, n_work] of whole-row groups (see te_hip.h)"""
+    _on_current_device(table)
+    _launch('te_mt_ranger_f32', table.data_ptr(), work.data_ptr(), n_tensors, n_work, tile_elems, float(step_lr), float(decay),
+            float(beta1), float(beta2), float(eps), float(alpha), int(bool(rectified)), int(bool(lookahead)))
+
+
 # --------------------------------------------------------------------------------------------- channel scale / dot
 @_op
 def chan_scale(x, s):

@@ -23,7 +23,9 @@ where some heads read a shared feature and the others their own activations; bot
 does not grow with the number of heads: ten for the real geometry (138 convolutions and 30 linears).  Planes of a few pixels take the
 launch's split-K route.  The EqualLinear of every head is one more launch (1 x 1 on the 1 x 1 plane), and te_psp_codes_f32 stacks,
 applies adjust_style over the head axis, permutes and adds the latent averages.  An image's codes are bitwise the same whatever batch it
-is in.  Eval only: there is no backward pass; training the encoder (pSp/training/coach_new.py) is out of scope.  Measured deviations and
+is in.  Eval only: there is no backward pass.  Of encoder training (pSp/training/coach_new.py) the loss (encoder_loss.EncoderLoss,
+DESIGN.md section 8j) and the optimiser (optim.Ranger / optim.encoder_optimizer, section 8k) exist; this network's own backward pass,
+and with it the training loop, is still out of scope.  Measured deviations and
 times: profiles/README.md, 'Encoder inversion'.
 """
 import argparse
