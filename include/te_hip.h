@@ -470,6 +470,18 @@ int te_small_gemm_splitk_f32(float* c, float* pre, float* ws, int S, const float
                              const float* residual, int I, int J, int K, int64_t sai, int64_t sak, int64_t sbk, int64_t sbj,
                              float alpha, float beta, int act, te_stream_t stream);
 
+/* Which of the 20 instantiations small_gemm_kernel<NW, AV, BV> (csrc/linear.hip) a launch runs, and on which grid (host only, nothing
+ * is launched: the answer is the plan that the three entry points themselves make and then dispatch on).  The plan reads the dims,
+ * nz (1 for te_small_gemm_f32), the operand strides, the z strides za / zb, b_tab (NULL: the uniform form; else nz <= 16 offsets)
+ * and the two base addresses mod 16 (a_mod16, b_mod16: 0 ... 15), nothing else.  splitk != 0: nz is S and K the whole reduction of
+ * te_small_gemm_splitk_f32; the answer is the plan of its chunk launch (K / S per chunk, za = K / S * sak, zb = K / S * sbk; the
+ * za, zb given are not read, b_tab must be NULL).
+ * form[TE_SMALL_GEMM_FORM_INTS]: [0] nw (waves that split K: 1, 2, 4, 8, 16)  [1] av  [2] bv (16-byte loads of A / of B)
+ * [3] [4] [5] grid x, y, z.  TE_ERR_NULL / TE_ERR_SHAPE / TE_ERR_UNSUPPORTED as the launches return them for the same arguments. */
+#define TE_SMALL_GEMM_FORM_INTS 6
+int te_small_gemm_form(int I, int J, int K, int nz, int64_t sai, int64_t sak, int64_t sbk, int64_t sbj, int64_t za, int64_t zb,
+                       const int64_t* b_tab, int a_mod16, int b_mod16, int splitk, int* form);
+
 /* D1  minibatch standard deviation + channel concat of the discriminator (reference: Discriminator.forward,
  * model_spatial_query.py:844-852) as one launch: with n = B / group, sample b = g * n + j belongs to set j;
  *   s_j = mean over the C*HW positions of sqrt(var_g x[g*n + j] + eps)      (biased variance over the `group` samples)

@@ -546,13 +546,17 @@ def rgb_wgrad_slabs(g, x):
 # --------------------------------------------------------------------------------------------- G2/A2
 @_op
 def small_gemm(I, J, K, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alpha=1.0, beta=1.0, act=0, want_pre=False,
-               rowsum_scale=None):
+               rowsum_scale=None, out=None):
     """C[I,J] = act(alpha * A B + beta * bias) + residual with strided operands (see te_hip.h); a / b are the base
     tensors (contiguous storage, addressed through the element strides).  Returns (C, pre | None, rowsum | None);
-    rowsum_scale != None asks for rowsum[i] = rowsum_scale * sum_k A(i,k)."""
-    c = torch.empty(I, J, device=a.device, dtype=a.dtype)
-    pre = torch.empty_like(c) if want_pre else None
-    rs = torch.empty(I, device=a.device, dtype=a.dtype) if rowsum_scale is not None else None
+    rowsum_scale != None asks for rowsum[i] = rowsum_scale * sum_k A(i,k).  out: the caller's (C, pre, rowsum) to write
+    into (a test's views inside guard bands), each None where it is not wanted."""
+    if out is not None:
+        c, pre, rs = out
+    else:
+        c = torch.empty(I, J, device=a.device, dtype=a.dtype)
+        pre = torch.empty_like(c) if want_pre else None
+        rs = torch.empty(I, device=a.device, dtype=a.dtype) if rowsum_scale is not None else None
     # a / b are addressed through explicit strides: only device / dtype are checked
     _launch('te_small_gemm_f32', _ptr(c), _ptr(pre), _raw(a), _raw(b), _ptr(bias), _ptr(residual), _ptr(rs),
             rowsum_scale if rowsum_scale is not None else 0.0, I, J, K, sai, sak, sbk, sbj, alpha, beta, act)
@@ -560,14 +564,28 @@ def small_gemm(I, J, K, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alph
 
 
 @_op
-def small_gemm_splitk(I, J, K, S, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alpha=1.0, beta=1.0, act=0, want_pre=False):
-    """small_gemm for wide reductions: K in S chunks over the grid, fixed-order second pass (see te_hip.h)."""
-    c = torch.empty(I, J, device=a.device, dtype=a.dtype)
-    pre = torch.empty_like(c) if want_pre else None
-    ws = torch.empty(S, I, J, device=a.device, dtype=a.dtype)
+def small_gemm_splitk(I, J, K, S, a, sai, sak, b, sbk, sbj, bias=None, residual=None, alpha=1.0, beta=1.0, act=0, want_pre=False,
+                      out=None):
+    """small_gemm for wide reductions: K in S chunks over the grid, fixed-order second pass (see te_hip.h).  out: the caller's
+    (C, pre | None, workspace [S, I, J]) to write into."""
+    if out is not None:
+        c, pre, ws = out
+    else:
+        c = torch.empty(I, J, device=a.device, dtype=a.dtype)
+        pre = torch.empty_like(c) if want_pre else None
+        ws = torch.empty(S, I, J, device=a.device, dtype=a.dtype)
     _launch('te_small_gemm_splitk_f32', _ptr(c), _ptr(pre), _ptr(ws), S, _raw(a), _raw(b), _ptr(bias), _ptr(residual), I, J, K, sai, sak,
             sbk, sbj, alpha, beta, act)
     return c, pre
+
+
+def small_gemm_form(I, J, K, nz, sai, sak, sbk, sbj, za=0, zb=0, b_tab=None, a_mod16=0, b_mod16=0, splitk=False):
+    """(nw, av, bv, grid x, y, z) that the small_gemm launches plan for these arguments (host only; splitk: nz is S, the chunk plan);
+    the negative TE_ERR_* code where they refuse"""
+    buf = (C.c_int * 6)()
+    bt = (C.c_int64 * max(len(b_tab), min(nz, 16)))(*b_tab) if b_tab is not None else None
+    rc = lib().te_small_gemm_form(I, J, K, nz, sai, sak, sbk, sbj, za, zb, bt, a_mod16, b_mod16, int(splitk), buf)
+    return rc if rc else tuple(buf)
 
 
 @_op

@@ -153,22 +153,62 @@ void launch_nw(const LinArgs& p, bool av, bool bv, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
-static int launch_small_gemm(LinArgs& p, int nz, hipStream_t s) {
-    const bool av = p.sak == 1 && p.sai % 4 == 0 && p.za % 4 == 0 && (reinterpret_cast<uintptr_t>(p.a) & 15) == 0;
-    bool bv = p.sbk == 1 && p.sbj % 4 == 0 && p.zb % 4 == 0 && (reinterpret_cast<uintptr_t>(p.b) & 15) == 0;
-    if (p.use_tab)
-        for (int z = 0; z < nz; ++z) bv = bv && p.b_tab[z] % 4 == 0;
-    dim3 grid((unsigned)te::cdiv(p.J, 32), (unsigned)te::cdiv(p.I, 32), (unsigned)nz);
+// which of the 20 instantiations a launch takes, and on which grid: decided from the dims, the strides, the z strides, the table of
+// per-z offsets (NULL: the uniform form) and the two base addresses mod 16 alone.  launch_planned_gemm dispatches on nothing else, and
+// te_small_gemm_form reports it.
+struct GemmPlan {
+    int nw;
+    bool av, bv;
+    dim3 grid;
+};
+
+static GemmPlan plan_small_gemm(int I, int J, int K, int nz, int64_t sai, int64_t sak, int64_t sbk, int64_t sbj, int64_t za, int64_t zb,
+                                const int64_t* b_tab, unsigned a_mod16, unsigned b_mod16) {
+    GemmPlan pl;
+    pl.av = sak == 1 && sai % 4 == 0 && za % 4 == 0 && a_mod16 == 0;
+    pl.bv = sbk == 1 && sbj % 4 == 0 && zb % 4 == 0 && b_mod16 == 0;
+    if (b_tab)
+        for (int z = 0; z < nz; ++z) pl.bv = pl.bv && b_tab[z] % 4 == 0;
+    pl.grid = dim3((unsigned)te::cdiv(J, 32), (unsigned)te::cdiv(I, 32), (unsigned)nz);
     // waves per tile: a wave's K slice <= 64 where possible, and more waves when the grid alone cannot fill the chip
-    const int64_t tiles = (int64_t)grid.x * grid.y * grid.z;
-    const int K = p.K;
-    int nw = K > 256 ? 8 : (K > 64 ? 4 : (K > 16 ? 2 : 1));
-    if (K >= 512 && (K > 512 || tiles < 2 * te::kNumCU)) nw = 16;
-    if (nw == 16) launch_nw<16>(p, av, bv, grid, s);
-    else if (nw == 8) launch_nw<8>(p, av, bv, grid, s);
-    else if (nw == 4) launch_nw<4>(p, av, bv, grid, s);
-    else if (nw == 2) launch_nw<2>(p, av, bv, grid, s);
-    else launch_nw<1>(p, av, bv, grid, s);
+    const int64_t tiles = (int64_t)pl.grid.x * pl.grid.y * pl.grid.z;
+    pl.nw = K > 256 ? 8 : (K > 64 ? 4 : (K > 16 ? 2 : 1));
+    if (K >= 512 && (K > 512 || tiles < 2 * te::kNumCU)) pl.nw = 16;
+    return pl;
+}
+
+static void launch_planned_gemm(const GemmPlan& pl, const LinArgs& p, hipStream_t s) {
+    if (pl.nw == 16) launch_nw<16>(p, pl.av, pl.bv, pl.grid, s);
+    else if (pl.nw == 8) launch_nw<8>(p, pl.av, pl.bv, pl.grid, s);
+    else if (pl.nw == 4) launch_nw<4>(p, pl.av, pl.bv, pl.grid, s);
+    else if (pl.nw == 2) launch_nw<2>(p, pl.av, pl.bv, pl.grid, s);
+    else launch_nw<1>(p, pl.av, pl.bv, pl.grid, s);
+}
+
+static int launch_small_gemm(LinArgs& p, int nz, hipStream_t s) {
+    launch_planned_gemm(plan_small_gemm(p.I, p.J, p.K, nz, p.sai, p.sak, p.sbk, p.sbj, p.za, p.zb, p.use_tab ? p.b_tab : nullptr,
+                                        (unsigned)(reinterpret_cast<uintptr_t>(p.a) & 15), (unsigned)(reinterpret_cast<uintptr_t>(p.b) & 15)),
+                        p, s);
+    return 0;
+}
+
+// the plan of a launch (host only; see te_hip.h)
+extern "C" int te_small_gemm_form(int I, int J, int K, int nz, int64_t sai, int64_t sak, int64_t sbk, int64_t sbj, int64_t za, int64_t zb,
+                                  const int64_t* b_tab, int a_mod16, int b_mod16, int splitk, int* form) {
+    TE_REQUIRE(form, TE_ERR_NULL, "te_small_gemm_form: NULL pointer");
+    TE_REQUIRE(I > 0 && J > 0 && K > 0 && nz > 0, TE_ERR_SHAPE, "te_small_gemm_form: bad dims");
+    TE_REQUIRE(a_mod16 >= 0 && a_mod16 < 16 && b_mod16 >= 0 && b_mod16 < 16, TE_ERR_SHAPE, "te_small_gemm_form: an address mod 16 is 0 ... 15");
+    if (splitk) {        // nz is S: the chunk plan of te_small_gemm_splitk_f32
+        TE_REQUIRE(K % nz == 0 && (K / nz) % 8 == 0, TE_ERR_SHAPE, "te_small_gemm_form: K must split into S chunks of a multiple of 8");
+        TE_REQUIRE(!b_tab, TE_ERR_UNSUPPORTED, "te_small_gemm_form: the split-K form has no offset table");
+        K /= nz;
+        za = (int64_t)K * sak;
+        zb = (int64_t)K * sbk;
+    }
+    TE_REQUIRE(!b_tab || nz <= 16, TE_ERR_UNSUPPORTED, "te_small_gemm_form: at most 16 table entries per launch");
+    const GemmPlan pl = plan_small_gemm(I, J, K, nz, sai, sak, sbk, sbj, za, zb, b_tab, (unsigned)a_mod16, (unsigned)b_mod16);
+    form[0] = pl.nw; form[1] = pl.av; form[2] = pl.bv;
+    form[3] = (int)pl.grid.x; form[4] = (int)pl.grid.y; form[5] = (int)pl.grid.z;
     return 0;
 }
 
