@@ -331,6 +331,20 @@ int te_wgrad_t2_wide(int on);
  * launch dispatches on this function; a host query for tests. */
 enum { TE_WG6_FP32 = 0, TE_WG6_3X3 = 1, TE_WG6_3X3_PAIR = 2, TE_WG6_T2_WIDE = 3, TE_WG6_T2 = 4, TE_WG6_T2_MASKED = 5, TE_WG6_1X1 = 6 };
 int te_wgrad6_form(int kind, int B, int Co, int Ci, int H, int W, int NB);
+/* The plan of a te_wgrad_f32 (NB = 1) / te_wgrad_group_f32 launch with S chunks per sample group (host only, nothing is launched: the
+ * answer is the plan that the launch itself makes and then dispatches on).  The plan reads the kind, the dims, S, NB, the switches that
+ * te_wgrad6_form reads and the two base addresses mod 16 (g_mod16, x_mod16: 0 ... 15), nothing else.
+ * form[TE_WGRAD_FORM_INTS]: [0] the te_wgrad6_form code of the kernel that takes the launch - TE_WG6_FP32 also where te_wgrad6_form
+ * names a split kernel but g or x is not 16-byte aligned.  The rest describes the launch of the fp32 kernel
+ * wgrad_mfma_kernel<KIND, NWP, WINO> (csrc/wgrad.hip) and is all zeros when a split kernel takes the launch:
+ * [1] nwp (waves along the plain operand's channels: 2 = 256 threads, 64 x 64 channels per block; 4 = 512 threads, 128 x 64)
+ * [2] wino (the pair form, what te_wgrad_pair_form reports)  [3] vec (16-byte staging path)  [4] db (two LDS operand images)
+ * [5] [6] TW, TH (cell tile)  [7] [8] tiles_x, tiles_y (cell tiles of one sample)  [9] [10] [11] grid x, y, z  [12] dynamic LDS bytes.
+ * TE_ERR_NULL / TE_ERR_SHAPE / TE_ERR_UNSUPPORTED as the launch returns them for the same arguments (bad dims, a group size that does
+ * not divide the batch, a grid too large, an image too large for a cell tile, a sample group of 2 GiB or more); a refusal leaves
+ * form untouched. */
+#define TE_WGRAD_FORM_INTS 13
+int te_wgrad_form(int kind, int B, int Co, int Ci, int H, int W, int S, int NB, int g_mod16, int x_mod16, int* form);
 int te_wgrad_f32(float* slabs, const float* g, const float* x, int kind, int B, int Co, int Ci, int H,
                  int W, int S, te_stream_t stream);
 /* GROUPED form for the PLAIN (unmodulated) weight gradient of small images: NB consecutive samples share one slab

@@ -1,14 +1,15 @@
 """Host-plan table: every answer of the library's host-only launch planners over one fixed grid of arguments.
 
-The planners (te_*_plan, te_*_count, te_*_cover, te_conv_packed_numel, te_*_tiles, te_wgrad_pair_form, te_wgrad6_form in
-include/te_hip.h) launch nothing and need no GPU.  Their answers fix the summation partition of the split launches (so every result
+The planners (te_*_plan, te_*_count, te_*_cover, te_conv_packed_numel, te_*_tiles, te_wgrad_pair_form, te_wgrad6_form, te_wgrad_form
+in include/te_hip.h) launch nothing and need no GPU.  Their answers fix the summation partition of the split launches (so every result
 bit) and are what the loop-trip and route tests assert their coverage with, yet a planner that drifts from its launch fails no other
 test.  table(lib) calls each of them over the grid below and returns {name: int array}; return codes are part of the table.
 
     python tests/host_plans.py LIB OUT.npz        # the table of any library file
 
 tests/golden/host_plans.npz is the table of the library before the planners were derived from the launch code's own geometry;
-tests/test_host_plans_cpu.py asserts that the current library still gives it.
+tests/test_host_plans_cpu.py asserts that the current library still gives it.  A planner that is added later is recorded next to its
+relatives from the library that introduces it, with every older answer unchanged (wgrad_form: the plan of the fp32 weight-gradient launch).
 """
 import ctypes as C
 import itertools
@@ -81,8 +82,14 @@ def _pack(L):
             'conv_pack_plan': [_two(L.te_conv_pack_plan, *g) for g in grid]}
 
 
+def _wgrad_form(L, *args):
+    """(rc, *form) of te_wgrad_form for aligned operands; the form starts as -1 so that a refusal shows it untouched"""
+    form = (C.c_int * len(_lib.WGRAD_FORM))(*([-1] * len(_lib.WGRAD_FORM)))
+    return (L.te_wgrad_form(*args, 0, 0, form),) + tuple(form)
+
+
 def _wgrad(L):
-    out = {'wgrad_slab_count': [], 'wgrad_group_plan': [], 'wgrad_pair_form': [], 'wgrad6_form': []}
+    out = {'wgrad_slab_count': [], 'wgrad_group_plan': [], 'wgrad_pair_form': [], 'wgrad6_form': [], 'wgrad_form': []}
     saved = L.te_wgrad_split_bf16(-1)
     try:
         for on in (0, 1):
@@ -97,6 +104,9 @@ def _wgrad(L):
                             out['wgrad_pair_form'].append(L.te_wgrad_pair_form(kind, Co, Ci, H, W))
                             # the kernel of the per-sample launch and of the planned grouped one
                             out['wgrad6_form'].append((L.te_wgrad6_form(kind, B, Co, Ci, H, W, 1), L.te_wgrad6_form(kind, B, Co, Ci, H, W, NB)))
+                            # the plan of the same two launches (16-byte aligned operands) with the planners' chunk counts
+                            out['wgrad_form'].append(_wgrad_form(L, kind, B, Co, Ci, H, W, out['wgrad_slab_count'][-1], 1) +
+                                                     _wgrad_form(L, kind, B, Co, Ci, H, W, S, NB))
     finally:
         L.te_wgrad_split_bf16(saved)
     out['wgrad_slab_count_bad'] = [L.te_wgrad_slab_count(0, *g) for g in ((0, 64, 64, 8, 8), (2, 0, 64, 8, 8), (2, 64, 64, 8, 0))]

@@ -3,6 +3,7 @@ against the direct kernel - forward layout and data-gradient layout (flipped, tr
 epilogue stage (demodulation scale, bias, leaky-ReLU with gain sqrt(2) / 1, residual, activation-gradient mask), single-tile
 and multi-tile images, several M blocks, edge tiles on all four sides - and the weight transform of the packing kernel.
 Reference: the grouped F.conv2d of ModulatedConv2d.forward (model_spatial_query.py:331-333), EqualConv2d.forward (:173-181)."""
+import ctypes as C
 import math
 
 import pytest
@@ -110,11 +111,26 @@ PAIR_SHAPES = [  # B, Ci, Co, H, W: full 32-cell rows (16-byte staging), ragged 
 
 @pytest.mark.parametrize('B,Ci,Co,H,W', PAIR_SHAPES)
 def test_weight_gradient_pair_form_vs_fp64(B, Ci, Co, H, W):
-    """slabs of the pair form, summed, against the fp64 correlation (the weight gradient of F.conv2d, model_spatial_query.py:331-335)"""
+    """slabs of the pair form, summed, against the fp64 correlation (the weight gradient of F.conv2d, model_spatial_query.py:331-335).
+    The launches are asserted to run the fp32 pair form through te_wgrad_form; where the split-bf16 kernel would take the shape
+    (whole 64-channel blocks, W % 32 == 0) its switch is off for the test."""
     assert _lib.wgrad_pair_form(_lib.CONV_3X3, Co, Ci, H, W)
     g = synth.normal((B, Co, H, W), f'pair.g.{Co}.{H}.{W}').to(DEV)
     x = synth.normal((B, Ci, H, W), f'pair.x.{Ci}.{H}.{W}').to(DEV)
-    slabs = _lib.wgrad_slabs(g, x, _lib.CONV_3X3, H, W)
+    old = _lib.wgrad_split()
+    try:
+        if _lib.wgrad_split_ok(_lib.CONV_3X3, Co, Ci, H, W):
+            _lib.wgrad_split(0)
+        L, nb, sc = _lib.lib(), C.c_int(0), C.c_int(0)
+        assert L.te_wgrad_group_plan(_lib.CONV_3X3, B, Co, Ci, H, W, C.byref(nb), C.byref(sc)) == 0
+        plans = [(L.te_wgrad_slab_count(_lib.CONV_3X3, B, Co, Ci, H, W), 1)] + ([(sc.value, nb.value)] if nb.value > 1 else [])
+        for S, NB in plans:      # the per-sample launch and the grouped one, as wgrad_slabs makes them
+            f = _lib.wgrad_form(_lib.CONV_3X3, B, Co, Ci, H, W, S, NB, g.data_ptr() % 16, x.data_ptr() % 16)
+            assert (f['form6'], f['nwp'], f['wino']) == (0, 4, 1), f
+        slabs = _lib.wgrad_slabs(g, x, _lib.CONV_3X3, H, W)
+        grouped = _lib.wgrad_slabs(g, x, _lib.CONV_3X3, H, W, group=True)
+    finally:
+        _lib.wgrad_split(old)
     got = slabs.double().sum(dim=(0, 1))
     want = torch.nn.grad.conv2d_weight(x.double(), (Co, Ci, 3, 3), g.double(), padding=1).reshape(Co, Ci, 9)
     assert rel_err(got, want) < 5e-6
@@ -124,7 +140,6 @@ def test_weight_gradient_pair_form_vs_fp64(B, Ci, Co, H, W):
         wb = torch.nn.grad.conv2d_weight(x[b:b + 1].double(), (Co, Ci, 3, 3), g[b:b + 1].double(), padding=1).reshape(Co, Ci, 9)
         assert rel_err(per[b], wb) < 5e-6
     # grouped form (plain gradient of small images: NB samples share a slab)
-    grouped = _lib.wgrad_slabs(g, x, _lib.CONV_3X3, H, W, group=True)
     assert rel_err(grouped.double().sum(dim=(0, 1)), want) < 5e-6
 
 

@@ -413,12 +413,29 @@ def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, m
 
 
 @_op
-def wgrad_slabs(g, x, kind, H, W, group=False):
+def wgrad_slabs(g, x, kind, H, W, group=False, S=None, NB=None, out=None):
     """correlation slabs [B, S, Co, Ci, taps]; group=True (PLAIN gradient only - nothing per sample is derived from the slabs):
-    [B / NB, S, Co, Ci, taps] with NB samples per slab where the plan finds that worthwhile (small images, big weights)"""
+    [B / NB, S, Co, Ci, taps] with NB samples per slab where the plan finds that worthwhile (small images, big weights).
+    S= / NB= (tests): the caller's chunk count and group size instead of the planners' - te_wgrad_f32 with S when NB is None,
+    te_wgrad_group_f32 with S and NB otherwise (S is required then); slabs [B / NB, S, Co, Ci, taps], written into `out` when given
+    (a contiguous tensor of that shape, e.g. a view inside a guarded buffer)."""
     g, x = g.contiguous(), x.contiguous()
     B, Co, Ci = g.shape[0], g.shape[1], x.shape[1]
     taps = 1 if kind == CONV_1X1 else 9
+    if S is not None or NB is not None:
+        if S is None or S < 1 or (NB is not None and (NB < 1 or B % NB)):
+            raise RuntimeError(f'te_hip: wgrad_slabs needs S >= 1 and a group size that divides the batch (S={S}, NB={NB}, B={B})')
+        shape = (B // (NB or 1), S, Co, Ci, taps)
+        if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != g.dtype or out.device != g.device):
+            raise RuntimeError(f'te_hip: wgrad_slabs out= must be a contiguous {shape} tensor like g')
+        slabs = out if out is not None else torch.empty(shape, device=g.device, dtype=g.dtype)
+        if NB is None:
+            _launch('te_wgrad_f32', _ptr(slabs), _ptr(g), _ptr(x), kind, B, Co, Ci, H, W, S)
+        else:
+            _launch('te_wgrad_group_f32', _ptr(slabs), _ptr(g), _ptr(x), kind, B, Co, Ci, H, W, S, NB)
+        return slabs
+    if out is not None:
+        raise RuntimeError('te_hip: wgrad_slabs out= needs an explicit S')
     if group:
         nb, sc = C.c_int(0), C.c_int(0)
         _check(lib().te_wgrad_group_plan(kind, B, Co, Ci, H, W, C.byref(nb), C.byref(sc)), 'te_wgrad_group_plan')
@@ -458,6 +475,18 @@ WGRAD6_FORMS = ('fp32', 'w6', 'w6pair', 't2wide', 't2narrow', 't2masked', 'p1') 
 def wgrad6_form(kind, B, Co, Ci, H, W, NB=1):
     """name of the kernel wgrad_slabs runs for this problem (16-byte aligned operands; NB samples per slab), see WGRAD6_FORMS"""
     return WGRAD6_FORMS[lib().te_wgrad6_form(kind, B, Co, Ci, H, W, NB)]
+
+
+WGRAD_FORM = ('form6', 'nwp', 'wino', 'vec', 'db', 'TW', 'TH', 'tiles_x', 'tiles_y', 'grid_x', 'grid_y', 'grid_z', 'lds')      # te_wgrad_form (te_hip.h)
+
+
+def wgrad_form(kind, B, Co, Ci, H, W, S, NB=1, g_mod16=0, x_mod16=0):
+    """the plan of the wgrad_slabs launch with S chunks and NB samples per slab (host only): a dict of WGRAD_FORM - 'form6' is the
+    te_wgrad6_form code of the kernel that runs (0: the fp32 kernel, which the other fields describe; they are zeros otherwise);
+    the negative TE_ERR_* code where the launch refuses"""
+    buf = (C.c_int * len(WGRAD_FORM))()
+    rc = lib().te_wgrad_form(kind, B, Co, Ci, H, W, S, NB, g_mod16, x_mod16, buf)
+    return rc if rc else dict(zip(WGRAD_FORM, buf))
 
 
 def wgrad_pair_form(kind, Co, Ci, H, W):

@@ -67,6 +67,10 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned of
 
 PROF_BUFFER(wgrad, 8192 * 8)
 
+// does the tile loop keep TWO LDS operand images (one barrier per tile) or one (two barriers)?  The kernel and the launch plan (LDS bytes,
+// te_wgrad_form) read it here; the reasons stand at the tile loop.
+template <int KIND, int NWP> constexpr bool kTwoImages = (KIND != TE_CONV_1X1) && (NWP == 4);
+
 // WINO (3x3 only): the cells of a stage are taken as horizontal PAIRS and the three taps of a kernel row come out of FOUR
 // products per pair instead of six - the 1-D Winograd form F(3,2), the transpose of the F(2,3) the forward kernel (wino.hip)
 // uses.  For the pair (g0, g1) of the output gradient and the four inputs e0..e3 under it (one tap row ky):
@@ -401,7 +405,7 @@ __global__ __launch_bounds__(NWP * 128, 2) void wgrad_mfma_kernel(const WgArgs p
     // 1x1 (one MFMA per k-step: too few to hide anything behind) and the 4-wave tile of the narrow layers (two images would
     // leave room for ONE block = one wave per SIMD on a CU; measured 1.17 vs 0.89 ms at 64 -> 64 @512^2) keep a single image and
     // two barriers per tile, so that several blocks share a CU instead
-    constexpr bool DB = (KIND != TE_CONV_1X1) && (NWP == 4);
+    constexpr bool DB = kTwoImages<KIND, NWP>;
     for (int tl = t_begin; tl < t_end; ++tl) {
         PROF_LAP(pc[5]);
         float* cur = smem + (DB ? ((tl - t_begin) & 1) * bufsz : 0);
@@ -502,7 +506,7 @@ inline CellTile cell_tile(int ncell, int H, int W) {
 }
 
 template <int KIND>
-bool fill_geometry(WgArgs& a) {
+bool fill_geometry(WgArgs& a, bool aligned16) {      // aligned16: g and x both start on a 16-byte boundary
     const CellTile t = cell_tile(WK<KIND>::NCELL, a.H, a.W);
     a.TW = t.TW; a.TH = t.TH;
     a.NC = a.TH * a.TW;                            // cells per stage (<= NCELL)
@@ -524,7 +528,7 @@ bool fill_geometry(WgArgs& a) {
     // the 16-byte staging path needs full 32-cell rows whose global rows are 16 B aligned, and its one edge pass
     // (QCH * QH * 2 = 512 scalars at the full 64-cell tile) takes 512 / NTHREADS sweeps of the block
     a.vec = (a.TW == 32 && a.W % 32 == 0 && a.NC == WK<KIND>::NCELL && a.H % a.TH == 0 && QCH * a.QH * 2 <= 512 &&
-             (((uintptr_t)a.g | (uintptr_t)a.x) & 15) == 0) ? 1 : 0;
+             aligned16) ? 1 : 0;
     return QCH * a.QH * a.QW <= WK<KIND>::NQ8 * 512 && a.NC <= WK<KIND>::NCELL;
 }
 
@@ -536,29 +540,47 @@ inline int pick_nwp(int Co, int Ci) { return (Co <= 64 && Ci <= 64) ? 2 : 4; }
 // same deviation from an fp64 reference (1.0e-6 vs 1.1e-6 relative).
 inline bool pair_form_3x3(int Co, int Ci, int NC) { return pick_nwp(Co, Ci) == 4 && NC % 4 == 0; }
 
+// The plan of a launch: everything that decides which kernel runs and how, made from the arguments alone.  plan_wgrad (below, next to the
+// entry points) fills it; wgrad_launch dispatches on it and te_wgrad_form reports it, so the report cannot drift from the launch.
+struct WgPlan {
+    int form6;                  // te_wgrad6_form code of the kernel that takes the launch; TE_WG6_FP32: wgrad_mfma_kernel and the fields below
+    int nwp, wino, db;          // the instantiation <KIND, nwp, wino> and whether it keeps two LDS images
+    WgArgs a;                   // the kernel's argument block, pointers unset
+    dim3 grid;
+    size_t lds;                 // dynamic LDS bytes
+};
+
+template <int KIND>
+int plan_wgrad_kind(WgPlan& pl, bool aligned16) {
+    WgArgs& a = pl.a;
+    if (!fill_geometry<KIND>(a, aligned16)) return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: unsupported image size %dx%d", a.H, a.W);
+    if ((int64_t)a.NB * a.Co * a.Hg * a.Wg * 4 >= (int64_t)OOB || (int64_t)a.NB * a.Ci * a.Hx * a.Wx * 4 >= (int64_t)OOB)
+        return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: a sample group exceeds 2 GiB");
+    pl.wino = (KIND == TE_CONV_3X3 && pair_form_3x3(a.Co, a.Ci, a.NC)) ? 1 : 0;
+    pl.nwp = pl.wino ? 4 : pick_nwp(a.Co, a.Ci);
+    pl.db = (pl.nwp == 4 ? kTwoImages<KIND, 4> : kTwoImages<KIND, 2>) ? 1 : 0;     // 8-wave 3x3 / T2: two operand images
+    const int PCH = pl.nwp * 32;
+    pl.lds = (pl.db ? 2 : 1) * sizeof(float) * ((size_t)PCH * a.PS + (size_t)QCH * a.QS);
+    if (pl.nwp == 2) pl.lds = std::max(pl.lds, sizeof(float) * 2 * WK<KIND>::NT * 16 * 64);     // K-split partial tiles (<= 2 groups)
+    constexpr bool GSHIFT = (KIND == TE_CONV_T2);
+    pl.grid = dim3((unsigned)(a.B / a.NB * a.S), (unsigned)te::cdiv(a.Co, GSHIFT ? QCH : PCH), (unsigned)te::cdiv(a.Ci, GSHIFT ? PCH : QCH));
+    return 0;
+}
+
 template <int KIND, int NWP, bool WINO>
-void launch_wgrad_t(const WgArgs& a, hipStream_t s) {
-    constexpr int PCH = NWP * 32;
-    size_t lds = ((KIND == TE_CONV_1X1 || NWP == 2) ? 1 : 2) * sizeof(float) * ((size_t)PCH * a.PS + (size_t)QCH * a.QS);   // 8-wave 3x3 / T2: two operand images
-    if (NWP == 2) lds = std::max(lds, sizeof(float) * 2 * (WINO ? 12 : WK<KIND>::NT) * 16 * 64);     // K-split partial tiles (<= 2 groups)
+void launch_wgrad_t(const WgPlan& pl, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
     te::allow_big_lds(attr_done, (const void*)wgrad_mfma_kernel<KIND, NWP, WINO>, 160 * 1024);
-    constexpr bool GSHIFT = (KIND == TE_CONV_T2);
-    dim3 grid((unsigned)(a.B / a.NB * a.S), (unsigned)te::cdiv(a.Co, GSHIFT ? QCH : PCH), (unsigned)te::cdiv(a.Ci, GSHIFT ? PCH : QCH));
-    wgrad_mfma_kernel<KIND, NWP, WINO><<<grid, NWP * 128, lds, s>>>(a);
+    wgrad_mfma_kernel<KIND, NWP, WINO><<<pl.grid, NWP * 128, pl.lds, s>>>(pl.a);
 }
 
 template <int KIND>
-int launch_wgrad(WgArgs a, hipStream_t s) {
-    if (!fill_geometry<KIND>(a)) return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: unsupported image size %dx%d", a.H, a.W);
-    if ((int64_t)a.NB * a.Co * a.Hg * a.Wg * 4 >= (int64_t)OOB || (int64_t)a.NB * a.Ci * a.Hx * a.Wx * 4 >= (int64_t)OOB)
-        return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: a sample group exceeds 2 GiB");
+void launch_planned_wgrad(const WgPlan& pl, hipStream_t s) {
     if constexpr (KIND == TE_CONV_3X3) {
-        if (pair_form_3x3(a.Co, a.Ci, a.NC)) { launch_wgrad_t<KIND, 4, true>(a, s); return 0; }
+        if (pl.wino) { launch_wgrad_t<KIND, 4, true>(pl, s); return; }
     }
-    if (pick_nwp(a.Co, a.Ci) == 2) launch_wgrad_t<KIND, 2, false>(a, s);
-    else launch_wgrad_t<KIND, 4, false>(a, s);
-    return 0;
+    if (pl.nwp == 2) launch_wgrad_t<KIND, 2, false>(pl, s);
+    else launch_wgrad_t<KIND, 4, false>(pl, s);
 }
 
 inline int n_cell_tiles(int kind, int H, int W) {      // (a kind without a kernel counts like the 3x3 one)
@@ -963,25 +985,62 @@ extern "C" int te_wgrad_f32(float* slabs, const float* g, const float* x, int ki
 // csrc/wgrad6.hip: the 3x3 correlation on the bf16 matrix pipe (three-piece split, fp32-equivalent); 1 = launched, 0 = not applicable
 int te_wgrad6_launch(float* slabs, const float* g, const float* x, int kind, int B, int Co, int Ci, int H, int W, int S, int NB, hipStream_t s);
 
+// planning half of a launch: the launch's own refusals in the launch's own order, then the kernel (a split kernel needs 16-byte aligned
+// operands, as te_wgrad6_launch decides) and, for the kernel of this file, its instantiation, geometry, grid and LDS
+static int plan_wgrad(int kind, int B, int Co, int Ci, int H, int W, int S, int NB, unsigned g_mod16, unsigned x_mod16, WgPlan& pl) {
+    TE_REQUIRE(B > 0 && Co > 0 && Ci > 0 && H > 0 && W > 0 && S > 0, TE_ERR_SHAPE, "te_wgrad_f32: bad dims");
+    TE_REQUIRE(NB > 0 && B % NB == 0, TE_ERR_SHAPE, "te_wgrad_group_f32: the group size must divide the batch");
+    TE_REQUIRE((int64_t)B * S <= 0x7FFFFFFF && te::cdiv(Co, QCH) <= 65535 && te::cdiv(Ci, QCH) <= 65535, TE_ERR_SHAPE,
+               "te_wgrad_f32: grid too large");
+    const bool aligned16 = ((g_mod16 | x_mod16) & 15) == 0;
+    pl = WgPlan{};
+    pl.form6 = aligned16 ? te_wgrad6_form(kind, B, Co, Ci, H, W, NB) : TE_WG6_FP32;
+    if (pl.form6 != TE_WG6_FP32) return 0;
+    WgArgs& a = pl.a;
+    a.B = B; a.Co = Co; a.Ci = Ci; a.H = H; a.W = W; a.S = S; a.NB = NB;
+    a.Hx = H; a.Wx = W;
+    switch (kind) {
+        case TE_CONV_3X3: a.Hg = H; a.Wg = W; return plan_wgrad_kind<TE_CONV_3X3>(pl, aligned16);
+        case TE_CONV_1X1: a.Hg = H; a.Wg = W; return plan_wgrad_kind<TE_CONV_1X1>(pl, aligned16);
+        case TE_CONV_T2: a.Hg = 2 * H + 1; a.Wg = 2 * W + 1; return plan_wgrad_kind<TE_CONV_T2>(pl, aligned16);
+        default: return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: unknown kind %d", kind);
+    }
+}
+
+// the plan of a launch (host only; see te_hip.h)
+extern "C" int te_wgrad_form(int kind, int B, int Co, int Ci, int H, int W, int S, int NB, int g_mod16, int x_mod16, int* form) {
+    TE_REQUIRE(form, TE_ERR_NULL, "te_wgrad_form: NULL pointer");
+    TE_REQUIRE(g_mod16 >= 0 && g_mod16 < 16 && x_mod16 >= 0 && x_mod16 < 16, TE_ERR_SHAPE, "te_wgrad_form: an address mod 16 is 0 ... 15");
+    WgPlan pl;
+    const int rc = plan_wgrad(kind, B, Co, Ci, H, W, S, NB, (unsigned)g_mod16, (unsigned)x_mod16, pl);
+    if (rc) return rc;
+    const bool own = pl.form6 == TE_WG6_FP32;       // (a split kernel: the fp32 fields stay zero)
+    const int f[TE_WGRAD_FORM_INTS] = {pl.form6, pl.nwp, pl.wino, pl.a.vec, pl.db, pl.a.TW, pl.a.TH, pl.a.tiles_x, pl.a.tiles_y,
+                                       own ? (int)pl.grid.x : 0, own ? (int)pl.grid.y : 0, own ? (int)pl.grid.z : 0, (int)pl.lds};
+    for (int i = 0; i < TE_WGRAD_FORM_INTS; ++i) form[i] = f[i];
+    return 0;
+}
+
+// dispatch half: the kernel and the instantiation are the plan's
 static int wgrad_launch(float* slabs, const float* g, const float* x, int kind, int B, int Co, int Ci, int H, int W, int S, int NB,
                         te_stream_t stream_) {
     TE_REQUIRE(slabs && g && x, TE_ERR_NULL, "te_wgrad_f32: NULL pointer");
-    TE_REQUIRE(B > 0 && Co > 0 && Ci > 0 && H > 0 && W > 0 && S > 0, TE_ERR_SHAPE, "te_wgrad_f32: bad dims");
-    TE_REQUIRE((int64_t)B * S <= 0x7FFFFFFF && te::cdiv(Co, QCH) <= 65535 && te::cdiv(Ci, QCH) <= 65535, TE_ERR_SHAPE,
-               "te_wgrad_f32: grid too large");
-    if (te_wgrad6_launch(slabs, g, x, kind, B, Co, Ci, H, W, S, NB, (hipStream_t)stream_) == 1) return te::launch_status("te_wgrad_f32");
-    WgArgs a{};
-    a.slabs = slabs; a.g = g; a.x = x; a.B = B; a.Co = Co; a.Ci = Ci; a.H = H; a.W = W; a.S = S; a.NB = NB;
-    a.Hx = H; a.Wx = W;
-    hipStream_t s = (hipStream_t)stream_;
-    int rc;
-    switch (kind) {
-        case TE_CONV_3X3: a.Hg = H; a.Wg = W; rc = launch_wgrad<TE_CONV_3X3>(a, s); break;
-        case TE_CONV_1X1: a.Hg = H; a.Wg = W; rc = launch_wgrad<TE_CONV_1X1>(a, s); break;
-        case TE_CONV_T2: a.Hg = 2 * H + 1; a.Wg = 2 * W + 1; rc = launch_wgrad<TE_CONV_T2>(a, s); break;
-        default: return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: unknown kind %d", kind);
-    }
+    WgPlan pl;
+    const int rc = plan_wgrad(kind, B, Co, Ci, H, W, S, NB, (unsigned)(reinterpret_cast<uintptr_t>(g) & 15),
+                              (unsigned)(reinterpret_cast<uintptr_t>(x) & 15), pl);
     if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    if (pl.form6 != TE_WG6_FP32) {
+        if (te_wgrad6_launch(slabs, g, x, kind, B, Co, Ci, H, W, S, NB, s) != 1)
+            return te::fail(TE_ERR_UNSUPPORTED, "te_wgrad_f32: the split kernel did not take the launch it was planned for");
+        return te::launch_status("te_wgrad_f32");
+    }
+    pl.a.slabs = slabs; pl.a.g = g; pl.a.x = x;
+    switch (kind) {
+        case TE_CONV_3X3: launch_planned_wgrad<TE_CONV_3X3>(pl, s); break;
+        case TE_CONV_1X1: launch_planned_wgrad<TE_CONV_1X1>(pl, s); break;
+        default: launch_planned_wgrad<TE_CONV_T2>(pl, s); break;       // (plan_wgrad has refused every other kind)
+    }
     return te::launch_status("te_wgrad_f32");
 }
 
