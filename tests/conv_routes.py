@@ -11,7 +11,8 @@ it runs under and the routes it is expected to take:
   NB > 1) or 'slabs' (per-sample slabs).
 
 Plain data and host code: tests/test_conv_routes_cpu.py checks the table against the predicates without a GPU,
-tests/test_gpu_conv_routes.py runs every entry against fp64.
+tests/test_gpu_conv_routes.py runs every entry against fp64.  in_hw, out_hw and ref_conv are the geometry and the fp64 reference of
+an op kind, for that module and for tests/test_gpu_conv_forms.py.
 """
 import contextlib
 import ctypes as C
@@ -19,6 +20,7 @@ import itertools
 from dataclasses import dataclass, field
 
 import torch
+import torch.nn.functional as F
 
 from transeditor_amd import _lib
 
@@ -136,6 +138,27 @@ EDGES = {
     'p1s6 M % 128': ('skip_p1s6', 'skip_p1s6_fwd_only'),
     'wgrad6 pair even B': ('3x3_m32', '3x3_m32_odd_batch'),
 }
+
+
+# ------------------------------------------------------------------------------------------------ geometry and reference of an op kind
+def in_hw(op, H, W):
+    """the input's size for the low-resolution size H x W"""
+    return (2 * H + 1, 2 * W + 1) if op == 'down' else (H, W)
+
+
+def out_hw(op, H, W):
+    return (2 * H + 1, 2 * W + 1) if op == 'up' else (H, W)
+
+
+def ref_conv(op, x, w):
+    """the op kind's convolution from stock torch ops, in the operands' precision"""
+    if op == '3x3':
+        return F.conv2d(x, w, padding=1)
+    if op in ('1x1', 'skip'):
+        return F.conv2d(x, w)
+    if op == 'up':
+        return F.conv_transpose2d(x, w.transpose(0, 1), stride=2)
+    return F.conv2d(x, w, stride=2)
 
 
 # ------------------------------------------------------------------------------------------------ switches

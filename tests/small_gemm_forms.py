@@ -48,11 +48,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from fp64_check import A32, KINK_CAP, S32, U32 as U, kink_keep, where64  # noqa: E402  (slope and gain as the kernel has them)
 from transeditor_amd import _lib  # noqa: E402
 
-U = 2.0 ** -24
-KINK_CAP = 1e-3                                    # the project's value (tests/test_gpu_loop_trips.py)
-A32, S32 = float(np.float32(0.2)), float(np.float32(2 ** 0.5))          # slope and gain as the kernel has them
 LAYOUTS = ('dense', 'off4', 'oddrow', 'padded', 'trans', 'every2')
 EPS = ('single', 'uniform', 'table', 'splitk')
 TAIL = 64                                          # spare elements behind every operand
@@ -329,10 +327,6 @@ def views64(e, o, g=None):
     return A, B, bias
 
 
-def _where64(mask, a, b):
-    return torch.where(mask, torch.tensor(a, dtype=torch.float64, device=mask.device), torch.tensor(b, dtype=torch.float64, device=mask.device))
-
-
 def gelu64(x):
     return 0.5 * x * (1.0 + torch.erf(x * math.sqrt(0.5)))
 
@@ -360,10 +354,10 @@ def reference(e, o, nw, g=None):
     pre_bound = L * U * P + U * bb.abs() + U * pre.abs()
     r = {'pre': pre, 'pre_bound': pre_bound, 'keep': None, 'L': L}
     if e.act == 3:
-        slope = _where64(pre > 0, S32, A32 * S32)
+        slope = where64(pre > 0, S32, A32 * S32)
         out = pre * slope
         bound = pre_bound * slope + 2 * U * out.abs()
-        r['keep'] = pre.abs() > pre_bound
+        r['keep'] = kink_keep(pre, pre_bound)
     elif e.act == 1:
         out = gelu64(pre)
         bound = 1.13 * pre_bound + gelu_term(pre)

@@ -12,11 +12,10 @@ import torch.nn.functional as F
 
 import arcface_restated as R
 from conftest import load_golden, rel_l2
+from fp64_check import SENTINEL, U32 as EPS, within
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
-SENTINEL = -777.25
 
 
 # ------------------------------------------------------------------------------------------- 1. batch norm -> padded convolution -> PReLU
@@ -90,12 +89,7 @@ def test_conv2d_prelu_with_the_affine_against_fp64(prelu_refs, case):
     """elementwise, no element left out (PReLU is Lipschitz: nothing near 0 needs excusing); torch's own fp32 on the CPU meets the
     same bound"""
     d = prelu_refs[case]
-    out = _run_prelu(d, case).double().cpu()
-    err, err_cpu = (out - d['o64']).abs(), (d['cpu32'].double() - d['o64']).abs()
-    print(f'conv2d_prelu {case}: K={d["K"]}, max err / bound {float((err / d["bound"]).max()):.3f} (torch fp32 on the CPU '
-          f'{float((err_cpu / d["bound"]).max()):.3f})')
-    assert bool((err_cpu <= d['bound']).all())
-    assert bool((err <= d['bound']).all())
+    within(f'conv2d_prelu {case}', f'K={d["K"]}', _run_prelu(d, case), d['o64'], d['bound'], yardstick=(d['cpu32'], 0.0))
 
 
 def test_conv2d_prelu_shift_is_not_a_bias():
@@ -110,7 +104,7 @@ def test_conv2d_prelu_shift_is_not_a_bias():
     o64, mag = _prelu_ref(d, case, torch.float64)
     bound = d['slope'].double().abs().clamp(min=1).view(1, -1, 1, 1) * (Ci * k * k + 5) * EPS * mag + EPS * o64.abs()
     out = _run_prelu(d, case).double().cpu()
-    assert bool(((out - o64).abs() <= bound).all())
+    within(f'conv2d_prelu {case} shift 10', 'y', out, o64, bound)
     w64, a64 = d['w'].double(), d['a'].double()
     folded_bias = d['b'].double() + (w64 * d['t'].double().view(1, -1, 1, 1)).sum((1, 2, 3))
     folded = F.prelu(F.conv2d(d['x'].double() * a64.view(1, -1, 1, 1), w64, folded_bias, s, pad), d['slope'].double())

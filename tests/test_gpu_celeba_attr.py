@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import celeba_attr_restated as R
+import scorer_checks
 from conftest import ROOT, load_golden, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -398,13 +399,7 @@ def test_against_the_reference(golden_runs, name):
 # ---------------------------------------------------------------------------------------------------------- 6. plumbing
 @pytest.fixture(scope='module')
 def generator():
-    from transeditor_amd import synth
-    from transeditor_amd.model_spatial_query import Generator
-    G = Generator(64, 512, 512, 2 * (int(np.log2(64)) - 1), n_trans=8, pixel_norm_op_dim=1)
-    sd = G.state_dict()
-    synth.fill_state_dict(sd, 5)
-    G.load_state_dict(sd)
-    return G.to(DEV)
+    return scorer_checks.small_generator(DEV)
 
 
 def _small_sd(seed):
@@ -433,20 +428,7 @@ def test_score_sweeps_with_two_scorers(networks):
 
 def test_fit_boundaries(generator, networks):
     from transeditor_amd.dex import fit_boundaries
-    scorer = networks['r16']['scorer']                                         # 64 px images: f = 4
-    kw = dict(n_sample=40, batch=16, ratio=0.25, seed=4)                       # batches of 16, 16 and 8; 7 + 7 training rows
-    res = fit_boundaries(generator, scorer, **kw)
-    assert res['scores'].shape == (40, 1) and res['scores'].is_cuda and bool(torch.isfinite(res['scores']).all())
-    assert float(res['scores'].std()) > 0 and 0 <= float(res['scores'].min()) and float(res['scores'].max()) <= 1
-    for k in ('z_boundary', 'p_boundary'):
-        b = res[k]
-        assert b.ndim == 2 and b.shape[0] == 1 and b.shape[1] % 512 == 0 and b.dtype == np.float32
-        assert abs(float(np.linalg.norm(b.astype(np.float64))) - 1.0) < 1e-6
-    for k in ('z_report', 'p_report'):
-        assert res[k]['n_train'] == 14 and res[k]['n_val'] == 6 and res[k]['chosen_num'] == 10
-    again = fit_boundaries(generator, scorer, **kw)
-    assert torch.equal(again['scores'], res['scores'])
-    assert np.array_equal(again['z_boundary'], res['z_boundary']) and np.array_equal(again['p_boundary'], res['p_boundary'])
+    scorer_checks.check_fit_boundaries(fit_boundaries, generator, networks['r16']['scorer'], score_range=(0.0, 1.0, True))   # 64 px images: f = 4
 
 
 def test_dropin_and_load_scorers(tmp_path, monkeypatch, networks):

@@ -3,7 +3,7 @@ _lib.conv(x, wp, kind, ...) with the kind given, so that no selector stands betw
 its entry's form through te_conv_form before it compares numbers, so a changed launch constant cannot silently move a case onto
 another instantiation.
 
-Reference: stock torch ops in fp64 on the same device - the convolution of tests/test_gpu_conv_routes.py (ref_conv) of x * isc with
+Reference: stock torch ops in fp64 on the same device - the convolution of tests/conv_routes.py (ref_conv) of x * isc with
 w * wscale, then osc, bias, leaky ReLU and gain, then + res, then the mask slope; the constants 0.2, sqrt(2), mask_gain and
 0.2 * mask_gain as the fp32 kernel has them.
 
@@ -18,7 +18,7 @@ max err / bound per entry is printed at the end of the module.  Measured on the 
 T2 0.032, 1x1 0.162 (its sums are 9 times shorter, so the worst-case bound is closer to the typical error); left out at most 4.9e-4.
 
 Leaky-ReLU kink: elements whose fp64 pre-activation lies within its own bound, (L + 4 + ksplit) u S, of 0 are left out (the slope may
-differ there); at most KINK_CAP = 0.1 % of an entry.  The operands come from a CPU generator, so the left-out share is a property
+differ there); at most KINK_CAP = 0.1 % of an entry (tests/fp64_check.py).  The operands come from a CPU generator, so the left-out share is a property
 of the table that a CPU run of reference() shows; the large T2 entries have no activation.
 
 Bitwise: a second run gives the same bits; for single-sample forms sample b of the batch launch equals a launch that holds only
@@ -32,13 +32,13 @@ import pytest
 import torch
 
 import conv_forms as cf
-import test_gpu_conv_routes as rt
-import test_gpu_loop_trips as tl
+import conv_routes as cr
+import fp64_check
+from fp64_check import A32, S32, U32 as U, where64, within
 from transeditor_amd import _lib
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-U = tl.U32
 WSCALE = 0.7
 MGAIN = 0.6
 OPS = {'3X3': '3x3', 'T2': 'up', 'S2': 'down', '1X1': '1x1'}
@@ -48,14 +48,7 @@ KPAD = 16                  # channel padding of the packed layouts; checked agai
 RESEED = {'s2_tc2_gen_multi_split': 1, 's2_tc2_fast_split': 1, 's2_tc2_fast_split_nsv_th': 1}
 RESULTS = []
 IDS = lambda e: e.name
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nmax err / bound per entry (tests/test_gpu_conv_forms.py):')
-    for name, what, ratio, left in RESULTS:
-        print(f'  {name:44s} {what:10s} {ratio:8.4f}   left out {left:.1e}')
+_report = fp64_check.report_fixture('max err / bound per entry (tests/test_gpu_conv_forms.py):', RESULTS, widths=(44, 10))
 
 
 def _products(entry):
@@ -75,7 +68,7 @@ def operands(entry, device=DEV):
     ks = 1 if entry.kind == '1X1' else 3
     g = torch.Generator().manual_seed(1000 + cf.TABLE.index(entry) + 100000 * RESEED.get(entry.name, 0))
     rn = lambda *shape: torch.randn(shape, generator=g, dtype=torch.float32)
-    o = {'x': rn(B, K, *rt._in_hw(op, H, W)), 'w': rn(M, K, ks, ks) / math.sqrt(K * ks * ks), 'bias': rn(M),
+    o = {'x': rn(B, K, *cr.in_hw(op, H, W)), 'w': rn(M, K, ks, ks) / math.sqrt(K * ks * ks), 'bias': rn(M),
          'isc': None, 'osc': None, 'res': None, 'mref': None}
     # biases off zero, of both signs: the window around the kink is as wide as the worst-case bound (1e-3 of S at K = 128), and
     # with pre-activations centred on 0 the smallest entries would leave out more than the cap
@@ -83,7 +76,7 @@ def operands(entry, device=DEV):
     if entry.has_isc:
         o['isc'] = 1 + 0.5 * rn(B, K)
         o['osc'] = (1 + 0.3 * rn(B, M)).abs() + 0.1
-    out_shape = (B, M) + rt._out_hw(op, H, W)
+    out_shape = (B, M) + cr.out_hw(op, H, W)
     if entry.epi in ('res', 'both'):
         o['res'] = rn(*out_shape)
     if entry.epi in ('mask', 'both'):
@@ -104,15 +97,15 @@ def reference(entry, o, ksplit):
         x = x * d(o['isc'])[:, :, None, None]
     osc = d(o['osc'])[:, :, None, None] if o['osc'] is not None else 1.0
     bias = d(o['bias'])[None, :, None, None]
-    pre = rt.ref_conv(op, x, w) * osc + bias
-    S = rt.ref_conv(op, x.abs(), w.abs()) * osc + bias.abs()              # (osc > 0 by construction)
+    pre = cr.ref_conv(op, x, w) * osc + bias
+    S = cr.ref_conv(op, x.abs(), w.abs()) * osc + bias.abs()              # (osc > 0 by construction)
     L = _products(entry)
     g = torch.ones_like(pre)
     keep = None
     if entry.act >= 3:
-        gain = tl.S32 if entry.act == 3 else 1.0
-        g = tl._where64(pre > 0, gain, tl.A32 * gain)
-        keep = pre.abs() > (L + 4 + (ksplit if ksplit > 1 else 0)) * U * S
+        gain = S32 if entry.act == 3 else 1.0
+        g = where64(pre > 0, gain, A32 * gain)
+        keep = fp64_check.kink_keep(pre, (L + 4 + (ksplit if ksplit > 1 else 0)) * U * S)
     y = pre * g
     bound = (L + 4) * U * S * g + 2 * U * y.abs()
     if ksplit > 1:
@@ -121,7 +114,7 @@ def reference(entry, o, ksplit):
         y = y + d(o['res'])
         bound = bound + U * y.abs()
     if o['mref'] is not None:
-        m = tl._where64(d(o['mref']) > 0, _f32(MGAIN), float(torch.tensor(0.2, dtype=torch.float32) * torch.tensor(MGAIN, dtype=torch.float32)))
+        m = where64(d(o['mref']) > 0, _f32(MGAIN), float(torch.tensor(0.2, dtype=torch.float32) * torch.tensor(MGAIN, dtype=torch.float32)))
         y = y * m
         bound = bound * m + U * y.abs()
     return y, bound, keep
@@ -147,8 +140,8 @@ def _pack(entry, o, dgrad=False):
 def _compare(entry, y, ref, bound, keep, ans, what='y'):
     if ans['nreg'] == 3:
         for name, sl in (('last row', (Ellipsis, slice(-1, None), slice(None))), ('last col', (Ellipsis, slice(None), slice(-1, None)))):
-            tl._within(entry, f'{what} {name}', y[sl], ref[sl], bound[sl], None if keep is None else keep[sl], results=RESULTS)
-    tl._within(entry, what, y, ref, bound, keep, results=RESULTS)
+            within(entry.name, f'{what} {name}', y[sl], ref[sl], bound[sl], None if keep is None else keep[sl], results=RESULTS)
+    within(entry.name, what, y, ref, bound, keep, results=RESULTS)
 
 
 @pytest.mark.parametrize('entry', cf.TABLE, ids=IDS)
@@ -188,9 +181,9 @@ def test_refused_combinations_raise(kind, shape, has_isc, epi):
     assert cf.answer(e) == -3
     B, K, M, H, W = shape
     op = OPS[kind]
-    x = torch.zeros((B, K) + rt._in_hw(op, H, W), device=DEV)
+    x = torch.zeros((B, K) + cr.in_hw(op, H, W), device=DEV)
     w = torch.zeros(M, K, 1 if kind == '1X1' else 3, 1 if kind == '1X1' else 3, device=DEV)
-    out = torch.zeros((B, M) + rt._out_hw(op, H, W), device=DEV)
+    out = torch.zeros((B, M) + cr.out_hw(op, H, W), device=DEV)
     with pytest.raises(RuntimeError, match='te_conv_res_f32'):
         _lib.conv(x, _lib.conv_pack(w, _lib.PACK_FWD), cf.KINDS[kind], M, H, W, isc=torch.ones(B, K, device=DEV) if has_isc else None,
                   res=out if epi in ('res', 'both') else None, mask_ref=out if epi in ('mask', 'both') else None)

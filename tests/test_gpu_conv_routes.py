@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 import conv_routes as cr
 from conftest import rel_err, rel_l2
+from fp64_check import off16
 from transeditor_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -51,40 +52,15 @@ def _gpu(shape, key, scale=1.0, offset=False):
     t = synth.normal(shape, key)
     if scale != 1.0:
         t = t * scale
-    if not offset:
-        return t.to(DEV)
-    # the same values as a contiguous view 4 bytes into its storage (not 16-byte aligned)
-    buf = torch.empty(t.numel() + 1, device=DEV)
-    v = buf[1:].view(shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
-
-
-def _in_hw(op, H, W):
-    return (2 * H + 1, 2 * W + 1) if op == 'down' else (H, W)
-
-
-def _out_hw(op, H, W):
-    return (2 * H + 1, 2 * W + 1) if op == 'up' else (H, W)
-
-
-def ref_conv(op, x, w):
-    if op == '3x3':
-        return F.conv2d(x, w, padding=1)
-    if op in ('1x1', 'skip'):
-        return F.conv2d(x, w)
-    if op == 'up':
-        return F.conv_transpose2d(x, w.transpose(0, 1), stride=2)
-    return F.conv2d(x, w, stride=2)
+    return off16(t, 4, DEV) if offset else t.to(DEV)
 
 
 def _operands(route, tag, offset=False):
     B, K, M, H, W = route.shape
     ks = 1 if route.op in ('1x1', 'skip') else 3
-    x = _gpu((B, K) + _in_hw(route.op, H, W), f'rt.x.{tag}', offset=offset)
+    x = _gpu((B, K) + cr.in_hw(route.op, H, W), f'rt.x.{tag}', offset=offset)
     w = _gpu((M, K, ks, ks), f'rt.w.{tag}', 1.0 / math.sqrt(K * ks * ks))
-    gy = _gpu((B, M) + _out_hw(route.op, H, W), f'rt.g.{tag}', offset=offset)
+    gy = _gpu((B, M) + cr.out_hw(route.op, H, W), f'rt.g.{tag}', offset=offset)
     return x, w, gy
 
 
@@ -104,7 +80,7 @@ def test_conv_core_first_order(route, offset):
         y = mc.conv_core(xd, wd, route.op, ws)
         gx, gw = torch.autograd.grad(y, (xd, wd), gy)
     x64, w64 = x.double().requires_grad_(True), w.double().requires_grad_(True)
-    y64 = ref_conv(route.op, x64, w64 * ws)
+    y64 = cr.ref_conv(route.op, x64, w64 * ws)
     gx64, gw64 = torch.autograd.grad(y64, (x64, w64), gy.double())
     sfx = ' (offset)' if offset else ''
     _record(route.name, 'core y' + sfx, rel_err(y, y64), FWD_TOL)
@@ -129,7 +105,7 @@ def test_conv_core_second_order(route):
             return torch.autograd.grad(gs.pow(2).sum() + gw.pow(2).sum(), (x, w))
 
         got = f(lambda a, b: mc.conv_core(a, b, route.op, ws), *(t.detach().clone().requires_grad_(True) for t in (x, w, s)))
-    ref = f(lambda a, b: ref_conv(route.op, a, b * ws), *(t.double().requires_grad_(True) for t in (x, w, s)))
+    ref = f(lambda a, b: cr.ref_conv(route.op, a, b * ws), *(t.double().requires_grad_(True) for t in (x, w, s)))
     for name, a, b in zip(('d2x', 'd2W'), got, ref):
         _record(route.name, 'core ' + name, rel_err(a, b), SO_TOL)
         _record(route.name, 'core ' + name + ' l2', rel_l2(a, b), SO_TOL)
@@ -165,13 +141,13 @@ def test_modconv_fused_node(route, scales, act):
         # (upstream gradient masked where the pre-activation is within round-off of the kink: the slope may differ there)
         L64 = [t.double().requires_grad_(True) for t in (x, w, isc, osc, bias)]
         o64 = _demod64(L64[1], L64[2], ws, eps) if scales == 'demod' else L64[3]
-        pre = ref_conv(route.op, L64[0] * L64[2][:, :, None, None], L64[1] * ws) * o64[:, :, None, None] + L64[4][None, :, None, None]
+        pre = cr.ref_conv(route.op, L64[0] * L64[2][:, :, None, None], L64[1] * ws) * o64[:, :, None, None] + L64[4][None, :, None, None]
         y64 = F.leaky_relu(pre, 0.2) * SQRT2 if act else pre
         g = gy.double() * (pre.detach().abs() > 1e-4) if act else gy.double()
         got = torch.autograd.grad(y, want, g.float())
     ref = torch.autograd.grad(y64, [t for i, t in enumerate(L64) if not (scales == 'demod' and i == 3)], g)
-    Hi, Wi = _in_hw(route.op, H, W)
-    Ho, Wo = _out_hw(route.op, H, W)
+    Hi, Wi = cr.in_hw(route.op, H, W)
+    Ho, Wo = cr.out_hw(route.op, H, W)
     names = ['dx', 'dW', 'disc'] + ([] if scales == 'demod' else ['dosc']) + ['dbias']
     bars = {'dx': FWD_TOL, 'dW': red_tol(B * H * W), 'disc': red_tol(Hi * Wi), 'dosc': red_tol(Ho * Wo), 'dbias': red_tol(B * Ho * Wo)}
     tag = f'mc[{scales},{"act" if act else "lin"}] '
@@ -233,10 +209,10 @@ def test_modconv_closed_second_order(route):
         leaves = [t.detach().clone().requires_grad_(True) for t in (x, w, isc, osc)]
         with mc.second_order():
             got = f(lambda x, w, s, d: mc.modconv(x, w, s, d, None, False, route.op, ws), *leaves)
-    ref = f(lambda x, w, s, d: ref_conv(route.op, x * s[:, :, None, None], w * ws) * d[:, :, None, None],
+    ref = f(lambda x, w, s, d: cr.ref_conv(route.op, x * s[:, :, None, None], w * ws) * d[:, :, None, None],
             *(t.double().requires_grad_(True) for t in (x, w, isc, osc)))
-    Hi, Wi = _in_hw(route.op, H, W)
-    Ho, Wo = _out_hw(route.op, H, W)
+    Hi, Wi = cr.in_hw(route.op, H, W)
+    Ho, Wo = cr.out_hw(route.op, H, W)
     _record(route.name, 'closed y', rel_err(got[0], ref[0]), FWD_TOL)
     for n, a, b, bar in zip(('dx', 'dW', 'disc', 'dosc'), got[1:5], ref[1:5],
                             (FWD_TOL, red_tol(B * H * W), red_tol(Hi * Wi), red_tol(Ho * Wo))):

@@ -2,12 +2,12 @@
 preprocessing and the centre crop in it, the softmax / score head, the whole network on small geometries and on the true one (224 px
 crop, 4096-wide fc layers, against what the reference's own classes return: tests/golden/dex_ref.npz), and the plumbing around it
 (fit_boundaries, score_sweeps, the input checks)."""
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import dex_restated as R
+import scorer_checks
 from conftest import load_golden, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -215,8 +215,7 @@ def _nondegenerate(p64, s64, attribute, bar):
         assert float(p64.max()) < 0.5
     else:
         assert 0.05 < float(p64[:, 0].min()) and float(p64[:, 0].max()) < 0.95
-    gaps = (s64.view(-1, 1) - s64.view(1, -1)).abs() + torch.eye(s64.shape[0], dtype=torch.float64) * 1e30
-    assert float(gaps.min()) > 100 * float(R.score_bar(bar, p64, attribute).max())
+    scorer_checks.rows_told_apart(s64, R.score_bar(bar, p64, attribute))
 
 
 @pytest.fixture(scope='module')
@@ -263,9 +262,7 @@ def test_scorer_end_to_end(e2e, S, crop, hidden, C, B):
 def test_preprocessed_path_matches(e2e):
     """what the drop-in hands over (BGR levels, uncropped) through te_vgg_stem_fwd_f32 against the fused stem on the RGB image"""
     d = e2e[E2E_CASES[0]]
-    x = d['x'].cpu()
-    v = torch.stack([x[:, 2], x[:, 1], x[:, 0]], 1).clamp(-1, 1).add(1).div(2).mul(255).round()
-    p = d['scorer'].probabilities(v.to(DEV), preprocessed=True)
+    p = d['scorer'].probabilities(scorer_checks.levels(d['x'].cpu()).to(DEV), preprocessed=True)
     assert rel_l2(p, d['p64']) <= 4 * d['yard']
 
 
@@ -312,13 +309,7 @@ def test_true_geometry_against_the_reference(true_geometry, attribute):
 # ---------------------------------------------------------------------------------------------------------- 5. plumbing
 @pytest.fixture(scope='module')
 def generator():
-    from transeditor_amd import synth
-    from transeditor_amd.model_spatial_query import Generator
-    G = Generator(64, 512, 512, 2 * (int(np.log2(64)) - 1), n_trans=8, pixel_norm_op_dim=1)
-    sd = G.state_dict()
-    synth.fill_state_dict(sd, 5)
-    G.load_state_dict(sd)
-    return G.to(DEV)
+    return scorer_checks.small_generator(DEV)
 
 
 @pytest.fixture(scope='module')
@@ -329,47 +320,12 @@ def small_scorer():
 
 def test_fit_boundaries(generator, small_scorer):
     from transeditor_amd.dex import fit_boundaries
-    kw = dict(n_sample=40, batch=16, ratio=0.25, seed=4)                                      # batches of 16, 16 and 8; 7 + 7 training rows
-    res = fit_boundaries(generator, small_scorer, **kw)
-    assert set(res) == {'z_boundary', 'p_boundary', 'z_report', 'p_report', 'scores'}
-    assert res['scores'].shape == (40, 1) and res['scores'].is_cuda and bool(torch.isfinite(res['scores']).all())
-    assert float(res['scores'].std()) > 0
-    for k in ('z_boundary', 'p_boundary'):
-        b = res[k]
-        assert b.ndim == 2 and b.shape[0] == 1 and b.shape[1] % 512 == 0 and b.dtype == np.float32
-        assert abs(float(np.linalg.norm(b.astype(np.float64))) - 1.0) < 1e-6
-    for k in ('z_report', 'p_report'):
-        assert res[k]['n_train'] == 14 and res[k]['n_val'] == 6 and res[k]['chosen_num'] == 10
-    again = fit_boundaries(generator, small_scorer, **kw)
-    assert torch.equal(again['scores'], res['scores'])
-    assert np.array_equal(again['z_boundary'], res['z_boundary']) and np.array_equal(again['p_boundary'], res['p_boundary'])
-    assert again['z_report'] == res['z_report'] and again['p_report'] == res['p_report']
+    scorer_checks.check_fit_boundaries(fit_boundaries, generator, small_scorer)
 
 
 def test_score_sweeps_on_the_device(small_scorer):
-    from transeditor_amd.edit_eval import score_sweeps
-    g = torch.Generator().manual_seed(12)
-    origin = (0.6 * torch.randn(2, 3, 64, 64, generator=g)).to(DEV)
-    sweeps = {k: (0.6 * torch.randn(2, 7, 3, 64, 64, generator=g)).to(DEV) for k in ('p', 'z', 'pz')}
-    res = score_sweeps({'age': small_scorer}, origin, sweeps, batch=4)                        # 14 images in batches of 4, 4, 4 and 2
-    want = small_scorer(origin).cpu().numpy()
-    for space in ('p', 'z', 'pz'):
-        got = res['age'][space]
-        assert got.shape == (2, 8) and got.dtype == np.float32
-        assert np.array_equal(got[:, 3], want)                                                # the origin, in the middle
-        each = small_scorer(sweeps[space].flatten(0, 1)).view(2, 7).cpu().numpy()
-        assert np.allclose(np.delete(got, 3, axis=1), each, rtol=1e-5, atol=0)                # (another batch split: not bitwise)
+    scorer_checks.check_score_sweeps('age', small_scorer, size=64, bitwise=False, in_unit_range=False)
 
 
 def test_scorer_input_checks(small_scorer):
-    with pytest.raises(ValueError, match='square'):
-        small_scorer(torch.zeros(1, 3, 64, 48, device=DEV))
-    with pytest.raises(ValueError, match='S >= 32'):
-        small_scorer(torch.zeros(1, 3, 30, 30, device=DEV))
-    with pytest.raises(ValueError, match='even'):
-        small_scorer(torch.zeros(1, 3, 63, 63, device=DEV))
-    with pytest.raises(ValueError, match=r'\[B,3,S,S\]'):
-        small_scorer(torch.zeros(1, 1, 64, 64, device=DEV))
-    with pytest.raises(RuntimeError, match='needs a GPU'):
-        small_scorer(torch.zeros(1, 3, 64, 64))
-    assert small_scorer(torch.zeros(2, 3, 32, 32, device=DEV)).shape == (2,)                  # S == crop: offset 0
+    scorer_checks.check_crop_scorer_inputs(small_scorer, 32)

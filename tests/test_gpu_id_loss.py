@@ -12,12 +12,11 @@ import torch.nn.functional as F
 import arcface_restated as R
 import id_loss_restated as IR
 from conftest import load_golden, rel_l2
+from fp64_check import SENTINEL, U32 as EPS, within
 from test_gpu_arcface import E2E_BOX, E2E_CASES, E2E_DIM, E2E_POOL, E2E_S, SE_SHAPES, STEM_CASES, _small_state_dict, _stem_weights
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
-SENTINEL = -777.25
 
 # ------------------------------------------------------------------------------------------------------------ 1. the data gradient
 # (B, forward Ci, forward Co, H, W, k, s, pad)
@@ -75,12 +74,8 @@ def test_dgrad_against_fp64(dgrad_refs, case):
     out = _run_dgrad(d, case)
     assert out.shape == d['acc64'].shape and out.dtype == torch.float32 and out.is_contiguous()
     bound = (d['K'] + 5) * EPS * d['mag']
-    err, err_cpu = (out.double().cpu() - d['acc64']).abs(), (d['cpu32'].double() - d['acc64']).abs()
     live = bound > 0                                         # (a 1x1 stride-2 layer leaves three of four inputs without a tap: exactly 0)
-    print(f'conv2d_dgrad {case}: K={d["K"]}, max err / bound {float((err[live] / bound[live]).max()):.3f} (torch fp32 on the CPU '
-          f'{float((err_cpu[live] / bound[live]).max()):.3f})')
-    assert bool((err_cpu <= bound).all())
-    assert bool((err <= bound).all())
+    within(f'conv2d_dgrad {case}', f'K={d["K"]}', out, d['acc64'], bound, yardstick=(d['cpu32'], 0.0))
     assert float(d['acc64'].abs().max()) > 1 and bool((out.cpu()[~live] == 0).all())
 
 
@@ -131,12 +126,7 @@ def test_dgrad_epilogues(dgrad_refs, case):
         want = IR.dgrad_epilogue(d['acc64'], **{n: (v.double() if torch.is_tensor(v) else v) for n, v in epi.items()})
         cpu = IR.dgrad_epilogue(d['cpu32'], **epi)
         bound = fac.double().view(1, -1, 1, 1) * base + EPS * want.abs()
-        got = _run_dgrad(d, case, **epi).double().cpu()
-        err, err_cpu = (got - want).abs(), (cpu.double() - want).abs()
-        live = bound > 0
-        print(f'conv2d_dgrad {case} {name}: max err / bound {float((err[live] / bound[live]).max()):.3f} (torch fp32 on the CPU '
-              f'{float((err_cpu[live] / bound[live]).max()):.3f})')
-        assert not bool(got.isnan().any()) and bool((err <= bound).all()) and bool((err_cpu <= bound).all()), name
+        within(f'conv2d_dgrad {case}', name, _run_dgrad(d, case, **epi), want, bound, yardstick=(cpu, 0.0))
     # the planted values took the slope: with slope 0 in those channels' place the outputs there are exactly 0
     zero = _run_dgrad(d, case, pre=pre, slope=torch.zeros(Ci)).cpu()
     assert bool((zero[~(pre > 0)] == 0).all()) and torch.equal(zero[pre > 0], _run_dgrad(d, case).cpu()[pre > 0])
@@ -305,10 +295,8 @@ def test_rows_unit_bwd(D):
     dot = (e64 * ge.double()).sum(1, keepdim=True)
     want = (ge.double() - e64 * dot) / norm
     bound = EPS * ((e64 * dot).abs() / norm + 3 * want.abs()) * (1 + 1e-3)
-    err = (got - want).abs()
-    print(f'rows_unit_bwd D={D}: max err / bound {float((err / bound).max()):.3f}; against the restatement of the contract in fp64 '
-          f'{rel_l2(got, IR.rows_unit_bwd(ge.double(), e64, a.double())):.2e}')
-    assert bool((err <= bound).all())
+    print(f'rows_unit_bwd D={D}: against the restatement of the contract in fp64 {rel_l2(got, IR.rows_unit_bwd(ge.double(), e64, a.double())):.2e}')
+    within(f'rows_unit_bwd D={D}', 'ga', got, want, bound)
     assert float((want * e64).sum(1).abs().max()) < 1e-6                       # the gradient is orthogonal to e
     assert torch.equal(_lib.rows_unit_bwd(ge[:1].to(DEV), e[:1].contiguous(), a[:1].to(DEV)).double().cpu(), got[:1])
     L, st = _lib.lib(), _lib._stream()

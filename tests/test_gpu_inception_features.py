@@ -10,12 +10,12 @@ import torch
 import torch.nn.functional as F
 
 import inception_restated as R
+import scorer_checks
 from conftest import ROOT, rel_l2
+from fp64_check import SENTINEL, U32 as EPS, kink_keep, within
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
-SENTINEL = -777.25
 
 # ---------------------------------------------------------------------------------------------------------- 1. the convolution
 # (B, Ci, Co, H, W, kh, kw, s, py, px): every kernel geometry of the network, both strides, odd sizes, a pixel tile that spans images,
@@ -29,7 +29,7 @@ SPLITS = 1                       # te_conv2d_f32 does not split K
 
 def _conv_case(case, seed=None):
     """x, w ~ N(0, 1); biases of scale 4 sqrt(K), four times the spread of the products' sum, so that few pre-activations lie near 0
-    (on the CPU, torch's fp32 convolution leaves out 0 to 0.02 % of the elements of these cases, far below the 1 % cap)"""
+    (on the CPU, torch's fp32 convolution leaves out 0 to 0.02 % of the elements of these cases, below the 0.1 % cap)"""
     B, Ci, Co, H, W, kh, kw = case[:7]
     g = torch.Generator().manual_seed(sum(p * v for p, v in zip((3, 5, 7, 11, 13, 17, 19, 23, 29, 31), case)) if seed is None else seed)
     x, w = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, kh, kw, generator=g)
@@ -41,8 +41,9 @@ def _conv_case(case, seed=None):
 @pytest.mark.parametrize('case', CONV_CASES, ids=lambda c: 'x'.join(map(str, c)))
 def test_conv2d_against_fp64(case, act):
     """|out - out64| <= (K + S + 2) 2^-24 (|w| * |x| + |bias|) elementwise: the bound of an fp32 chain of K products, S partial sums,
-    the bias and the final rounding.  Under ReLU, elements whose fp64 pre-activation is within the bound of 0 are left out (at most
-    1 % of them)."""
+    the bias and the final rounding.  Under ReLU, elements whose fp64 pre-activation is within the bound of 0 are left out, at most
+    fp64_check.KINK_CAP = 0.1 % of them.  The share is a property of the seeded operands and the fp64 reference: 18 of 116160 elements,
+    1.6e-4, in the last case and none in the eleven others."""
     from transeditor_amd import _lib
     B, Ci, Co, H, W, kh, kw, s, py, px = case
     x, w, b = _conv_case(case)
@@ -51,12 +52,7 @@ def test_conv2d_against_fp64(case, act):
     pre = F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=(py, px))
     assert out.shape == pre.shape and out.dtype == torch.float32 and out.is_contiguous()
     bound = (K + SPLITS + 2) * EPS * F.conv2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=s, padding=(py, px))
-    err = (out.double().cpu() - (torch.relu(pre) if act else pre)).abs()
-    keep = torch.ones_like(pre, dtype=torch.bool) if not act else pre.abs() > bound
-    share = 1.0 - float(keep.double().mean())
-    print(f'conv2d {case} act={act}: K={K}, max err / bound {float((err / bound)[keep].max()):.3f}, left out {share:.4f}')
-    assert share <= 0.01
-    assert bool((err <= bound)[keep].all())
+    within(f'conv2d {case} act={act}', f'K={K}', out, torch.relu(pre) if act else pre, bound, kink_keep(pre, bound) if act else None)
 
 
 # ---------------------------------------------------------------------------------------------------------- 2. slice writes
@@ -234,13 +230,7 @@ def test_features_input_checks(nets):
 # ---------------------------------------------------------------------------------------------------------- 8. the metric's plumbing
 @pytest.fixture(scope='module')
 def generator():
-    from transeditor_amd import synth
-    from transeditor_amd.model_spatial_query import Generator
-    G = Generator(64, 512, 512, 2 * (int(np.log2(64)) - 1), n_trans=8, pixel_norm_op_dim=1)
-    sd = G.state_dict()
-    synth.fill_state_dict(sd, 5)
-    G.load_state_dict(sd)
-    return G.to(DEV)
+    return scorer_checks.small_generator(DEV)
 
 
 def test_fid_with_the_extractor(nets, generator):

@@ -14,21 +14,22 @@ stores, 2^-53 fp64):
   step, 2^-25.  The fp64 kernels are compared with a reference of their own precision, so its round-off counts too: twice the bound.
 * the convolution cases: the bars of tests/test_gpu_conv_routes.py.
 Elements whose fp64 pre-activation lies within the bound of 0 are left out of a leaky-ReLU comparison (the slope may differ there);
-at most 0.1 % of a case.  For the forward and dx cases of the plane walks a plane's bits must not depend on the launch: the first
+at most 0.1 % of a case (tests/fp64_check.py: KINK_CAP).  For the forward and dx cases of the plane walks a plane's bits must not depend on the launch: the first
 zgroups planes and the last plane of the big launch equal launches that hold only those planes.
 
 `max err / bound` and the left-out share per case are printed at the end of the module.
 """
 import math
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import conv_routes as cr
+import fp64_check
 import loop_trips as lt
 from conftest import rel_err
+from fp64_check import A32, ALPHA, AS32, S32, SCALE, U, U32, where64
 from transeditor_amd import _lib
 from transeditor_amd.op.chanscale import chan_scale
 from transeditor_amd.op.fir_act import blur_bias_act
@@ -37,23 +38,10 @@ from transeditor_amd.op.upfirdn2d import upfirdn2d
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-U = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.float64: 2.0 ** -53}
-U32 = U[torch.float32]
-ALPHA, SCALE = 0.2, 2 ** 0.5
-A32, S32 = float(np.float32(ALPHA)), float(np.float32(SCALE))            # the constants as the fp32 kernels receive them
-AS32 = float(np.float32(ALPHA) * np.float32(SCALE))                      # alpha * scale, formed in fp32 by the FIR kernels
-KINK_CAP = 1e-3
 CONV_TOL = 1e-5                                                          # tests/test_gpu_conv_routes.py: FWD_TOL
 RESULTS = []
 IDS = lambda e: e.name
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nmax err / bound per case (tests/test_gpu_loop_trips.py):')
-    for name, what, ratio, left in RESULTS:
-        print(f'  {name:22s} {what:18s} {ratio:8.4f}   left out {left:.1e}')
+_report = fp64_check.report_fixture('max err / bound per case (tests/test_gpu_loop_trips.py):', RESULTS)
 
 
 def _randn(shape, seed, dtype=torch.float32):
@@ -62,21 +50,9 @@ def _randn(shape, seed, dtype=torch.float32):
     return torch.randn(shape, generator=g, device=DEV, dtype=torch.float32).to(dtype)
 
 
-def _within(entry, what, got, ref, bound, keep=None, results=RESULTS):
-    """assert |got - ref| <= bound elementwise (where `keep`), after recording max err / bound and the left-out share (in `results`: this
-    module's report, or that of another module which shares the check)"""
-    err = (got.double() - ref).abs()
-    ratio = err / bound.clamp_min(1e-300)
-    left = 0.0
-    if keep is not None:
-        left = 1.0 - float(keep.double().mean())
-        ratio = torch.where(keep, ratio, torch.zeros_like(ratio))
-    worst = float(ratio.max())
-    results.append((entry.name, what, worst, left))
-    print(f'{entry.name} {what}: max err / bound {worst:.4f}, left out {left:.1e}')
-    assert torch.isfinite(got).all()
-    assert left <= KINK_CAP, f'{entry.name} {what}: {left:.2e} of the elements sit on the kink'
-    assert worst <= 1.0, f'{entry.name} {what}: max err / bound {worst:.3f}'
+def _within(entry, what, got, ref, bound, keep=None):
+    """the elementwise check of tests/fp64_check.py, recorded for this module's report"""
+    fp64_check.within(entry.name, what, got, ref, bound, keep, results=RESULTS)
 
 
 def _rel(entry, what, got, ref, bar):
@@ -113,12 +89,8 @@ def fir64(x, k, up=1, down=1, pad=(0, 0, 0, 0)):
     return out[..., ::down, ::down]
 
 
-def _where64(mask, a, b):
-    return torch.where(mask, torch.tensor(a, dtype=torch.float64, device=mask.device), torch.tensor(b, dtype=torch.float64, device=mask.device))
-
-
 def slope64(ref):
-    return _where64(ref > 0, S32, AS32)
+    return where64(ref > 0, S32, AS32)
 
 
 def _pad4(p):
@@ -153,7 +125,7 @@ def test_blur_bias_act_forward(entry):
         y = blur_bias_act(x, k, b, pad)
         x64, k64, b64 = x.double(), k.double(), b.double()[None, :, None, None]
         pre = fir64(x64, k64, pad=_pad4(pad)) + b64
-        gain = _where64(pre > 0, S32, A32 * S32)
+        gain = where64(pre > 0, S32, A32 * S32)
         y64 = pre * gain
         mag = fir64(x64.abs(), k64, pad=_pad4(pad)) + b64.abs()
         keep = pre.abs() > (16 + 2) * U32 * mag                      # off the kink by more than the pre-activation's own bound

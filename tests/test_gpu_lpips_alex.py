@@ -18,12 +18,11 @@ import torch.nn.functional as F
 
 import lpips_alex_restated as R
 from conftest import ROOT
+from fp64_check import SENTINEL, U32 as EPS, kink_keep, within
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
 FLOOR = 2.0 ** -20
-SENTINEL = -777.25
 K = 363
 
 
@@ -62,24 +61,19 @@ def stem_refs():
 @pytest.mark.parametrize('case', STEM_CASES, ids=lambda c: 'x'.join(map(str, c)))
 def test_stem_against_fp64(stem_refs, case):
     """|out - out64| <= (K + 8) 2^-24 (|w| * |s(x)| + |b|), K = 363: test_gpu_pose.py's K + S + 3 with S = 1 plus up to four roundings
-    for the scaling.  Elements whose fp64 pre-activation lies within the bound of 0 are left out (at most 1 %); torch's fp32 CPU result
-    meets the bound on the same elements with under 0.1 % left out."""
+    for the scaling.  Elements whose fp64 pre-activation lies within the bound of 0 are left out, at most fp64_check.KINK_CAP = 0.1 %;
+    torch's fp32 CPU result meets the bound on the same elements.  The share is a property of the seeded operands and the fp64
+    reference: none of 512, 1 of 9072 (1.1e-4) and 16 of 254016 (6.3e-5) elements in the three cases."""
     from transeditor_amd import _lib
     N, H, W, Co = case
     d = stem_refs[case]
     out = _lib.alex_stem_fwd(d['x'].to(DEV), d['w'].to(DEV), d['b'].to(DEV))
     assert out.shape == d['pre'].shape == (N, Co, (H - 7) // 4 + 1, (W - 7) // 4 + 1) and out.dtype == torch.float32 and out.is_contiguous()
     pre, bound = d['pre'], d['bound']
-    keep = pre.abs() > bound
-    share = 1.0 - float(keep.double().mean())
+    keep = kink_keep(pre, bound)
     want = torch.relu(pre)
-    err = (out.double().cpu() - want).abs()
-    err_cpu = (torch.relu(d['cpu32']).double() - want).abs()
-    print(f'alex stem {case}: max err / bound {float((err / bound)[keep].max()):.3f} (torch fp32 on the CPU: '
-          f'{float((err_cpu / bound)[keep].max()):.3f}), left out {share:.5f}, positive {float((want > 0).double().mean()):.2f}')
-    assert share <= 0.01
-    assert share < 0.001 and bool((err_cpu <= bound)[keep].all())              # the yardstick itself
-    assert bool((err <= bound)[keep].all())
+    print(f'alex stem {case}: positive {float((want > 0).double().mean()):.2f}')
+    within(f'alex stem {case}', 'y', out, want, bound, keep, yardstick=(torch.relu(d['cpu32']), 0.001))
     assert bool((out.cpu()[~keep] >= 0).all())
 
 

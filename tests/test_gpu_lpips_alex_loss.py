@@ -18,12 +18,11 @@ import torch.nn.functional as F
 import lpips_alex_loss_restated as LR
 import lpips_alex_restated as R
 from conftest import ROOT
+from fp64_check import SENTINEL, U32 as EPS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
 FLOOR = 2.0 ** -20
-SENTINEL = -777.25
 WIDTHS = (8, 16, 24, 16, 16)
 
 

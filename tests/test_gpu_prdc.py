@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import prdc_restated as R
+import scorer_checks
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -155,14 +156,8 @@ def pooled(image):
 
 @pytest.fixture(scope='module')
 def sampler():
-    from transeditor_amd import synth
     from transeditor_amd.inference import GeneratorSampler
-    from transeditor_amd.model_spatial_query import Generator
-    G = Generator(64, 512, 512, 2 * (int(np.log2(64)) - 1), n_trans=8, pixel_norm_op_dim=1)
-    sd = G.state_dict()
-    synth.fill_state_dict(sd, 21)
-    G.load_state_dict(sd)
-    return GeneratorSampler(G.to(DEV))
+    return GeneratorSampler(scorer_checks.small_generator(DEV, seed=21))
 
 
 def test_evaluate_prdc_end_to_end(sampler):

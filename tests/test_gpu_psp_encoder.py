@@ -10,11 +10,10 @@ import torch.nn.functional as F
 import arcface_restated as R
 import psp_encoder_restated as P
 from conftest import load_golden, rel_l2
+from fp64_check import SENTINEL, U32 as EPS, within
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
-SENTINEL = -777.25
 SLOPE = 0.01
 _IDS = dict(ids=lambda c: 'x'.join(map(str, c)))
 
@@ -137,13 +136,8 @@ def test_heads_split_against_fp64(split_refs, H):
     """elementwise, no element left out; bound (K + S + 5) 2^-24 (|w| * |x| + |bias|) + 2^-24 |out|; torch's fp32 on the CPU meets it too"""
     d = split_refs[H]
     assert d['S'] > 1
-    got = _run_split(d).double().cpu()
-    err, err_cpu = (got - d['o64']).abs(), (d['cpu32'].double() - d['o64']).abs()
-    print(f'conv2d_heads split {H} -> {H // 2}: S={d["S"]}, max err / bound {float((err / d["bound"]).max()):.4f} (torch fp32 on the CPU '
-          f'{float((err_cpu / d["bound"]).max()):.4f})')
     assert 0.2 < float((d['o64'] < 0).double().mean()) < 0.8
-    assert bool((err_cpu <= d['bound']).all())
-    assert bool((err <= d['bound']).all())
+    within(f'conv2d_heads split {H} -> {H // 2}', f'S={d["S"]}', _run_split(d), d['o64'], d['bound'], yardstick=(d['cpu32'], 0.0))
 
 
 @pytest.mark.parametrize('H', SPLIT_PLANES)
@@ -249,10 +243,7 @@ def test_upsample_add_against_fp64(src, dst):
     want = F.interpolate(x.double(), size=dst, mode='bilinear', align_corners=True) + y.double()
     bound = 4 * EPS * (F.interpolate(x.double().abs(), size=dst, mode='bilinear', align_corners=True) + y.double().abs())
     cpu32 = F.interpolate(x, size=dst, mode='bilinear', align_corners=True) + y
-    err, err_cpu = (got.double().cpu() - want).abs(), (cpu32.double() - want).abs()
-    print(f'upsample_add {src} -> {dst}: max err / bound {float((err / bound).max()):.3f} (torch fp32 on the CPU {float((err_cpu / bound).max()):.3f})')
-    assert bool((err_cpu <= bound).all())
-    assert bool((err <= bound).all())
+    within(f'upsample_add {src} -> {dst}', 'y', got, want, bound, yardstick=(cpu32, 0.0))
     if src == dst:
         assert torch.equal(got.cpu(), x + y)
     if src == (5, 5):                                                            # exact taps: the even outputs are x + y, the odd ones midpoints
@@ -277,8 +268,8 @@ def test_psp_codes_against_fp64(B, Ns, Np, D, T, avg):
     p64, pm = l64[:, Ns:].permute(0, 2, 1), l64[:, Ns:].abs().permute(0, 2, 1)
     if avg:
         z64, zm, p64, pm = z64 + za.double(), zm + za.double().abs(), p64 + pa.double(), pm + pa.double().abs()
-    assert bool(((z.double().cpu() - z64).abs() <= (Ns + 3) * EPS * zm).all())
-    assert bool(((p.double().cpu() - p64).abs() <= (Ns + 3) * EPS * pm).all())
+    within(f'psp_codes B={B} Ns={Ns} Np={Np} D={D} T={T} avg={avg}', 'z', z, z64, (Ns + 3) * EPS * zm)
+    within(f'psp_codes B={B} Ns={Ns} Np={Np} D={D} T={T} avg={avg}', 'p', p, p64, (Ns + 3) * EPS * pm)
     if not avg:
         assert torch.equal(p.cpu(), lat[:, Ns:].permute(0, 2, 1))
     z1, p1 = _lib.psp_codes(dev(lat[1:2].contiguous()), dev(A), dev(bz), Np, dev(za), dev(pa))

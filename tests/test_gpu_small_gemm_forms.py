@@ -16,7 +16,7 @@ max err / bound per entry and the worst per form key are printed at the end of t
 key (any entry point, any output): MEASURED below, copied from that report; the bound is not tuned to it.  By output: c 0.481, pre 0.482,
 c against the GELU of the kernel's own pre 0.488, row sums 0.250, the last row sum of a ragged I 0.082; left out at most 8.2e-4.
 
-Leaky-ReLU kink: elements whose fp64 pre-activation lies within its own bound of 0 are left out; at most KINK_CAP = 0.1 % of an entry,
+Leaky-ReLU kink: elements whose fp64 pre-activation lies within its own bound of 0 are left out; at most KINK_CAP = 0.1 % of an entry (tests/fp64_check.py),
 none of an entry with fewer than 1000 outputs (tests/test_small_gemm_forms_cpu.py holds the table to that on the CPU).
 
 Untouched memory: c, pre, the row sums and the split-K workspace are views inside larger buffers prefilled with PATTERN; after the launch
@@ -33,18 +33,15 @@ import dataclasses
 import pytest
 import torch
 
+import fp64_check
 import small_gemm_forms as sf
-import test_gpu_loop_trips as tl
+from fp64_check import U32 as U, guarded, untouched
 from transeditor_amd import _lib
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-U = sf.U
-GUARD = 256
-PATTERN = -12345.5
 RESULTS = []
 IDS = lambda e: e.name
-assert sf.KINK_CAP == tl.KINK_CAP and U == tl.U32 and (sf.A32, sf.S32) == (tl.A32, tl.S32)
 
 # worst max err / bound per form key (nw, av, bv), any entry point, any output; MI355X (a record, nothing asserts it)
 MEASURED = {(1, 0, 0): 0.4815, (1, 0, 1): 0.2947, (1, 1, 0): 0.2781, (1, 1, 1): 0.4233, (2, 0, 0): 0.1910, (2, 0, 1): 0.0489, (2, 1, 0): 0.1700,
@@ -52,32 +49,8 @@ MEASURED = {(1, 0, 0): 0.4815, (1, 0, 1): 0.2947, (1, 1, 0): 0.2781, (1, 1, 1): 
             (8, 1, 0): 0.1174, (8, 1, 1): 0.1323, (16, 0, 0): 0.1238, (16, 0, 1): 0.0014, (16, 1, 0): 0.0972, (16, 1, 1): 0.2320}
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nmax err / bound per entry (tests/test_gpu_small_gemm_forms.py):')
-    worst = {}
-    for name, what, ratio, left in RESULTS:
-        print(f'  {name:52s} {what:34s} {ratio:8.4f}   left out {left:.1e}')
-        k = sf.BY_NAME[name].key
-        worst[k] = max(worst.get(k, 0.0), ratio)
-    print('worst per form key (nw, av, bv):')
-    for k in sorted(worst):
-        print(f'  {k}: {worst[k]:.4f}')
-
-
-def _guarded(numel):
-    buf = torch.full((GUARD + numel + GUARD,), PATTERN, device=DEV)
-    return buf, buf[GUARD:GUARD + numel]
-
-
-def _untouched(e, what, buf, numel, addressed=None):
-    """everything of buf outside the addressed set still holds the pattern (addressed: bool mask over the numel inner elements)"""
-    assert bool((buf[:GUARD] == PATTERN).all()) and bool((buf[GUARD + numel:] == PATTERN).all()), f'{e.name}: {what} written outside its buffer'
-    if addressed is not None:
-        inner = buf[GUARD:GUARD + numel]
-        assert bool((inner[~addressed] == PATTERN).all()), f'{e.name}: {what} written between the addressed elements'
-        assert bool((inner[addressed] != PATTERN).all()), f'{e.name}: {what} has addressed elements that were not written'
+_report = fp64_check.report_fixture('max err / bound per entry (tests/test_gpu_small_gemm_forms.py):', RESULTS, lambda name: sf.BY_NAME[name].key,
+                                    'worst per form key (nw, av, bv):', widths=(52, 34))
 
 
 def _bases(e, o, g, a_shift=0, b_shift=0):
@@ -93,27 +66,27 @@ def launch(e, o, g=None):
     assert (am, bm) == (4 * g.a_off % 16, 4 * g.b_off % 16), 'the base pointers have the alignment the table says'
     I, J, K = e.I, e.J, e.K
     if e.ep in ('single', 'splitk'):
-        cb, c = _guarded(I * J)
-        pb, pre = _guarded(I * J) if e.pre else (None, None)
+        cb, c = guarded(I * J, DEV)
+        pb, pre = guarded(I * J, DEV) if e.pre else (None, None)
         out = {'rs': None}
         if e.ep == 'single':
-            rb, rsv = _guarded(I) if rs is not None else (None, None)
+            rb, rsv = guarded(I, DEV) if rs is not None else (None, None)
             _lib.small_gemm(I, J, K, a, g.sai, g.sak, b, g.sbk, g.sbj, o['bias'], o['res'], alpha, beta, e.act, want_pre=bool(e.pre), rowsum_scale=rs,
                             out=(c.view(I, J), pre.view(I, J) if e.pre else None, rsv))
             if rs is not None:
-                _untouched(e, 'row sums', rb, I, torch.ones(I, dtype=torch.bool, device=DEV))
+                untouched(e.name, 'row sums', rb, I, torch.ones(I, dtype=torch.bool, device=DEV))
                 out['rs'] = rsv[None]
         else:
-            wb, ws = _guarded(e.nz * I * J)
+            wb, ws = guarded(e.nz * I * J, DEV)
             _lib.small_gemm_splitk(I, J, K, e.nz, a, g.sai, g.sak, b, g.sbk, g.sbj, o['bias'], o['res'], alpha, beta, e.act, want_pre=bool(e.pre),
                                    out=(c.view(I, J), pre.view(I, J) if e.pre else None, ws.view(e.nz, I, J)))
-            _untouched(e, 'workspace', wb, e.nz * I * J, torch.ones(e.nz * I * J, dtype=torch.bool, device=DEV))
-        _untouched(e, 'c', cb, I * J, torch.ones(I * J, dtype=torch.bool, device=DEV))
+            untouched(e.name, 'workspace', wb, e.nz * I * J, torch.ones(e.nz * I * J, dtype=torch.bool, device=DEV))
+        untouched(e.name, 'c', cb, I * J, torch.ones(I * J, dtype=torch.bool, device=DEV))
         if e.pre:
-            _untouched(e, 'pre', pb, I * J, torch.ones(I * J, dtype=torch.bool, device=DEV))
+            untouched(e.name, 'pre', pb, I * J, torch.ones(I * J, dtype=torch.bool, device=DEV))
         out.update(c=c.view(1, I, J), pre=pre.view(1, I, J) if e.pre else None)
         return out
-    cb, c = _guarded(g.c_numel)
+    cb, c = guarded(g.c_numel, DEV)
     tab = e.ep == 'table'
     _lib.small_gemm_batched(c, a, b, o['bias'], e.nz, g.za, g.zc, I, J, K, g.sai, g.sak, g.sbk, g.sbj, g.sci, g.scj, zb=g.zb, zbias=g.zbias,
                             b_tab=list(g.b_tab) if tab else None, bias_tab=list(g.bias_tab) if tab else None, alpha=alpha, beta=beta, act=e.act)
@@ -121,12 +94,12 @@ def launch(e, o, g=None):
     addressed = torch.zeros(g.c_numel, dtype=torch.bool, device=DEV)
     addressed.as_strided(*view).fill_(True)
     assert int(addressed.sum()) == e.nz * I * J
-    _untouched(e, 'c', cb, g.c_numel, addressed)
+    untouched(e.name, 'c', cb, g.c_numel, addressed)
     return {'c': c.as_strided(*view), 'pre': None, 'rs': None}
 
 
 def _within(e, what, got, ref, bound, keep=None):
-    tl._within(e, what, got, ref, bound, keep, results=RESULTS)
+    fp64_check.within(e.name, what, got, ref, bound, keep, results=RESULTS)
     if keep is not None and keep.numel() < 1000:
         assert bool(keep.all()), f'{e.name} {what}: an entry of fewer than 1000 outputs leaves none out'
 

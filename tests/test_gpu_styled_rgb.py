@@ -47,12 +47,12 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err, rel_l2
+from fp64_check import U32 as EPS32, off16
 from transeditor_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 SQRT2 = math.sqrt(2.0)
-EPS32 = 2.0 ** -24
 
 FWD_TOL = 1e-5
 SO_TOL = 1e-4
@@ -82,20 +82,11 @@ def _f32(v):
     return float(np.float32(v))
 
 
-def _offset_view(t):
-    """the same values as a contiguous view 4 bytes into its storage (not 16-byte aligned)"""
-    buf = torch.empty(t.numel() + 1, device=DEV)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
-
-
 def _gpu(shape, key, scale=1.0, offset=False):
     t = synth.normal(shape, key)
     if scale != 1.0:
         t = t * scale
-    return _offset_view(t) if offset else t.to(DEV)
+    return off16(t, 4, DEV) if offset else t.to(DEV)
 
 
 # ================================================================================================ A. the kernels at the binding
@@ -114,7 +105,7 @@ def _a_inputs(shape, offset=False):
     idx = torch.arange(0, flat.numel(), max(1, flat.numel() // 13))
     flat[idx[0::2]] = 0.0
     flat[idx[1::2]] = -0.0
-    ref = _offset_view(ref) if offset else ref.to(DEV)
+    ref = off16(ref, 4, DEV) if offset else ref.to(DEV)
     grgb = _gpu((n, 3, H, W), 'srgb.A.grgb.' + tag)
     wrgb = (synth.normal((3, C), 'srgb.A.w.' + tag) * torch.tensor([1.0, 10.0, 100.0])[:, None]).to(DEV)
     srgb = (1 + 0.5 * synth.normal((n, C), 'srgb.A.s.' + tag)).to(DEV)
@@ -385,7 +376,7 @@ def test_node_offset_upstream_gradients():
     c = _b_case(1)
     leaves = _dev_leaves(c['t'])
     a, rgb = _node(leaves, c['cfg'])
-    ga, grgb = _offset_view(c['t']['ga']), _offset_view(c['t']['grgb'])
+    ga, grgb = off16(c['t']['ga'], 4, DEV), off16(c['t']['grgb'], 4, DEV)
     assert ga.data_ptr() % 16 == 4 and grgb.data_ptr() % 16 == 4
     got = torch.autograd.grad([a, rgb], leaves, [ga, grgb])
     for name, g, want in zip(LEAVES, got, c['got']['both']):
@@ -420,7 +411,7 @@ def test_rgb_bindings_take_offset_operands(which):
         return _lib.rgb_wgrad_slabs(g, x)
 
     dense = run(x.to(DEV), g.to(DEV))
-    xo, go = _offset_view(x), _offset_view(g)
+    xo, go = off16(x, 4, DEV), off16(g, 4, DEV)
     assert xo.data_ptr() % 16 == 4 and go.data_ptr() % 16 == 4
     off = run(xo, go)
     assert torch.equal(off, dense)

@@ -1,18 +1,18 @@
 """The VGG16 fc7 feature extractor of the PRDC metric (transeditor_amd.vgg_features, csrc/vggfc.hip, te_vgg_stem_fwd_f32) against fp64
 restatements (tests/vgg_restated.py): the weight-streaming fc kernel, its batch independence and refusals, the adaptive average pool,
 the stem without the scaling layer, the whole network, and the metric's plumbing around it."""
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import lpips_restated as LR
+import scorer_checks
 import vgg_restated as R
 from conftest import rel_l2
+from fp64_check import U32 as EPS, kink_keep, within
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-EPS = 2.0 ** -24
 
 
 # ---------------------------------------------------------------------------------------------------------- 1. the fc kernel
@@ -31,7 +31,9 @@ def _fc_case(I, J, K, seed):
 @pytest.mark.parametrize('I,J,K', FC_SHAPES)
 def test_fc_stream_against_fp64(I, J, K, act):
     """|c - c64| <= (K + S + 2) 2^-24 (|A| |W|^T + |bias|): the bound of an fp32 chain of K products, S partial sums, the bias and the
-    final rounding.  Under ReLU, elements whose fp64 pre-activation is within the bound of 0 are left out (at most 1 % of them)."""
+    final rounding.  Under ReLU, elements whose fp64 pre-activation is within the bound of 0 are left out, at most 1 % of them: the
+    share is a property of the seeded operands and the fp64 reference, and I = 65, J = 130, K = 4096 (S = 32) leaves out 13 of its 8450
+    elements, 1.5e-3, more than the 0.1 % of fp64_check.KINK_CAP.  The other shapes: 3.9e-4 at (5, 4096, 1568), none at the first three."""
     from transeditor_amd import _lib
     a, w, b = _fc_case(I, J, K, 1000 * I + J + K)
     S = _lib.fc_stream_splits(J, K)
@@ -40,12 +42,8 @@ def test_fc_stream_against_fp64(I, J, K, act):
     assert c.shape == (I, J) and c.dtype == torch.float32
     pre = a.double() @ w.double().T + b.double()
     bound = (K + S + 2) * EPS * (a.double().abs() @ w.double().abs().T + b.double().abs())
-    err = (c.double() - (torch.relu(pre) if act else pre)).abs()
-    keep = torch.ones_like(pre, dtype=torch.bool) if not act else pre.abs() > bound
-    share = 1.0 - float(keep.double().mean())
-    print(f'fc_stream I={I} J={J} K={K} act={act}: S={S}, max err / bound {float((err / bound)[keep].max()):.3f}, left out {share:.4f}')
-    assert share <= 0.01
-    assert bool((err <= bound)[keep].all())
+    within(f'fc_stream I={I} J={J} K={K} act={act}', f'S={S}', c, torch.relu(pre) if act else pre, bound, kink_keep(pre, bound) if act else None,
+           cap=0.01)
 
 
 # ---------------------------------------------------------------------------------------------------------- 2. batch independence
@@ -192,13 +190,7 @@ def test_features_input_checks(net):
 # ---------------------------------------------------------------------------------------------------------- 7. the metric's plumbing
 @pytest.fixture(scope='module')
 def generator():
-    from transeditor_amd import synth
-    from transeditor_amd.model_spatial_query import Generator
-    G = Generator(64, 512, 512, 2 * (int(np.log2(64)) - 1), n_trans=8, pixel_norm_op_dim=1)
-    sd = G.state_dict()
-    synth.fill_state_dict(sd, 5)
-    G.load_state_dict(sd)
-    return G.to(DEV)
+    return scorer_checks.small_generator(DEV)
 
 
 def test_evaluate_prdc_with_the_extractor(net, generator):

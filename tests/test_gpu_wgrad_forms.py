@@ -25,7 +25,7 @@ Bound, elementwise, from the arithmetic, untuned; u = 2^-24.
 max err / bound per entry and the worst per key are printed at the end of the module; MEASURED below is a copy of that report from the
 MI355X, which nothing asserts.
 
-Untouched memory: the slabs are a view inside a buffer prefilled with PATTERN, GUARD elements on either side.  After the launch no slab
+Untouched memory: the slabs are a view inside a buffer prefilled with PATTERN, GUARD elements on either side (tests/fp64_check.py).  After the launch no slab
 element holds the pattern (every element is written, the zeros of an empty chunk included: an empty chunk's slab is exactly 0) and both
 guards still do.
 
@@ -39,17 +39,14 @@ import dataclasses
 import pytest
 import torch
 
-import test_gpu_loop_trips as tl
+import fp64_check
 import wgrad_forms as wf
 from transeditor_amd import _lib
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-GUARD = 256
-PATTERN = -12345.5
 RESULTS = []
 IDS = lambda e: e.name
-assert wf.U == tl.U32
 
 # worst max err / bound per key (kind, nwp, wino, vec, db); MI355X (a record, nothing asserts it)
 MEASURED = {('1x1', 2, 0, 0, 0): 0.4959, ('1x1', 2, 0, 1, 0): 0.0537, ('1x1', 4, 0, 0, 0): 0.4934, ('1x1', 4, 0, 1, 0): 0.0612,
@@ -58,18 +55,8 @@ MEASURED = {('1x1', 2, 0, 0, 0): 0.4959, ('1x1', 2, 0, 1, 0): 0.0537, ('1x1', 4,
             ('t2', 4, 0, 1, 1): 0.1605}
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nmax err / bound per entry (tests/test_gpu_wgrad_forms.py):')
-    worst = {}
-    for name, what, ratio, left in RESULTS:
-        print(f'  {name:56s} {what:12s} {ratio:8.4f}   left out {left:.1e}')
-        k = wf.BY_NAME[name].key
-        worst[k] = max(worst.get(k, 0.0), ratio)
-    print('worst per key (kind, nwp, wino, vec, db):')
-    for k in sorted(worst):
-        print(f'  {k}: {worst[k]:.4f}')
+_report = fp64_check.report_fixture('max err / bound per entry (tests/test_gpu_wgrad_forms.py):', RESULTS, lambda name: wf.BY_NAME[name].key,
+                                    'worst per key (kind, nwp, wino, vec, db):', widths=(56, 12))
 
 
 def launch(e, g, x):
@@ -78,14 +65,13 @@ def launch(e, g, x):
     numel = 1
     for d in shape:
         numel *= d
-    buf = torch.full((GUARD + numel + GUARD,), PATTERN, device=DEV)
-    out = buf[GUARD:GUARD + numel].view(shape)
+    buf, inner = fp64_check.guarded(numel, DEV)
+    out = inner.view(shape)
     assert (g.data_ptr() % 16, x.data_ptr() % 16) == (e.off, e.off), 'the operands have the alignment the table says'
     with wf.switch(e.sw):
         got = _lib.wgrad_slabs(g, x, wf.KIND[e.kind], e.H, e.W, S=e.S, NB=None if e.NB == 1 else e.NB, out=out)
     assert got.data_ptr() == out.data_ptr()
-    assert bool((buf[:GUARD] == PATTERN).all()) and bool((buf[GUARD + numel:] == PATTERN).all()), f'{e.name}: written outside the slabs'
-    assert bool((out != PATTERN).all()), f'{e.name}: {int((out == PATTERN).sum())} slab elements were not written'
+    fp64_check.untouched(e.name, 'the slabs', buf, numel, torch.ones(numel, dtype=torch.bool, device=DEV))         # every element is written
     return out
 
 
@@ -101,7 +87,7 @@ def test_form_against_fp64(entry):
         for s, t in enumerate(e.trips):
             if t == 0:
                 assert bool((got[:, s] == 0).all()), f'{e.name}: the slab of empty chunk {s} is not all zeros'
-        tl._within(e, 'slabs', got, ref, bound, results=RESULTS)
+        fp64_check.within(e.name, 'slabs', got, ref, bound, results=RESULTS)
         again = launch(e, g, x)
     assert torch.equal(got, again), f'{e.name}: a second run gives other bits ({int((got != again).sum())} elements)'
 

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import pose_restated as R
+import scorer_checks
 from conftest import ROOT, rel_l2
 
 SMALL = (8, 12, 16, 20)
@@ -145,8 +146,7 @@ def test_restatement_shapes(sd):
     p = R.probabilities(x, sd, torch.float32, 62)
     assert tuple(p.shape) == (2, 2) and float((p.sum(1) - 1).abs().max()) < 1e-5
     assert tuple(R.features(x, sd, torch.float64, 62).shape) == (2, 20)
-    v = torch.stack([x[:, 2], x[:, 1], x[:, 0]], 1).clamp(-1, 1).add(1).div(2).mul(255).round()
-    assert torch.equal(R.probabilities(v, sd, torch.float32, 62, preprocessed=True), p)
+    assert torch.equal(R.probabilities(scorer_checks.levels(x), sd, torch.float32, 62, preprocessed=True), p)
     cal = R.state_dict(0, widths=SMALL, images=x, crop=62)                                       # calibrated on the images
     lg = R.logits(x, cal, torch.float64, 62)
     assert abs(float((lg - cal['extra_layer.bias'].double()).std()) - 1) < 1e-5                  # the weight: unit spread of f @ w.T

@@ -25,9 +25,9 @@ from dataclasses import dataclass
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from fp64_check import U32 as U, off16  # noqa: E402
 from transeditor_amd import _lib  # noqa: E402
 
-U = 2.0 ** -24
 K3, KT, K1 = '3x3', 't2', '1x1'
 KIND = {K3: _lib.CONV_3X3, KT: _lib.CONV_T2, K1: _lib.CONV_1X1}
 NCELL = {K3: 64, KT: 32, K1: 64}
@@ -272,15 +272,7 @@ def operands(e, device='cpu', seed=None, off=None):
     16-byte alignment.  The values depend on the seed and the dims only: an entry and its 4-bytes-off twin hold the same numbers."""
     gen = torch.Generator().manual_seed(3000 + TABLE.index(e) if seed is None else seed)
     off = e.off if off is None else off
-    out = []
-    for shape in (g_shape(e), (e.B, e.Ci, e.H, e.W)):
-        v = torch.randn(shape, generator=gen, dtype=torch.float32)
-        buf = torch.zeros(v.numel() + 4, dtype=torch.float32, device=device)
-        t = buf[off // 4:off // 4 + v.numel()].view(shape)
-        t.copy_(v)
-        assert t.data_ptr() % 16 == off and t.is_contiguous()
-        out.append(t)
-    return out
+    return [off16(torch.randn(shape, generator=gen, dtype=torch.float32), off, device) for shape in (g_shape(e), (e.B, e.Ci, e.H, e.W))]
 
 
 def chunk_masks(e, f, device):
