@@ -302,19 +302,21 @@ def test_modconv_host_argument_logic():
         M.modconv(x, w, demod_eps=1e-8)                                       # demodulation without a style scale
     dgrad_pack = lambda op: M._PACK[M._ROUTES[M._ADJOINT[op]][0]][True]      # (layout the fp32 data gradient of `op` reads)
     assert dgrad_pack('up') == dgrad_pack('down') != dgrad_pack('3x3')
+    from transeditor_amd.op import weight_cache
     with M.second_order(), M.no_weight_grads():
-        assert M._STATE == {'second_order': True, 'skip_w': True}
-    assert M._STATE == {'second_order': False, 'skip_w': False}
+        assert M._STATE.second_order is True and M.weights_skipped() is True
+    assert M._STATE.second_order is False and M.weights_skipped() is False
     # forward-side hints and the frozen-weight cache are thread-local (nn.DataParallel worker threads, a sampler next to a
     # training loop); the skip flag travels on a token the nodes keep, because backward runs on the autograd engine's thread
     import threading
     seen = {}
 
     def other():
-        seen['so'] = M._STATE['second_order']
-        seen['frozen'] = M._STATE.frozen_on
+        seen['so'] = M._STATE.second_order
+        seen['frozen'] = weight_cache._CACHES.frozen_on
         seen['graph_is_default'] = M.current_graph() is M._DEFAULT_GRAPH
-    with M.second_order() as tok, M.frozen_weights({}):
+    with M.second_order() as tok, weight_cache.frozen_weights({}):
+        assert weight_cache._CACHES.frozen_on is True
         assert M.current_graph() is tok and tok is not M._DEFAULT_GRAPH
         t = threading.Thread(target=other)
         t.start()
@@ -463,7 +465,7 @@ def test_packed_weight_cache_refresh_logic(monkeypatch):
     views dropped, temporaries never cached"""
     import torch
     from transeditor_amd import _lib
-    from transeditor_amd.op import modconv as mc
+    from transeditor_amd.op import weight_cache as mc
     calls = {'single': 0, 'multi': []}
 
     def conv_pack(w, kind, wscale=1.0):
@@ -515,6 +517,7 @@ def test_forward_plans_and_packs_once(monkeypatch, libpath):
     import conv_routes as cr
     from transeditor_amd import _lib
     from transeditor_amd.op import modconv as mc
+    from transeditor_amd.op.weight_cache import packed_weights_cache
     log = []
 
     def conv_pack(w, kind, wscale=1.0):
@@ -555,14 +558,14 @@ def test_forward_plans_and_packs_once(monkeypatch, libpath):
         # (b)
         del log[:]
         cache = {}
-        with mc.packed_weights_cache(cache), torch.no_grad():
+        with packed_weights_cache(cache), torch.no_grad():
             mc._fwd_raw(x, w, op, wscale=0.5)
         assert log == [('pack2', pf, pb), ('conv', cf, pf)] and sorted(k[2] for k in cache) == sorted((pf, pb))
         # (c): no cache open; a cache open but a forward that records; the helper asked for one layout
         del log[:]
         with torch.no_grad():
             mc._fwd_raw(x, w, op, wscale=0.5)
-        with mc.packed_weights_cache({}):
+        with packed_weights_cache({}):
             mc._fwd_raw(x, w, op, wscale=0.5)
         assert log == [('pack', pf), ('conv', cf, pf)] * 2
         del log[:]

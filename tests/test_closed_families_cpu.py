@@ -202,8 +202,8 @@ def emulated_conv_ops(monkeypatch):
 
 @pytest.mark.parametrize('kind', ['3x3', '1x1', 'up', 'down'])
 def test_conv_trio_algebra(emulated_conv_ops, kind):
-    """y = conv(x, wscale w) through _ConvFwd and, by differentiation, _ConvDgrad / _ConvWgrad (each one's backward is the
-    other two, with the same constant): value, both gradients, second differentiation, for the four kinds"""
+    """y = conv(x, wscale w) through _Fwd entered without scales (conv_core) and, by differentiation, _Dgrad / _Wgrad (each one's
+    backward is the other two, with the same constant): value, both gradients, second differentiation, for the four kinds"""
     torch.manual_seed(3)
     ks = 1 if kind == '1x1' else 3
     x = torch.randn(2, 3, 7 if kind == 'down' else 4, 9 if kind == 'down' else 5, dtype=torch.float64, requires_grad=True)
@@ -216,13 +216,15 @@ def test_conv_trio_algebra(emulated_conv_ops, kind):
         assert torch.allclose(a, b, rtol=1e-10, atol=1e-12), name
 
 
-@pytest.mark.parametrize('kind,demod', [('3x3', True), ('up', True), ('1x1', False), ('1x1', True)])
+@pytest.mark.parametrize('kind,demod', [('3x3', True), ('up', True), ('1x1', False), ('1x1', True), ('3x3', 'alone')])
 def test_closed_modulated_conv_family_algebra(emulated_conv_ops, monkeypatch, kind, demod):
-    """the five-linear family of the modulated convolution (op/modconv.py::_MCFwd / _MCDgrad / _MCWgrad: style scale and
-    demodulation INSIDE the convolution calls, the scale gradients as channel dots divided by the scale) against the broadcast
+    """the five-linear family of the modulated convolution (op/modconv.py::_Fwd / _Dgrad / _Wgrad entered through modconv_closed: style
+    scale and demodulation INSIDE the convolution calls, the scale gradients as channel dots divided by the scale) against the broadcast
     expression: value, all four first gradients (recorded), and the gradient of a scalar of THOSE w.r.t. every input - which walks
     every backward branch of the three Functions (ModulatedConv2d.forward, model_spatial_query.py:296-337; ToRGB without
-    demodulation :416-425)"""
+    demodulation :416-425).  demod='alone': a demodulation and NO style scale - no caller builds it, the family allows it (each
+    scale is handled on its own)"""
+    style = demod != 'alone'
     monkeypatch.setattr(modconv, '_closed_ok', lambda x: True)
     torch.manual_seed(6)
     B, Ci, Co = 2, 3, 4
@@ -231,25 +233,28 @@ def test_closed_modulated_conv_family_algebra(emulated_conv_ops, monkeypatch, ki
     w = torch.randn(Co, Ci, ks, ks, dtype=torch.float64, requires_grad=True)
     s = (1 + 0.3 * torch.randn(B, Ci, dtype=torch.float64)).requires_grad_(True)
     d = (1 + 0.3 * torch.randn(B, Co, dtype=torch.float64)).requires_grad_(True) if demod else None
-    ins = (x, w, s) + ((d,) if demod else ())
+    scales = ((s,) if style else ()) + ((d,) if demod else ())
+    ins = (x, w) + scales
+    pair = lambda sc: ((sc[0] if style else None), (sc[-1] if demod else None))
 
-    def plain(x, w, s, d=None):
-        y = _conv_ref(x * s[:, :, None, None], w * 0.21, kind)
+    def plain(x, w, *sc):
+        s, d = pair(sc)
+        y = _conv_ref(x if s is None else x * s[:, :, None, None], w * 0.21, kind)
         return y if d is None else y * d[:, :, None, None]
 
-    def ours(x, w, s, d=None):
-        return modconv.modconv_closed(x, w, s, d, kind, 0.21)
+    def ours(x, w, *sc):
+        return modconv.modconv_closed(x, w, *pair(sc), kind, 0.21)
     gy = torch.randn_like(plain(*ins))
     want = _second_order(plain, ins, gy)
     got = _second_order(ours, ins, gy)
     names = ['y'] + [f'g{i}' for i in range(len(ins))] + [f'G{i}' for i in range(len(ins))]
     for name, a, b in zip(names, got, want):
         assert torch.allclose(a, b, rtol=1e-9, atol=1e-11), name
-    # an exactly-zero style scale does not poison the scale gradient (the division sees the smallest normal number instead)
-    s0 = s.detach().clone()
+    # an exactly-zero scale does not poison the scale gradient (the division sees the smallest normal number instead)
+    s0 = scales[0].detach().clone()
     s0[0, 1] = 0.0
     s0.requires_grad_(True)
-    y = ours(x, w, s0, d) if demod else ours(x, w, s0)
+    y = ours(x, w, s0, *scales[1:])
     gs, = torch.autograd.grad(y, s0, gy)
     assert torch.isfinite(gs).all()
 

@@ -135,7 +135,7 @@ def test_refresh_packed_weights_equals_single_packs():
     ModulatedConv2d; untouched parameters are left alone and a stale entry is really rewritten."""
     import torch
     from transeditor_amd import _lib
-    from transeditor_amd.op.modconv import packed, packed2, packed_weights_cache, refresh_packed_weights
+    from transeditor_amd.op.weight_cache import packed, packed2, packed_weights_cache, refresh_packed_weights
     torch.manual_seed(3)
     ps = [torch.nn.Parameter(torch.randn(*s, device='cuda')) for s in [(1, 24, 40, 3, 3), (64, 3, 1, 1), (512, 512, 3, 3), (130, 66, 1, 1)]]
     views = [p[0] if p.dim() == 5 else p for p in ps]

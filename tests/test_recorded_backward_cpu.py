@@ -174,7 +174,7 @@ def test_weights_skipped_predicate_across_threads():
     t.start()
     assert inside.wait(10)
     try:
-        assert recorded.weights_skipped() and recorded._STATE['skip_w']
+        assert recorded.weights_skipped() and recorded.weights_skipped(recorded._STATE.graph)
     finally:
         done.set()
         t.join()

@@ -18,7 +18,7 @@ if 'oldcomposite' in sys.argv:        # A/B: chan_scale -> conv trio -> chan_sca
 dev = 'cuda'
 ts = TrainStep(default_args(size=256, batch=16), dev)
 real = torch.randn(16, 3, 256, 256, device=dev).clamp(-1, 1)
-from transeditor_amd.op.modconv import packed_weights_cache      # noqa: E402
+from transeditor_amd.op.weight_cache import packed_weights_cache      # noqa: E402
 step = ts.path_step if which == 'path' else (lambda: ts.r1_step(real))
 
 

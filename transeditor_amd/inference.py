@@ -6,7 +6,7 @@ call a FROZEN generator under no_grad with a fixed batch shape, thousands of tim
 re-packs every weight, recomputes the demodulation squares and issues ~500 small launches from Python; at sampling batch
 sizes the GPU then waits for the host.  ``GeneratorSampler``:
 
-* keeps the packed weights and demodulation squares of every layer (op.modconv.frozen_weights), validated against each
+* keeps the packed weights and demodulation squares of every layer (op.weight_cache.frozen_weights), validated against each
   parameter's version counter;
 * captures the whole forward of a given (batch, keyword) signature into ONE hipGraph (torch.cuda.CUDAGraph: HIP stream
   capture of the te_* launches on torch's capture stream) and replays it: one host call per batch instead of ~500.
@@ -23,7 +23,7 @@ grow memory or replay stale values; the number of captured signatures is bounded
 """
 import torch
 
-from .op.modconv import frozen_weights
+from .op.weight_cache import frozen_weights
 
 
 class GeneratorSampler:

@@ -36,6 +36,7 @@ from .op import modulation, styled_rgb
 from .op.stddev import minibatch_stddev
 from .op.style import demod
 from .op.token_mlp import token_mlp
+from .op.weight_cache import _CACHES as _weight_caches
 
 CHANNELS = lambda cm: {4: 512, 8: 512, 16: 512, 32: 512, 64: 256 * cm, 128: 128 * cm, 256: 64 * cm,
                        512: 32 * cm, 1024: 16 * cm}     # :473-483
@@ -373,8 +374,8 @@ class Generator(nn.Module):                                                     
         m, a = conv.conv, conv.activate
         w = m.weight.view(m.weight.shape[1:])
         wr = to_rgb.conv.weight.view(to_rgb.conv.weight.shape[1:])
-        if (torch.is_grad_enabled() and not conv.layer_noise_injection and not _modconv_state['second_order']
-                and not _modconv_state.frozen_on and m.kind == '3x3' and m.demodulate and not to_rgb.conv.demodulate
+        if (torch.is_grad_enabled() and not conv.layer_noise_injection and not _modconv_state.second_order
+                and not _weight_caches.frozen_on and m.kind == '3x3' and m.demodulate and not to_rgb.conv.demodulate
                 and to_rgb.conv.kind == '1x1' and a.bias is not None and a.negative_slope == 0.2
                 and abs(a.scale - 2 ** 0.5) < 1e-12 and styled_rgb.supported(x, w, wr)):
             out, rgb = styled_rgb.styled_conv_rgb(x, w, m.modulation(style_c) if s_c is None else s_c, a.bias, wr,
@@ -458,7 +459,7 @@ class Generator(nn.Module):                                                     
             mods += [conv_up.conv.modulation, conv.conv.modulation, to_rgb.conv.modulation]
             index += [i, i + 1, i + 2]
             i += 2
-        if not _modconv_state['second_order'] and modulation.supported(latent, mods):
+        if not _modconv_state.second_order and modulation.supported(latent, mods):
             sm = modulation.batched_modulation(latent.contiguous(), mods, index)
         else:
             sm = [None] * len(mods)
@@ -561,7 +562,7 @@ class ResBlock(nn.Module):                                                      
                 and tuple(c2[0].kernel.shape) == (4, 4) and tuple(sk[0].kernel.shape) == (4, 4))
 
     def fusable(self, input):
-        return (input.is_cuda and input.dtype == torch.float32 and not _modconv_state['second_order'] and input.shape[2] >= 8
+        return (input.is_cuda and input.dtype == torch.float32 and not _modconv_state.second_order and input.shape[2] >= 8
                 and input.shape[3] >= 8 and input.shape[2] % 2 == 0 and input.shape[3] % 2 == 0 and self._standard())
 
     def forward(self, input, stem=None):
@@ -622,7 +623,7 @@ class Discriminator(nn.Module):                                                 
             out = self.convs(input)
         batch = out.shape[0]
         # :844-852 minibatch stddev + concat: one launch (op/stddev.py)
-        out = minibatch_stddev(out, self.stddev_group, self.stddev_feat, second_order=_modconv_state['second_order'], chunks=chunks)
+        out = minibatch_stddev(out, self.stddev_group, self.stddev_feat, second_order=_modconv_state.second_order, chunks=chunks)
         out = self.final_conv(out)
         return self.final_linear(out.view(batch, -1))
 

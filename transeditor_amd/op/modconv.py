@@ -10,25 +10,26 @@ instead of the reference's B materialised weight copies + grouped convolution.
 
 Two layers of autograd functions:
 
-* ``conv_core`` / ``_ConvDgrad`` / ``_ConvWgrad`` — the plain bilinear convolution trio, closed
-  under differentiation (each one's backward is expressed with the other two), so anything
-  built on them is differentiable to any order (R1 / path-length regularisers).
+* ``_Fwd`` / ``_Dgrad`` / ``_Wgrad`` — the convolution with optional style and demodulation
+  scales inside the kernels, a family closed under differentiation (each one's backward is
+  expressed with the other two), so anything built on them is differentiable to any order
+  (R1 / path-length regularisers).  ``conv_core`` enters it without scales (the plain bilinear
+  convolution), ``modconv_closed`` with them.
 * ``modconv`` (``_ModConvFused``) — the fast path: scales, bias and activation fused into the
   kernels, a hand-written backward that produces dx, dW, ds, dd from ONE data-gradient conv and
   ONE correlation pass (per-sample slabs + te_wgrad_reduce; ``_modconv_bwd``).  When its backward
   is itself being recorded (create_graph) it re-derives the gradients through the differentiable
-  trio (``recorded_backward``), so double backward stays exact.
+  family (``recorded_backward``), so double backward stays exact.
 
 The hints of the regulariser steps (``second_order()``, ``no_weight_grads()``) and their per-thread
-state live in op/recorded.py and are re-exported here; the two weight caches below keep their fields
-on the same state object.
+state live in op/recorded.py and are re-exported here; the packed-weight and frozen-weight caches
+live in op/weight_cache.py.
 
 kinds: '3x3' (stride 1, pad 1), '1x1', 'up' (3x3 transposed stride 2 -> (2H+1)x(2W+1); the blur
 that follows in the reference, model_spatial_query.py:318-321, is a separate upfirdn2d), 'down' (3x3 stride 2,
 pad 0 over a (2H+1)x(2W+1) input -> HxW: the discriminator's blurred downsampling conv, :744-768; it is the
 adjoint kernel pair of 'up').
 """
-import contextlib
 import os
 
 import torch
@@ -41,149 +42,14 @@ from .fused_act import fused_leaky_relu
 from .recorded import (_DEFAULT_GRAPH, _STATE, current_graph, latent_producer_section, no_weight_grads, recorded_backward,      # noqa: F401
                        second_order, weights_skipped)
 from .style import demod
-
-
-# Frozen-weight cache (inference-only pipeline): inside `frozen_weights()` a forward that needs no gradient
-# reuses the packed weight layout and the demodulation squares wsq[Co,Ci] of every layer instead of re-deriving them from
-# the [Co,Ci,k,k] parameter on every call.  Opt-in because weights can be rewritten behind autograd's back (the reference's
-# accumulate() goes through `.data`, train_spatial_query.py:60-61, which does not touch the version counter): whoever opens
-# the context promises the weights stay put (inference.GeneratorSampler); an entry is still re-validated against the
-# parameter's version counter and storage address.  Thread-local: a sampler in one thread does not switch the training
-# forward of another thread to cached weights.
-@contextlib.contextmanager
-def frozen_weights(cache):
-    """`cache`: a dict owned by the caller (lives as long as the weights it describes)."""
-    old = (_STATE.frozen_on, _STATE.frozen_cache)
-    _STATE.frozen_on, _STATE.frozen_cache = True, cache
-    try:
-        yield
-    finally:
-        _STATE.frozen_on, _STATE.frozen_cache = old
-
-
-# Packed-weight cache for a TRAINING loop that owns every write to the weights (train_step.TrainStep): inside
-# `packed_weights_cache(d)` the packed layouts of a weight tensor are kept in `d` and reused as long as the tensor's version
-# counter and storage address are unchanged.  One iteration runs the discriminator three times and the generator twice
-# between optimiser steps (train_spatial_query.py:173-224), the regulariser steps pack the same weight once per autograd
-# node: ~45 of ~110 packing launches per iteration disappear.  Opt-in and thread-local for the same reason as the
-# frozen-weight cache: a write through `.data` does not move the version counter (FusedAdam / MultiTensorEMA do bump it).
-@contextlib.contextmanager
-def packed_weights_cache(cache):
-    old = _STATE.pack_cache
-    _STATE.pack_cache = cache
-    try:
-        yield
-    finally:
-        _STATE.pack_cache = old
-
-
-@contextlib.contextmanager
-def cache_of(ctx):
-    """Backward functions run on the autograd engine's device thread, where the forward thread's `packed_weights_cache()` is
-    not visible (thread-local): a node keeps the cache it was built under (`ctx.pack_cache`, set by `keep_cache`) and re-opens
-    it around its backward, so the layouts packed there - the data-gradient layout of the closed trio in the recorded R1 /
-    path-length backward - are cached like the forward's.  Entries stay validated by version counter and storage address."""
-    c = getattr(ctx, 'pack_cache', None)
-    if c is None or _STATE.pack_cache is not None:
-        yield
-        return
-    with packed_weights_cache(c):
-        yield
-
-
-def keep_cache(ctx):
-    ctx.pack_cache = _STATE.pack_cache
-
-
-def _pack_key(w, pack_kind, wscale):
-    return (w.data_ptr(), tuple(w.shape), pack_kind, float(wscale))
-
-
-def _cacheable(w):
-    """only model parameters (or views of them) are cached: an intermediate tensor (the `ggw` of a double backward) may share
-    address, shape and version 0 with an earlier one"""
-    if _STATE.pack_cache is None:
-        return None
-    base = w._base if w._base is not None else w
-    return base if isinstance(base, torch.nn.Parameter) else None
-
-
-def refresh_packed_weights(cache):
-    """Re-derive every stale layout held by `cache` in ONE launch (te_conv_pack_weights_multi_f32), into new buffers.  Called right after an
-    optimiser step: the layers that use the weights next then hit the cache instead of issuing ~60 small packing launches per
-    iteration.  An entry whose parameter is gone / resized is dropped; entries of untouched parameters cost nothing."""
-    jobs, fresh = [], []
-    for key, (ver, wp, base) in list(cache.items()):
-        ptr, shape, pack_kind, wscale = key
-        if base._version == ver:
-            continue
-        n = 1
-        for d in shape:
-            n *= d
-        if not (base.data_ptr() == ptr and base.numel() == n and base.is_contiguous() and len(shape) == 4):
-            del cache[key]                # a partial view of the parameter (or a resized one): repacked at its next use
-            continue
-        # a FRESH buffer per stale layout: the old one may still be held by an autograd node (ctx.wp_bwd / ctx.packs of a graph
-        # that outlives the optimiser step - retain_graph, a custom step order); rewriting it in place would make that graph
-        # differentiate through the NEW weights without an error
-        jobs.append((torch.empty_like(wp), base.detach().view(shape), pack_kind, wscale))      # (ModulatedConv2d.weight is [1,Co,Ci,k,k]: same storage)
-        fresh.append((key, base))
-    _lib.conv_pack_multi(jobs)
-    for (key, base), job in zip(fresh, jobs):
-        cache[key] = (base._version, job[0], base)
-    return len(jobs)
-
-
-def packed(w, pack_kind, wscale=1.0):
-    """packed layout `pack_kind` of w (through the cache when one is open)"""
-    base = _cacheable(w)
-    if base is None:
-        return _lib.conv_pack(w, pack_kind, wscale)
-    cache, key = _STATE.pack_cache, _pack_key(w, pack_kind, wscale)
-    ent = cache.get(key)
-    if ent is None or ent[0] != w._version or ent[2] is not base:
-        ent = cache[key] = (w._version, _lib.conv_pack(w, pack_kind, wscale), base)      # (keeps the storage alive: the key stays valid)
-    return ent[1]
-
-
-def packed2(w, kind_a, kind_b, wscale=1.0):
-    """two layouts of w; one launch when both have to be produced"""
-    base = _cacheable(w)
-    if base is None:
-        return _lib.conv_pack2(w, kind_a, kind_b, wscale)
-    cache = _STATE.pack_cache
-    ka, kb = _pack_key(w, kind_a, wscale), _pack_key(w, kind_b, wscale)
-    ea, eb = cache.get(ka), cache.get(kb)
-    va = ea is not None and ea[0] == w._version and ea[2] is base
-    vb = eb is not None and eb[0] == w._version and eb[2] is base
-    if va and vb:
-        return ea[1], eb[1]
-    if not va and not vb:
-        wa, wb = _lib.conv_pack2(w, kind_a, kind_b, wscale)
-        cache[ka], cache[kb] = (w._version, wa, base), (w._version, wb, base)
-        return wa, wb
-    return packed(w, kind_a, wscale), packed(w, kind_b, wscale)
-
-
-def _frozen_entry(w, kind, wscale, want_wsq, pack_kind=_lib.PACK_FWD):
-    base = w._base if w._base is not None else w
-    key = (id(base), w.data_ptr(), tuple(w.shape), kind, float(wscale), pack_kind)
-    stamp = (base._version, base.data_ptr())
-    ent = _STATE.frozen_cache.get(key)
-    if ent is None or ent['stamp'] != stamp:
-        ent = {'stamp': stamp, 'wp': _lib.conv_pack(w, pack_kind, wscale), 'wsq': None, 'keep': base}
-        _STATE.frozen_cache[key] = ent
-    if want_wsq and ent['wsq'] is None:
-        w3 = w.reshape(w.shape[0], w.shape[1], -1)
-        ent['wsq'] = (w3 * wscale).square().sum(dim=2).contiguous()
-    return ent
+from .weight_cache import _CACHES, cache_of, frozen_entry, keep_cache, packed, packed2
 
 
 def _modconv_frozen(x, w, isc, osc, bias, act, kind, wscale, demod_eps):
     """forward only, weights taken from the frozen cache (no autograd node is created)"""
     H, W = _lowres_hw(kind, False, x)
     pk, ck = fwd_kinds(kind, x.shape[0], w, H, W)
-    ent = _frozen_entry(w, kind, wscale, demod_eps is not None, pk)
+    ent = frozen_entry(w, kind, wscale, demod_eps is not None, pk)
     if demod_eps is not None:
         osc = _lib.demod_from_wsq(ent['wsq'], isc, demod_eps)
     if _rgb_ok(kind, w.shape[0], w.shape[1], x, osc, act):
@@ -302,7 +168,7 @@ def _fwd_raw(x, w, kind, isc=None, osc=None, bias=None, act=0, wscale=1.0, with_
     """with_bwd_pack: also return (the data-gradient packing of w, the convolution kind it is packed for) for _dgrad_raw(wp=...)."""
     H, W = _lowres_hw(kind, False, x)
     # (a no-grad forward inside a training loop: the same weights meet a backward later in the iteration, so pack for it ahead)
-    ahead = _STATE.pack_cache is not None and torch.is_grad_enabled() is False
+    ahead = _CACHES.pack_cache is not None and torch.is_grad_enabled() is False
     wp, ck, bwd = packed_route(kind, x.shape[0], w, H, W, wscale, with_bwd_pack or ahead)
     y = _lib.conv(x, wp, ck, w.shape[0], H, W, isc, osc, bias, act)
     return (y, bwd) if with_bwd_pack else y
@@ -351,61 +217,6 @@ def _wgrad_plain(gy, x, kind, ksize, wscale):
     return gw.reshape(Co, Ci, ksize, ksize)
 
 
-# The plain convolution y = conv(x, wscale * w) and its two gradients: a trio closed under differentiation (each one's
-# backward is the other two, with the same constant wscale), so anything built on it differentiates to any order.
-class _ConvFwd(Function):
-    @staticmethod
-    def forward(ctx, x, w, kind, wscale):
-        ctx.save_for_backward(x, w)
-        ctx.kind, ctx.wscale = kind, wscale
-        ctx.graph = current_graph()
-        keep_cache(ctx)
-        return _fwd_raw(x, w, kind, wscale=wscale)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        skip_w = weights_skipped(ctx.graph)
-        with cache_of(ctx):
-            gx = _ConvDgrad.apply(gy, w, ctx.kind, ctx.wscale) if ctx.needs_input_grad[0] else None
-            gw = _ConvWgrad.apply(gy, x, ctx.kind, w.shape[2], ctx.wscale) if (ctx.needs_input_grad[1] and not skip_w) else None
-        return gx, gw, None, None
-
-
-class _ConvDgrad(Function):
-    @staticmethod
-    def forward(ctx, gy, w, kind, wscale):
-        ctx.save_for_backward(gy, w)
-        ctx.kind, ctx.wscale = kind, wscale
-        keep_cache(ctx)
-        return _dgrad_raw(gy, w, kind, wscale=wscale)
-
-    @staticmethod
-    def backward(ctx, ggx):
-        gy, w = ctx.saved_tensors
-        with cache_of(ctx):
-            g_gy = _ConvFwd.apply(ggx, w, ctx.kind, ctx.wscale) if ctx.needs_input_grad[0] else None
-            g_w = _ConvWgrad.apply(gy, ggx, ctx.kind, w.shape[2], ctx.wscale) if ctx.needs_input_grad[1] else None
-        return g_gy, g_w, None, None
-
-
-class _ConvWgrad(Function):
-    @staticmethod
-    def forward(ctx, gy, x, kind, ksize, wscale):
-        ctx.save_for_backward(gy, x)
-        ctx.kind, ctx.wscale = kind, wscale
-        keep_cache(ctx)
-        return _wgrad_plain(gy, x, kind, ksize, wscale)
-
-    @staticmethod
-    def backward(ctx, ggw):
-        gy, x = ctx.saved_tensors
-        with cache_of(ctx):
-            g_gy = _ConvFwd.apply(x, ggw, ctx.kind, ctx.wscale) if ctx.needs_input_grad[0] else None
-            g_x = _ConvDgrad.apply(gy, ggw, ctx.kind, ctx.wscale) if ctx.needs_input_grad[1] else None
-        return g_gy, g_x, None, None, None
-
-
 def set_split_bf16(on):
     """ONE switch for every split-bf16 kernel: the convolution kinds (gated here, by USE_SPLIT_BF16) and the weight-gradient kernels
     (gated in the library, te_wgrad_split_bf16).  Assigning `modconv.USE_SPLIT_BF16 = x` does the same (module property below), so an
@@ -416,21 +227,21 @@ def set_split_bf16(on):
     return on
 
 
-def conv_core(x, w, kind='3x3', wscale=1.0):
-    """Plain convolution y = conv(x, wscale * w) (w [Co,Ci,k,k]), differentiable to any order."""
-    return _ConvFwd.apply(x, w, kind, float(wscale))
-
-
-# The MODULATED convolution y = d (.) conv(s (.) x, wscale w) as a family closed under differentiation.  It is one
-# five-linear form  P(gy, x, w, s, d) = sum gy[b,co,p (+) t] x[b,ci,p] w[co,ci,t] s[b,ci] d[b,co]  seen from its five
-# arguments: y = dP/dgy, the data gradient dP/dx, the weight gradient dP/dw, and the two scale gradients
+# The convolution y = d (.) conv(s (.) x, wscale w) as ONE family closed under differentiation (_Fwd / _Dgrad / _Wgrad below), with
+# the style scale s[b,ci] and the demodulation d[b,co] each optional: without them it is the plain convolution (conv_core), with
+# them the modulated one (modconv_closed).  It is one five-linear form
+#     P(gy, x, w, s, d) = sum gy[b,co,p (+) t] x[b,ci,p] w[co,ci,t] s[b,ci] d[b,co]
+# seen from its five arguments: y = dP/dgy, the data gradient dP/dx, the weight gradient dP/dw, and the two scale gradients
 #     dP/ds[b,ci] = sum_p x * (dP/dx) / s ,      dP/dd[b,co] = sum_p gy * (dP/dgy) / d
 # (the sums are te_chan_dot_f32 passes, the divisions [B,C]-sized).  The derivative of dP/da with respect to b, contracted with
-# a cotangent c, is dP/db with a := c - so the three Functions below name each other in their backwards and anything built on
-# them differentiates to any order.  Unlike the chan_scale -> conv_core -> chan_scale composite of rounds 2-3, the style scale
-# and the demodulation ride INSIDE the convolution kernels (staging / epilogue, the arguments the fused first-order path has
+# a cotangent c, is dP/db with a := c - so the three Functions name each other in their backwards, with the same constant wscale,
+# and anything built on them differentiates to any order.  Unlike the chan_scale -> conv_core -> chan_scale composite of rounds
+# 2-3, the scales ride INSIDE the convolution kernels (staging / epilogue, the arguments the fused first-order path has
 # always used): per layer and order, three activation-sized elementwise passes and their autograd accumulations disappear
 # (path-length step: 161 chan_scale launches and ~5 ms per step).
+# What depends on a scale being there, each scale on its own: its gradient (and the tensor saved for it); the ToRGB streaming
+# kernels, which want a style scale; and the weight gradient's slabs - per sample and through the reducer once a scale weighs the
+# samples, the group plan of _wgrad_plain otherwise.  no_weight_grads() is honoured by the forward member's backward only.
 _SCALE_FLOOR = 1e-20
 
 
@@ -475,17 +286,21 @@ def _chan_dot(a, b):
     return _ChanDot.apply(a.contiguous(), b.contiguous())
 
 
-class _MCFwd(Function):
+def _dense(scale):
+    return None if scale is None else scale.contiguous()
+
+
+class _Fwd(Function):
     @staticmethod
-    def forward(ctx, x, w, s, d, kind, wscale):
+    def forward(ctx, x, w, s, d, kind, wscale):        # d (.) conv(s (.) x, wscale w)
         ctx.kind, ctx.wscale = kind, wscale
         ctx.graph = current_graph()
         keep_cache(ctx)
-        if _rgb_ok(kind, w.shape[0], w.shape[1], x, d):
+        if s is not None and _rgb_ok(kind, w.shape[0], w.shape[1], x, d):
             y = _lib.rgb_fwd(x, w.reshape(3, w.shape[1]), s.contiguous(), None, wscale)
         else:
-            y = _fwd_raw(x, w, kind, s.contiguous(), None if d is None else d.contiguous(), None, 0, wscale)
-        ctx.save_for_backward(x, w, s, d, y)
+            y = _fwd_raw(x, w, kind, _dense(s), _dense(d), None, 0, wscale)
+        ctx.save_for_backward(x, w, s, d, None if d is None else y)      # (y: for dP/dd only)
         return y
 
     @staticmethod
@@ -494,23 +309,23 @@ class _MCFwd(Function):
         need = ctx.needs_input_grad
         skip_w = weights_skipped(ctx.graph)
         with cache_of(ctx):
-            gx = _MCDgrad.apply(gy, w, s, d, ctx.kind, ctx.wscale) if (need[0] or need[2]) else None
-            gw = _MCWgrad.apply(gy, x, s, d, ctx.kind, w.shape[2], ctx.wscale) if (need[1] and not skip_w) else None
+            gx = _Dgrad.apply(gy, w, s, d, ctx.kind, ctx.wscale) if (need[0] or need[2]) else None
+            gw = _Wgrad.apply(gy, x, s, d, ctx.kind, w.shape[2], ctx.wscale) if (need[1] and not skip_w) else None
         gs = _chan_dot(gx, x) / s if need[2] else None
-        gd = _chan_dot(gy, y) / d if (d is not None and need[3]) else None
+        gd = _chan_dot(gy, y) / d if need[3] else None
         return (gx if need[0] else None), gw, gs, gd, None, None
 
 
-class _MCDgrad(Function):
+class _Dgrad(Function):
     @staticmethod
     def forward(ctx, gy, w, s, d, kind, wscale):       # s (.) dgrad(d (.) gy, wscale w), shaped like the convolution's input
         ctx.kind, ctx.wscale = kind, wscale
         keep_cache(ctx)
-        if _rgb_ok(kind, w.shape[0], w.shape[1], gy, d):
+        if s is not None and _rgb_ok(kind, w.shape[0], w.shape[1], gy, d):
             gx = _lib.rgb_dgrad(gy, w.reshape(3, w.shape[1]), s.contiguous(), w.shape[1], wscale)
         else:
-            gx = _dgrad_raw(gy, w, kind, isc=None if d is None else d.contiguous(), osc=s.contiguous(), wscale=wscale)
-        ctx.save_for_backward(gy, w, s, d, gx)
+            gx = _dgrad_raw(gy, w, kind, isc=_dense(d), osc=_dense(s), wscale=wscale)
+        ctx.save_for_backward(gy, w, s, d, None if s is None else gx)    # (gx: for dP/ds only)
         return gx
 
     @staticmethod
@@ -518,26 +333,28 @@ class _MCDgrad(Function):
         gy, w, s, d, gx = ctx.saved_tensors
         need = ctx.needs_input_grad
         with cache_of(ctx):
-            y2 = _MCFwd.apply(ggx, w, s, d, ctx.kind, ctx.wscale) if (need[0] or (d is not None and need[3])) else None
-            gw = _MCWgrad.apply(gy, ggx, s, d, ctx.kind, w.shape[2], ctx.wscale) if need[1] else None
+            y2 = _Fwd.apply(ggx, w, s, d, ctx.kind, ctx.wscale) if (need[0] or need[3]) else None
+            gw = _Wgrad.apply(gy, ggx, s, d, ctx.kind, w.shape[2], ctx.wscale) if need[1] else None
         gs = _chan_dot(ggx, gx) / s if need[2] else None
-        gd = _chan_dot(gy, y2) / d if (d is not None and need[3]) else None
+        gd = _chan_dot(gy, y2) / d if need[3] else None
         return (y2 if need[0] else None), gw, gs, gd, None, None
 
 
-class _MCWgrad(Function):
+class _Wgrad(Function):
     @staticmethod
     def forward(ctx, gy, x, s, d, kind, ksize, wscale):    # wscale * sum_b d_b s_b (correlation slab of sample b)  [Co,Ci,k,k]
         ctx.kind, ctx.wscale = kind, wscale
         keep_cache(ctx)
         ctx.save_for_backward(gy, x, s, d)
+        if s is None and d is None:       # nothing per sample is derived from the slabs: samples may share one (the group plan)
+            return _wgrad_plain(gy, x, kind, ksize, wscale)
         Co, Ci = gy.shape[1], x.shape[1]
         gyc, xc = gy.contiguous(), x.contiguous()
-        if _rgb_ok(kind, Co, Ci, x, d):
+        if s is not None and _rgb_ok(kind, Co, Ci, x, d):
             slabs = _lib.rgb_wgrad_slabs(gyc, xc)
         else:
             slabs = _wgrad_raw(gyc, xc, kind)
-        gw, _, _ = _lib.wgrad_reduce(slabs, slabs[0, 0], wscale, s.contiguous(), None if d is None else d.contiguous(), want_w=True)
+        gw, _, _ = _lib.wgrad_reduce(slabs, slabs[0, 0], wscale, _dense(s), _dense(d), want_w=True)
         return gw.reshape(Co, Ci, ksize, ksize)
 
     @staticmethod
@@ -545,10 +362,10 @@ class _MCWgrad(Function):
         gy, x, s, d = ctx.saved_tensors
         need = ctx.needs_input_grad
         with cache_of(ctx):
-            y2 = _MCFwd.apply(x, ggw, s, d, ctx.kind, ctx.wscale) if (need[0] or (d is not None and need[3])) else None
-            gx = _MCDgrad.apply(gy, ggw, s, d, ctx.kind, ctx.wscale) if (need[1] or need[2]) else None
+            y2 = _Fwd.apply(x, ggw, s, d, ctx.kind, ctx.wscale) if (need[0] or need[3]) else None
+            gx = _Dgrad.apply(gy, ggw, s, d, ctx.kind, ctx.wscale) if (need[1] or need[2]) else None
         gs = _chan_dot(gx, x) / s if need[2] else None
-        gd = _chan_dot(gy, y2) / d if (d is not None and need[3]) else None
+        gd = _chan_dot(gy, y2) / d if need[3] else None
         return (y2 if need[0] else None), (gx if need[1] else None), gs, gd, None, None, None
 
 
@@ -559,14 +376,19 @@ def _closed_ok(x):
 USE_CLOSED_MODCONV = True      # False: the chan_scale -> conv_core -> chan_scale composite of rounds 2-3 (A/B measurements)
 
 
+def conv_core(x, w, kind='3x3', wscale=1.0):
+    """Plain convolution y = conv(x, wscale * w) (w [Co,Ci,k,k]), differentiable to any order: the closed family without scales."""
+    return _Fwd.apply(x, w, None, None, kind, float(wscale))
+
+
 def modconv_closed(x, w, isc, osc, kind='3x3', wscale=1.0):
     """osc (.) conv(isc (.) x, wscale * w), differentiable to any order with the scales inside the convolution kernels"""
-    return _MCFwd.apply(x, w, _nonzero(isc), _nonzero(osc), kind, float(wscale))
+    return _Fwd.apply(x, w, _nonzero(isc), _nonzero(osc), kind, float(wscale))
 
 
 def _composite(x, w, isc, osc, bias, act, kind, wscale=1.0):
     """The same function as the fused kernel, built from any-order differentiable pieces (the equalised-lr constant rides
-    in the weight packing of the trio: no `w * wscale` pass, no scaling pass for its gradient)."""
+    in the weight packing of the family: no `w * wscale` pass, no scaling pass for its gradient)."""
     if USE_CLOSED_MODCONV and isc is not None and kind in ('3x3', 'up', '1x1') and _closed_ok(x):
         y = modconv_closed(x, w, isc, osc, kind, wscale)
         if act:
@@ -623,34 +445,27 @@ class _ModConvFused(Function):
     def forward(ctx, x, w, isc, osc, bias, act, kind, wscale, demod_eps):
         # demod_eps != None: osc is the demodulation coefficient of (w, isc), computed here (te_demod_fwd_f32) and
         # differentiated here (its dW / d style are accumulated into the convolution's own in the backward)
-        ctx.demod = None
+        ctx.act, ctx.kind, ctx.wscale = act, kind, wscale
+        ctx.demod = ctx.wp_bwd = None
         keep_cache(ctx)
         if demod_eps is not None:
             w3 = w.reshape(w.shape[0], w.shape[1], -1)
             osc, wsq = _lib.demod_fwd(w3, isc, wscale, demod_eps)
             ctx.demod = (demod_eps, wsq)
         ctx.rgb = _rgb_ok(kind, w.shape[0], w.shape[1], x, osc, act)
-        if ctx.rgb:
-            out = _lib.rgb_fwd(x, w.reshape(w.shape[0], w.shape[1]), isc, bias, wscale)
-            ctx.save_for_backward(x, w, isc, osc, bias, None)
-            ctx.act, ctx.kind, ctx.wscale = act, kind, wscale
-            return out
         # from-RGB stem (1x1 FROM 3 channels, unmodulated: the discriminator's first layer, :815): write-bound, the same
         # streaming kernels with the operands' roles exchanged instead of a 3-of-16-channels MFMA stage
-        ctx.stem = (kind == '1x1' and w.shape[1] == 3 and isc is None and osc is None
+        ctx.stem = (not ctx.rgb and kind == '1x1' and w.shape[1] == 3 and isc is None and osc is None
                     and _lib.rgb_supported(3, w.shape[0], x.shape[2] * x.shape[3]))
-        if ctx.stem:
+        if ctx.rgb:
+            out = _lib.rgb_fwd(x, w.reshape(w.shape[0], w.shape[1]), isc, bias, wscale)
+        elif ctx.stem:
             out = _lib.rgb_expand(x, w.reshape(w.shape[0], 3).t(), bias, _act_code(act), wscale)
-            ctx.save_for_backward(x, w, isc, osc, bias, out if act else None)
-            ctx.act, ctx.kind, ctx.wscale = act, kind, wscale
-            return out
-        ctx.wp_bwd = None
-        if ctx.needs_input_grad[0]:         # a backward will want dx: pack the data-gradient layout in the same launch (+ its kind)
+        elif ctx.needs_input_grad[0]:       # a backward will want dx: pack the data-gradient layout in the same launch (+ its kind)
             out, ctx.wp_bwd = _fwd_raw(x, w, kind, isc, osc, bias, _act_code(act), wscale, with_bwd_pack=True)
         else:
             out = _fwd_raw(x, w, kind, isc, osc, bias, _act_code(act), wscale)
-        ctx.save_for_backward(x, w, isc, osc, bias, out if act else None)
-        ctx.act, ctx.kind, ctx.wscale = act, kind, wscale
+        ctx.save_for_backward(x, w, isc, osc, bias, out if act else None)      # (ToRGB has no activation)
         return out
 
     @staticmethod
@@ -664,7 +479,7 @@ class _ModConvFused(Function):
         act, kind, wscale = ctx.act, ctx.kind, ctx.wscale
         need = ctx.needs_input_grad
         if torch.is_grad_enabled():
-            # double backward requested: differentiate the composite built from the closed trio (op/recorded.py)
+            # double backward requested: differentiate the composite built from the closed family (op/recorded.py)
             dm = ctx.demod is not None           # osc is then a function of (w, isc) inside this node, rebuilt from their aliases
 
             def build(x, w, isc, osc, bias):
@@ -677,7 +492,7 @@ class _ModConvFused(Function):
             g, g_bias = _lib.bias_act_bwd(g, out, 0.2, _act_gain(act), want_bias=bias is not None)
         elif bias is not None and need[4]:
             g_bias = g.sum(dim=(0, 2, 3))
-        if getattr(ctx, 'stem', False):
+        if ctx.stem:
             gx = _lib.rgb_fwd(g, w.reshape(w.shape[0], 3).t().contiguous(), None, None, wscale) if need[0] else None
             gw = None
             if need[1]:
@@ -685,7 +500,7 @@ class _ModConvFused(Function):
                 gw = gw * wscale if wscale != 1.0 else gw
             return gx, gw, None, None, g_bias, None, None, None, None
         wsq = ctx.demod[1] if ctx.demod is not None else None
-        gx, gw, gisc, gosc = _modconv_bwd(g, x, w, isc, osc, kind, wscale, need[:4], getattr(ctx, 'wp_bwd', None), ctx.rgb, wsq)
+        gx, gw, gisc, gosc = _modconv_bwd(g, x, w, isc, osc, kind, wscale, need[:4], ctx.wp_bwd, ctx.rgb, wsq)
         return gx, gw, gisc, gosc, g_bias, None, None, None, None
 
 
@@ -705,7 +520,7 @@ def modconv(x, w, isc=None, osc=None, bias=None, act=False, kind='3x3', wscale=1
         return _composite(x, w, isc, osc, bias, act, kind, float(wscale))
     isc = isc.contiguous() if isc is not None else None
     osc = osc.contiguous() if osc is not None else None
-    if _STATE.frozen_on and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, isc, osc, bias))):
+    if _CACHES.frozen_on and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, isc, osc, bias))):
         return _modconv_frozen(x, w, isc, osc, bias, act, kind, float(wscale), demod_eps)
     return _ModConvFused.apply(x, w, isc, osc, bias, act, kind, float(wscale), demod_eps)
 

@@ -6,9 +6,8 @@ Both hints are optional: ``second_order()`` around the forward makes the ops bui
 finds out in its backward that it is being recorded (``torch.is_grad_enabled()``) and goes through ``recorded_backward``.
 
 Threading: forward passes may run concurrently from several Python threads (the reference's metrics wrap the generator in
-nn.DataParallel; te_hip.h promises thread-safe entry points), so `second_order` and the weight caches of op/modconv.py (which keep
-their fields on the same `_STATE` object) are THREAD-LOCAL.  `skip_w` cannot be: it is read inside backward functions, which the
-autograd engine runs on its own per-device thread.  It therefore lives on a small token object (`_Graph`) that every
+nn.DataParallel; te_hip.h promises thread-safe entry points), so `second_order` is THREAD-LOCAL (`_STATE`).  `skip_w` cannot be:
+it is read inside backward functions, which the autograd engine runs on its own per-device thread.  It therefore lives on a small token object (`_Graph`) that every
 `second_order()` context creates and every node built inside it keeps (`ctx.graph`); `no_weight_grads()` flips the flag on the
 calling thread's most recent token (and on the process-wide default token that nodes built outside any `second_order()` context
 share).  Backward functions ask `weights_skipped()`.
@@ -30,23 +29,12 @@ _DEFAULT_GRAPH = _Graph()
 
 
 class _Local(threading.local):
-    """per-thread state with dict-style access (`_STATE['second_order']`); every thread starts from the defaults"""
+    """per-thread state; every thread starts from the defaults"""
 
     def __init__(self):
         self.second_order = False
         self.second_wrt = None               # second_order(wrt=...): where the recorded backward will stop
         self.graph = _DEFAULT_GRAPH          # token of the current / most recent second_order() context of this thread
-        self.frozen_on = False               # (the two weight caches of op/modconv.py)
-        self.frozen_cache = None
-        self.pack_cache = None               # dict while a packed_weights_cache() context is open on this thread
-
-    def __getitem__(self, k):
-        if k == 'skip_w':
-            return self.graph.skip_w or _DEFAULT_GRAPH.skip_w
-        return getattr(self, k)
-
-    def __eq__(self, other):                 # (tests compare against a plain dict)
-        return {'second_order': self.second_order, 'skip_w': self['skip_w']} == other
 
 
 _STATE = _Local()

@@ -25,9 +25,10 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from .modconv import _act_code, _composite, _dgrad_raw, _wgrad_plain, cache_of, keep_cache, packed_route
+from .modconv import _act_code, _composite, _dgrad_raw, _wgrad_plain, packed_route
 from .recorded import recorded_backward
 from .upfirdn2d import _geometry, flipped_taps, upfirdn2d
+from .weight_cache import cache_of, keep_cache
 
 _SQRT2 = math.sqrt(2.0)
 

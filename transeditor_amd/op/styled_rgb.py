@@ -18,9 +18,10 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from .modconv import _composite, _fwd_raw, _modconv_bwd, cache_of, keep_cache
+from .modconv import _composite, _fwd_raw, _modconv_bwd
 from .recorded import recorded_backward, weights_skipped
 from .style import demod
+from .weight_cache import cache_of, keep_cache
 
 _SQRT2 = 2 ** 0.5
 

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from .op import modconv
+from .op.weight_cache import packed_weights_cache
 from .op.noisereg import noise_normalize_, noise_regularize
 from .optim import FusedAdam
 
@@ -111,7 +111,7 @@ def project(g_ema, imgs, percept, *, step=10000, lr=0.1, lr_rampup=0.05, lr_ramp
     try:
         for p in params:
             p.requires_grad_(False)
-        with torch.random.fork_rng(devices=[dev] if dev.type == 'cuda' else []), modconv.packed_weights_cache({}):
+        with torch.random.fork_rng(devices=[dev] if dev.type == 'cuda' else []), packed_weights_cache({}):
             torch.manual_seed(seed)
             with torch.no_grad():                                               # :155-163, once per call
                 latent_dim = 512

@@ -22,7 +22,8 @@ from torch import autograd
 from torch.nn import functional as F
 
 from .model_spatial_query import Discriminator, Generator
-from .op.modconv import no_weight_grads, packed_weights_cache, refresh_packed_weights, second_order
+from .op.modconv import no_weight_grads, second_order
+from .op.weight_cache import packed_weights_cache, refresh_packed_weights
 from .optim import FusedAdam, MultiTensorEMA
 from .utils import distributed as D
 from .utils.sample import prepare_noise_new, prepare_param
