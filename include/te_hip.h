@@ -11,7 +11,7 @@
  *         weight-gradient kernel and with it the slab partition - results are fp32-equivalent, not bit-identical, across its values;
  *       - five test and tool hooks, te_conv_wino6_form, te_conv_wino6_tiles_per_block, te_conv_s2s6_form, te_conv_t2s6_form and
  *         te_wgrad_t2_wide, which select between kernels of one kind, or between grids of one kernel, with bit-identical results
- *         (tests compare the two live kernels of a kind on one input);
+ *         (tests compare the two live kernels of a kind on one input); te_conv_split_form and te_wgrad6_form name the kernel that a launch takes under them;
  *       - TE_XCD_INTERLEAVED, read once from the environment: the order in which the convolution launches hand tiles to the XCDs
  *         (te_common.h); results are bit-identical;
  *       - the per-thread last-error string;
@@ -241,6 +241,26 @@ int te_conv_splitk_count(int kind, int B, int K, int M, int H, int W);
 #define TE_CONV_FORM_REGION 8
 #define TE_CONV_FORM_INTS (TE_CONV_FORM_HEAD + 3 * TE_CONV_FORM_REGION)
 int te_conv_form(int kind, int B, int K, int M, int H, int W, int has_isc, int epi, int with_ws, int* form);
+/* The same for the four split-bf16 kinds TE_CONV_3X3W6, TE_CONV_S2S6, TE_CONV_T2S6 and TE_CONV_1X1S6 (the other kinds:
+ * TE_ERR_UNSUPPORTED): which kernel of the kind a launch runs and on which grid, under the current values of te_conv_wino6_form,
+ * te_conv_wino6_tiles_per_block, te_conv_s2s6_form and te_conv_t2s6_form (host only, nothing is launched: the answer is the plan that the
+ * kind's launch itself makes and then dispatches on).  has_isc: style scales given (the ISC instantiation; TE_CONV_1X1S6 takes none:
+ * TE_ERR_UNSUPPORTED); with_scratch: TE_CONV_T2S6 is given its column scratch (te_conv_t2s6_ws_floats), ignored for the other kinds.
+ * form[TE_CONV_SPLIT_FORM_INTS]:
+ *   [0] two_image   the two-image kernel (a block owns 128 output channels; TE_CONV_1X1S6 has no other), 0 = the ping-pong kernel
+ *   [1] pair16      TE_CONV_3X3W6 at W == 16: two samples side by side in a tile row
+ *   [2] mblocks  [3] ntiles  [4] blocks (grid x)  [5] idle: blocks of the grid that get no tile (ntiles % 8 != 0, or runs that stay empty)
+ *   [6] tpb, [7] lists   two-image TE_CONV_3X3W6: tiles per run as set or chosen automatically (1: a tile per block) and the runs per
+ *                        XCD that follow from it (0: a tile per block); zeros elsewhere
+ *   [8] lds         dynamic LDS bytes of the (body) kernel
+ *   [9] edge_ct  [10] edge_line_tiles  [11] edge_blocks   TE_CONV_T2S6: t2_edge_kernel's CT (4 where H >= 64 and W >= 64, else 2), its line
+ *                        tiles per (sample, 64 output channels) and its grid x; zeros elsewhere
+ *   [12] scratch    TE_CONV_T2S6: the body kernel hands the last input column to the edge kernel through the scratch
+ *   [13] isc        the ISC instantiation
+ * TE_ERR_NULL / TE_ERR_SHAPE on bad arguments and the launch's own refusal with the launch's code (te_conv_*_supported: TE_ERR_UNSUPPORTED);
+ * a refusal leaves form untouched.  Operand alignment is the launch's affair: the plan does not depend on it. */
+#define TE_CONV_SPLIT_FORM_INTS 14
+int te_conv_split_form(int kind, int B, int K, int M, int H, int W, int has_isc, int with_scratch, int* form);
 /* 1 if TE_CONV_3X3W covers the problem: K % 8 == 0, W % 32 == 0, and M % 128 == 0 with H % 4 == 0, or M % 64 == 0 with
  * H % 8 == 0, or M % 32 == 0 with H % 16 == 0 (block tile = 128 / 64 / 32 output channels x 4 / 8 / 16 rows x 32 columns):
  * every 3x3 stride-1 layer of the generator and discriminator from 32x32 up incl. the 32 / 64-channel tail of FFHQ-1024; the

@@ -1,7 +1,7 @@
 """Host-plan table: every answer of the library's host-only launch planners over one fixed grid of arguments.
 
-The planners (te_*_plan, te_*_count, te_*_cover, te_conv_packed_numel, te_*_tiles, te_wgrad_pair_form, te_wgrad6_form, te_wgrad_form
-in include/te_hip.h) launch nothing and need no GPU.  Their answers fix the summation partition of the split launches (so every result
+The planners (te_*_plan, te_*_count, te_*_cover, te_conv_packed_numel, te_*_tiles, te_wgrad_pair_form, te_wgrad6_form, te_wgrad_form,
+te_conv_split_form in include/te_hip.h) launch nothing and need no GPU.  Their answers fix the summation partition of the split launches (so every result
 bit) and are what the loop-trip and route tests assert their coverage with, yet a planner that drifts from its launch fails no other
 test.  table(lib) calls each of them over the grid below and returns {name: int array}; return codes are part of the table.
 
@@ -9,7 +9,8 @@ test.  table(lib) calls each of them over the grid below and returns {name: int 
 
 tests/golden/host_plans.npz is the table of the library before the planners were derived from the launch code's own geometry;
 tests/test_host_plans_cpu.py asserts that the current library still gives it.  A planner that is added later is recorded next to its
-relatives from the library that introduces it, with every older answer unchanged (wgrad_form: the plan of the fp32 weight-gradient launch).
+relatives from the library that introduces it, with every older answer unchanged (wgrad_form: the plan of the fp32 weight-gradient launch;
+conv_split_form: the plan of the split-bf16 forward launches under three settings of their form hooks).
 """
 import ctypes as C
 import itertools
@@ -74,6 +75,35 @@ def _two(fn, *args, second=C.c_int):
 def _conv(L):
     return {'conv_splitk_count': [L.te_conv_splitk_count(kind, B, K, M, H, W)
                                   for kind in CONV_KINDS for B in BATCHES for K in CHANNELS for M in CHANNELS for H, W in SIZES]}
+
+
+SPLIT_KINDS = (_lib.CONV_3X3W6, _lib.CONV_S2S6, _lib.CONV_T2S6, _lib.CONV_1X1S6)
+SPLIT_HOOKS = ((2, 0, 1, 1), (3, 3, 2, 2), (1, 0, 0, 0))          # te_conv_wino6_form, _tiles_per_block, te_conv_s2s6_form, te_conv_t2s6_form
+
+
+def _split_form(L):
+    """(rc, *form) of te_conv_split_form under the default hooks, the forced two-image forms with runs of three, and the ping-pong forms;
+    with style scales and scratch, and without; the form starts as -1 so that a refusal shows it untouched"""
+    n = len(_lib.CONV_SPLIT_FORM)
+    hooks = (L.te_conv_wino6_form, L.te_conv_wino6_tiles_per_block, L.te_conv_s2s6_form, L.te_conv_t2s6_form)
+    saved = [h(-1) for h in hooks]
+    out = []
+    try:
+        for values in SPLIT_HOOKS:
+            for h, v in zip(hooks, values):
+                h(v)
+            for kind in SPLIT_KINDS:
+                for B in BATCHES:
+                    for K in CHANNELS:
+                        for M in CHANNELS:
+                            for H, W in SIZES:
+                                for flag in (0, 1):
+                                    form = (C.c_int * n)(*([-1] * n))
+                                    out.append((L.te_conv_split_form(kind, B, K, M, H, W, flag, flag, form),) + tuple(form))
+    finally:
+        for h, v in zip(hooks, saved):
+            h(v)
+    return {'conv_split_form': out}
 
 
 def _pack(L):
@@ -144,7 +174,7 @@ REFUSAL_CODE_FREE = ('upfirdn2d_plan', 'blur_actgrad_plan', 'blur_gradact_plan')
 def table(L):
     """{name: int64 array, one row per grid point} of every planner answer of library L"""
     t = {}
-    for part in (_conv, _pack, _wgrad, _reduce, _fir):
+    for part in (_conv, _split_form, _pack, _wgrad, _reduce, _fir):
         t.update(part(L))
     return {k: np.asarray(v, dtype=np.int64) for k, v in t.items()}
 

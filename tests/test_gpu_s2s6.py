@@ -144,6 +144,7 @@ def test_split_bf16_strided_kernel_forms_are_bit_identical(B, K, M, H, W):
     try:
         for form in (0, 2):
             _lib.s2s6_form(form)
+            assert _lib.conv_split_form(_lib.CONV_S2S6, B, K, M, H, W, True)['two_image'] == int(form == 2 and M % 128 == 0)
             out[form] = (_lib.conv(x, u6, _lib.CONV_S2S6, M, H, W, isc, osc, bias, 3),
                          _lib.conv(x, u6, _lib.CONV_S2S6, M, H, W, None, None, bias, 4, res=res, mask_ref=mref, mask_gain=1.3),
                          _lib.conv(x, u6, _lib.CONV_S2S6, M, H, W))

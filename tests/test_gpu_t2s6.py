@@ -122,6 +122,8 @@ def test_last_row_and_column_kernel_with_and_without_the_column_scratch(B, K, M,
     bias = synth.normal((M,), 't6.eb').to(DEV)
     wp = _lib.conv_pack(w, _lib.PACK_T6FWD, 0.9)
     assert _lib.lib().te_conv_t2s6_ws_floats(B, K, H) == B * K * H
+    with_scratch, bare_form = (_lib.conv_split_form(_lib.CONV_T2S6, B, K, M, H, W, styled, scr) for scr in (True, False))
+    assert (with_scratch['scratch'], bare_form['scratch']) == (1, 0) and with_scratch['edge_ct'] == bare_form['edge_ct'] == (4 if H >= 64 and W >= 64 else 2)
     got = _lib.conv(x, wp, _lib.CONV_T2S6, M, H, W, isc, osc, bias, 3)
     bare = torch.empty_like(got)
     rc = _lib.lib().te_conv_res_f32(bare.data_ptr(), None, x.data_ptr(), wp.data_ptr(), isc.data_ptr() if styled else None, osc.data_ptr(),
@@ -154,6 +156,7 @@ def test_split_bf16_transposed_kernel_forms_are_bit_identical(B, K, M, H, W):
     try:
         for form in (0, 2):
             _lib.t2s6_form(form)
+            assert _lib.conv_split_form(_lib.CONV_T2S6, B, K, M, H, W, True)['two_image'] == int(form == 2 and M % 128 == 0)
             out[form] = (_lib.conv(x, u6, _lib.CONV_T2S6, M, H, W, isc, osc, bias, 3), _lib.conv(x, u6, _lib.CONV_T2S6, M, H, W, None, None, bias, 4),
                          _lib.conv(x, u6, _lib.CONV_T2S6, M, H, W))
     finally:

@@ -226,8 +226,10 @@ def test_split_bf16_weight_gradient_transposed_kind_wide_form_is_bit_identical(B
     old = _lib.wgrad_t2_wide(-1)
     try:
         _lib.wgrad_t2_wide(0)
+        assert _lib.wgrad6_form(_lib.CONV_T2, B, Co, Ci, H, W) == 't2narrow'
         narrow = _lib.wgrad_slabs(g, x, _lib.CONV_T2, H, W)
         _lib.wgrad_t2_wide(1)
+        assert _lib.wgrad6_form(_lib.CONV_T2, B, Co, Ci, H, W) == 't2wide'
         wide = _lib.wgrad_slabs(g, x, _lib.CONV_T2, H, W)
     finally:
         _lib.wgrad_t2_wide(old)

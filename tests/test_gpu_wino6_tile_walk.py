@@ -63,10 +63,13 @@ def test_tile_walk_is_bit_identical_to_the_ping_pong_kernel(B, K, M, H, W, style
     old_form, old_tpb = _lib.wino6_form(-1), _lib.wino6_tiles_per_block(-1)
     try:
         _lib.wino6_form(1)
+        assert _lib.conv_split_form(_lib.CONV_3X3W6, B, K, M, H, W, styled)['two_image'] == 0          # the ping-pong kernel
         want = three_epilogues(x, u6, M, isc, osc, bias, res, mref)
         _lib.wino6_form(3)
         for n in (2, 3, 0):
             _lib.wino6_tiles_per_block(n)
+            f = _lib.conv_split_form(_lib.CONV_3X3W6, B, K, M, H, W, styled)
+            assert f['two_image'] == 1 and (f['tpb'] == n or n == 0) and (f['lists'] > 0) == (f['tpb'] >= 2), f      # the two-image kernel on runs of n
             got = three_epilogues(x, u6, M, isc, osc, bias, res, mref)
             for k, (a, b) in enumerate(zip(want, got)):
                 assert torch.isfinite(b).all(), f'tiles_per_block {n}, epilogue {k}: outputs nobody wrote'
@@ -84,6 +87,8 @@ def test_tile_walk_vs_fp64():
     want = F.conv2d(x.double() * isc.double()[:, :, None, None], w.double(), padding=1)
     old_form, old_tpb = _lib.wino6_form(3), _lib.wino6_tiles_per_block(3)
     try:
+        f = _lib.conv_split_form(_lib.CONV_3X3W6, B, K, M, H, W, True)
+        assert (f['two_image'], f['tpb']) == (1, 3) and f['lists'] > 0
         got = conv_w6(x, _lib.conv_pack(w, _lib.PACK_W6FWD), M, isc)
     finally:
         _lib.wino6_form(old_form)

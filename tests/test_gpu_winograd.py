@@ -292,6 +292,8 @@ def test_split_bf16_winograd_non_finite_inputs_propagate_like_the_direct_kernel(
         xp[b, k, y, xx] = v
     old = _lib.wino6_form(form)
     try:
+        if form in (1, 3):
+            assert _lib.conv_split_form(_lib.CONV_3X3W6, B, K, M, H, W)['two_image'] == int(form == 3 and M % 128 == 0)
         got = _lib.conv(xp, _lib.conv_pack(w, _lib.PACK_W6FWD), _lib.CONV_3X3W6, M, H, W)
     finally:
         _lib.wino6_form(old)
@@ -325,6 +327,8 @@ def test_split_bf16_kernel_forms_are_bit_identical(B, K, M, H, W):
     try:
         for form in (1, 3):
             _lib.wino6_form(form)
+            f = _lib.conv_split_form(_lib.CONV_3X3W6, B, K, M, H, W, True)
+            assert f['two_image'] == int(form == 3 and M % 128 == 0 and W >= 32) and f['pair16'] == int(W == 16)
             out[form] = (_lib.conv(x, u6, _lib.CONV_3X3W6, M, H, W, isc, osc, bias, 3),
                          _lib.conv(x, u6, _lib.CONV_3X3W6, M, H, W, None, None, bias, 4, res=res, mask_ref=mref, mask_gain=1.3),
                          _lib.conv(x, u6, _lib.CONV_3X3W6, M, H, W))

@@ -383,6 +383,19 @@ def conv_form(kind, B, K, M, H, W, has_isc=False, epi='none', with_ws=True):
     return form
 
 
+CONV_SPLIT_FORM = ('two_image', 'pair16', 'mblocks', 'ntiles', 'blocks', 'idle', 'tpb', 'lists', 'lds', 'edge_ct', 'edge_line_tiles', 'edge_blocks',
+                   'scratch', 'isc')      # te_conv_split_form (te_hip.h)
+
+
+def conv_split_form(kind, B, K, M, H, W, has_isc=False, with_scratch=True):
+    """the plan of the conv() launch of a split-bf16 kind (CONV_3X3W6, CONV_S2S6, CONV_T2S6, CONV_1X1S6) under the current form hooks
+    (host only): a dict of CONV_SPLIT_FORM; the negative TE_ERR_* code where the launch refuses.  conv() always hands CONV_T2S6 its
+    column scratch: with_scratch=True is what it launches."""
+    buf = (C.c_int * len(CONV_SPLIT_FORM))()
+    rc = lib().te_conv_split_form(kind, B, K, M, H, W, int(has_isc), int(with_scratch), buf)
+    return rc if rc else dict(zip(CONV_SPLIT_FORM, buf))
+
+
 @_op
 def conv(x, wp, kind, M, H, W, isc=None, osc=None, bias=None, act=0, res=None, mask_ref=None, mask_gain=1.0, split=True):
     """H, W = LOW-resolution size (see te_hip.h).  x [B,K,Hin,Win].  split=False: no split-K workspace is handed over (what

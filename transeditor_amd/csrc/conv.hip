@@ -1262,6 +1262,29 @@ extern "C" int te_conv_form(int kind, int B, int K, int M, int H, int W, int has
     return 0;
 }
 
+// what te_conv_res_f32 would launch for the four split-bf16 kinds (host only): the planning half of the kind's launch, written out
+extern "C" int te_conv_split_form(int kind, int B, int K, int M, int H, int W, int has_isc, int with_scratch, int* form) {
+    if (!form) return TE_ERR_NULL;
+    if (B <= 0 || K <= 0 || M <= 0 || H <= 0 || W <= 0 || kind < 0 || kind >= TE_CONV_KINDS) return TE_ERR_SHAPE;
+    Split6Form f;
+    int rc;
+    switch (kind) {
+        case TE_CONV_3X3W6: rc = te_wino6_split_form(B, K, M, H, W, f); break;
+        case TE_CONV_S2S6: rc = te_s2s6_split_form(B, K, M, H, W, f); break;
+        case TE_CONV_T2S6: rc = te_t2s6_split_form(B, K, M, H, W, with_scratch, f); break;
+        case TE_CONV_1X1S6:
+            TE_REQUIRE(!has_isc, TE_ERR_UNSUPPORTED, "te_conv_f32(TE_CONV_1X1S6): plain product + residual only (no scales, bias, activation or mask)");
+            rc = te_p1s6_split_form(B, K, M, H, W, f);
+            break;
+        default: return TE_ERR_UNSUPPORTED;
+    }
+    if (rc) return rc;
+    const int v[TE_CONV_SPLIT_FORM_INTS] = {f.two_image, f.pair16, f.mblocks, f.ntiles, f.blocks, f.idle, f.tpb, f.lists, f.lds,
+                                            f.edge_ct, f.edge_line_tiles, f.edge_blocks, f.scratch, kind == TE_CONV_1X1S6 ? 0 : (has_isc != 0)};
+    std::copy(v, v + TE_CONV_SPLIT_FORM_INTS, form);
+    return 0;
+}
+
 extern "C" int te_conv_res_f32(float* out, float* ws, const float* in, const float* wp, const float* isc, const float* osc,
                                const float* bias, const float* res, const float* mask_ref, float mask_gain, int act, int kind,
                                int B, int K, int M, int H, int W, te_stream_t stream_) {

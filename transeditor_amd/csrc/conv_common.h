@@ -44,3 +44,21 @@ int te_t2s6_edge_launch(float* out, const float* in, const float* wplain, const 
 // csrc/p1s6.hip (round 6): the 1x1 convolution on the bf16 matrix pipe (three-piece split: fp32-equivalent), plain product + optional
 // residual; kind TE_CONV_1X1S6, weights packed TE_PACK_P6FWD / TE_PACK_P6DGRAD in MFMA fragment order
 int te_p1s6_launch(float* out, const float* in, const float* U, const float* res, int B, int K, int M, int H, int W, hipStream_t s);
+
+// The plan of a launch of one of the four kinds above, as te_conv_split_form (te_hip.h) writes it out.  Each file's launch fills it in its
+// planning half - every decision that does not touch the device - and then dispatches on it and on nothing else; te_*_split_form runs
+// the same planning half and launches nothing.  Zeros where a field does not apply to the kind.
+struct Split6Form {
+    int two_image;                                  // the two-image kernel (a block owns 128 output channels), else the ping-pong kernel
+    int pair16;                                     // wino6: two 16-column samples side by side in a tile row
+    int mblocks, ntiles, blocks;                    // M blocks per tile, tiles, grid x
+    int idle;                                       // blocks of the grid that get no tile (an empty run)
+    int tpb, lists;                                 // wino6 two-image: tiles per run that the launch asked for (1: a tile per block), runs per XCD (0: a tile per block)
+    int lds;                                        // dynamic LDS bytes
+    int edge_ct, edge_line_tiles, edge_blocks;      // T2S6: t2_edge_kernel's CT (2 or 4), its line tiles per (sample, M tile), its grid x
+    int scratch;                                    // T2S6: the column scratch hands the last input column from the body to the edge kernel
+};
+int te_wino6_split_form(int B, int K, int M, int H, int W, Split6Form& f);
+int te_s2s6_split_form(int B, int K, int M, int H, int W, Split6Form& f);
+int te_t2s6_split_form(int B, int K, int M, int H, int W, int with_scratch, Split6Form& f);
+int te_p1s6_split_form(int B, int K, int M, int H, int W, Split6Form& f);

@@ -208,19 +208,36 @@ extern "C" int te_conv_p1s6_supported(int B, int K, int M, int H, int W) {
     return ((int64_t)K * hw * 4 < 0x7FFFFFFF && blocks < 0x7FFFFFF0 && blocks >= te::kNumCU / 2) ? 1 : 0;
 }
 
-int te_p1s6_launch(float* out, const float* in, const float* U, const float* res, int B, int K, int M, int H, int W, hipStream_t s) {
+// The planning half of te_p1s6_launch (everything that does not touch the device): the geometry of `a` and the plan `f`, on which the
+// launch dispatches and which te_p1s6_split_form reports.  The kind has one kernel, the two-image form.
+static int p1s6_plan(P1Args& a, Split6Form& f, int B, int K, int M, int H, int W) {
     TE_REQUIRE(te_conv_p1s6_supported(B, K, M, H, W), TE_ERR_UNSUPPORTED,
                "te_conv_f32(TE_CONV_1X1S6): needs K %% 64 == 0, M %% 128 == 0, H W %% 256 == 0 (te_conv_p1s6_supported)");
-    TE_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(res) |
-                 reinterpret_cast<uintptr_t>(in)) & 15) == 0, TE_ERR_UNSUPPORTED, "te_conv_f32(TE_CONV_1X1S6): 16-byte aligned tensors required");
-    P1Args a{};
-    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.res = res;
     a.B = B; a.K = K; a.M = M; a.HW = H * W;
     a.tiles_per_sample = a.HW / TPX; a.mblocks = M / (2 * BM);
     a.ntiles = B * a.tiles_per_sample;
     a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.ntiles, 8) : 0;
-    const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
-    const size_t lds = 2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)T_CHUNKS * 16;
-    split6_launch<p1s6_kernel>(dim3((unsigned)blocks), WT, lds, s, a);
+    f = Split6Form{};
+    f.two_image = 1;
+    f.mblocks = a.mblocks; f.ntiles = a.ntiles; f.blocks = (int)(te::cdiv(a.ntiles, 8) * 8 * a.mblocks);
+    f.idle = (int)split6_idle_blocks(a.ntiles, a.nt8, a.mblocks, 0);
+    f.lds = (int)(2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)T_CHUNKS * 16);
+    return 0;
+}
+
+int te_p1s6_split_form(int B, int K, int M, int H, int W, Split6Form& f) {
+    P1Args a{};
+    return p1s6_plan(a, f, B, K, M, H, W);
+}
+
+int te_p1s6_launch(float* out, const float* in, const float* U, const float* res, int B, int K, int M, int H, int W, hipStream_t s) {
+    P1Args a{};
+    Split6Form f;
+    const int rc = p1s6_plan(a, f, B, K, M, H, W);
+    if (rc) return rc;
+    TE_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(res) |
+                 reinterpret_cast<uintptr_t>(in)) & 15) == 0, TE_ERR_UNSUPPORTED, "te_conv_f32(TE_CONV_1X1S6): 16-byte aligned tensors required");
+    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.res = res;
+    split6_launch<p1s6_kernel>(dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
     return te::launch_status("te_conv_f32(TE_CONV_1X1S6)");
 }

@@ -418,28 +418,46 @@ extern "C" int te_conv_s2s6_form(int form) {
     return old;
 }
 
-int te_s2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, const float* res,
-                   const float* mask_ref, float mask_gain, int act, int B, int K, int M, int H, int W, hipStream_t s) {
+// The planning half of te_s2s6_launch (everything that does not touch the device): the geometry of `a` and the plan `f`, on which the
+// launch dispatches and which te_s2s6_split_form reports
+static int s2s6_plan(S2Args& a, Split6Form& f, int B, int K, int M, int H, int W) {
     TE_REQUIRE(te_conv_s2s6_supported(B, K, M, H, W), TE_ERR_UNSUPPORTED,
                "te_conv_f32(TE_CONV_S2S6): needs K %% 16 == 0 (>= 32), M %% 64 == 0, H %% 8 == 0, W %% 16 == 0 (te_conv_s2s6_supported)");
-    TE_REQUIRE((reinterpret_cast<uintptr_t>(U) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0, TE_ERR_UNSUPPORTED,
-               "te_conv_f32(TE_CONV_S2S6): 16-byte aligned packed weights required");
-    S2Args a{};
-    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.isc = isc; a.osc = osc; a.bias = bias; a.res = res;
-    a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
     a.B = B; a.K = K; a.M = M; a.H = H; a.W = W; a.Hi = 2 * H + 1; a.Wi = 2 * W + 1;
     a.tiles_x = W / TWO; a.tiles_y = H / TH; a.mblocks = M / BM;
     a.ntiles = B * a.tiles_x * a.tiles_y;
     a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.ntiles, 8) : 0;
-    const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
-    const size_t lds = (size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4;
+    int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
     const int form = g_s2_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
+    f = Split6Form{};
     if (split6_two_image(form, M, blocks_q)) {
+        f.two_image = 1;
         a.mblocks = M / (2 * BM);
-        SPLIT6_LAUNCH_ISC(s2s6q_kernel, isc, dim3((unsigned)blocks_q), WT, lds, s, a);
-    } else {
-        SPLIT6_LAUNCH_ISC(s2s6_kernel, isc, dim3((unsigned)blocks), WT, lds, s, a);
+        blocks = blocks_q;
     }
+    f.mblocks = a.mblocks; f.ntiles = a.ntiles; f.blocks = (int)blocks;
+    f.idle = (int)split6_idle_blocks(a.ntiles, a.nt8, a.mblocks, 0);
+    f.lds = (int)((size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4);
+    return 0;
+}
+
+int te_s2s6_split_form(int B, int K, int M, int H, int W, Split6Form& f) {
+    S2Args a{};
+    return s2s6_plan(a, f, B, K, M, H, W);
+}
+
+int te_s2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, const float* res,
+                   const float* mask_ref, float mask_gain, int act, int B, int K, int M, int H, int W, hipStream_t s) {
+    S2Args a{};
+    Split6Form f;
+    const int rc = s2s6_plan(a, f, B, K, M, H, W);
+    if (rc) return rc;
+    TE_REQUIRE((reinterpret_cast<uintptr_t>(U) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0, TE_ERR_UNSUPPORTED,
+               "te_conv_f32(TE_CONV_S2S6): 16-byte aligned packed weights required");
+    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.isc = isc; a.osc = osc; a.bias = bias; a.res = res;
+    a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
+    if (f.two_image) SPLIT6_LAUNCH_ISC(s2s6q_kernel, isc, dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
+    else SPLIT6_LAUNCH_ISC(s2s6_kernel, isc, dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
     return te::launch_status("te_conv_f32(TE_CONV_S2S6)");
 }

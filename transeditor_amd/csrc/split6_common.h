@@ -127,6 +127,19 @@ __device__ __forceinline__ bool split6_tile_list(int ntiles, int nt8, int mblock
 // wherever M % 128 == 0 (tests)
 inline bool split6_two_image(int form_sel, int M, int64_t blocks_q) { return form_sel >= 1 && M % 128 == 0 && (form_sel == 2 || blocks_q >= te::kNumCU); }
 
+// ---- host: the blocks that split6_tile (lists == 0: a grid of 8 ceil(ntiles / 8) mblocks) or split6_tile_list (8 lists mblocks) leaves
+// without a tile, by the same arithmetic: an XCD with nb tiles fills min(nb, slots) of its slots
+inline int64_t split6_idle_blocks(int ntiles, int nt8, int mblocks, int lists) {
+    const int64_t slots = lists ? lists : te::cdiv(ntiles, 8);
+    int64_t idle = 0;
+    for (int xcd = 0; xcd < 8; ++xcd) {
+        const int first = nt8 ? (int)(((int64_t)xcd * ntiles) >> 3) : xcd;
+        const int nb = nt8 ? (int)(((int64_t)(xcd + 1) * ntiles) >> 3) - first : (ntiles - xcd + 7) >> 3;
+        idle += slots - std::min<int64_t>(nb, slots);
+    }
+    return idle * mblocks;
+}
+
 // ---- host: one launch of a kernel that needs more than 64 KB of dynamic LDS.  hipFuncSetAttribute is done once per (kernel, device):
 // one flag per instantiation of this template, i.e. per kernel.
 template <auto KERNEL, class Args>

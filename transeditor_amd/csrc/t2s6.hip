@@ -665,30 +665,65 @@ extern "C" int te_conv_t2s6_form(int form) {
     return old;
 }
 
-// the body cells [0, H) x [0, W) of the transposed convolution (output rows 0 .. 2H - 1, columns 0 .. 2W - 1); conv.hip adds the last
-// output row and column with te_t2s6_edge_launch (below)
-int te_t2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, int act,
-                   int B, int K, int M, int H, int W, hipStream_t s, float* colbuf) {
+// The planning half of the kind's two launches (everything that does not touch the device): the geometry of the body kernel's `a` and of
+// the edge kernel's `e`, and the plan `f`, on which both launches dispatch and which te_t2s6_split_form reports.
+static int t2s6_plan(T2Args& a, T2EdgeArgs& e, Split6Form& f, int B, int K, int M, int H, int W, bool with_scratch) {
     TE_REQUIRE(te_conv_t2s6_supported(B, K, M, H, W), TE_ERR_UNSUPPORTED,
                "te_conv_f32(TE_CONV_T2S6): needs K %% 16 == 0 (>= 32), M %% 64 == 0, H %% 8 == 0, W %% 16 == 0 (te_conv_t2s6_supported)");
-    TE_REQUIRE((reinterpret_cast<uintptr_t>(U) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0, TE_ERR_UNSUPPORTED,
-               "te_conv_f32(TE_CONV_T2S6): 16-byte aligned packed weights required");
-    T2Args a{};
-    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.isc = isc; a.osc = osc; a.bias = bias; a.act = act; a.colbuf = colbuf;
     a.B = B; a.K = K; a.M = M; a.H = H; a.W = W; a.Ho = 2 * H + 1; a.Wo = 2 * W + 1;
     a.tiles_x = W / TWC; a.tiles_y = H / TH; a.mblocks = M / BM;
     a.ntiles = B * a.tiles_x * a.tiles_y;
     a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.ntiles, 8) : 0;
-    const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
-    const size_t lds = 2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4;
+    int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
     const int form = g_t2_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
+    f = Split6Form{};
     if (split6_two_image(form, M, blocks_q)) {
+        f.two_image = 1;
         a.mblocks = M / (2 * BM);
-        SPLIT6_LAUNCH_ISC(t2s6q_kernel, isc, dim3((unsigned)blocks_q), WT, lds, s, a);
-    } else {
-        SPLIT6_LAUNCH_ISC(t2s6_kernel, isc, dim3((unsigned)blocks), WT, lds, s, a);
+        blocks = blocks_q;
     }
+    f.mblocks = a.mblocks; f.ntiles = a.ntiles; f.blocks = (int)blocks;
+    f.idle = (int)split6_idle_blocks(a.ntiles, a.nt8, a.mblocks, 0);
+    f.lds = (int)(2 * (size_t)U_SLOTS * 1024 + 2 * (size_t)TP_DWORDS * 4);
+    f.scratch = with_scratch;
+    // the last output row and column (t2_edge_kernel)
+    e.B = B; e.K = K; e.M = M; e.H = H; e.W = W; e.Ho = 2 * H + 1; e.Wo = 2 * W + 1;
+    const bool wide = W >= 64 && H >= 64;      // (32-cell tiles for every shape measured the same: 43.5 us against 42.2 us per launch on average)
+    const int EC = wide ? 64 : 32;
+    e.row_tiles = (int)te::cdiv(W, EC);                       // cells 0 .. W - 1 of the last output row
+    e.line_tiles = e.row_tiles + (int)te::cdiv(H + 1, EC);    // + cells 0 .. H of the last output column
+    e.mtiles = M / EM;
+    const int64_t eblocks = (int64_t)e.line_tiles * e.mtiles * B;
+    TE_REQUIRE(eblocks < 0x7FFFFFF0, TE_ERR_UNSUPPORTED, "te_conv_f32(TE_CONV_T2S6): too many edge blocks");
+    f.edge_ct = wide ? 4 : 2; f.edge_line_tiles = e.line_tiles; f.edge_blocks = (int)eblocks;
+    return 0;
+}
+
+int te_t2s6_split_form(int B, int K, int M, int H, int W, int with_scratch, Split6Form& f) {
+    T2Args a{};
+    T2EdgeArgs e{};
+    Split6Form g;
+    const int rc = t2s6_plan(a, e, g, B, K, M, H, W, with_scratch != 0);
+    if (rc) return rc;
+    f = g;
+    return 0;
+}
+
+// the body cells [0, H) x [0, W) of the transposed convolution (output rows 0 .. 2H - 1, columns 0 .. 2W - 1); conv.hip adds the last
+// output row and column with te_t2s6_edge_launch (below)
+int te_t2s6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, int act,
+                   int B, int K, int M, int H, int W, hipStream_t s, float* colbuf) {
+    T2Args a{};
+    T2EdgeArgs e{};
+    Split6Form f;
+    const int rc = t2s6_plan(a, e, f, B, K, M, H, W, colbuf != nullptr);
+    if (rc) return rc;
+    TE_REQUIRE((reinterpret_cast<uintptr_t>(U) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0, TE_ERR_UNSUPPORTED,
+               "te_conv_f32(TE_CONV_T2S6): 16-byte aligned packed weights required");
+    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.isc = isc; a.osc = osc; a.bias = bias; a.act = act; a.colbuf = colbuf;
+    if (f.two_image) SPLIT6_LAUNCH_ISC(t2s6q_kernel, isc, dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
+    else SPLIT6_LAUNCH_ISC(t2s6_kernel, isc, dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
     return te::launch_status("te_conv_f32(TE_CONV_T2S6)");
 }
 
@@ -697,22 +732,19 @@ int te_t2s6_edge_launch(float* out, const float* in, const float* wplain, const 
                         int B, int K, int M, int H, int W, int Kp, int Mp, hipStream_t s, const float* colbuf) {
     TE_REQUIRE(K % 16 == 0 && M % EM == 0 && (reinterpret_cast<uintptr_t>(wplain) & 15) == 0 && Mp % 4 == 0, TE_ERR_UNSUPPORTED,
                "te_conv_f32(TE_CONV_T2S6): the edge kernel needs K %% 16 == 0, M %% 64 == 0 and 16-byte aligned weights");
+    T2Args body{};
     T2EdgeArgs a{};
+    Split6Form f;
+    const int rc = t2s6_plan(body, a, f, B, K, M, H, W, colbuf != nullptr);
+    if (rc) return rc;
     a.out = out; a.in = in; a.wp = wplain; a.isc = isc; a.osc = osc; a.bias = bias; a.act = act; a.colbuf = colbuf;
-    a.B = B; a.K = K; a.M = M; a.H = H; a.W = W; a.Kp = Kp; a.Mp = Mp; a.Ho = 2 * H + 1; a.Wo = 2 * W + 1;
-    const bool wide = W >= 64 && H >= 64;      // (32-cell tiles for every shape measured the same: 43.5 us against 42.2 us per launch on average)
-    const int EC = wide ? 64 : 32;
-    a.row_tiles = (int)te::cdiv(W, EC);                       // cells 0 .. W - 1 of the last output row
-    a.line_tiles = a.row_tiles + (int)te::cdiv(H + 1, EC);    // + cells 0 .. H of the last output column
-    a.mtiles = M / EM;
-    const int64_t blocks = (int64_t)a.line_tiles * a.mtiles * B;
-    TE_REQUIRE(blocks < 0x7FFFFFF0, TE_ERR_UNSUPPORTED, "te_conv_f32(TE_CONV_T2S6): too many edge blocks");
-    if (wide) {
-        if (isc) t2_edge_kernel<true, 4><<<dim3((unsigned)blocks), ET, 0, s>>>(a);
-        else t2_edge_kernel<false, 4><<<dim3((unsigned)blocks), ET, 0, s>>>(a);
+    a.Kp = Kp; a.Mp = Mp;
+    if (f.edge_ct == 4) {
+        if (isc) t2_edge_kernel<true, 4><<<dim3((unsigned)f.edge_blocks), ET, 0, s>>>(a);
+        else t2_edge_kernel<false, 4><<<dim3((unsigned)f.edge_blocks), ET, 0, s>>>(a);
     } else {
-        if (isc) t2_edge_kernel<true, 2><<<dim3((unsigned)blocks), ET, 0, s>>>(a);
-        else t2_edge_kernel<false, 2><<<dim3((unsigned)blocks), ET, 0, s>>>(a);
+        if (isc) t2_edge_kernel<true, 2><<<dim3((unsigned)f.edge_blocks), ET, 0, s>>>(a);
+        else t2_edge_kernel<false, 2><<<dim3((unsigned)f.edge_blocks), ET, 0, s>>>(a);
     }
     return te::launch_status("te_conv_f32(TE_CONV_T2S6) edge");
 }

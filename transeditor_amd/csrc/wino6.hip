@@ -788,37 +788,55 @@ extern "C" int te_conv_wino6_supported(int B, int K, int M, int H, int W) {
     return ((int64_t)K * H * W * 4 * (wide ? 1 : 2) < 0x7FFFFFFF && tiles * (M / BM) < 0x7FFFFFF0) ? 1 : 0;
 }
 
-int te_wino6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, const float* res,
-                    const float* mask_ref, float mask_gain, int act, int B, int K, int M, int H, int W, hipStream_t s) {
+// The planning half of te_wino6_launch: everything of the launch that does not touch the device.  Fills the geometry of `a` and the plan `f`;
+// the launch dispatches on `f` and on nothing else, te_wino6_split_form reports it.
+static int wino6_plan(Wino6Args& a, Split6Form& f, int B, int K, int M, int H, int W) {
     TE_REQUIRE(te_conv_wino6_supported(B, K, M, H, W), TE_ERR_UNSUPPORTED,
                "te_conv_f32(TE_CONV_3X3W6): needs K %% 32 == 0, M %% 64 == 0, W %% 32 == 0 (or W == 16 and an even batch), H %% 8 == 0 (te_conv_wino6_supported)");
-    TE_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(res) |
-                 reinterpret_cast<uintptr_t>(mask_ref)) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0, TE_ERR_UNSUPPORTED,
-               "te_conv_f32(TE_CONV_3X3W6): 16-byte aligned tensors required");
-    Wino6Args a{};
-    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.isc = isc; a.osc = osc; a.bias = bias; a.res = res;
-    a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
     a.B = B; a.K = K; a.M = M; a.H = H; a.W = W;
     a.lgpw = W >= TW ? 4 : 3;
     a.tiles_x = W >= TW ? W / TW : 1; a.tiles_y = H / TH; a.mblocks = M / BM;
     a.ntiles = (W >= TW ? B : B / 2) * a.tiles_x * a.tiles_y;
     a.nt8 = te::xcd_banded() ? (int)te::cdiv(a.ntiles, 8) : 0;
-    const int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
+    int64_t blocks = te::cdiv(a.ntiles, 8) * 8 * a.mblocks;
     const int form = g_w6_form.load(std::memory_order_relaxed);
     const int64_t blocks_q = te::cdiv(a.ntiles, 8) * 8 * (M / (2 * BM));
+    f = Split6Form{};
+    f.pair16 = W < TW;
     if (W >= TW && split6_two_image(form - 1, M, blocks_q)) {     // (forms 2 / 3 of te_conv_wino6_form; W == 16: the ping-pong kernel only)
+        f.two_image = 1;
         a.mblocks = M / (2 * BM);
         // the tile walk: a block takes a run of consecutive tiles of its XCD and carries the pipeline across them (wino6q_kernel).
         const int nt8c = (int)te::cdiv(a.ntiles, 8);                   // tiles of the fullest XCD
         int tpb = g_w6_tpb.load(std::memory_order_relaxed);
         if (tpb == 0) tpb = w6_auto_tpb(nt8c, a.mblocks);
         a.lists = tpb >= 2 ? (int)te::cdiv(nt8c, tpb) : 0;
-        const int64_t blocks2 = a.lists ? (int64_t)8 * a.lists * a.mblocks : blocks_q;
-        const size_t lds = (size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4;
-        SPLIT6_LAUNCH_ISC(wino6q_kernel, isc, dim3((unsigned)blocks2), WT, lds, s, a);
-    } else {
-        const size_t lds = (size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4;
-        SPLIT6_LAUNCH_ISC(wino6p_kernel, isc, dim3((unsigned)blocks), WT, lds, s, a);
+        blocks = a.lists ? (int64_t)8 * a.lists * a.mblocks : blocks_q;
+        f.tpb = tpb; f.lists = a.lists;
     }
+    f.mblocks = a.mblocks; f.ntiles = a.ntiles; f.blocks = (int)blocks;
+    f.idle = (int)split6_idle_blocks(a.ntiles, a.nt8, a.mblocks, a.lists);
+    f.lds = (int)((size_t)U_CHUNKS * 16 + 2 * (size_t)TP_DWORDS * 4);
+    return 0;
+}
+
+int te_wino6_split_form(int B, int K, int M, int H, int W, Split6Form& f) {
+    Wino6Args a{};
+    return wino6_plan(a, f, B, K, M, H, W);
+}
+
+int te_wino6_launch(float* out, const float* in, const float* U, const float* isc, const float* osc, const float* bias, const float* res,
+                    const float* mask_ref, float mask_gain, int act, int B, int K, int M, int H, int W, hipStream_t s) {
+    Wino6Args a{};
+    Split6Form f;
+    const int rc = wino6_plan(a, f, B, K, M, H, W);
+    if (rc) return rc;
+    TE_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(res) |
+                 reinterpret_cast<uintptr_t>(mask_ref)) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0, TE_ERR_UNSUPPORTED,
+               "te_conv_f32(TE_CONV_3X3W6): 16-byte aligned tensors required");
+    a.out = out; a.in = in; a.U = reinterpret_cast<const u32x4*>(U); a.isc = isc; a.osc = osc; a.bias = bias; a.res = res;
+    a.mref = mask_ref; a.mgain = mask_gain; a.act = act;
+    if (f.two_image) SPLIT6_LAUNCH_ISC(wino6q_kernel, isc, dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
+    else SPLIT6_LAUNCH_ISC(wino6p_kernel, isc, dim3((unsigned)f.blocks), WT, (size_t)f.lds, s, a);
     return te::launch_status("te_conv_f32(TE_CONV_3X3W6)");
 }
