@@ -475,6 +475,20 @@ int te_blur_actgrad_plan(int64_t major, int in_h, int in_w, int kh, int kw, int 
                          int* zgroups, int* tiles);
 int te_blur_gradact_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                          int* zgroups, int* tiles);
+/* The plan of a FIR launch (host only, nothing is launched: the answer is the plan that the launch itself makes and then dispatches
+ * on; te_upfirdn2d_plan, te_blur_actgrad_plan, te_blur_gradact_plan and te_blur_actgrad_tiles are views of the same plan).
+ * op 0: te_upfirdn2d_f32, 1: te_blur_actgrad_f32, 2: te_blur_gradact_f32; the two blur ops ignore minor, up and down.
+ * form[TE_FIR_FORM_INTS]: [0] the kernel (TE_FIR_*: fir_direct_kernel, blur44_kernel<MODE, D, EXT>, fir_tile_kernel<2,1,4,4>,
+ * <1,2,4,4>, <1,1,4,4,AG>)  [1] [2] [3] MODE, D, EXT of blur44_kernel (0 for the other kernels)  [4] [5] ext_x, ext_y: the last tile
+ * column / row also filters one more output column / row (the +1 rule)  [6] [7] rows and columns of an output tile (32 x 64 blur44,
+ * 16 x 64 fir_tile, 0 x 0 direct)  [8] [9] tiles_x, tiles_y per plane  [10] zgroups (plane groups: the block of group pg filters the
+ * planes pg, pg + zgroups, ... < major)  [11] grid x  [12] threads per block.  [4] ... [10] are 0 where the direct kernel runs.
+ * Refuses what the launch refuses, with the launch's code (the epilogue arguments of te_upfirdn2d_f32 are not part of the plan), and a
+ * launch of no planes (major == 0) with TE_ERR_SHAPE; a refusal leaves form untouched. */
+enum { TE_FIR_DIRECT = 0, TE_FIR_BLUR44 = 1, TE_FIR_TILE_UP2 = 2, TE_FIR_TILE_DOWN2 = 3, TE_FIR_TILE_AG = 4 };
+#define TE_FIR_FORM_INTS 13
+int te_fir_form(int op, int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                int pad_x0, int pad_x1, int pad_y0, int pad_y1, int* form);
 int64_t te_upfirdn2d_direct_cover(int64_t outputs);
 int64_t te_chan_scale_cover(int64_t rows, int64_t hw, int aligned16);
 int64_t te_bias_act_f32_cover(int64_t size_x, int64_t step_b, int aligned16, int* vec);

@@ -1,7 +1,7 @@
 """Host-plan table: every answer of the library's host-only launch planners over one fixed grid of arguments.
 
 The planners (te_*_plan, te_*_count, te_*_cover, te_conv_packed_numel, te_*_tiles, te_wgrad_pair_form, te_wgrad6_form, te_wgrad_form,
-te_conv_split_form in include/te_hip.h) launch nothing and need no GPU.  Their answers fix the summation partition of the split launches (so every result
+te_conv_split_form, te_fir_form in include/te_hip.h) launch nothing and need no GPU.  Their answers fix the summation partition of the split launches (so every result
 bit) and are what the loop-trip and route tests assert their coverage with, yet a planner that drifts from its launch fails no other
 test.  table(lib) calls each of them over the grid below and returns {name: int array}; return codes are part of the table.
 
@@ -10,7 +10,8 @@ test.  table(lib) calls each of them over the grid below and returns {name: int 
 tests/golden/host_plans.npz is the table of the library before the planners were derived from the launch code's own geometry;
 tests/test_host_plans_cpu.py asserts that the current library still gives it.  A planner that is added later is recorded next to its
 relatives from the library that introduces it, with every older answer unchanged (wgrad_form: the plan of the fp32 weight-gradient launch;
-conv_split_form: the plan of the split-bf16 forward launches under three settings of their form hooks).
+conv_split_form: the plan of the split-bf16 forward launches under three settings of their form hooks; fir_form: the plan of the three
+FIR launches, the upfirdn2d grid under op 0 and the blur grid under ops 1 and 2).
 """
 import ctypes as C
 import itertools
@@ -158,9 +159,18 @@ def blur_grid():
     return [(m, h, w, kh, kw, *pads) for m, h, w in FIR_SHAPES + BLUR_BAD for kh, kw in BLUR_TAPS for pads in BLUR_PADS]
 
 
+def _fir_form(L, op, *args):
+    """(rc, *form) of te_fir_form; the form starts as -1 so that a refusal shows it untouched"""
+    n = len(_lib.FIR_FORM)
+    form = (C.c_int * n)(*([-1] * n))
+    return (L.te_fir_form(op, *args, form),) + tuple(form)
+
+
 def _fir(L):
     blur = blur_grid()
-    return {'upfirdn2d_plan': [_two(L.te_upfirdn2d_plan, *g) for g in fir_grid()],
+    return {'fir_form': [_fir_form(L, 0, *g) for g in fir_grid()] +
+                        [_fir_form(L, op, m, h, w, 1, kh, kw, 1, 1, 1, 1, *pads) for op in (1, 2) for m, h, w, kh, kw, *pads in blur],
+            'upfirdn2d_plan': [_two(L.te_upfirdn2d_plan, *g) for g in fir_grid()],
             'blur_actgrad_plan': [_two(L.te_blur_actgrad_plan, *g) for g in blur],
             'blur_gradact_plan': [_two(L.te_blur_gradact_plan, *g) for g in blur],
             'blur_actgrad_tiles': [L.te_blur_actgrad_tiles(*g[1:]) for g in blur],

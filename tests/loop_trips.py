@@ -7,8 +7,8 @@ stride over the rest.  In the other unit tests every one of these loops runs onc
 
 An entry names the op, its shape and arguments, the loop it targets and the trips it expects as (fewest, most) over the blocks
 (threads) of the launch.  The expected trips are data; what a launch really does comes from the library's host-side queries
-(te_*_plan / te_*_cover in include/te_hip.h, each of which calls the grid function of the launch), never from constants restated
-here.  tests/test_loop_trips_cpu.py checks the table against the queries without a GPU, tests/test_gpu_loop_trips.py runs every
+(te_*_plan / te_*_cover / te_fir_form in include/te_hip.h, each of which calls the grid function of the launch), never from constants
+restated here; a plane-walk entry's `loop` is asserted against the instantiation that te_fir_form plans.  tests/test_loop_trips_cpu.py checks the table against the queries without a GPU, tests/test_gpu_loop_trips.py runs every
 entry against fp64 after re-asserting its trips.
 """
 import ctypes as C
@@ -113,6 +113,20 @@ def fir_plan(entry):
     up, down = a.get('up', 1), a.get('down', 1)
     p0, p1 = a['pad']
     return (B * Cn,) + _plan(L.te_upfirdn2d_plan, B * Cn, H, W, 1, len(taps), len(taps), up, up, down, down, p0, p1, p0, p1)
+
+
+def fir_loop(entry):
+    """the kernel instantiation that te_fir_form plans for a plane-walk entry, as csrc/upfirdn2d.hip spells it"""
+    from fir_forms import loop_name
+    B, Cn, H, W = entry.shape
+    a = entry.args
+    if entry.op in ('blur_actgrad', 'blur_gradact'):
+        f = _lib.fir_form(entry.op, B * Cn, H, W, a['gpad'])
+    else:
+        up, down, k = a.get('up', 1), a.get('down', 1), len(a.get('taps', BLUR))
+        f = _lib.fir_form('upfirdn2d', B * Cn, H, W, a['pad'] * 2, k, k, (up, up), (down, down))
+    assert not isinstance(f, int), f'{entry.name}: te_fir_form refuses ({f})'
+    return loop_name(f)
 
 
 def walk_trips(planes, zgroups):
@@ -222,7 +236,8 @@ def check(entry):
     """raise AssertionError naming the entry when its loop does not make the declared trips"""
     got = actual(entry)
     assert got == entry.trips, f'{entry.name} {entry.op} {entry.shape} {entry.args}: expected trips {entry.trips} of {entry.loop}, the library plans {got}'
-    if entry in PLANE_WALKS:      # a last trip that some blocks have and others do not
+    if entry in PLANE_WALKS:      # the instantiation the entry names; a last trip that some blocks have and others do not
+        assert fir_loop(entry) == entry.loop, f'{entry.name}: expected {entry.loop}, the library plans {fir_loop(entry)}'
         assert got[1] == got[0] + 1 and got[0] >= 2, f'{entry.name}: trips {got}'
         assert fir_plan(entry)[0] % 8 != 0, f'{entry.name}: plane count is a multiple of 8'
     else:

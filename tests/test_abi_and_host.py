@@ -64,6 +64,7 @@ def test_bindings_pinned_by_hand():
         'te_conv_form': (I, [I, I, I, I, I, I, I, I, I, P]),
         'te_small_gemm_form': (I, [I, I, I, I, L, L, L, L, L, L, P, I, I, I, P]),
         'te_wgrad_form': (I, [I, I, I, I, I, I, I, I, I, I, P]),
+        'te_fir_form': (I, [I, L, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
         'te_lpips_allpairs_dist_f32': (I, [P, P, P, P, I, I, P]),
         'te_conv2d_prelu_f32': (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
         'te_fid_moments_f64': (I, [P, P, P, P, L, I, I, P]),
@@ -387,7 +388,7 @@ def test_roctx_ranges_behind_env_switch():
     assert not [f.__name__ for f in _lib._OPS if hasattr(f, '__wrapped__') or getattr(_lib, f.__name__) is not f]
     # the host-only predicates and hooks carry no range
     assert not {'wino_ok', 'wino6_form', 'wgrad_split', 'rgb_supported', 'bias_act_bwd_rgb_supported', 'fid_moments_ws_bytes',
-                'fc_stream_splits', 'wgrad6_form', 'wgrad_form', 'layer_norm_supported', 'small_gemm_form'} & set(ranged)
+                'fc_stream_splits', 'wgrad6_form', 'wgrad_form', 'fir_form', 'layer_norm_supported', 'small_gemm_form'} & set(ranged)
 
 
 def test_fused_adam_loads_reference_style_optimizer_state():

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import te_oracle as O
-from transeditor_amd import synth
+from transeditor_amd import _lib, synth
 from transeditor_amd.op import upfirdn2d
 from transeditor_amd.op.fir_act import blur_bias_act
 
@@ -21,7 +21,7 @@ def rel(a, b):
 def test_upfirdn2d_random_shapes(seed):
     g = torch.Generator().manual_seed(seed)
     ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))
-    worst = (0.0, '')
+    worst, drawn = (0.0, ''), set()
     for i in range(40):
         B, C = ri(1, 3), ri(1, 9)
         H, W = ri(3, 80), ri(3, 140)
@@ -33,6 +33,8 @@ def test_upfirdn2d_random_shapes(seed):
         k = O.fir_kernel(taps, float(up * up))
         if (H * up + p0 + p1 - k.shape[0]) // down + 1 <= 0 or (W * up + p0 + p1 - k.shape[1]) // down + 1 <= 0:
             continue
+        f = _lib.fir_form('upfirdn2d', B * C, H, W, (p0, p1, p0, p1), *k.shape, (up, up), (down, down))
+        drawn.add((f['kernel'], f['mode'], f['D'], f['ext']))
         x = synth.normal((B, C, H, W), f'ff.{seed}.{i}').requires_grad_(True)
         y_ref = O.upfirdn2d(x, k, up, down, (p0, p1))
         gy = synth.normal(tuple(y_ref.shape), f'ffg.{seed}.{i}')
@@ -44,6 +46,7 @@ def test_upfirdn2d_random_shapes(seed):
         e = max(rel(y, y_ref), rel(gx, gx_ref))
         if e > worst[0]:
             worst = (e, f'B={B} C={C} {H}x{W} up={up} down={down} taps={taps} pad=({p0},{p1})')
+    print(f'seed {seed}: forward launches drawn (kernel, MODE, D, EXT): {sorted(drawn)}')
     assert worst[0] < 1e-5, worst
 
 

@@ -29,7 +29,8 @@ import conv_routes as cr
 import fp64_check
 import loop_trips as lt
 from conftest import rel_err
-from fp64_check import A32, ALPHA, AS32, S32, SCALE, U, U32, where64
+from fir_restated import fir64, fir_bound as _fir_bound, slope64
+from fp64_check import A32, ALPHA, S32, SCALE, U, U32, where64
 from transeditor_amd import _lib
 from transeditor_amd.op.chanscale import chan_scale
 from transeditor_amd.op.fir_act import blur_bias_act
@@ -69,36 +70,8 @@ def taps2d(taps, dtype=torch.float32, gain=1.0):
     return (k / k.sum() * gain).to(dtype).to(DEV)          # (1,3,3,1) / 64 and (1,2,1) / 16 are exact in every format here
 
 
-def fir64(x, k, up=1, down=1, pad=(0, 0, 0, 0)):
-    """upfirdn2d of x [..., H, W] (fp64) from slices: zero insertion, zero padding (pads >= 0), true convolution with k, decimation"""
-    px0, px1, py0, py1 = pad
-    H, W = x.shape[-2:]
-    if up > 1:
-        z = x.new_zeros(x.shape[:-2] + (H * up, W * up))
-        z[..., ::up, ::up] = x
-        x = z
-    x = F.pad(x, (px0, px1, py0, py1))
-    kh, kw = k.shape
-    oh, ow = x.shape[-2] - kh + 1, x.shape[-1] - kw + 1
-    kf = torch.flip(k, [0, 1])
-    out = None
-    for a in range(kh):
-        for c in range(kw):
-            t = x[..., a:a + oh, c:c + ow] * kf[a, c]
-            out = t if out is None else out + t
-    return out[..., ::down, ::down]
-
-
-def slope64(ref):
-    return where64(ref > 0, S32, AS32)
-
-
 def _pad4(p):
     return (p[0], p[1], p[0], p[1])
-
-
-def _fir_bound(absfir, y64, T, gain=1.0, absb=0.0):
-    return (T + 2) * U32 * (absfir + absb) * gain + U32 * y64.abs()
 
 
 def _planes(t, lo, hi):

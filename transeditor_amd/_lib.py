@@ -271,6 +271,24 @@ def blur_gradact(g, ref, k_flipped, pad, alpha, scale):
     return gx, partial.sum(dim=(0, 2))
 
 
+FIR_KERNELS = ('direct', 'blur44', 'tile_up2', 'tile_down2', 'tile_ag')                     # TE_FIR_* (te_hip.h)
+FIR_FORM = ('kernel', 'mode', 'D', 'ext', 'ext_x', 'ext_y', 'tile_h', 'tile_w', 'tiles_x', 'tiles_y', 'zgroups', 'grid_x', 'threads')   # te_fir_form
+FIR_OPS = {'upfirdn2d': 0, 'blur_actgrad': 1, 'blur_gradact': 2}
+
+
+def fir_form(op, major, in_h, in_w, pad, kh=4, kw=4, up=(1, 1), down=(1, 1), minor=1):
+    """the plan of the te_upfirdn2d_f32 / te_blur_actgrad_f32 / te_blur_gradact_f32 launch (op: a key of FIR_OPS) over `major` planes
+    of in_h x in_w with pad = (px0, px1, py0, py1) and up / down = (x, y) (host only): a dict of FIR_FORM with 'kernel' as a name of
+    FIR_KERNELS; the negative TE_ERR_* code where the launch refuses"""
+    buf = (C.c_int * len(FIR_FORM))()
+    rc = lib().te_fir_form(FIR_OPS[op], major, in_h, in_w, minor, kh, kw, up[0], up[1], down[0], down[1], *pad, buf)
+    if rc:
+        return rc
+    f = dict(zip(FIR_FORM, buf))
+    f['kernel'] = FIR_KERNELS[f['kernel']]
+    return f
+
+
 # --------------------------------------------------------------------------------------------- F1
 @_op
 def conv_pack(w, kind_pack, wscale=1.0):

@@ -255,11 +255,22 @@ inline unsigned tile_grid(FirParams& q) {
 // grid of the direct kernels: one output per thread up to the cap, the threads stride over the rest
 inline int fir_direct_grid(int64_t total) { return (int)std::min<int64_t>(te::cdiv(total, 256), te::kNumCU * 16); }
 
+// The plan of a FIR launch: which kernel and instantiation run, with the geometry the grid functions have filled into q.  plan_fir /
+// plan_blur_bwd (below) make it; the three launches dispatch on it, te_fir_form and the te_*_plan queries report it.
+enum FirKernel { FIRK_DIRECT = TE_FIR_DIRECT, FIRK_BLUR44 = TE_FIR_BLUR44, FIRK_TILE_UP2 = TE_FIR_TILE_UP2,
+                 FIRK_TILE_DOWN2 = TE_FIR_TILE_DOWN2, FIRK_TILE_AG = TE_FIR_TILE_AG };
+struct FirPlan {
+    FirParams q;                  // the kernel's argument: geometry, and for the tiled kernels ext_x / ext_y / tiles_x / tiles_y / zgroups
+    int kernel = FIRK_DIRECT;
+    int mode = 0, D = 0, ext = 0; // blur44_kernel<MODE, D, EXT>; 0 for the other kernels
+    int tile_h = 0, tile_w = 0;   // output tile of the tiled kernels
+    unsigned grid = 0;
+    bool walks() const { return kernel != FIRK_DIRECT; }
+};
+
 template <int UP, int DOWN, int KH, int KW>
-void launch_tile(float* out, const float* x, const float* k, const float* b, const FirParams& p, hipStream_t s) {
-    FirParams q = p;
-    dim3 grid(tile_grid(q), 1u, 1u);
-    fir_tile_kernel<UP, DOWN, KH, KW><<<grid, 256, 0, s>>>(out, x, k, b, q);
+void launch_tile(float* out, const float* x, const float* k, const float* b, const FirPlan& pl, hipStream_t s) {
+    fir_tile_kernel<UP, DOWN, KH, KW><<<dim3(pl.grid, 1u, 1u), 256, 0, s>>>(out, x, k, b, pl.q);
 }
 
 
@@ -517,20 +528,37 @@ inline unsigned blur44_grid(FirParams& q) {
     return xcd_grid(q, tx_n, ty_n, fir_planes_z(q.major, 2 * tiles));
 }
 
-template <int AG>
-void launch_blur44(float* out, const float* x, const float* k, const float* b, const FirParams& p, hipStream_t s, const float* ref,
+// plan of a blur44_kernel<MODE, D, EXT> launch for the geometry in pl.q: D = (-pad_x0) & 3, EXT where the launch has an extra column
+// or row (the +1 rule)
+inline void plan_blur44(FirPlan& pl, int mode) {
+    pl.kernel = FIRK_BLUR44;
+    pl.mode = mode;
+    pl.grid = blur44_grid(pl.q);
+    pl.D = (-pl.q.pad_x0) & 3;
+    pl.ext = pl.q.ext_x || pl.q.ext_y;
+    pl.tile_h = BOH; pl.tile_w = BOW;
+}
+// plan of a fir_tile_kernel launch
+inline void plan_tile(FirPlan& pl, int kernel) {
+    pl.kernel = kernel;
+    pl.grid = tile_grid(pl.q);
+    pl.tile_h = TOH; pl.tile_w = TOW;
+}
+
+template <int MODE>
+void launch_blur44(float* out, const float* x, const float* k, const float* b, const FirPlan& pl, hipStream_t s, const float* ref,
                    float* partial) {
-    FirParams q = p;
-    dim3 grid(blur44_grid(q), 1u, 1u);
-    auto go = [&](auto EXT) {       // EXT: the launch has an extra column / row (the +1 rule); D = (-pad_x0) & 3
-        switch ((-p.pad_x0) & 3) {
-            case 0: blur44_kernel<AG, 0, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            case 1: blur44_kernel<AG, 1, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            case 2: blur44_kernel<AG, 2, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
-            default: blur44_kernel<AG, 3, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+    const dim3 grid(pl.grid, 1u, 1u);
+    const FirParams& q = pl.q;
+    auto go = [&](auto EXT) {
+        switch (pl.D) {
+            case 0: blur44_kernel<MODE, 0, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+            case 1: blur44_kernel<MODE, 1, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+            case 2: blur44_kernel<MODE, 2, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
+            default: blur44_kernel<MODE, 3, decltype(EXT)::value><<<grid, 256, 0, s>>>(out, x, k, b, q, ref, partial); break;
         }
     };
-    if (q.ext_x || q.ext_y) go(std::true_type{});
+    if (pl.ext) go(std::true_type{});
     else go(std::false_type{});
 }
 
@@ -557,8 +585,28 @@ inline FirParams fir_geometry(int64_t major, int in_h, int in_w, int minor, int 
 }
 // te_blur_actgrad_f32 takes the blur kernel unless a row is narrower than one 16-byte group
 inline bool actgrad_blur44(const FirParams& p) { return p.in_w >= 4; }
-// grid of a fused blur backward pass; fills q like blur44_grid / tile_grid (shared by the launch, the plans and te_blur_actgrad_tiles)
-inline unsigned blur_bwd_grid(FirParams& q) { return actgrad_blur44(q) ? blur44_grid(q) : tile_grid(q); }
+
+// The planning half of te_upfirdn2d_f32 for a checked problem p (major > 0): route, instantiation and grid.
+inline FirPlan plan_fir(const FirParams& p) {
+    FirPlan pl;
+    pl.q = p;
+    switch (fir_route(p)) {
+        case FIR_BLUR44: plan_blur44(pl, 0); break;
+        case FIR_TILE_UP2: plan_tile(pl, FIRK_TILE_UP2); break;
+        case FIR_TILE_DOWN2: plan_tile(pl, FIRK_TILE_DOWN2); break;
+        default: pl.grid = (unsigned)fir_direct_grid(p.major * p.out_h * p.out_w * p.minor);
+    }
+    return pl;
+}
+// The planning half of the two fused blur backward passes (mode 1: te_blur_actgrad_f32, 2: te_blur_gradact_f32), shared by the
+// launch, the plans, te_fir_form and te_blur_actgrad_tiles.
+inline FirPlan plan_blur_bwd(const FirParams& p, int mode) {
+    FirPlan pl;
+    pl.q = p;
+    if (mode == 2 || actgrad_blur44(p)) plan_blur44(pl, mode);
+    else plan_tile(pl, FIRK_TILE_AG);
+    return pl;
+}
 
 // Argument conditions and geometry of a general upfirdn2d problem, shared by the three launches and te_upfirdn2d_plan (which has no
 // epilogue to check): one place says what is refused and with which code.  major == 0 passes (an empty launch).
@@ -588,6 +636,13 @@ int blur_bwd_problem(const char* what, FirParams& p, int64_t major, int in_h, in
     return 0;
 }
 
+// Limits of the two launches on top of blur_bwd_problem (the te_blur_*_plan queries do not apply them, te_fir_form does)
+int blur_bwd_limits(const char* what, int64_t major, int in_h, int in_w) {
+    TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "%s: too many planes", what);
+    TE_REQUIRE((int64_t)in_h * in_w * 4 < 0x7FFFFFFF, TE_ERR_UNSUPPORTED, "%s: plane too large", what);
+    return 0;
+}
+
 // body of te_blur_actgrad_f32 (MODE 1) and te_blur_gradact_f32 (MODE 2)
 template <int MODE>
 int blur_bwd_launch(const char* what, float* gx, float* partial, const float* g, const float* ref, const float* k, int64_t major, int in_h,
@@ -598,21 +653,17 @@ int blur_bwd_launch(const char* what, float* gx, float* partial, const float* g,
     if (const int rc = blur_bwd_problem(what, p, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, min_w, nonneg_pads)) return rc;
     p.size_b = 1; p.act = 0; p.alpha = alpha; p.scale = scale;
     if (major == 0) return 0;
-    TE_REQUIRE(major <= 0x7FFFFFFF / 4, TE_ERR_SHAPE, "%s: too many planes", what);
-    TE_REQUIRE((int64_t)in_h * in_w * 4 < 0x7FFFFFFF, TE_ERR_UNSUPPORTED, "%s: plane too large", what);
-    if (MODE == 2 || actgrad_blur44(p)) {
-        launch_blur44<MODE>(gx, g, k, nullptr, p, s, ref, partial);
-    } else {
-        dim3 grid(tile_grid(p), 1u, 1u);
-        fir_tile_kernel<1, 1, 4, 4, true><<<grid, 256, 0, s>>>(gx, g, k, nullptr, p, ref, partial);
-    }
+    if (const int rc = blur_bwd_limits(what, major, in_h, in_w)) return rc;
+    const FirPlan pl = plan_blur_bwd(p, MODE);
+    if (pl.kernel == FIRK_BLUR44) launch_blur44<MODE>(gx, g, k, nullptr, pl, s, ref, partial);
+    else fir_tile_kernel<1, 1, 4, 4, true><<<dim3(pl.grid, 1u, 1u), 256, 0, s>>>(gx, g, k, nullptr, pl.q, ref, partial);
     return te::launch_status(what);
 }
 
-// what a plan hands out: the grid function has filled q
-inline int plan_out(const FirParams& q, bool walks, int* zgroups, int* tiles) {
-    *zgroups = walks ? q.zgroups : 0;
-    *tiles = walks ? q.tiles_x * q.tiles_y : 0;
+// what the te_*_plan queries hand out of a plan
+inline int plan_out(const FirPlan& pl, int* zgroups, int* tiles) {
+    *zgroups = pl.walks() ? pl.q.zgroups : 0;
+    *tiles = pl.walks() ? pl.q.tiles_x * pl.q.tiles_y : 0;
     return 0;
 }
 
@@ -622,8 +673,8 @@ inline int plan_out(const FirParams& q, bool walks, int* zgroups, int* tiles) {
 extern "C" int te_blur_actgrad_tiles(int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
     FirParams p = fir_geometry(1, in_h, in_w, 1, kh, kw, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1);
     if (p.out_h <= 0 || p.out_w <= 0) return TE_ERR_SHAPE;
-    blur_bwd_grid(p);
-    return p.tiles_x * p.tiles_y;
+    const FirPlan pl = plan_blur_bwd(p, 1);
+    return pl.q.tiles_x * pl.q.tiles_y;
 }
 
 extern "C" int te_blur_actgrad_f32(float* gx, float* partial, const float* g, const float* ref, const float* k, int64_t major,
@@ -710,14 +761,12 @@ extern "C" int te_upfirdn2d_f32(float* out, const float* x, const float* k, int6
     p.size_b = (int)size_b; p.act = act; p.alpha = alpha; p.scale = (b || act) ? scale : 1.f;
     if (major == 0) return 0;
     hipStream_t s = (hipStream_t)stream_;
-    switch (fir_route(p)) {
-        case FIR_BLUR44: launch_blur44<0>(out, x, k, b, p, s, nullptr, nullptr); break;
-        case FIR_TILE_UP2: launch_tile<2, 1, 4, 4>(out, x, k, b, p, s); break;
-        case FIR_TILE_DOWN2: launch_tile<1, 2, 4, 4>(out, x, k, b, p, s); break;
-        default: {
-            const int64_t total = major * p.out_h * p.out_w * minor;
-            fir_direct_kernel<<<fir_direct_grid(total), 256, 0, s>>>(out, x, k, b, p);
-        }
+    const FirPlan pl = plan_fir(p);
+    switch (pl.kernel) {
+        case FIRK_BLUR44: launch_blur44<0>(out, x, k, b, pl, s, nullptr, nullptr); break;
+        case FIRK_TILE_UP2: launch_tile<2, 1, 4, 4>(out, x, k, b, pl, s); break;
+        case FIRK_TILE_DOWN2: launch_tile<1, 2, 4, 4>(out, x, k, b, pl, s); break;
+        default: fir_direct_kernel<<<pl.grid, 256, 0, s>>>(out, x, k, b, pl.q);
     }
     return te::launch_status("te_upfirdn2d_f32");
 }
@@ -734,30 +783,52 @@ extern "C" int te_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, i
     if (const int rc = fir_problem("te_upfirdn2d_plan", p, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1))
         return rc;
     if (major == 0) return TE_ERR_SHAPE;      // nothing is launched: there is no plan
-    const FirRoute route = fir_route(p);
-    if (route == FIR_BLUR44) blur44_grid(p);
-    else if (route != FIR_DIRECT) tile_grid(p);
-    return plan_out(p, route != FIR_DIRECT, zgroups, tiles);
+    return plan_out(plan_fir(p), zgroups, tiles);
 }
 
 static int blur_bwd_plan(const char* what, int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
-                         int* zgroups, int* tiles, int min_w, bool nonneg_pads) {
+                         int* zgroups, int* tiles, int mode, int min_w, bool nonneg_pads) {
     if (!zgroups || !tiles) return TE_ERR_NULL;
     FirParams p;
     if (const int rc = blur_bwd_problem(what, p, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, min_w, nonneg_pads)) return rc;
     if (major == 0) return TE_ERR_SHAPE;      // nothing is launched: there is no plan
-    blur_bwd_grid(p);
-    return plan_out(p, true, zgroups, tiles);
+    return plan_out(plan_blur_bwd(p, mode), zgroups, tiles);
 }
 
 extern "C" int te_blur_actgrad_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                     int* zgroups, int* tiles) {
-    return blur_bwd_plan("te_blur_actgrad_plan", major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, zgroups, tiles, 1, true);
+    return blur_bwd_plan("te_blur_actgrad_plan", major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, zgroups, tiles, 1, 1, true);
 }
 
 extern "C" int te_blur_gradact_plan(int64_t major, int in_h, int in_w, int kh, int kw, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                     int* zgroups, int* tiles) {
-    return blur_bwd_plan("te_blur_gradact_plan", major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, zgroups, tiles, 4, false);
+    return blur_bwd_plan("te_blur_gradact_plan", major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, zgroups, tiles, 2, 4, false);
+}
+
+// The plan itself (see te_hip.h): the planning half of the launch `op`, after the launch's own argument checks.
+extern "C" int te_fir_form(int op, int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                           int pad_x0, int pad_x1, int pad_y0, int pad_y1, int* form) {
+    TE_REQUIRE(form, TE_ERR_NULL, "te_fir_form: NULL pointer");
+    TE_REQUIRE(op >= 0 && op <= 2, TE_ERR_UNSUPPORTED, "te_fir_form: op is 0 (upfirdn2d_f32), 1 (blur_actgrad) or 2 (blur_gradact)");
+    FirParams p;
+    FirPlan pl;
+    if (op == 0) {
+        if (const int rc = fir_problem("te_fir_form", p, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1))
+            return rc;
+        if (major == 0) return TE_ERR_SHAPE;      // nothing is launched: there is no plan
+        pl = plan_fir(p);
+    } else {
+        if (const int rc = blur_bwd_problem("te_fir_form", p, major, in_h, in_w, kh, kw, pad_x0, pad_x1, pad_y0, pad_y1, op == 2 ? 4 : 1, op == 1))
+            return rc;
+        if (major == 0) return TE_ERR_SHAPE;
+        if (const int rc = blur_bwd_limits("te_fir_form", major, in_h, in_w)) return rc;
+        pl = plan_blur_bwd(p, op);
+    }
+    const bool w = pl.walks();
+    const int f[TE_FIR_FORM_INTS] = {pl.kernel, pl.mode, pl.D, pl.ext, w ? pl.q.ext_x : 0, w ? pl.q.ext_y : 0, pl.tile_h, pl.tile_w,
+                                     w ? pl.q.tiles_x : 0, w ? pl.q.tiles_y : 0, w ? pl.q.zgroups : 0, (int)pl.grid, 256};
+    for (int i = 0; i < TE_FIR_FORM_INTS; ++i) form[i] = f[i];
+    return 0;
 }
 
 extern "C" int64_t te_upfirdn2d_direct_cover(int64_t outputs) {
