@@ -382,7 +382,10 @@ int te_wgrad_group_f32(float* slabs, const float* g, const float* x, int kind, i
  *   gosc[b,co]   = sum_{ci,t,s} wscale*w[co,ci,t] * isc[b,ci] * slab      (gosc may be NULL)
  * isc / osc NULL = all ones.  All three outputs are WRITTEN.  Shares of different thread blocks (channel tiles, slab chunks,
  * samples) meet through the caller's workspace `ws` of te_wgrad_reduce_ws_floats(...) floats and a fixed-order second pass:
- * bit-reproducible, no atomics, no memset. */
+ * bit-reproducible, no atomics, no memset.  The launch plans once (path, counts, where each output's parts lie in `ws`) and
+ * te_wgrad_reduce_ws_floats is the largest reservation over the plans a launch with the same wants (want_* = the output
+ * pointer is not NULL) can take, whatever the alignment of its tensors and with or without an osc operand; a plan that would
+ * carve more is refused with TE_ERR_SHAPE before anything is launched. */
 int64_t te_wgrad_reduce_ws_floats(int B, int S, int Co, int Ci, int taps, int want_w, int want_isc, int want_osc);
 int te_wgrad_reduce_f32(float* gw, float* gisc, float* gosc, float* ws, const float* slabs, const float* w,
                         float wscale, const float* isc, const float* osc, int B, int S, int Co, int Ci,

@@ -24,7 +24,7 @@ def _bits_equal(a, b):
     return (a is None and b is None) or torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
-REDUCE_CASES = [   # B, S, Co, Ci, taps, (isc, osc)
+REDUCE_CASES = [   # B, S, Co, Ci, taps, (isc, osc[, element offset of the slabs inside their buffer])
     (4, 3, 64, 64, 9, (True, True)),        # fused single pass, one chunk group
     (16, 16, 32, 32, 9, (True, True)),      # fused, slab chunks split over blockIdx.z (narrow layer): dW through parts as well
     (3, 5, 128, 96, 9, (True, False)),      # fused, odd batch (tail sample), no demodulation
@@ -37,12 +37,19 @@ REDUCE_CASES = [   # B, S, Co, Ci, taps, (isc, osc)
     (8, 4, 512, 512, 1, (False, False)),    # plain 1x1 (discriminator skip): dW only, chunks over (b, s)
     (4, 64, 3, 128, 1, (True, False)),      # ToRGB path, chunks split over blockIdx.z
     (16, 2, 3, 512, 1, (True, False)),      # ToRGB path, one chunk group
+    (2, 3, 5, 7, 9, (True, True)),          # generic in scalar form: Co Ci taps = 315 is no multiple of 4
+    (4, 8, 3, 64, 1, (True, True)),         # ToRGB-shaped with an osc operand and d osc wanted: the generic path takes it
+    (4, 3, 64, 64, 9, (True, True, 1)),     # fused-eligible, slabs 4 bytes past a 16-byte boundary: generic scalar path, workspace sized with the fused path in view
 ]
 
 
 @pytest.mark.parametrize('B,S,Co,Ci,taps,mods', REDUCE_CASES)
 def test_wgrad_reduce_paths_vs_fp64_and_bit_reproducible(B, S, Co, Ci, taps, mods):
     slabs = synth.normal((B, S, Co, Ci, taps), f'det.slab.{B}.{S}.{Co}.{Ci}').to(DEV)
+    if len(mods) > 2:                                                 # a contiguous view at element mods[2] of a larger buffer
+        buf = torch.empty(slabs.numel() + mods[2], device=DEV)
+        slabs = buf[mods[2]:].view(slabs.shape).copy_(slabs)
+        assert slabs.is_contiguous() and buf.data_ptr() % 16 == 0 and slabs.data_ptr() % 16 == 4 * mods[2]
     w = synth.normal((Co, Ci, taps), f'det.w.{Co}.{Ci}.{taps}').to(DEV)
     isc = (1 + 0.3 * synth.normal((B, Ci), 'det.isc')).to(DEV) if mods[0] else None
     osc = (1 + 0.3 * synth.normal((B, Co), 'det.osc')).to(DEV) if mods[1] else None

@@ -114,13 +114,16 @@ __device__ __forceinline__ bool split6_tile_list(int ntiles, int nt8, int mblock
 }
 
 // ---- a body shared by two kernels (s2s6.hip: the ping-pong and the two-image form of the kind are one function template, the kernels
-// the runtime sees are thin __global__ wrappers).  The body is declared `__device__ __attribute__((optnone))` and called as
+// the runtime sees are thin __global__ wrappers; wgrad6.hip: the 64 x 64, masked and wide forms of the transposed kind).  The body is declared `__device__ __attribute__((optnone))` and called as
 // `[[clang::always_inline]] body<...>(p);` (the attribute at the call takes precedence): the optimiser leaves the stand-alone function
 // alone, lambdas included, and the code is optimised once, inside its kernel, as if it had been written there.  A plain __forceinline__
 // body is optimised on its own first and again after inlining; the passes are not idempotent, and the kernels came out further from
 // the code that was measured (s2s6_kernel<false>: 156 VGPRs against 163, 49 s_waitcnt against 37; profiles/refactor_split6_forms_isa.txt
 // has every form that was tried and what is left with this one).  t2s6.hip keeps its two kernels written out: merged the same way, its
 // two-image kernel was 0.7 - 0.9 % slower in small launches in both timing visits (profiles/refactor_split6_forms_time.txt).
+// The inlined body meets the kernel's passes later than code written in the kernel: a subexpression that two places are to share has to
+// be visible to the first common-subexpression pass (not behind a short-circuit `&&`, not in a loop still to be unrolled) - wgrad6t_body's
+// `active` (profiles/refactor_wgrad6t_isa.txt: with that, all of wgrad6.hip's kernels are the instruction streams of the written-out code).
 
 // ---- host: which form of a kind to launch.  form_sel = the kind's form hook counted from its two-image default: 0 = ping-pong, 1 = the
 // two-image form where M % 128 == 0 and its grid (blocks_q: half as many blocks) still gives every CU a block, 2 = the two-image form

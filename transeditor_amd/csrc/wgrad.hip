@@ -895,7 +895,7 @@ inline void launch_sum_parts(const SumJob* jobs, int n, hipStream_t s) {
     sum_parts_kernel<<<dim3(sum_parts_grid(mx), (unsigned)n), 256, 0, s>>>(t);
 }
 
-// chunk counts of the reducer paths (shared by te_wgrad_reduce_ws_floats and the launch)
+// chunk counts of the reducer paths (plan_reduce's)
 inline bool reduce_fused_ok(int Co, int Ci, int taps) { return taps == 9 && Co % FROWS == 0 && Ci % 32 == 0 && Co / FROWS <= 65535; }
 // (chunk splits nzs, batch splits nzb) of the fused reducer: two blocks of two waves per CU where the problem allows, every block
 // still sums >= 4 (sample, chunk) slabs so that the dW parts stay <= a quarter of the slab bytes
@@ -911,6 +911,71 @@ inline int reduce_few_nz(int B, int S, int Ci) {
 inline int reduce_w_nchunk(int B, int S, int64_t E, bool vec) {
     const int64_t blocks = te::cdiv(vec ? E / 4 : E, RTHREADS);
     return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)B * S, te::cdiv(2 * te::kNumCU, blocks)));
+}
+
+// The plan of a reduction: which path runs, its counts and grids, and where the first pass writes each output, made from the arguments
+// alone.  plan_reduce fills it; te_wgrad_reduce_f32 launches what it names, te_wgrad_reduce_ws_floats is the largest `reserved` over the
+// plans a launch with the same wants can take and te_wgrad_reduce_plan reads the dW output of the aligned one: the workspace's size, its
+// carve and the reported second pass cannot drift apart.
+struct RdOut {                  // one output of the first pass
+    int64_t off;                // float offset of its parts in the workspace; < 0: the first pass writes the final tensor, no second pass
+    int parts; int64_t n;       // partial tensors and elements of each (what SumJob needs)
+};
+enum RdPath { RD_FUSED, RD_FEW, RD_GENERIC };
+struct RdPlan {
+    RdPath path; bool vec;                  // vec: wgrad_reduce_w4_kernel, not wgrad_reduce_w_kernel, on the generic path
+    int nzs, nzb, nzf, nchunk, nY;          // the path's counts (1 where the path has none)
+    dim3 grid, grid_sc;                     // the path's kernel (generic: the dW kernel) and the generic path's wgrad_reduce_sc_kernel
+    RdOut w, isc, osc;
+    int64_t used, reserved;                 // floats the carve uses <= floats the path reserves
+};
+
+// al_sgw: slabs, gw and ws are 16-byte aligned; al_w: w is.  has_osc: the launch carries an osc operand.
+RdPlan plan_reduce(int B, int S, int Co, int Ci, int taps, bool want_w, bool want_isc, bool want_osc, bool has_osc, bool al_sgw, bool al_w) {
+    const int64_t E = (int64_t)Co * Ci * taps;
+    RdPlan pl{};
+    pl.nzs = pl.nzb = pl.nzf = pl.nchunk = pl.nY = 1;
+    pl.w = RdOut{-1, 1, E}; pl.isc = RdOut{-1, 1, (int64_t)B * Ci}; pl.osc = RdOut{-1, 1, (int64_t)B * Co};
+    auto carve = [&](RdOut& o, int parts) { o.off = pl.used; o.parts = parts; pl.used += (int64_t)parts * o.n; };
+    if (reduce_fused_ok(Co, Ci, taps) && al_sgw && al_w) {                 // single-pass path: every block's share of d osc and d isc is a part
+        pl.path = RD_FUSED;
+        reduce_fused_split(B, S, Co, Ci, pl.nzs, pl.nzb);
+        const int nz = pl.nzs * pl.nzb, nX = Ci / 32;
+        pl.nY = Co / FROWS;
+        if (want_osc) carve(pl.osc, pl.nzs * nX);
+        if (want_isc) carve(pl.isc, pl.nzs * pl.nY);
+        if (want_w && nz > 1) carve(pl.w, nz);
+        pl.grid = dim3((unsigned)nX, (unsigned)pl.nY, (unsigned)nz);
+        pl.reserved = pl.used;
+    } else if (taps == 1 && Co <= 4 && !want_osc && !has_osc) {             // ToRGB
+        pl.path = RD_FEW;
+        // few, long per-thread streams when the image is large (S up to a few hundred): split them over blockIdx.z
+        pl.nzf = reduce_few_nz(B, S, Ci);
+        if (want_w) carve(pl.w, pl.nzf * B);                                // (always parts: a block owns one sample)
+        if (want_isc && pl.nzf > 1) carve(pl.isc, pl.nzf);
+        pl.grid = dim3((unsigned)te::cdiv(Ci, RTHREADS), (unsigned)B, (unsigned)pl.nzf);
+        pl.reserved = pl.used;
+    } else {
+        pl.path = RD_GENERIC;
+        pl.vec = E % 4 == 0 && al_sgw;
+        if (want_w) {
+            pl.nchunk = reduce_w_nchunk(B, S, E, pl.vec);
+            if (pl.nchunk > 1) carve(pl.w, pl.nchunk);
+            pl.grid = dim3((unsigned)te::cdiv(pl.vec ? E / 4 : E, RTHREADS), (unsigned)pl.nchunk);
+        }
+        if (want_isc || want_osc) {
+            pl.nY = (int)te::cdiv(Co, COB);
+            if (want_isc && pl.nY > 1) carve(pl.isc, pl.nY);
+            pl.grid_sc = dim3((unsigned)B, (unsigned)pl.nY);
+        }
+        // The reservation of this path is older than its carve and callers size buffers by it: a single chunk and a single channel
+        // block count as parts, and a ToRGB-shaped problem reserves what it would on the ToRGB path (the size was never a function
+        // of osc).
+        pl.reserved = (want_w ? pl.nchunk * E : 0) + (want_isc ? (int64_t)pl.nY * pl.isc.n : 0);
+        if (taps == 1 && Co <= 4)
+            pl.reserved = std::max(pl.reserved, plan_reduce(B, S, Co, Ci, taps, want_w, want_isc, false, false, al_sgw, al_w).reserved);
+    }
+    return pl;
 }
 
 }  // namespace
@@ -1044,28 +1109,14 @@ static int wgrad_launch(float* slabs, const float* g, const float* x, int kind, 
     return te::launch_status("te_wgrad_f32");
 }
 
-// floats of workspace te_wgrad_reduce_f32 needs for this problem (an upper bound over the alignment-dependent paths)
+// floats of workspace te_wgrad_reduce_f32 needs for this problem: the largest reservation over the plans a launch with these wants can
+// take - aligned operands, a misaligned w, misaligned tensors, each with and without an osc operand
 extern "C" int64_t te_wgrad_reduce_ws_floats(int B, int S, int Co, int Ci, int taps, int want_w, int want_isc, int want_osc) {
     if (B <= 0 || S <= 0 || Co <= 0 || Ci <= 0 || (taps != 1 && taps != 9)) return TE_ERR_SHAPE;
-    const int64_t E = (int64_t)Co * Ci * taps;
     int64_t n = 0;
-    if (reduce_fused_ok(Co, Ci, taps)) {
-        int nzs, nzb;
-        reduce_fused_split(B, S, Co, Ci, nzs, nzb);
-        if (want_osc) n += (int64_t)nzs * (Ci / 32) * B * Co;
-        if (want_isc) n += (int64_t)nzs * (Co / FROWS) * B * Ci;
-        if (want_w && nzs * nzb > 1) n += (int64_t)nzs * nzb * E;
-    }
-    int64_t m = 0;                                         // the generic path (also the fall-back of a misaligned fused problem)
-    if (want_w) m += (int64_t)std::max(reduce_w_nchunk(B, S, E, false), reduce_w_nchunk(B, S, E, E % 4 == 0)) * E;
-    if (want_isc) m += (int64_t)te::cdiv(Co, COB) * B * Ci;
-    int64_t f = 0;                                         // ToRGB path
-    if (taps == 1 && Co <= 4) {
-        const int nzf = reduce_few_nz(B, S, Ci);
-        if (want_w) f += (int64_t)nzf * B * E;
-        if (want_isc && nzf > 1) f += (int64_t)nzf * B * Ci;
-    }
-    return std::max(n, std::max(m, f));
+    for (int v = 0; v < 6; ++v)
+        n = std::max(n, plan_reduce(B, S, Co, Ci, taps, want_w != 0, want_isc != 0, want_osc != 0, v & 1, v < 4, v < 2).reserved);
+    return n;
 }
 
 // Second pass of the dW output of te_wgrad_reduce_f32 with 16-byte aligned tensors and only dW wanted (host only): *parts = partial
@@ -1073,17 +1124,9 @@ extern "C" int64_t te_wgrad_reduce_ws_floats(int B, int S, int Co, int Ci, int t
 // trip of its full grid covers.
 extern "C" int te_wgrad_reduce_plan(int B, int S, int Co, int Ci, int taps, int* parts, int64_t* cover) {
     if (B <= 0 || S <= 0 || Co <= 0 || Ci <= 0 || (taps != 1 && taps != 9) || !parts || !cover) return TE_ERR_SHAPE;
-    const int64_t E = (int64_t)Co * Ci * taps;
-    if (reduce_fused_ok(Co, Ci, taps)) {
-        int nzs, nzb;
-        reduce_fused_split(B, S, Co, Ci, nzs, nzb);
-        *parts = nzs * nzb;
-    } else if (taps == 1 && Co <= 4) {
-        *parts = reduce_few_nz(B, S, Ci) * B;
-    } else {
-        *parts = reduce_w_nchunk(B, S, E, E % 4 == 0);
-    }
-    *cover = (int64_t)sum_parts_grid(E) * 256;
+    const RdPlan pl = plan_reduce(B, S, Co, Ci, taps, true, false, false, false, true, true);
+    *parts = pl.w.parts;
+    *cover = (int64_t)sum_parts_grid(pl.w.n) * 256;
     return 0;
 }
 
@@ -1092,60 +1135,43 @@ extern "C" int te_wgrad_reduce_f32(float* gw, float* gisc, float* gosc, float* w
                                    te_stream_t stream_) {
     TE_REQUIRE(slabs && w, TE_ERR_NULL, "te_wgrad_reduce_f32: NULL pointer");
     TE_REQUIRE(B > 0 && S > 0 && Co > 0 && Ci > 0 && (taps == 1 || taps == 9), TE_ERR_SHAPE, "te_wgrad_reduce_f32: bad dims");
-    TE_REQUIRE(ws || te_wgrad_reduce_ws_floats(B, S, Co, Ci, taps, gw != nullptr, gisc != nullptr, gosc != nullptr) == 0, TE_ERR_NULL,
-               "te_wgrad_reduce_f32: this problem needs the workspace (te_wgrad_reduce_ws_floats)");
+    const int64_t ws_floats = te_wgrad_reduce_ws_floats(B, S, Co, Ci, taps, gw != nullptr, gisc != nullptr, gosc != nullptr);
+    TE_REQUIRE(ws || ws_floats == 0, TE_ERR_NULL, "te_wgrad_reduce_f32: this problem needs the workspace (te_wgrad_reduce_ws_floats)");
     hipStream_t s = (hipStream_t)stream_;
-    const int64_t E = (int64_t)Co * Ci * taps;
+    const bool al_sgw = ((reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(gw) | reinterpret_cast<uintptr_t>(ws)) & 15) == 0;
+    const RdPlan pl = plan_reduce(B, S, Co, Ci, taps, gw != nullptr, gisc != nullptr, gosc != nullptr, osc != nullptr, al_sgw,
+                                  (reinterpret_cast<uintptr_t>(w) & 15) == 0);
+    TE_REQUIRE(pl.used <= ws_floats, TE_ERR_SHAPE, "te_wgrad_reduce_f32: the plan carves more than te_wgrad_reduce_ws_floats answers");
+    // where the first pass writes an output (its parts in the workspace, or the final tensor) and, for parts, the job that adds them
     SumJob jobs[3];
     int nj = 0;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(gw) |
-                         reinterpret_cast<uintptr_t>(ws);
-    if (reduce_fused_ok(Co, Ci, taps) && (al & 15) == 0) {                                          // single-pass path
-        int nzs, nzb;
-        reduce_fused_split(B, S, Co, Ci, nzs, nzb);
-        const int nz = nzs * nzb, nX = Ci / 32, nY = Co / FROWS;
-        float* p = ws;
-        float* po = nullptr; float* pi = nullptr; float* pw = gw;
-        if (gosc) { po = p; p += (size_t)nzs * nX * B * Co; jobs[nj++] = SumJob{gosc, po, nzs * nX, (int64_t)B * Co}; }
-        if (gisc) { pi = p; p += (size_t)nzs * nY * B * Ci; jobs[nj++] = SumJob{gisc, pi, nzs * nY, (int64_t)B * Ci}; }
-        if (gw && nz > 1) { pw = p; p += (size_t)nz * E; jobs[nj++] = SumJob{gw, pw, nz, E}; }
-        dim3 grid((unsigned)nX, (unsigned)nY, (unsigned)nz);
-        wgrad_reduce_fused_kernel<<<grid, FTHREADS, 0, s>>>(pw, pi, po, slabs, w, wscale, isc, osc, B, S, Co, Ci, nzs);
-        launch_sum_parts(jobs, nj, s);
-        return te::launch_status("te_wgrad_reduce_f32");
-    }
-    if (taps == 1 && Co <= 4 && !gosc && !osc) {                                                   // ToRGB
-        // few, long per-thread streams when the image is large (S up to a few hundred): split them over blockIdx.z
-        const int nzf = reduce_few_nz(B, S, Ci);
-        float* p = ws;
-        float* pw = nullptr; float* pi = gisc;
-        if (gw) { pw = p; p += (size_t)nzf * B * E; jobs[nj++] = SumJob{gw, pw, nzf * B, E}; }
-        if (gisc && nzf > 1) { pi = p; p += (size_t)nzf * B * Ci; jobs[nj++] = SumJob{gisc, pi, nzf, (int64_t)B * Ci}; }
-        dim3 grid((unsigned)te::cdiv(Ci, RTHREADS), (unsigned)B, (unsigned)nzf);
-        wgrad_reduce_few_kernel<<<grid, RTHREADS, 0, s>>>(pw, pi, slabs, w, wscale, isc, B, S, Co, Ci);
-        launch_sum_parts(jobs, nj, s);
-        return te::launch_status("te_wgrad_reduce_f32");
-    }
-    float* p = ws;
-    if (gw) {
-        const bool vec = (E % 4 == 0) && ((reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(gw) | reinterpret_cast<uintptr_t>(ws)) & 15) == 0;
-        const int64_t blocks = te::cdiv(vec ? E / 4 : E, RTHREADS);
-        const int nchunk = reduce_w_nchunk(B, S, E, vec);
-        float* pw = gw;
-        if (nchunk > 1) { pw = p; p += (size_t)nchunk * E; jobs[nj++] = SumJob{gw, pw, nchunk, E}; }
-        if (vec) wgrad_reduce_w4_kernel<<<dim3((unsigned)blocks, (unsigned)nchunk), RTHREADS, 0, s>>>(pw, slabs, wscale, isc, osc, B, S,
-                                                                                                    Co, Ci, taps, nchunk);
-        else wgrad_reduce_w_kernel<<<dim3((unsigned)blocks, (unsigned)nchunk), RTHREADS, 0, s>>>(pw, slabs, wscale, isc, osc, B, S, Co,
-                                                                                               Ci, taps, nchunk);
-    }
-    if (gisc || gosc) {
-        const int nY = (int)te::cdiv(Co, COB);
-        float* pi = gisc;
-        if (gisc && nY > 1) { pi = p; p += (size_t)nY * B * Ci; jobs[nj++] = SumJob{gisc, pi, nY, (int64_t)B * Ci}; }
-        dim3 grid((unsigned)B, (unsigned)nY);
-        if (taps == 9) wgrad_reduce_sc_kernel<9><<<grid, RTHREADS, 0, s>>>(pi, gosc, slabs, w, wscale, isc, osc, B, S, Co, Ci);
-        else wgrad_reduce_sc_kernel<1><<<grid, RTHREADS, 0, s>>>(pi, gosc, slabs, w, wscale, isc, osc, B, S, Co, Ci);
+    auto first_pass = [&](const RdOut& o, float* out) {
+        if (!out || o.off < 0) return out;
+        jobs[nj++] = SumJob{out, ws + o.off, o.parts, o.n};
+        return ws + o.off;
+    };
+    float* po = first_pass(pl.osc, gosc);           // (the order of the jobs is free: each output is summed on its own)
+    float* pi = first_pass(pl.isc, gisc);
+    float* pw = first_pass(pl.w, gw);
+    switch (pl.path) {
+        case RD_FUSED:
+            wgrad_reduce_fused_kernel<<<pl.grid, FTHREADS, 0, s>>>(pw, pi, po, slabs, w, wscale, isc, osc, B, S, Co, Ci, pl.nzs);
+            break;
+        case RD_FEW:
+            wgrad_reduce_few_kernel<<<pl.grid, RTHREADS, 0, s>>>(pw, pi, slabs, w, wscale, isc, B, S, Co, Ci);
+            break;
+        case RD_GENERIC:
+            if (gw) {
+                if (pl.vec) wgrad_reduce_w4_kernel<<<pl.grid, RTHREADS, 0, s>>>(pw, slabs, wscale, isc, osc, B, S, Co, Ci, taps, pl.nchunk);
+                else wgrad_reduce_w_kernel<<<pl.grid, RTHREADS, 0, s>>>(pw, slabs, wscale, isc, osc, B, S, Co, Ci, taps, pl.nchunk);
+            }
+            if (gisc || gosc) {
+                if (taps == 9) wgrad_reduce_sc_kernel<9><<<pl.grid_sc, RTHREADS, 0, s>>>(pi, po, slabs, w, wscale, isc, osc, B, S, Co, Ci);
+                else wgrad_reduce_sc_kernel<1><<<pl.grid_sc, RTHREADS, 0, s>>>(pi, po, slabs, w, wscale, isc, osc, B, S, Co, Ci);
+            }
+            break;
     }
     launch_sum_parts(jobs, nj, s);
     return te::launch_status("te_wgrad_reduce_f32");
 }
+

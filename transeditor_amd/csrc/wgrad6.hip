@@ -322,229 +322,55 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
 constexpr int GI = 3 * 3 * 2 * TC;            // elements of one g-row image: 1 152 (18 KB)
 constexpr int XI = 3 * 2 * TC;                // elements of one x-row image: 384 (6 KB)
 constexpr int NGR = 5;
+constexpr size_t wgrad6t_lds_bytes(bool wide) { return (size_t)(NGR * GI + 2 * (wide ? 2 : 1) * XI) * 16; }      // g ring + double-buffered x rows (WIDE: of two x tiles)
 
 // NARROW (round 6): Co or Ci is an odd multiple of 32 (the 64 -> 32 up-sampling layer of the FFHQ-1024 generator): the last channel block
 // of that side has 32 valid channels.  Lanes past them read the last valid channel again (no access outside the tensor; their LDS
 // elements only feed wave tiles that are not computed), and the waves whose 32 x 32 tile lies in the padding skip MFMAs and stores.
-template <bool NARROW>
-__global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) {
+//
+// WIDE (round 6, Ci % 128 == 0 - every transposed-kind layer of the FFHQ-256 model): the block tile is 64 channels of g x 128 channels
+// of x.  The counters place the 64 x 64 form BELOW the power cap (45.5 % MFMA busy at 2.2 GHz, HBM reads 2.1x the algorithmic bytes): its
+// vector-ALU staging - which a wave's own MFMAs do not hide (r05_wgrad6.log) - is the g unit plus an x unit per wave and step of 54
+// MFMAs, and waves 2, 3 repeat the x units of waves 0, 1.  The wide form has half the staging instructions, LDS writes and g loads per
+// MFMA, and reads g Ci / 128 instead of Ci / 64 times.
+//
+// The forms of the kernel, written once (optnone here + always_inline at the call in the kernels below: see "a body shared by two
+// kernels" in split6_common.h).  Everything outside the `if constexpr (WIDE)` branches - loads, split, staging program, ring
+// arithmetic, operand reads of g - is the same code for all of them, and every slab element sees the same products in the same order:
+// bit-identical slabs (tests/test_gpu_wgrad6.py).
+template <bool NARROW, bool WIDE>
+__device__ __attribute__((optnone)) void wgrad6t_body(const Wg6Args& p) {
+    static_assert(!(NARROW && WIDE), "the wide form has no masked variant: Ci % 128 == 0 and Co % 64 == 0");
+    constexpr int NX = WIDE ? 2 : 1;              // 64-channel x tiles of the block
+    constexpr int XROW = NX * XI;                 // x-row image: [x tile NX][piece 3][k half 2][channel 64]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* lds = reinterpret_cast<u32x4*>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wco = wid >> 1, wci = wid & 1;                  // multiplying: the wave's 32 x 32 tile
-    const int rsel = wid >> 1, q = wid & 1;                   // staging: g row 2i + 3 + rsel, cells 8 q .. 8 q + 7 of the step; lane = channel
+    const int wco = wid >> 1, wci = wid & 1;                  // multiplying: the wave's 32 x 32 tile (of every x tile)
+    const int rsel = wid >> 1, q = wid & 1;                   // staging: g row 2i + 3 + rsel (WIDE: and x tile rsel), cells 8 q .. 8 q + 7 of the step; lane = channel
 
     const Wg6Chunk ck = wg6_chunk(p.S, p.NB * (p.W / 16));
     const int s_chunk = ck.s, bgrp = ck.bgrp, b = bgrp * p.NB;
-    const int co0 = blockIdx.y * TC, ci0 = blockIdx.z * TC;
+    const int co0 = blockIdx.y * TC, ci0 = blockIdx.z * (NX * TC);
     const int Hg = 2 * p.H + 1, Wg = 2 * p.W + 1;
     const size_t gplane = (size_t)Hg * Wg, xplane = (size_t)p.H * p.W;
     // addresses = uniform 64-bit base (scalar registers) + this lane's 32-bit byte offset (its channel): the scalar-base form of the
     // global loads, no 64-bit vector arithmetic in the step
     const float* gblk = p.g + ((size_t)b * p.Co + co0) * gplane;             // channel block of the group's first sample
     const float* xblk = p.x + ((size_t)b * p.Ci + ci0) * xplane;
-    const int g_ch = NARROW ? min(lane, p.Co - co0 - 1) : lane, x_ch = NARROW ? min(lane, p.Ci - ci0 - 1) : lane;
+    const int g_ch = NARROW ? min(lane, p.Co - co0 - 1) : lane;
+    int x_ch;
+    if constexpr (WIDE) x_ch = rsel * TC + lane;              // (waves 2, 3 stage the second x tile: no wave repeats another's unit)
+    else x_ch = NARROW ? min(lane, p.Ci - ci0 - 1) : lane;
     const unsigned g_lane = (unsigned)(g_ch * gplane * 4), x_lane = (unsigned)(x_ch * xplane * 4);       // bytes (host-checked < 2 GiB)
-    const bool active = !NARROW || (co0 + wco * 32 < p.Co && ci0 + wci * 32 < p.Ci);                     // wave-uniform
+    // (wave-uniform.  `&`, not `&&`: the body reaches its kernel unoptimised, and the first common-subexpression pass there has to see
+    //  `ci0 + wci * 32` in the entry block to share it with the epilogue's `ci` - written `&&` the masked kernel forms it twice)
+    const bool active = !NARROW || ((co0 + wco * 32 < p.Co) & (ci0 + wci * 32 < p.Ci));
 
-    f32x16 acc[9];                                            // [ky * 3 + kx]
+    f32x16 acc[NX][9];                                        // [x tile][ky * 3 + kx]; WIDE: 2 x 9 accumulators = 288 registers of the 512 a lone wave per SIMD owns
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    // rows past the end are clamped to the last row (their registers are never used: no element of g or x is padding)
-    auto load_g = [&](float (&rg)[17], int bb, int cx, int grow) {
-        const char* src = reinterpret_cast<const char*>(gblk + (size_t)bb * p.Co * gplane + (size_t)min(grow, Hg - 1) * Wg + 2 * (16 * cx + 8 * q));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const f32x4 v = *reinterpret_cast<const f32x4u*>(src + 16 * k + g_lane);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rg[4 * k + e] = v[e];
-        }
-        rg[16] = *reinterpret_cast<const float*>(src + 64 + g_lane);
-    };
-    auto load_x = [&](float (&rx)[8], int bb, int cx, int xrow) {
-        const char* src = reinterpret_cast<const char*>(xblk + (size_t)bb * p.Ci * xplane + (size_t)min(xrow, p.H - 1) * p.W + 16 * cx + 8 * q);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const f32x4 v = *reinterpret_cast<const f32x4u*>(src + 16 * k + x_lane);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rx[4 * k + e] = v[e];
-        }
-    };
-    // split of one packed pair of values in three steps; units 0..4: even columns of the g unit (pair d = columns 4d, 4d + 2; the
-    // last one holds column 16 alone), 5..8: odd columns (4d + 1, 4d + 3), 9..12: the x unit
-    unsigned pe[3][5], po[3][4], px[3][4];
-    float v0 = 0.f, v1 = 0.f, f0 = 0.f, f1 = 0.f;
-    auto unit_step = [&](const float (&rg)[17], const float (&rx)[8], int u, int step) {
-        unsigned& d0 = u < 5 ? pe[0][u] : (u < 9 ? po[0][u - 5] : px[0][u - 9]);
-        unsigned& d1 = u < 5 ? pe[1][u] : (u < 9 ? po[1][u - 5] : px[1][u - 9]);
-        unsigned& d2 = u < 5 ? pe[2][u] : (u < 9 ? po[2][u - 5] : px[2][u - 9]);
-        if (step == 0) {
-            if (u < 5) { v0 = rg[4 * u]; v1 = u < 4 ? rg[4 * u + 2] : 0.f; }
-            else if (u < 9) { v0 = rg[4 * (u - 5) + 1]; v1 = rg[4 * (u - 5) + 3]; }
-            else { v0 = rx[2 * (u - 9)]; v1 = rx[2 * (u - 9) + 1]; }
-        }
-        split6_step3(step, v0, v1, v0, v1, f0, f1, d0, d1, d2);
-    };
-    const int w_elem = q * TC + lane;             // + ((piece * 3 + component) * 2) * 64 (g) / (piece * 2) * 64 (x)
-    auto write_g = [&](int gimg, int comp, int pc) {          // component 0: even columns, 1: odd columns, 2: even columns from the second on
-        u32x4 v;
-        if (comp == 0) { v[0] = pe[pc][0]; v[1] = pe[pc][1]; v[2] = pe[pc][2]; v[3] = pe[pc][3]; }
-        else if (comp == 1) { v[0] = po[pc][0]; v[1] = po[pc][1]; v[2] = po[pc][2]; v[3] = po[pc][3]; }
-        else {
-#pragma unroll
-            for (int d = 0; d < 4; ++d) v[d] = __builtin_amdgcn_alignbit(pe[pc][d + 1], pe[pc][d], 16);
-        }
-        lds[gimg * GI + (pc * 3 + comp) * 2 * TC + w_elem] = v;
-    };
-    auto write_x = [&](int ximg, int pc) {
-        u32x4 v; v[0] = px[pc][0]; v[1] = px[pc][1]; v[2] = px[pc][2]; v[3] = px[pc][3];
-        lds[NGR * GI + ximg * XI + pc * 2 * TC + w_elem] = v;
-    };
-    // the staging program: slots 0..38 = 13 units x 3 steps, the writes of a finished group in the slot of its last step (the
-    // shifted component in slots 39..41)
-    auto stage_slot = [&](const float (&rg)[17], const float (&rx)[8], int k, int gimg, int ximg) {
-        if (k < 39) unit_step(rg, rx, k / 3, k % 3);
-        if (k == 14) { write_g(gimg, 0, 0); write_g(gimg, 0, 1); write_g(gimg, 0, 2); }
-        if (k == 26) { write_g(gimg, 1, 0); write_g(gimg, 1, 1); write_g(gimg, 1, 2); }
-        if (k == 38) { write_x(ximg, 0); write_x(ximg, 1); write_x(ximg, 2); }
-        if (k >= 39 && k < 42) write_g(gimg, 2, k - 39);
-    };
-
-    const int tiles_x = p.W / 16;
-    const int sps = tiles_x * p.H, n_steps = sps * p.NB;
-    const int a_elem = half * TC + wco * 32 + l31;
-    const int b_elem = NGR * GI + half * TC + wci * 32 + l31;
-
-    PROF_ONLY(unsigned long long pc_mult = 0, pc_head = 0, pc_bar = 0;)
-    PROF_T(pstart);
-    PROF_ONLY(int nstep_done = 0;)
-    float rg[17], rx[8], ng[17], nx[8];
-    for (int sg = 0; sg < ck.nseg; ++sg) {
-    int t, t_end;
-    wg6_segment(ck, sg, p.S, p.H, n_steps, t, t_end);
-    while (t < t_end) {
-        const int bb = t / sps, rem = t - bb * sps, cx = rem / p.H, ya = rem - cx * p.H;
-        const int n = min(p.H - ya, t_end - t), yb = ya + n;
-        t += n;
-        PROF_T(th0);
-        // ---- head of a sweep: g rows 2 ya .. 2 ya + 3 into ring slots 0..3, x row ya into buffer ya & 1, registers of the first step
-        {
-            float g0[17], g1[17];
-            load_g(g0, bb, cx, 2 * ya + rsel);
-            load_g(g1, bb, cx, 2 * ya + 2 + rsel);
-            load_x(nx, bb, cx, ya);
-            load_g(rg, bb, cx, 2 * ya + 3 + rsel);
-            load_x(rx, bb, cx, ya + 1);
-#pragma unroll
-            for (int k = 0; k < 42; ++k) stage_slot(g0, nx, k, rsel, ya & 1);
-#pragma unroll
-            for (int k = 0; k < 42; ++k) stage_slot(g1, nx, k, 2 + rsel, ya & 1);
-#pragma unroll
-            for (int i = 0; i < 17; ++i) asm volatile("" :: "v"(rg[i]));          // (wait for the first step's registers here: wgrad6_kernel)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(rx[i]));
-        }
-        split6_barrier();
-        PROF_T(th1);
-        PROF_ACC(pc_head, th0, th1);
-        int s0 = 0;                                           // ring slot of g row 2 y
-        for (int y = ya; y < yb; ++y) {
-            PROF_T(tm0);
-            load_g(ng, bb, cx, 2 * y + 5 + rsel);             // registers of the step after next
-            load_x(nx, bb, cx, y + 2);
-            int wslot = s0 + 3 + rsel; wslot -= wslot >= NGR ? NGR : 0;
-            int a_base[3];
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) { int sl = s0 + ky; sl -= sl >= NGR ? NGR : 0; a_base[ky] = sl * GI + a_elem; }
-            const int b_base = b_elem + (y & 1) * XI;
-            bf16x8 av[2][3], bx[3];
-            auto rd_a = [&](int tp, int pc) {
-                const int ky = tp / 3, kx = tp % 3;
-                av[tp & 1][pc] = __builtin_bit_cast(bf16x8, lds[a_base[ky] + (pc * 3 + kx) * 2 * TC]);
-            };
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};        // small terms first: mm, hl, lh, hm, mh, hh
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) { bx[pc] = __builtin_bit_cast(bf16x8, lds[b_base + pc * 2 * TC]); rd_a(0, pc); }
-#pragma unroll
-            for (int tp = 0; tp < 9; ++tp) {
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int qq = 0; qq < 6; ++qq) {
-                    if (active) acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[tp & 1][PA[qq]], bx[PB[qq]], acc[tp], 0, 0, 0);
-                    if (tp + 1 < 9 && qq < 3) rd_a(tp + 1, qq);
-                    stage_slot(rg, rx, tp * 6 + qq, wslot, (y + 1) & 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            PROF_T(tm1);
-#pragma unroll
-            for (int i = 0; i < 17; ++i) rg[i] = ng[i];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rx[i] = nx[i];
-            s0 += 2; s0 -= s0 >= NGR ? NGR : 0;
-            split6_barrier();
-            PROF_T(tm2);
-            PROF_ACC(pc_mult, tm0, tm1); PROF_ACC(pc_bar, tm1, tm2); PROF_ONLY(++nstep_done;)
-        }
-    }
-    }
-    PROF_ONLY({
-        const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        if (lane == 0 && lin < 2048) {
-            unsigned long long* d = te_wgrad6_prof_buf + ((size_t)lin * 4 + wid) * 4;
-            d[0] = pc_mult; d[1] = pc_head; d[2] = pc_bar;
-            d[3] = ((unsigned long long)nstep_done << 40) | ((__builtin_readcyclecounter() - pstart) & 0xFFFFFFFFFFull);
-        }
-    })
-
-    if (!active) return;
-    float* sl = p.slabs + ((size_t)bgrp * p.S + s_chunk) * p.Co * p.Ci * 9;
-    const int ci = ci0 + wci * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        float* dst = sl + ((size_t)co * p.Ci + ci) * 9;
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) dst[tp] = acc[tp][r];
-    }
-}
-
-// WIDE form of the transposed kind (round 6, Ci % 128 == 0 - every transposed-kind layer of the FFHQ-256 model): the block tile is 64
-// channels of g x 128 channels of x.  The counters place wgrad6t_kernel BELOW the power cap (45.5 % MFMA busy at 2.2 GHz, HBM reads 2.1x the
-// algorithmic bytes): its vector-ALU staging - which a wave's own MFMAs do not hide (r05_wgrad6.log) - is the g unit (17 columns, 3
-// components) plus an x unit per wave and step of 54 MFMAs, and waves 2, 3 repeated the x units of waves 0, 1.  Here a wave multiplies
-// its 32 rows of g by 32 channels of BOTH x tiles (108 MFMAs per step, 2 x 9 accumulators = 288 registers of the 512 a lone wave per SIMD
-// owns), stages the same g unit and - waves 2, 3 - an x unit of the second tile: half the staging instructions, LDS writes and g loads
-// per MFMA, and g is read Ci / 128 instead of Ci / 64 times.  Same products in the same order per slab element: bit-identical slabs.
-__global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
-    constexpr bool NARROW = false;
-    constexpr int XI2 = 2 * XI;                   // x-row image of this form: [x tile 2][piece 3][k half 2][channel 64]
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    u32x4* lds = reinterpret_cast<u32x4*>(smem_raw);
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wco = wid >> 1, wci = wid & 1;                  // multiplying: the wave's 32 x 32 tile
-    const int rsel = wid >> 1, q = wid & 1;                   // staging: g row 2i + 3 + rsel and x tile rsel, cells 8 q .. 8 q + 7 of the step; lane = channel
-
-    const Wg6Chunk ck = wg6_chunk(p.S, p.NB * (p.W / 16));
-    const int s_chunk = ck.s, bgrp = ck.bgrp, b = bgrp * p.NB;
-    const int co0 = blockIdx.y * TC, ci0 = blockIdx.z * 2 * TC;
-    const int Hg = 2 * p.H + 1, Wg = 2 * p.W + 1;
-    const size_t gplane = (size_t)Hg * Wg, xplane = (size_t)p.H * p.W;
-    // addresses = uniform 64-bit base (scalar registers) + this lane's 32-bit byte offset (its channel): the scalar-base form of the
-    // global loads, no 64-bit vector arithmetic in the step
-    const float* gblk = p.g + ((size_t)b * p.Co + co0) * gplane;             // channel block of the group's first sample
-    const float* xblk = p.x + ((size_t)b * p.Ci + ci0) * xplane;
-    const int g_ch = lane, x_ch = rsel * TC + lane;           // (waves 2, 3 stage the second x tile: no wave repeats another's unit)
-    const unsigned g_lane = (unsigned)(g_ch * gplane * 4), x_lane = (unsigned)(x_ch * xplane * 4);       // bytes (host-checked < 2 GiB)
-
-    f32x16 acc[2][9];                                         // [x tile][ky * 3 + kx]
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NX; ++j)
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -598,7 +424,8 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
     };
     auto write_x = [&](int ximg, int pc) {
         u32x4 v; v[0] = px[pc][0]; v[1] = px[pc][1]; v[2] = px[pc][2]; v[3] = px[pc][3];
-        lds[NGR * GI + ximg * XI2 + rsel * XI + pc * 2 * TC + w_elem] = v;
+        if constexpr (WIDE) lds[NGR * GI + ximg * XROW + rsel * XI + pc * 2 * TC + w_elem] = v;
+        else lds[NGR * GI + ximg * XI + pc * 2 * TC + w_elem] = v;
     };
     // the staging program: slots 0..38 = 13 units x 3 steps, the writes of a finished group in the slot of its last step (the
     // shifted component in slots 39..41)
@@ -656,8 +483,8 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
             int a_base[3];
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) { int sl = s0 + ky; sl -= sl >= NGR ? NGR : 0; a_base[ky] = sl * GI + a_elem; }
-            const int b_base = b_elem + (y & 1) * XI2;
-            bf16x8 av[2][3], bx[2][3];
+            const int b_base = b_elem + (y & 1) * XROW;
+            bf16x8 av[2][3], bx[NX][3];
             auto rd_a = [&](int tp, int pc) {
                 const int ky = tp / 3, kx = tp % 3;
                 av[tp & 1][pc] = __builtin_bit_cast(bf16x8, lds[a_base[ky] + (pc * 3 + kx) * 2 * TC]);
@@ -666,21 +493,23 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) {
                 bx[0][pc] = __builtin_bit_cast(bf16x8, lds[b_base + pc * 2 * TC]);
-                bx[1][pc] = __builtin_bit_cast(bf16x8, lds[b_base + XI + pc * 2 * TC]);
+                if constexpr (WIDE) bx[1][pc] = __builtin_bit_cast(bf16x8, lds[b_base + XI + pc * 2 * TC]);
                 rd_a(0, pc);
             }
+            // a tap's 6 piece products for each x tile in turn (WIDE: 108 MFMAs per step), the 42-slot staging program behind them
 #pragma unroll
             for (int tp = 0; tp < 9; ++tp) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < NX; ++j)
 #pragma unroll
                     for (int qq = 0; qq < 6; ++qq) {
-                        acc[j][tp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[tp & 1][PA[qq]], bx[j][PB[qq]], acc[j][tp], 0, 0, 0);
+                        if (active) acc[j][tp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[tp & 1][PA[qq]], bx[j][PB[qq]], acc[j][tp], 0, 0, 0);
                         if (tp + 1 < 9 && j == 0 && qq < 3) rd_a(tp + 1, qq);          // (the other operand slot: last used by tap tp - 1)
-                        // the 42-slot staging program behind every other MFMA of the first 84 (108 per step)
-                        const int k = tp * 12 + j * 6 + qq;
-                        if ((k & 1) == 0) stage_slot(rg, rx, k >> 1, wslot, (y + 1) & 1);
+                        if constexpr (WIDE) {                                          // a slot behind every other MFMA of the first 84
+                            const int k = tp * 12 + j * 6 + qq;
+                            if ((k & 1) == 0) stage_slot(rg, rx, k >> 1, wslot, (y + 1) & 1);
+                        } else stage_slot(rg, rx, tp * 6 + qq, wslot, (y + 1) & 1);    // a slot behind each of the first 42 of 54
                         __builtin_amdgcn_sched_barrier(0);
                     }
             }
@@ -705,10 +534,13 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
         }
     })
 
+    if (!active) return;
     float* sl = p.slabs + ((size_t)bgrp * p.S + s_chunk) * p.Co * p.Ci * 9;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int ci = ci0 + j * TC + wci * 32 + l31;
+    for (int j = 0; j < NX; ++j) {
+        int ci;
+        if constexpr (WIDE) ci = ci0 + j * TC + wci * 32 + l31;
+        else ci = ci0 + wci * 32 + l31;           // (`active`'s sum: see there)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int co = co0 + wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -718,6 +550,11 @@ __global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) {
         }
     }
 }
+
+// the names the runtime, the profiles and the tools see: the 64 x 64 form (NARROW: its masked variant) and the wide form
+template <bool NARROW>
+__global__ __launch_bounds__(WT, 1) void wgrad6t_kernel(const Wg6Args p) { [[clang::always_inline]] wgrad6t_body<NARROW, false>(p); }
+__global__ __launch_bounds__(WT, 1) void wgrad6tw_kernel(const Wg6Args p) { [[clang::always_inline]] wgrad6t_body<false, true>(p); }
 
 // ---------------------------------------------------------------------------------------------------------------- 1x1 kind (round 6)
 // TE_CONV_1X1 (the weight gradient of the discriminator's ResBlock skip convolutions, model_spatial_query.py:173-181 / :780-798):
@@ -959,15 +796,15 @@ int te_wgrad6_launch(float* slabs, const float* g, const float* x, int kind, int
             return 1;
         }
         case TE_WG6_T2_WIDE: {           // wide form: 64 x 128 channels per block
-            split6_launch<wgrad6tw_kernel>(dim3(grid.x, grid.y, (unsigned)(Ci / (2 * TC))), WT, (size_t)(NGR * GI + 4 * XI) * 16, s, a);
+            split6_launch<wgrad6tw_kernel>(dim3(grid.x, grid.y, (unsigned)(Ci / (2 * TC))), WT, wgrad6t_lds_bytes(true), s, a);
             return 1;
         }
         case TE_WG6_T2: {
-            split6_launch<wgrad6t_kernel<false>>(grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s, a);
+            split6_launch<wgrad6t_kernel<false>>(grid, WT, wgrad6t_lds_bytes(false), s, a);
             return 1;
         }
         case TE_WG6_T2_MASKED: {
-            split6_launch<wgrad6t_kernel<true>>(grid, WT, (size_t)(NGR * GI + 2 * XI) * 16, s, a);
+            split6_launch<wgrad6t_kernel<true>>(grid, WT, wgrad6t_lds_bytes(false), s, a);
             return 1;
         }
         case TE_WG6_3X3_PAIR: {
