@@ -120,10 +120,28 @@ __device__ __forceinline__ bool split6_tile_list(int ntiles, int nt8, int mblock
 // body is optimised on its own first and again after inlining; the passes are not idempotent, and the kernels came out further from
 // the code that was measured (s2s6_kernel<false>: 156 VGPRs against 163, 49 s_waitcnt against 37; profiles/refactor_split6_forms_isa.txt
 // has every form that was tried and what is left with this one).  t2s6.hip keeps its two kernels written out: merged the same way, its
-// two-image kernel was 0.7 - 0.9 % slower in small launches in both timing visits (profiles/refactor_split6_forms_time.txt).
+// two-image kernel was 0.7 - 0.9 % slower in small launches in both timing visits (profiles/refactor_split6_forms_time.txt), and a
+// second attempt that went for the written-out kernels' instruction streams did not reach them (profiles/refactor_t2s6_isa.txt).
 // The inlined body meets the kernel's passes later than code written in the kernel: a subexpression that two places are to share has to
 // be visible to the first common-subexpression pass (not behind a short-circuit `&&`, not in a loop still to be unrolled) - wgrad6t_body's
 // `active` (profiles/refactor_wgrad6t_isa.txt: with that, all of wgrad6.hip's kernels are the instruction streams of the written-out code).
+// Why, and what else follows from it (refactor_t2s6_isa.txt has the evidence).  The mandatory inliner runs inside the call-graph walk,
+// BEHIND the module's early passes (simplifycfg, sroa, early-cse; ipsccp; mem2reg, one instcombine).  Code written in a kernel goes
+// through those early passes while its lambdas are still calls and threadIdx.x is still an opaque call, and once more through sroa /
+// early-cse / value propagation / instcombine after the lambdas are inlined; the top-level code of an inlined body sees only the second
+// round, with the lambdas' code already around it.  The lambdas themselves are treated alike in both forms.  So:
+//  - only top-level expressions over locals that no lambda captures by reference can come out differently; what a lambda computes is safe;
+//  - write such an expression as the early instcombine would leave it.  `readfirstlane(tid >> 6)` becomes `readfirstlane(tid) >> 6` there
+//    (the shift is hoisted while the sign of tid is unknown, and `wid >> 2` stays an arithmetic shift of the readfirstlane - one sign
+//    extension later on): written that way in the body, the decode of the wave index is the kernel's.  A single-use `2 * (wq & 1)` becomes
+//    `(wq << 1) & 2` before a lambda's `wq & 1` can be merged with it: write the doubled form where it is first used;
+//  - a temporary array that a lambda of the kernel declares must stay in that lambda (sroa gives it the type of the first pass that
+//    sees it: `bf16x8 av[2][3]` moved from `multiply` to the body turned 108 LDS reads from <8 x i16> plus a cast into <8 x bfloat>);
+//  - the body is compiled as at -O0 by the front end: `a * b + c` is `llvm.fmuladd` without the `contract` flag instead of fmul / fadd
+//    `contract`.  The instructions are the same fused ones; only the IR differs;
+//  - integer ranges are the limit: the kernel's value propagation narrows `rest / 20`, `rest % 5` to 8-bit divisions after the early
+//    instcombine has simplified `gt < 200 ? gt : 0`; in the inlined body both happen in the other order and a later pass repairs most, not
+//    all, of it.  No source form was found for that one, nor for which of two equal `wq >> 1` the weight DMA's address ends up sharing.
 
 // ---- host: which form of a kind to launch.  form_sel = the kind's form hook counted from its two-image default: 0 = ping-pong, 1 = the
 // two-image form where M % 128 == 0 and its grid (blocks_q: half as many blocks) still gives every CU a block, 2 = the two-image form

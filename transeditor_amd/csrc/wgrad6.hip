@@ -168,8 +168,11 @@ __global__ __launch_bounds__(WT, 1) void wgrad6_kernel(const Wg6Args p) {
             const f32x2 t = {v0, v1};
             pcs[2][d] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
         }
-        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(f0), "+v"(f1));          // (own copy of split6_step4<false>: through the shared step the
-                                                                             //  register allocation of this kernel changes; see split6_common.h)
+        // (own copy of split6_step4<false>.  Tried again with `split6_step4<false>(step, v0, v1, v0, v1, f0, f1, pcs[0][d], pcs[1][d],
+        //  pcs[2][d])` behind the step-0 block: same registers, LDS and instruction counts by class, but 18 / 15 regions of the two
+        //  instantiations move - the conversion and the two masks of a step trade places with the subtractions and the loop counter of
+        //  the neighbouring slot, one s_waitcnt less with PAIR.  Not the code that was measured, so the copy stays.)
+        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(f0), "+v"(f1));
     };
     // element index of this lane inside an image: ((piece * 4 + j) * 2 + kh) * 64 + lane
     const int w_elem = kh * TC + lane;
@@ -604,7 +607,9 @@ __global__ __launch_bounds__(WT, 1) void wgrad6p_kernel(const Wg6Args p) {
         }
     };
     // split of one packed pair in three steps (wgrad6t_kernel: unit_step); units 0..3: the g unit, 4..7: the x unit
-    // (own copy of split6_step3: through the shared step the register allocation of this kernel changes; see split6_common.h)
+    // (own copy of split6_step3.  Tried again with `split6_step3(step, v0, v1, v0, v1, f0, f1, d0, d1, d2)` behind the step-0 loads: 77
+    //  scalar registers instead of 78, one more vector instruction, 17 s_waitcnt instead of 13 - the row loads of the next step are issued
+    //  before the first split instead of behind it and waited for in more places.  Not the code that was measured, so the copy stays.)
     unsigned pg[3][4], px[3][4];
     float v0 = 0.f, v1 = 0.f, f0 = 0.f, f1 = 0.f;
     auto unit_step = [&](const float (&rg)[8], const float (&rx)[8], int u, int step) {
