@@ -1253,6 +1253,75 @@ int te_upsample_add_f32(float* out, const float* x, const float* y, int64_t plan
 int te_psp_codes_f32(float* z, float* p, const float* lat, const float* A, const float* bz, const float* z_avg, const float* p_avg,
                      int64_t B, int Ns, int Np, int D, int T, te_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M10b  training the heads of the dual-space pSp encoder (pSp/training/coach_new.py:128-135 loss.backward() through
+ * psp_encoders_new.py:11-32 GradualStyleBlock, :84-101 _upsample_add and :120-138 the head loops, the stack and adjust_style, which the
+ * reference leaves to torch autograd): the backward pass of everything M10 puts on the backbone, with the weight gradients (the
+ * backbone itself needs training-mode batch norm and is not here).  csrc/psp_heads_bwd.hip.  NCHW fp32, no atomics, every sum a
+ * fixed-order chain or a fixed-shape tree: bit-reproducible from run to run.  Every check is made before any launch; nothing is
+ * launched on a refusal.
+ *
+ * te_conv2d_heads_dgrad_f32 (replaces autograd's conv2d backward w.r.t. the input and the LeakyReLU backward in front of it, head by
+ * head): the data gradient of te_conv2d_heads_f32 with shared = 0.  g is the channel slice [gc0, gc0 + G*Cg) of a contiguous
+ * [B,gCtot,Ho,Wo]; gx [B,G*Ci,H,W]:
+ *     acc[b, h*Ci + ci, y, x] = sum over (co,ky,kx) with y = s*oy - py + ky, x = s*ox - px + kx of g[b, gc0 + h*Cg + co, oy, ox] * w[h,co,ci,ky,kx]
+ *     gx = act == NULL ? acc : (act[b, h*Ci + ci, y, x] > 0 ? acc : acc * slope)
+ * act [B,G*Ci,H,W] is the kept OUTPUT of the leaky layer the gradient enters: slope > 0, so its sign is the pre-activation's and the
+ * forward pass keeps nothing extra; torch's rule holds at 0, -0 and NaN (they take the slope).  wt is te_conv2d_dgrad_f32's layout with
+ * one block per head: for each phase (ry, rx), ry-major, the heads' blocks [Ci, Cg, ny, nx] one behind the other ([G*Ci, Cg*ny*nx] per
+ * phase), taps flipped.  It is te_conv2d_dgrad_f32's launch with one more gather (the workgroup's 64-channel block of gx names its
+ * head, the head the channel offset into g): a stride-2 layer is four dense stride-1 phases stored with a pitch of 2, and for every
+ * head the result is bitwise te_conv2d_dgrad_f32 on that head alone with pre = the head's slice of act and slope[] filled with the
+ * scalar.  kh = kw = 1 on a 1 x 1 plane is the grouped EqualLinear backwards.  A NaN in g reaches exactly the inputs of its own head
+ * and image whose window holds it.  Ci % 64 != 0, slope <= 0 (or NaN), a kernel above 7 x 7, a stride outside {1, 2}: TE_ERR_UNSUPPORTED;
+ * a NULL gx, g or wt: TE_ERR_NULL; sizes, padding and slice as te_conv2d_dgrad_f32 / te_conv2d_heads_f32: TE_ERR_SHAPE.
+ * (The heads that read a SHARED feature need no entry point: the sum over heads of their data gradients is te_conv2d_dgrad_f32 with
+ * Co = G*Cg on w viewed as [G*Cg,Ci,kh,kw], whose `add` accumulates the several consumers of one feature.)
+ *
+ * te_conv2d_heads_wgrad_f32 (replaces autograd's conv2d backward w.r.t. weight and bias): of te_conv2d_heads_f32 and, with G = 1, of
+ * the lateral te_conv2d_f32.  g as above, already multiplied by the leaky ReLU' (what the data gradient of the layer above wrote);
+ * x [B,Ci,H,W] (shared != 0) or [B,G*Ci,H,W]; gw [G,Cg,Ci,kh,kw], gb [G*Cg]:
+ *     gw[h,m,c,ky,kx] = sum over (b,oy,ox), b-major then row-major, of g[b, gc0 + h*Cg + m, oy, ox] * x[b, (shared ? c : h*Ci + c), s*oy+ky-py, s*ox+kx-px]
+ *     gb[h*Cg + m]    = sum over (b,oy,ox) of g[b, gc0 + h*Cg + m, oy, ox]
+ * with x = 0 outside the plane.  A GEMM with M = Cg per head, N = Ci*kh*kw and the reduction r = (b,oy,ox) of length R = B*Ho*Wo on
+ * the fp32-input MFMA, 64 x 64 tiles, 32-deep steps with the k permutation of csrc/conv2d_body.h; both operands are gathers.  Inside a
+ * step r is summed in the MFMA's order, the steps ascend.  A tap that only ever sees padding is exactly +0 (finite g).  gb: one wave
+ * per channel, lane l sums r = l, l + 64, ... ascending, the lanes meet in a fixed butterfly.  The grid depends on geometry alone.
+ * Two routes, chosen from (M, N, R) alone, never from G: unsplit (S = 1; ws may be NULL), or R cut into S ranges of whole steps in
+ * ascending order whose partial gw go to ws[S][G*Cg][N] and are summed over s ascending by a second kernel; a NULL ws or ws_bytes
+ * below S * G*Cg * N * 4 is TE_ERR_WORKSPACE.  splits = 0 takes the rule, S = te_conv2d_heads_wgrad_splits(Cg, Ci, kh, kw, B, Ho, Wo)
+ * (few tiles and a long R: the two laterals); splits = n in [1, 16] runs n ranges instead (tests and measurements; every range must be
+ * non-empty, else TE_ERR_SHAPE).  te_conv2d_heads_wgrad_ws_bytes is the rule's workspace (0 where S = 1); both helpers return a
+ * negative TE_ERR_* on bad arguments.  G heads in one launch give the bits of G launches of one head.  Cg % 64 != 0, a kernel above
+ * 7 x 7, a stride outside {1, 2}: TE_ERR_UNSUPPORTED; a NULL gw, gb, g or x: TE_ERR_NULL; the rest as te_conv2d_f32: TE_ERR_SHAPE.
+ *
+ * te_upsample_add_bwd_f32 (the adjoint of te_upsample_add_f32 w.r.t. x; the gradient of y is g itself): g [planes,H,W], gx and the
+ * optional add [planes,h,w].  A GATHER: source pixel (i, j) sums, output rows ascending, then columns ascending, g[oy,ox] * (wy * wx)
+ * over the outputs whose tap reaches it, one fma chain opened by the first term, with the very weights the forward formed (the same
+ * integer quotient and remainder, l1 rounded once, l0 = 1 - l1; wy * wx one rounding); then + add where add != NULL.  A tap of weight 0
+ * contributes nothing, so equal sizes give gx = g bit for bit; h = 1 or w = 1 puts the whole row's / plane's sum on the one pixel.
+ * Limits and refusals are te_upsample_add_f32's.
+ *
+ * te_psp_codes_bwd_f32 (the adjoint of te_psp_codes_f32; the latent averages are constants): gz [B,D,T], gp [B,D,Np], lat [B,Ns+Np,D],
+ * A [T,Ns] (folded, as the forward takes it) -> glat [B,Ns+Np,D], gA [T,Ns], gbz [T]:
+ *     glat[b, j, c]      = sum_t A[t, j] * gz[b, c, t]  (j < Ns)          t ascending, one fp64 fma chain, rounded once
+ *     glat[b, Ns + u, c] = gp[b, c, u]                                    a copy
+ *     gA[t, j]           = sum over (b, c) of gz[b, c, t] * lat[b, j, c]   one wave: lane l takes (b, c) = l, l + 64, ... (b-major) as one
+ *     gbz[t]             = sum over (b, c) of gz[b, c, t]                  fp64 chain, a fixed fp64 butterfly, rounded once
+ * gA is the gradient of the FOLDED A: the caller multiplies it by EqualLinear's scale to reach the stored parameter.  Limits are
+ * te_psp_codes_f32's.
+ */
+int te_conv2d_heads_dgrad_f32(float* gx, const float* g, const float* wt, const float* act, int B, int G, int Ci, int Cg, int H, int W, int kh,
+                              int kw, int s, int py, int px, int gCtot, int gc0, float slope, te_stream_t stream);
+int te_conv2d_heads_wgrad_splits(int Cg, int Ci, int kh, int kw, int64_t B, int Ho, int Wo);
+int64_t te_conv2d_heads_wgrad_ws_bytes(int64_t B, int G, int Cg, int Ci, int kh, int kw, int Ho, int Wo);
+int te_conv2d_heads_wgrad_f32(float* gw, float* gb, float* ws, int64_t ws_bytes, const float* g, const float* x, int B, int G, int Ci, int Cg,
+                              int H, int W, int kh, int kw, int s, int py, int px, int gCtot, int gc0, int shared, int splits,
+                              te_stream_t stream);
+int te_upsample_add_bwd_f32(float* gx, const float* g, const float* add, int64_t planes, int h, int w, int H, int W, te_stream_t stream);
+int te_psp_codes_bwd_f32(float* glat, float* gA, float* gbz, const float* gz, const float* gp, const float* lat, const float* A, int64_t B,
+                         int Ns, int Np, int D, int T, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1669,6 +1669,102 @@ def psp_codes(lat, A, bz, Np, z_avg=None, p_avg=None):
     return z, p
 
 
+# --------------------------------------------------------------------------------------------- M10b training the encoder's heads
+def heads_dgrad_weight(w, stride=1, pad=(0, 0)):
+    """w [G,Cg,Ci,kh,kw] -> the flat weight conv2d_heads_dgrad reads: dgrad_weight's phases, each holding the heads' blocks [Ci,Cg,ny,nx]
+    one behind the other.  Made once per step (the weights change); plain torch on whatever device w is on."""
+    if w.ndim != 5:
+        raise RuntimeError(f'te_hip: heads_dgrad_weight expects [G,Cg,Ci,kh,kw], got {tuple(w.shape)}')
+    blocks = []
+    for k0y, ny in dgrad_phases(w.shape[3], stride, pad[0]):
+        for k0x, nx in dgrad_phases(w.shape[4], stride, pad[1]):
+            blocks.append(w[:, :, :, k0y::stride, k0x::stride].flip(3, 4).transpose(1, 2).reshape(-1))
+    return torch.cat(blocks).contiguous()
+
+
+def _grad_slice(who, g, c0, Cn, B, Ho, Wo):
+    """the check of a gradient read as the channel slice [c0, c0 + Cn) of g [B,Ctot,Ho,Wo]"""
+    if g.ndim != 4 or g.shape[0] != B or tuple(g.shape[2:]) != (Ho, Wo) or c0 < 0 or c0 + Cn > g.shape[1]:
+        raise RuntimeError(f'te_hip: {who}: g must be [{B},Ctot,{Ho},{Wo}] with channels [{c0}, {c0} + {Cn}) inside it, got {tuple(g.shape)}')
+
+
+@_op
+def conv2d_heads_dgrad(g, wt, x_shape, G, kernel, stride=1, pad=(0, 0), act=None, slope=0.01, c0=0):
+    """the data gradient of conv2d_heads(shared=False): g the channels [c0, c0 + G*Cg) of [B,Ctot,Ho,Wo], wt = heads_dgrad_weight(w, stride,
+    pad), x_shape = (B, G*Ci, H, W) of the forward's input, kernel = (kh, kw) -> gx [B,G*Ci,H,W], multiplied by the leaky ReLU' of the layer
+    it enters where that layer's kept output act [B,G*Ci,H,W] is given (act > 0 ? 1 : slope).  The ABI refuses a Ci that is no multiple of
+    64 and a slope that is not positive; nothing is launched then."""
+    B, Cx, H, W = x_shape
+    kh, kw = kernel
+    taps = sum(a[1] for a in dgrad_phases(kh, stride, pad[0])) * sum(a[1] for a in dgrad_phases(kw, stride, pad[1]))
+    if G < 1 or Cx % G or wt.ndim != 1 or wt.numel() % (Cx * max(taps, 1)) or (act is not None and tuple(act.shape) != (B, Cx, H, W)):
+        raise RuntimeError(f'te_hip: conv2d_heads_dgrad: inconsistent shapes wt {tuple(wt.shape)}, x {tuple(x_shape)}, {G} heads, a {kh} x {kw} '
+                           f'kernel, stride {stride}, pad {tuple(pad)}, act {None if act is None else tuple(act.shape)}')
+    Cg = wt.numel() // (Cx * taps)
+    _grad_slice('conv2d_heads_dgrad', g, c0, G * Cg, B, *conv2d_out_hw(H, W, kh, kw, stride, pad))
+    gx = torch.empty(B, Cx, H, W, device=g.device, dtype=g.dtype)
+    _launch('te_conv2d_heads_dgrad_f32', _ptr(gx), _ptr(g), _ptr(wt), _ptr(act), B, G, Cx // G, Cg, H, W, kh, kw, stride, pad[0], pad[1],
+            g.shape[1], c0, float(slope))
+    return gx
+
+
+def conv2d_heads_wgrad_splits(Cg, Ci, kh, kw, B, Ho, Wo):
+    """the number of ranges of r = (b, oy, ox) te_conv2d_heads_wgrad_f32 runs for (M = Cg, N = Ci * kh * kw, R = B * Ho * Wo); 1 is the
+    unsplit route (no head count enters)"""
+    S = lib().te_conv2d_heads_wgrad_splits(Cg, Ci, kh, kw, B, Ho, Wo)
+    if S < 0:
+        raise RuntimeError(f'te_conv2d_heads_wgrad_splits failed ({S}) for Cg={Cg}, Ci={Ci}, a {kh} x {kw} kernel, B={B} and a {Ho} x {Wo} plane')
+    return S
+
+
+@_op
+def conv2d_heads_wgrad(g, x, w_shape, stride=1, pad=(0, 0), shared=False, c0=0, splits=0):
+    """the weight and bias gradient of conv2d_heads (and, with G = 1, of conv2d): g the channels [c0, c0 + G*Cg) of [B,Ctot,Ho,Wo], already
+    multiplied by the activation's derivative; x the forward's input, [B,Ci,H,W] (shared) or [B,G*Ci,H,W]; w_shape = (G, Cg, Ci, kh, kw)
+    -> (gw [G,Cg,Ci,kh,kw], gb [G*Cg]).  splits 0: the ABI's rule; n >= 1: n ranges of the reduction (1 is the unsplit route)."""
+    if len(w_shape) != 5 or x.ndim != 4 or x.shape[1] != w_shape[2] * (1 if shared else w_shape[0]):
+        raise RuntimeError(f'te_hip: conv2d_heads_wgrad: inconsistent shapes x {tuple(x.shape)}, w {tuple(w_shape)}, shared={bool(shared)}')
+    (B, _, H, W), (G, Cg, Ci, kh, kw) = x.shape, w_shape
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, stride, pad)
+    _grad_slice('conv2d_heads_wgrad', g, c0, G * Cg, B, Ho, Wo)
+    gw = torch.empty(G, Cg, Ci, kh, kw, device=g.device, dtype=g.dtype)
+    gb = torch.empty(G * Cg, device=g.device, dtype=g.dtype)
+    S = splits if splits else (conv2d_heads_wgrad_splits(Cg, Ci, kh, kw, B, Ho, Wo) if Ho > 0 and Wo > 0 and Cg % 64 == 0 else 1)
+    ws = torch.empty(S * gw.numel(), device=g.device, dtype=g.dtype) if S > 1 else None
+    _launch('te_conv2d_heads_wgrad_f32', _ptr(gw), _ptr(gb), _ptr(ws), 0 if ws is None else ws.numel() * 4, _ptr(g), _ptr(x), B, G, Ci, Cg, H, W,
+            kh, kw, stride, pad[0], pad[1], g.shape[1], c0, 1 if shared else 0, splits)
+    return gw, gb
+
+
+@_op
+def upsample_add_bwd(g, x_shape, add=None):
+    """the adjoint of upsample_add with respect to x: g [B,C,H,W], x_shape = (B, C, h, w) -> gx [B,C,h,w] (+ add [B,C,h,w] where given);
+    the gradient of y is g itself"""
+    if g.ndim != 4 or len(x_shape) != 4 or tuple(g.shape[:2]) != tuple(x_shape[:2]) or (add is not None and tuple(add.shape) != tuple(x_shape)):
+        raise RuntimeError(f'te_hip: upsample_add_bwd expects g [B,C,H,W] and x_shape (B, C, h, w), got {tuple(g.shape)}, {tuple(x_shape)} and add '
+                           f'{None if add is None else tuple(add.shape)}')
+    B, Cn, h, w = x_shape
+    gx = torch.empty(B, Cn, h, w, device=g.device, dtype=g.dtype)
+    _launch('te_upsample_add_bwd_f32', _ptr(gx), _ptr(g), _ptr(add), B * Cn, h, w, g.shape[2], g.shape[3])
+    return gx
+
+
+@_op
+def psp_codes_bwd(gz, gp, lat, A):
+    """the adjoint of psp_codes: gz [B,D,T], gp [B,D,Np], lat [B,Ns+Np,D], A [T,Ns] (folded) -> (glat [B,Ns+Np,D], gA [T,Ns] for the FOLDED
+    A, gbz [T])"""
+    if gz.ndim != 3 or gp.ndim != 3 or lat.ndim != 3 or A.ndim != 2 or gz.shape[2] != A.shape[0] or tuple(gz.shape[:2]) != tuple(gp.shape[:2]) \
+            or tuple(lat.shape) != (gz.shape[0], A.shape[1] + gp.shape[2], gz.shape[1]):
+        raise RuntimeError(f'te_hip: psp_codes_bwd: inconsistent shapes gz {tuple(gz.shape)}, gp {tuple(gp.shape)}, lat {tuple(lat.shape)}, '
+                           f'A {tuple(A.shape)}')
+    (B, D, T), Np, Ns = gz.shape, gp.shape[2], A.shape[1]
+    glat = torch.empty_like(lat, memory_format=torch.contiguous_format)
+    gA = torch.empty(T, Ns, device=gz.device, dtype=gz.dtype)
+    gbz = torch.empty(T, device=gz.device, dtype=gz.dtype)
+    _launch('te_psp_codes_bwd_f32', _ptr(glat), _ptr(gA), _ptr(gbz), _ptr(gz), _ptr(gp), _ptr(lat), _ptr(A), B, Ns, Np, D, T)
+    return glat, gA, gbz
+
+
 # --------------------------------------------------------------------------------------------- roctx ranges (SURVEY §5 tracing)
 # TE_ROCTX=1: every wrapper marked @_op above runs inside a roctx range "te:<op> <shape of its first tensor>", so a
 # `rocprofv3 --kernel-trace --marker-trace` timeline attributes kernels to operators instead of showing template names only

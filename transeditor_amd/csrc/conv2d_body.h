@@ -6,6 +6,7 @@
 //     irse.hip        te_conv2d_prelu[_keep]_f32, te_id_stem_{fwd,keep}_f32 (ArcFace IR-SE50)
 //     irse_bwd.hip    te_conv2d_dgrad_f32, te_id_stem_bwd_f32 (its backward pass: the adjoint is the same loop over the gradient)
 //     psp_heads.hip   te_conv2d_heads_f32 (the pSp encoder's grouped heads)
+//     psp_heads_bwd.hip  te_conv2d_heads_dgrad_f32 (their data gradient; dgrad_body.h holds what it shares with irse_bwd.hip)
 // A new network on this loop adds a gather, an epilogue and an entry point, and no launcher: the entry point checks what is its own,
 // fills its Args (ConvArgs or a struct derived from it; fill_args does the shared checks and the shared fields) and calls
 // launch<Gather, Epi[, Part]>(a, stream).  Compile-time policies make the variants:

@@ -13,10 +13,12 @@
 // image's outputs independent of the batch it is in.
 #include "te_common.h"
 #include "conv2d_body.h"
+#include "psp_upsample.h"
 
 namespace {
 
 using namespace te::conv2d;
+using te::psp::corner_tap;
 
 constexpr int kMaxSplits = 16;
 // The split rule, from (K, Ho * Wo) alone (measured: profiles/README.md, 'Encoder inversion'): a plane of at most kSplitPlane pixels
@@ -93,18 +95,7 @@ inline bool heads_dims_ok(int Ci, int kh, int kw, int Ho, int Wo) {
 }
 
 // ------------------------------------------------------------------------------------------------------ upsample and add
-// align_corners=True: src = o * (in - 1) / (out - 1) (0 where out == 1), in integers: the quotient is the first tap, the remainder
-// over out - 1 the second tap's weight, rounded once.  A tap of weight 0 is not read into the mix, so equal sizes give x + y.
-__device__ __forceinline__ void corner_tap(int o, int in_size, int out_size, int& i0, int& i1, float& l0, float& l1) {
-    if (out_size == 1) { i0 = i1 = 0; l0 = 1.f; l1 = 0.f; return; }
-    const int64_t num = (int64_t)o * (in_size - 1), den = out_size - 1;
-    i0 = (int)(num / den);
-    const int64_t rem = num - (int64_t)i0 * den;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = (float)rem / (float)den;
-    l0 = 1.f - l1;
-}
-
+// corner_tap (psp_upsample.h): the taps and their weights.  A tap of weight 0 is not read into the mix, so equal sizes give x + y.
 __device__ __forceinline__ float mix(float l0, float a, float l1, float b) { return l1 == 0.f ? a : fmaf(l1, b, __fmul_rn(l0, a)); }
 
 __global__ __launch_bounds__(256) void upsample_add_kernel(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ y,

@@ -23,9 +23,10 @@ where some heads read a shared feature and the others their own activations; bot
 does not grow with the number of heads: ten for the real geometry (138 convolutions and 30 linears).  Planes of a few pixels take the
 launch's split-K route.  The EqualLinear of every head is one more launch (1 x 1 on the 1 x 1 plane), and te_psp_codes_f32 stacks,
 applies adjust_style over the head axis, permutes and adds the latent averages.  An image's codes are bitwise the same whatever batch it
-is in.  Eval only: there is no backward pass.  Of encoder training (pSp/training/coach_new.py) the loss (encoder_loss.EncoderLoss,
-DESIGN.md section 8j) and the optimiser (optim.Ranger / optim.encoder_optimizer, section 8k) exist; this network's own backward pass,
-and with it the training loop, is still out of scope.  Measured deviations and
+is in.  Eval only here.  Of encoder training (pSp/training/coach_new.py) the loss (encoder_loss.EncoderLoss),
+the optimiser (optim.Ranger / optim.encoder_optimizer, section 8k) and the backward pass of everything that sits on the backbone
+(psp_heads_train.TrainableHeads, section 8l: the heads can be fine-tuned on a frozen backbone) exist; the backbone's own backward
+pass, and with it full encoder training, is still out of scope.  Measured deviations and
 times: profiles/README.md, 'Encoder inversion'.
 """
 import argparse
@@ -156,7 +157,8 @@ def parse_state_dict(sd, path='state_dict', taps=TAPS, units=None, dtype=torch.f
     scale = 1.0 / math.sqrt(D)                                                                   # EqualLinear(D, D, lr_mul=1)
     lin_w = torch.stack([(heads[k][i]['lin_w'].detach().double() * scale).to(dtype) for k, i in order]).view(Ns + Np, D, D, 1, 1).contiguous()
     lin_b = torch.cat([heads[k][i]['lin_b'].detach().to(dtype) for k, i in order]).contiguous()
-    return dict(stem=stem, units=parsed, lat1=lat1, lat2=lat2, launches=launches, lin=(lin_w, lin_b),
+    stored = dict(lin_w=torch.stack([heads[k][i]['lin_w'].detach().to(dtype) for k, i in order]).contiguous(), A=A.detach().to(dtype).contiguous())
+    return dict(stem=stem, units=parsed, lat1=lat1, lat2=lat2, launches=launches, lin=(lin_w, lin_b), stored=stored,
                 A=(A.detach().double() * (1.0 / math.sqrt(Ns))).to(dtype).contiguous(), bz=bz.detach().to(dtype).contiguous(),
                 geometry=dict(D=D, Ns=Ns, Np=Np, T=T, depth=d0, counts=counts, sizes={f'r{d0 + 1}': nf, f'r{d0}': nm + nf}), keys=read)
 
@@ -185,11 +187,13 @@ class DualSpaceEncoder(torch.nn.Module):
             self.register_buffer(f'{name}_b', None if t is None else t[1])
         self.register_buffer('z_avg', None if z_avg is None else _avg(z_avg, _AVG_KEYS[self.from_plus_space][0], g['D'], g['T'], path))
         self.register_buffer('p_avg', None if p_avg is None else _avg(p_avg, _AVG_KEYS[self.from_plus_space][1], g['D'], g['Np'], path))
-        self.program = []
+        self.program, self.launch_heads = [], []
+        self.stored = net['stored']                                   # EqualLinear weights as the file holds them (CPU): what training starts from
         for n, l in enumerate(net['launches']):
             self.register_buffer(f'h{n}_w', l['w'])
             self.register_buffer(f'h{n}_b', l['b'])
             self.program.append((n, l['src'], l['dst'], l['shared'], l['c0'], len(l['heads'])))
+            self.launch_heads.append(tuple(l['heads']))
         self.eval()
         if torch.cuda.is_available():
             self.to('cuda')
@@ -226,15 +230,19 @@ class DualSpaceEncoder(torch.nn.Module):
         lat = _lib.conv2d_heads(bufs['r0'], self.lin_w, self.lin_b, 1, (0, 0), False, 1.0, splits=rule(D, 1))
         return lat.view(B, n, D)
 
-    def features(self, images):
-        """[B,3,S,S] -> {'c3', 'p2', 'p1'} (the latter two where a head reads them)"""
+    def backbone(self, images):
+        """[B,3,S,S] -> [c1, c2, c3], the features after units taps[0..2]: the seam between the backbone and what sits on it"""
         a = _lib.conv2d_prelu(images, self.stem_w, self.stem_b, self.stem_slope, None, None, 1, (1, 1))
         c = []
         for i in range(self.taps[2] + 1):
             a = unit_forward(self, i, a)
             if i in self.taps:
                 c.append(a)
-        del a
+        return c
+
+    def features(self, images):
+        """[B,3,S,S] -> {'c3', 'p2', 'p1'} (the latter two where a head reads them)"""
+        c = self.backbone(images)
         feats = {'c3': c[2]}
         if self.lat1_w is not None:
             feats['p2'] = _lib.upsample_add(c[2], _lib.conv2d(c[1], self.lat1_w, self.lat1_b, 1, (0, 0), act=0))
